@@ -9,12 +9,15 @@ space-time system  dst = (Alpha (x) K + Beta (x) M) src  on synthetic data resid
 N = 1: BASELINE.json configs[1] (72^3 cells, Q4, cG(2) -> 2 blocks, 48 275 138 space-time DoFs).
 N > 1: BASELINE configs[2] - the fixed 144^3-cell mesh with vertices perturbed by 0.15 h (general-geometry
 path, 383 M space-time DoFs) cut into N z-slabs: STRONG scaling, as north_star asks (>= 6x at 8 GPUs); one
-packed interface-plane exchange per vmult over RCCL send/recv, no other collective on the data path.  The
-line also carries the time of the SAME mesh on one GPU (rank 0 runs it after the timed region), because the
+packed interface-plane exchange per vmult over RCCL send/recv, no other collective on the data path.  With
+--full the line also carries the time of the SAME mesh on one GPU (rank 0 runs it after the timed region), because the
 default N = 1 line is configs[1] and not the one-GPU point of this curve.  --scaling weak: every rank owns a
 72 x 72 x 72-cell slab of a 72 x 72 x 72N mesh instead.  The JSON says which ran.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus "roofline" and "cpu_baseline".
+Prints ONE JSON line (rank 0) with the driver's contract plus "roofline".  A plain run does only what that line
+needs; --full adds what is measured beside it: the CPU baseline ("cpu_baseline") and, at N > 1 with strong
+scaling, the one-GPU point of the same mesh.  --dump-outputs DIR writes the last timed step's result vector
+(a fixed, seeded sample of it where it is large) as DIR/<name>.npy, to compare two builds output for output.
 """
 import argparse
 import importlib
@@ -97,6 +100,26 @@ def measured_traffic(kernel_name, general):
         return None, None
 
 
+DUMP_BYTES = 48 << 20  # what --dump-outputs writes in all (every rank together)
+
+
+def dump_outputs(dirname, arrays, budget):
+    """Write every device tensor of `arrays` (name -> tensor) as <dirname>/<name>.npy in its own float type.  A tensor
+    larger than its equal share of `budget` bytes is written as a sample: the elements at sorted indices drawn from a
+    generator with a fixed seed, so the same arguments sample the same positions in every run and every build."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        n = share // t.element_size()
+        if t.numel() > n:
+            g = torch.Generator().manual_seed(4242)
+            idx = torch.randint(t.numel(), (n,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
 def bench_stokes(args, stfem, torch, dev):
     """BASELINE configs[4] on one GPU: SystemMatrixStokes::vmult (operators.h:825-867), FE_Q(2)^3 x FE_Q(1) x cG(time_degree), unit cube,
     homogeneous Dirichlet velocity.  A step = one space-time vmult; inputs resident in HBM; HIP events on the launch stream."""
@@ -108,7 +131,7 @@ def bench_stokes(args, stfem, torch, dev):
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234)
     sizes = {0: 3 * op.n_velocity, 1: op.n_pressure}
-    keep, src, dst = [], [None] * (2 * nt), [None] * (2 * nt)
+    keep, src, dst, results = [], [None] * (2 * nt), [None] * (2 * nt), {}
     for d in range(nt):
         for v in range(2):
             j = stfem.stokes_block_index(nt, 0, v, d)
@@ -116,6 +139,7 @@ def bench_stokes(args, stfem, torch, dev):
             b = torch.zeros(sizes[v], dtype=torch.float64, device=dev)
             keep += [a, b]
             src[j], dst[j] = a.data_ptr(), b.data_ptr()
+            results[f"dst_{('velocity', 'pressure')[v]}_t{d}"] = b
     for _ in range(args.warmup):
         op.st_vmult(Alpha, Beta, 1, nt, dst, src)
     torch.cuda.synchronize()
@@ -128,6 +152,8 @@ def bench_stokes(args, stfem, torch, dev):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kms = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, results, DUMP_BYTES)
     dofs = nt * (3 * op.n_velocity + op.n_pressure)
     alg_bytes = 16.0 * dofs
     achieved = alg_bytes / (kms * 1e-3) / 1e9
@@ -186,11 +212,19 @@ def main():
                     help="sweep the slab's two interface cell layers first and its interior while their planes travel "
                          "(dealii-stfem_amd/distributed.py: OverlappedSlabOperator; with --exchange abi for N > 1; at N = 1 it measures what "
                          "the three-part sweep costs over one sweep)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline line does not need: the CPU baseline (heat lines) and, at N > 1 with "
+                         "strong scaling, the whole mesh on rank 0's GPU after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result vector as DIR/<name>.npy (a fixed, seeded sample "
+                         "where it is large; %d MB in all)" % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-one-gpu-point", action="store_true",
-                    help="N > 1, strong scaling: do not run the whole mesh on rank 0's GPU after the timed region")
+                    help="with --full, N > 1, strong scaling: do not run the whole mesh on rank 0's GPU after the timed region")
     ap.add_argument("--cpu-cells", type=int, default=0, help="cells per direction of the CPU baseline mesh (0: as the GPU run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -431,6 +465,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:  # every rank its own slab (interface planes as that rank holds them)
+        dump_outputs(args.dump_outputs, {"dst" if world == 1 else f"dst_rank{rank}": dst_t}, DUMP_BYTES // world)
 
     # units: owned space-time DoFs of all ranks (interface planes counted once)
     own = slab.n_owned_planes(p) * plane * nb
@@ -445,9 +481,9 @@ def main():
     xms = sum(a.elapsed_time(b) for a, b in exchange_ms) / len(exchange_ms) if exchange_ms else 0.0
 
     # strong scaling: the one-GPU point of THIS curve, measured here (the default N = 1 line is configs[1], another mesh).
-    # Rank 0 runs the whole mesh on its GPU after the timed region; the other ranks wait at the final barrier.
+    # With --full, rank 0 runs the whole mesh on its GPU after the timed region; the other ranks wait at the final barrier.
     one_gpu_ms = None
-    if world > 1 and args.scaling == "strong" and rank == 0 and not args.no_one_gpu_point and args.backend == "nccl":
+    if args.full and world > 1 and args.scaling == "strong" and rank == 0 and not args.no_one_gpu_point and args.backend == "nccl":
         try:
             del dst, src
             del dst_t, src_t
@@ -527,7 +563,7 @@ def main():
                          if traffic is not None else traffic_file,
                          "kernel_ms": kms, "algorithmic_bytes_per_launch": alg_bytes},
         }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(stfem, p, r, args.cpu_cells or args.cells,
                                                max(1, min(16, len(os.sched_getaffinity(0)))))  # a 1-GPU box grants 16 cores
         print(json.dumps(out))

@@ -633,6 +633,88 @@ def vector_convert(dst, src, stream=None):
     _check(lib().stfem_vector_convert(dst._h, src._h, stream), "stfem_vector_convert")
 
 
+# ------------------------------------------------------- around the operator: load vectors, error norms (8 f-3)
+
+def _check_driver(status, what):
+    """_check with the text the driver entry points keep of their failing HIP call"""
+    if status != 0:
+        raise StfemError(status, what + ": " + lib().stfem_driver_last_error().decode() if status == -3 else what)
+
+
+def support_points(ctx):
+    """[n_dofs, 3]: the nodes in the order of the vectors (VectorTools::interpolate = evaluate + upload)"""
+    out = np.zeros((ctx.n_dofs, 3))
+    _check(lib().stfem_support_points(ctx._h, _p(out)), "stfem_support_points")
+    return out
+
+
+def quadrature_points(ctx, nq):
+    """[n_cells, nq^3, 3]: the points of QGauss(nq)^3, q = qx + nq (qy + nq qz)"""
+    out = np.zeros((ctx.n_cells, max(int(nq), 0) ** 3, 3))
+    _check(lib().stfem_quadrature_points(ctx._h, nq, _p(out) if out.size else None), "stfem_quadrature_points")
+    return out
+
+
+def _points_array(ctx, nq, values, per_point, what):
+    if values is None:
+        return None, None
+    a = np.ascontiguousarray(values, dtype=np.float64)
+    if 1 <= nq <= 8:  # other nq: the library reports the error
+        assert a.size == ctx.n_cells * nq ** 3 * per_point, what
+    return a, _p(a)
+
+
+def integrate_rhs(ctx, nq, f, dst, block=0, stream=None):
+    """block `block` of dst = (f, phi_i) with QGauss(nq), f [n_cells, nq^3] at quadrature_points; constrained rows 0"""
+    a, ptr = _points_array(ctx, nq, f, 1, "f")
+    _check_driver(lib().stfem_integrate_rhs(ctx._h, nq, ptr, dst._h, block, stream), "stfem_integrate_rhs")
+
+
+def integrate_rhs_product(ctx, nq, amplitude, frequency, dst, block=0, stream=None):
+    """the same with f(x) = amplitude * prod_d sin(2 pi frequency x_d) evaluated on the device"""
+    _check_driver(lib().stfem_integrate_rhs_product(ctx._h, nq, amplitude, frequency, dst._h, block, stream), "stfem_integrate_rhs_product")
+
+
+def integrate_difference(ctx, nq, u, block, exact, exact_grad=None, stream=None):
+    """(sum JxW (u_h - u)^2, max |u_h - u|, sum JxW |grad u_h - grad u|^2) of block `block` of u; exact [n_cells, nq^3],
+    exact_grad [n_cells, nq^3, 3] or None (third entry 0)"""
+    e, pe = _points_array(ctx, nq, exact, 1, "exact")
+    g, pg = _points_array(ctx, nq, exact_grad, 3, "exact_grad")
+    out = np.zeros(3)
+    _check_driver(lib().stfem_integrate_difference(ctx._h, nq, u._h, block, pe, pg, _p(out), stream), "stfem_integrate_difference")
+    return out
+
+
+def integrate_difference_product(ctx, nq, u, block, amplitude, frequency, stream=None):
+    """the same against amplitude * prod_d sin(2 pi frequency x_d) and its gradient, evaluated on the device"""
+    out = np.zeros(3)
+    _check_driver(lib().stfem_integrate_difference_product(ctx._h, nq, u._h, block, amplitude, frequency, _p(out), stream), "stfem_integrate_difference_product")
+    return out
+
+
+def vector_axpby(ctx, a, x, b, y, stream=None):
+    """y = a x + b y on every block; a zero factor means "not read"; x and y may be the same vector"""
+    _check_driver(lib().stfem_vector_axpby(ctx._h, a, x._h, b, y._h, stream), "stfem_vector_axpby")
+
+
+def vector_set_zero(ctx, y, stream=None):
+    _check_driver(lib().stfem_vector_set_zero(ctx._h, y._h, stream), "stfem_vector_set_zero")
+
+
+def gauss_rule(n):
+    """QGauss(n) on [0, 1] -> (points, weights)"""
+    x, w = np.zeros(max(int(n), 1)), np.zeros(max(int(n), 1))
+    _check(lib().stfem_gauss_rule(n, _p(x), _p(w)), "stfem_gauss_rule")
+    return x, w
+
+
+def fe_time_points(ttype, r):
+    """support points of the temporal basis (fe_time.cc:152-161): Gauss-Lobatto for cG(r), right Gauss-Radau for dG(r)"""
+    x = np.zeros(max(int(r), 0) + 1)
+    _check(lib().stfem_fe_time_points(ttype, r, _p(x)), "stfem_fe_time_points")
+    return x
+
+
 # ------------------------------------------------------------------------------- Stokes (8a-14)
 
 def stokes_block_index(n_timedofs, timestep, variable, timedof, variable_major=True):
@@ -776,6 +858,45 @@ class StokesMatrixFreeOperator:
                                                      _p(g), _p(z), d, getattr(src_u, "ptr", src_u),
                                                      getattr(src_p, "ptr", src_p), stream),
                "stfem_stokes_st_vmult_slice_add")
+
+    @property
+    def n_cells(self):
+        return int(np.prod(self.ncell))
+
+    def pressure_quadrature_points(self, nq):
+        """[n_cells, nq^3, 3]: QGauss(nq)^3 on the cells (axis-aligned uniform meshes)"""
+        out = np.zeros((self.n_cells, max(int(nq), 1) ** 3, 3))
+        _check(lib().stfem_stokes_pressure_quadrature_points(self._h, nq, _p(out)), "stfem_stokes_pressure_quadrature_points")
+        return out
+
+    def pressure_difference(self, nq, p, exact, stream=None):
+        """(sum JxW (p_h - p)^2, max |p_h - p|) of the device pressure vector p against exact [n_cells, nq^3] at those points"""
+        e = np.ascontiguousarray(exact, dtype=np.float64)
+        if 1 <= nq <= 8:
+            assert e.size == self.n_cells * nq ** 3
+        out = np.zeros(2)
+        _check(lib().stfem_stokes_pressure_difference(self._h, nq, getattr(p, "ptr", p), _p(e), _p(out), stream),
+               "stfem_stokes_pressure_difference")
+        return out
+
+    def pressure_mean_vectors(self):
+        """(ones, weights, volume): coefficients of p = 1, (1, psi_j), and the volume: mean(p) = weights . p / volume"""
+        ones, weights, volume = np.zeros(self.n_pressure), np.zeros(self.n_pressure), C.c_double(0.0)
+        _check(lib().stfem_stokes_pressure_mean_vectors(self._h, _p(ones), _p(weights), C.byref(volume)),
+               "stfem_stokes_pressure_mean_vectors")
+        return ones, weights, volume.value
+
+
+def stokes_dgp_prolongate(fine, coarse, dst, src, add=False, stream=None):
+    """FE_DGP(1) pressure: dst_fine (+)= embedding of src_coarse; `fine` has twice the cells of `coarse` per direction"""
+    _check(lib().stfem_stokes_dgp_prolongate(fine._h, coarse._h, getattr(dst, "ptr", dst), getattr(src, "ptr", src), int(bool(add)), stream),
+           "stfem_stokes_dgp_prolongate")
+
+
+def stokes_dgp_restrict(fine, coarse, dst, src, add=False, stream=None):
+    """dst_coarse (+)= the transpose of the embedding applied to src_fine"""
+    _check(lib().stfem_stokes_dgp_restrict(fine._h, coarse._h, getattr(dst, "ptr", dst), getattr(src, "ptr", src), int(bool(add)), stream),
+           "stfem_stokes_dgp_restrict")
 
 
 class StokesPreconditionVanka:

@@ -271,6 +271,7 @@ int stfem_vector_create(stfem_ctx *c, int nb, stfem_vec **out)
   stfem_vec *v = new (std::nothrow) stfem_vec;
   if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   v->ctx = c;
+  v->device = c->device;
   v->nb = nb;
   v->owns = true;
   v->blk.assign(nb, nullptr);
@@ -294,6 +295,7 @@ int stfem_vector_wrap(stfem_ctx *c, int nb, void *const *blocks, stfem_vec **out
   stfem_vec *v = new (std::nothrow) stfem_vec;
   if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   v->ctx = c;
+  v->device = c->device;
   v->nb = nb;
   v->owns = false;
   for (int b = 0; b < nb; ++b) {
@@ -325,7 +327,7 @@ void stfem_vector_destroy(stfem_vec *v)
 {
   if (!v) return;
   if (v->owns) {
-    (void)hipSetDevice(v->ctx->device);
+    (void)hipSetDevice(v->device);
     for (void *p : v->blk)
       if (p) (void)hipFree(p);
   }

@@ -126,14 +126,21 @@ __device__ double product_value(const ProductFn &f, const double x[3], double gr
   return f.amplitude * s[0] * s[1] * s[2];
 }
 
-// rhs_a += sum_q JxW_q f_q phi_a(x_q); one workgroup per cell; constrained rows stay 0
+// rhs_a += sum_q JxW_q f_q phi_a(x_q); one workgroup per cell; constrained rows stay 0.  One launch covers the cells of ONE
+// parity (cx & 1, cy & 1, cz & 1) = (par & 1, par >> 1 & 1, par >> 2): two of them share no DoF, so the plain `+=` below has no
+// race, and the eight launches in a fixed sequence give every shared DoF a fixed order of its up-to-eight contributions - the
+// load vector repeats bitwise (a global atomicAdd here made it depend on timing).
 template <typename T>
-__global__ __launch_bounds__(256) void integrate_rhs_kernel(const CellGeomParams g, const double *__restrict__ fq, T *__restrict__ dst, const ProductFn pf)
+__global__ __launch_bounds__(256) void integrate_rhs_kernel(const CellGeomParams g, const double *__restrict__ fq, T *__restrict__ dst, const ProductFn pf,
+                                                            const int par)
 {
   extern __shared__ double sm[]; // [nq^3] JxW f
   const int n = g.p + 1, nq = g.nq, nq3 = nq * nq * nq, nloc = n * n * n;
-  const long long cell = blockIdx.x;
-  const int cx = int(cell % g.ncx), cy = int((cell / g.ncx) % g.ncy), cz = int(cell / ((long long)g.ncx * g.ncy));
+  const int px = par & 1, py = (par >> 1) & 1, pz = par >> 2;
+  const int hx = (g.ncx - px + 1) / 2, hy = (g.ncy - py + 1) / 2; // cells of this parity per direction
+  const long long b = blockIdx.x;
+  const int cx = 2 * int(b % hx) + px, cy = 2 * int((b / hx) % hy) + py, cz = 2 * int(b / ((long long)hx * hy)) + pz;
+  const long long cell = cx + (long long)g.ncx * (cy + (long long)g.ncy * cz);
   for (int q = threadIdx.x; q < nq3; q += 256) {
     const int qx = q % nq, qy = (q / nq) % nq, qz = q / (nq * nq);
     const double xi[3] = {g.xq[qx], g.xq[qy], g.xq[qz]};
@@ -160,7 +167,7 @@ __global__ __launch_bounds__(256) void integrate_rhs_kernel(const CellGeomParams
         const double syz = g.S[qy * n + ay] * g.S[qz * n + az];
         for (int qx = 0; qx < nq; ++qx) s += sm[qx + nq * (qy + nq * qz)] * g.S[qx * n + ax] * syz;
       }
-    atomicAdd(dst + ix + (long long)g.nx * (iy + (long long)g.ny * iz), T(s));
+    dst[ix + (long long)g.nx * (iy + (long long)g.ny * iz)] += T(s);
   }
 }
 
@@ -376,12 +383,15 @@ static int integrate_rhs_impl(stfem_ctx *c, int nq, const double *f_at_points, c
     e = hipMemcpyAsync(d_f, f_at_points, nf * sizeof(double), hipMemcpyHostToDevice, st);
   }
   if (e == hipSuccess) e = hipMemsetAsync(dst->blk[block], 0, size_t(c->ndofs) * c->es, st);
-  if (e == hipSuccess) {
-    const size_t lds = size_t(nq) * nq * nq * sizeof(double);
+  const size_t lds = size_t(nq) * nq * nq * sizeof(double);
+  (void)hipGetLastError(); // an error some earlier, unrelated call left behind is not this call's
+  for (int par = 0; par < 8 && e == hipSuccess; ++par) { // fixed sequence on one stream: see the kernel
+    const long long nblk = (long long)((c->nc[0] - (par & 1) + 1) / 2) * ((c->nc[1] - ((par >> 1) & 1) + 1) / 2) * ((c->nc[2] - (par >> 2) + 1) / 2);
+    if (nblk == 0) continue;
     if (c->prec)
-      hipLaunchKernelGGL(integrate_rhs_kernel<float>, dim3((unsigned)c->ncells), dim3(256), lds, st, geo.g, d_f, static_cast<float *>(dst->blk[block]), pf);
+      hipLaunchKernelGGL(integrate_rhs_kernel<float>, dim3((unsigned)nblk), dim3(256), lds, st, geo.g, d_f, static_cast<float *>(dst->blk[block]), pf, par);
     else
-      hipLaunchKernelGGL(integrate_rhs_kernel<double>, dim3((unsigned)c->ncells), dim3(256), lds, st, geo.g, d_f, static_cast<double *>(dst->blk[block]), pf);
+      hipLaunchKernelGGL(integrate_rhs_kernel<double>, dim3((unsigned)nblk), dim3(256), lds, st, geo.g, d_f, static_cast<double *>(dst->blk[block]), pf, par);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -431,6 +441,7 @@ static int integrate_difference_impl(stfem_ctx *c, int nq, const stfem_vec *u, i
   if (e == hipSuccess) {
     const int n = c->p + 1;
     const size_t lds = (size_t(n) * n * n + 3 * 256) * sizeof(double);
+    (void)hipGetLastError();
     if (c->prec)
       hipLaunchKernelGGL(integrate_difference_kernel<float>, dim3((unsigned)c->ncells), dim3(256), lds, st, geo.g,
                          static_cast<const float *>(u->blk[block]), d_e, d_g, d_out, pf);

@@ -49,6 +49,7 @@ int stfem_internal_set_gradient(stfem_ctx *c, const double *p, const double (*w)
 
 struct stfem_vec {
   stfem_ctx *ctx = nullptr;
+  int device = 0; // of ctx, kept here: a garbage-collected caller may destroy the context before its vectors
   int nb = 0;
   bool owns = false;
   std::vector<void *> blk; // device arrays of the context's element type

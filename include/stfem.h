@@ -330,7 +330,8 @@ const char *stfem_vanka_last_error(void);
  * support_points:    out[ndofs][3], the nodes in the order of the vectors (VectorTools::interpolate = evaluate + upload)
  * quadrature_points: out[cell][q][3], q = qx + nq (qy + nq qz)
  * integrate_rhs:     block `block` of dst = (f, phi_i) with QGauss(nq), constrained rows 0
- *                    (VectorTools::create_right_hand_side with the zero-boundary constraints).  Synchronous.
+ *                    (VectorTools::create_right_hand_side with the zero-boundary constraints).  Synchronous.  The cells of a
+ *                    shared DoF are summed in a fixed order: bitwise reproducible.
  * integrate_difference: out = { sum JxW (u_h - u)^2, max |u_h - u|, sum JxW |grad u_h - grad u|^2 } over the
  *                    quadrature points (VectorTools::integrate_difference for L2_norm squared, Linfty_norm,
  *                    H1_seminorm squared); exact_grad_at_points [cell][q][3] may be NULL (third entry 0).  Synchronous.

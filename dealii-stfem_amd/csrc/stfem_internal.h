@@ -1,5 +1,5 @@
 // Internal layout of the opaque handles of include/stfem.h, shared by the translation units of the
-// library (stfem_capi.hip, stfem_vanka.hip).  Not part of the boundary.
+// library (stfem_capi.hip, stfem_vanka.hip; the Stokes operator's own: stfem_stokes_internal.h).  Not part of the boundary.
 #pragma once
 #include "../../include/stfem.h"
 

@@ -1,0 +1,138 @@
+// What the translation units of the Stokes two-field operator share (stfem_stokes.hip and stfem_stokes_{cell,coupling,boundary,
+// pressure}.hip): the description of a launch, the context and the launchers.  Not part of the boundary.
+#pragma once
+#include "stfem_internal.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <vector>
+
+constexpr int MAXOUT = 8; // destination pairs of a launch with one source
+constexpr int MAXSRC = 4; // sources, and destination pairs, of a launch with several sources
+
+// One set of launches:  out_u[o] (=, +=) sum_s wKu[s][o] (nu K u_s - B^T p_s) + wM[s][o] M u_s,  out_p[o] (=, +=) sum_s wKp[s][o] B u_s
+struct StokesParams {
+  const double *vertices; // device, (nc+1)^3 * 3
+  int ncx, ncy, ncz;
+  int ndu[3], ndp[3];
+  long long Nu, Np;
+  int dmask;
+  double nu;
+  // nsrc >= 1 sources (ps[s] == nullptr: u_s is read alone, mass only).  With several sources (SystemMatrixStokes::vmult with up to
+  // MAXSRC source time dofs and up to MAXSRC destination pairs in ONE set of launches) a cell is evaluated for every source in turn,
+  // the weighted results are summed in registers and scattered once; with one source the weights are applied at scatter time.
+  int nsrc;
+  const double *us[MAXSRC], *ps[MAXSRC];
+  int nout;
+  double *out_u[MAXOUT], *out_p[MAXOUT]; // (nullptr: this part of the pair is not written)
+  // [source][destination pair]: the kernels with one source walk row 0 with the destination index, as they walk out_u / out_p
+  // (with the destination index first that walk needed a second scaled index: more scalar registers spilled in the cell kernel)
+  double wKu[MAXSRC][MAXOUT], wKp[MAXSRC][MAXOUT], wM[MAXSRC][MAXOUT];
+  int store_u[MAXOUT], store_p[MAXOUT]; // 1: the first cell to touch a DoF (lowest colour) stores, the others add; 0: all add
+  double Su[9], Du[9], Sp[6]; // [q*3+a], [q*3+a], [q*2+a]
+  double xq[3], wq[3];
+  int interleave;             // cell -> half-wave assignment (see the cell kernel)
+  int colour;                 // this launch handles the cells with (cx & 1) + 2 (cy & 1) + 4 (cz & 1) == colour
+  int cart;                   // axis-aligned uniform cells: constant diagonal Jacobian
+  double hinv[3], detJ;       // 1 / h_d, hx hy hz
+  // pressure space: 0 = FE_Q(1) on the vertex lattice, 1 = FE_DGP(1), the reference's dGPressure (tests/tp_03stokes.cc:83-86):
+  // four DoFs per cell, deal.II's basis 1, l(xi), l(eta), l(zeta) with l(x) = sqrt 3 (2 x - 1), p[cell * 4 + j]
+  int pdg;
+  double l1q[3];              // l at the three Gauss points
+};
+
+// The coupling kernels of the Kronecker path (stfem_stokes_coupling.hip)
+struct CouplingParams {
+  int ncx, ncy, ncz;
+  int ndu[3], ndp[3];
+  long long Nu;
+  int dmask, pdg;
+  double h[3];
+  // 1D reference integrals, Q2 node a: FE_Q(1): N[a][j], C[a][j], j = 0, 1; FE_DGP(1): N[a][0] = int phi_a, N[a][1] = int l phi_a (same for C)
+  double N[3][2], C[3][2];
+  int nsrc, nout;
+  const double *u[MAXSRC], *p[MAXSRC];
+  double *out_u[MAXOUT], *out_p[MAXOUT];
+  double wKu[MAXOUT][MAXSRC], wKp[MAXOUT][MAXSRC]; // [output][source]
+  int store_p[MAXOUT];
+};
+
+// The weak (Nitsche) boundary faces (stfem_stokes_boundary.hip)
+struct BoundaryParams {
+  int weak_mask;
+  double gamma1, gamma2;
+  int foff[7];             // first work item (cell of a face, t1 fastest) of every face, [6] = total
+  const double *g;         // rhs mode: Dirichlet data at the face quadrature points [point][3]; nullptr: operator mode
+  double Eu[6], EDu[6], Ep[4]; // end-point tables [s * n + a]: FE_Q(2) values / derivatives, FE_Q(1) values at 0 and 1
+};
+
+struct stfem_stokes_ctx {
+  int device = 0;
+  int nc[3] = {0, 0, 0};
+  int ndu[3] = {0, 0, 0}, ndp[3] = {0, 0, 0};
+  long long Nu = 0, Np = 0;
+  int dmask = 0;
+  double nu = 1.0;
+  double *d_vertices = nullptr;
+  int n_cu = 256;
+  StokesParams base;
+  int pspace = 0; // 0 = FE_Q(1), 1 = FE_DGP(1)
+  // axis-aligned uniform meshes: the scalar FE_Q(2) context whose pencil sweep applies nu K + wM M to the velocity components,
+  // and the 1D tables of the coupling kernels
+  stfem_ctx *scalar = nullptr;
+  CouplingParams coupling;
+  // the divergence kernel reads the sources and writes the pressure destinations only: it runs beside the velocity sweep on the
+  // side stream - ONE per device, shared by all Stokes contexts (stokes_side_stream), not owned - forked from and joined to the
+  // caller's stream with the two events of this context
+  hipStream_t side = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  stfem_ctx *pressure_space = nullptr; // scalar context behind the pressure vectors (stfem_stokes_pressure_ctx), made on demand
+  double *d_pq = nullptr;              // exact values at the pressure quadrature points (stfem_stokes_pressure_difference)
+  size_t pq_points = 0;
+  double *d_pred = nullptr;            // its reduction results
+  // weak (Nitsche) / outflow boundary faces (operators.h:1206-1211): bit f = 2 d + s
+  int weak_mask = 0, outflow_mask = 0;
+  double penalty1 = 20.0, penalty2 = 10.0;
+  BoundaryParams bnd;
+  double *d_g = nullptr; // Dirichlet data at the face quadrature points (stfem_stokes_nitsche_rhs)
+  size_t g_points = 0;
+  std::vector<double> h_vertices;
+};
+
+__device__ __forceinline__ bool constrained_u(const StokesParams &prm, int ix, int iy, int iz)
+{
+  return ((prm.dmask & 1) && ix == 0) || ((prm.dmask & 2) && ix == prm.ndu[0] - 1) ||
+         ((prm.dmask & 4) && iy == 0) || ((prm.dmask & 8) && iy == prm.ndu[1] - 1) ||
+         ((prm.dmask & 16) && iz == 0) || ((prm.dmask & 32) && iz == prm.ndu[2] - 1);
+}
+
+// Orders the LDS traffic of one wave (a cell lives in one half of a wave: no workgroup barrier needed)
+__device__ __forceinline__ void wave_fence()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+#pragma GCC visibility push(hidden) // (the library exports what include/stfem.h declares)
+extern thread_local char g_stokes_err[256]; // stfem_stokes_last_hip_error
+
+// The eight colour launches of the cell kernel (general meshes; stfem_stokes_cell.hip)
+int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st);
+// The coupling kernels (stfem_stokes_coupling.hip): out_u -= sum_s wKu B^T p_s; out_p (=, +=) sum_s wKp B u_s.  They report through
+// hipGetLastError.
+void stokes_grad_launch(const CouplingParams &k, hipStream_t st);
+void stokes_div_launch(const CouplingParams &k, long long Np, hipStream_t st);
+// The eight colour launches of the boundary kernel (stfem_stokes_boundary.hip); d_g: the Dirichlet data of the rhs mode, or nullptr
+int stokes_boundary_launch(stfem_stokes_ctx *c, StokesParams &prm, const double *d_g, hipStream_t st);
+#pragma GCC visibility pop
+
+#define STOKES_TRY(call)                                                   \
+  do {                                                                     \
+    hipError_t e_ = (call);                                                \
+    if (e_ != hipSuccess) {                                                \
+      snprintf(g_stokes_err, sizeof(g_stokes_err), "%s: %s", #call, hipGetErrorString(e_)); \
+      return STFEM_ERR_HIP;                                                \
+    }                                                                      \
+  } while (0)

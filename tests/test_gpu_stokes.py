@@ -169,6 +169,98 @@ def test_stokes_axis_aligned_mesh_vs_oracle(nc, upper, mask, stfem):
             assert np.linalg.norm(dst[j].download() - ref[j]) <= TOL * np.linalg.norm(ref[j]) + 1e-14, (plane, j)
 
 
+def _st_vmult_vs_oracle(stfem, op, orc, r, ns, variable_major):
+    """SystemMatrixStokes::vmult with the weights of cG(r), ns time steps at once, against the oracle; destinations pre-filled"""
+    Alpha_vm, Beta_vm, _, _ = stfem.get_fe_time_weights_stokes(stfem.CGP, r, 1.0 / 16, ns)
+    nt, nb = r, 2 * r * ns
+    perm = np.zeros(nb, dtype=int)
+    for it in range(ns):
+        for v in range(2):
+            for d in range(nt):
+                perm[stfem.stokes_block_index(nt, it, v, d, variable_major)] = stfem.stokes_block_index(nt, it, v, d, True)
+    Alpha, Beta = Alpha_vm[np.ix_(perm, perm)], Beta_vm[np.ix_(perm, perm)]
+    rng = np.random.default_rng(100 * r + ns)
+    blocks = [None] * nb
+    for it in range(ns):
+        for d in range(nt):
+            blocks[stfem.stokes_block_index(nt, it, 0, d, variable_major)] = rng.uniform(-1, 1, 3 * orc.n_u)
+            blocks[stfem.stokes_block_index(nt, it, 1, d, variable_major)] = rng.uniform(-1, 1, orc.n_p)
+    ref = orc.st_vmult(Alpha, Beta, ns, nt, blocks, variable_major)
+    var = [0 if b.size == 3 * orc.n_u else 1 for b in blocks]
+    src = [op.initialize_dof_vector(v, b) for v, b in zip(var, blocks)]
+    dst = [op.initialize_dof_vector(v, np.full(b.size, 11.0)) for v, b in zip(var, blocks)]
+    op.st_vmult(Alpha, Beta, ns, nt, dst, src, variable_major)
+    for j in range(nb):
+        assert np.linalg.norm(ref[j]) > 0
+        assert np.linalg.norm(dst[j].download() - ref[j]) <= TOL * np.linalg.norm(ref[j]) + 1e-14, (r, ns, variable_major, j)
+
+
+# more than four source time dofs: one set of launches per source, whose destinations are partly overwritten (the first launch to
+# reach a block) and partly accumulated into
+MANY_SOURCES = [(1, 5), (1, 8), (3, 2)]  # (r, time steps at once)
+
+
+@pytest.mark.parametrize("variable_major", [True, False])
+@pytest.mark.parametrize("r,ns", MANY_SOURCES)
+def test_stokes_axis_aligned_many_sources_vs_oracle(r, ns, variable_major, stfem):
+    """axis-aligned mesh, FE_Q(1) pressure (Kronecker path; a source with one destination overwritten and one accumulated into: the
+    pressure gradient rides in the velocity sweep only where the overwritten destination is the only one, here the gradient kernel
+    serves both.  Before the launches had one description this case lost the gradient term of the accumulated destination: cG(1)
+    with 5 and 8 steps missed the bound with 4.2e-3 and 4.0e-3 against 5e-13)"""
+    from oracle import oracle
+    nc, upper, mask, nu = (5, 4, 6), (1.0, 1.0, 1.0), 0b111011, 0.7
+    op = stfem.StokesMatrixFreeOperator(nc, upper=upper, dirichlet_mask=mask, viscosity=nu)
+    orc = oracle.StokesOracle(nc, stfem.mesh_vertices(nc, (0, 0, 0), upper), mask, nu)
+    _st_vmult_vs_oracle(stfem, op, orc, r, ns, variable_major)
+
+
+@pytest.mark.parametrize("r,ns", MANY_SOURCES)
+def test_stokes_perturbed_many_sources_vs_oracle(r, ns, stfem):
+    """the same shapes through the cell kernel"""
+    from oracle import oracle
+    nc, mask, nu = (5, 4, 6), 0b111011, 0.7
+    verts = stfem.mesh_vertices(nc, distort=0.15, seed=77)
+    op = stfem.StokesMatrixFreeOperator(nc, vertices=verts, dirichlet_mask=mask, viscosity=nu)
+    _st_vmult_vs_oracle(stfem, op, oracle.StokesOracle(nc, verts, mask, nu), r, ns, True)
+
+
+@pytest.mark.parametrize("r,ns", MANY_SOURCES)
+def test_stokes_dg_pressure_many_sources_vs_oracle(r, ns, stfem):
+    """the same shapes with the FE_DGP(1) pressure (axis-aligned mesh)"""
+    from oracle import oracle
+    nc, mask, nu = (5, 4, 6), 0b111011, 0.7
+    op = stfem.StokesMatrixFreeOperator(nc, dirichlet_mask=mask, viscosity=nu, dg_pressure=True)
+    orc = oracle.StokesOracle(nc, stfem.mesh_vertices(nc), mask, nu, dg_pressure=True)
+    _st_vmult_vs_oracle(stfem, op, orc, r, ns, True)
+
+
+@pytest.mark.parametrize("cart", [True, False])
+@pytest.mark.parametrize("npairs", [8, 9])
+def test_stokes_vmult_slice_add_many_destinations(npairs, cart, stfem):
+    """vmult_slice_add with as many destination pairs as one launch takes (8) and one more"""
+    from oracle import oracle
+    nc, mask, nu = (3, 4, 2), 63, 1.7
+    verts = stfem.mesh_vertices(nc) if cart else stfem.mesh_vertices(nc, distort=0.1, seed=3)
+    op = stfem.StokesMatrixFreeOperator(nc, vertices=None if cart else verts, dirichlet_mask=mask, viscosity=nu)
+    orc = oracle.StokesOracle(nc, verts, mask, nu)
+    ns, nt = npairs, 1
+    nb = 2 * ns * nt
+    rng = np.random.default_rng(12)
+    Gamma, Zeta = rng.uniform(-1, 1, nb), rng.uniform(-1, 1, nb)
+    assert np.all(np.abs(Gamma) > 1e-3) and np.all(np.abs(Zeta) > 1e-3)  # no entry is skipped: npairs destination pairs
+    U, Pp = rng.uniform(-1, 1, 3 * orc.n_u), rng.uniform(-1, 1, orc.n_p)
+    ku, kp = orc.apply(U, Pp)
+    mu, _ = orc.apply(U, Pp, 0.0, 1.0)
+    init = [rng.uniform(-1, 1, 3 * orc.n_u if j % 2 == 0 else orc.n_p) for j in range(nb)]
+    dst = [op.initialize_dof_vector(j % 2, init[j]) for j in range(nb)]
+    op.st_vmult_slice_add(Gamma, Zeta, ns, nt, dst, op.initialize_dof_vector(0, U), op.initialize_dof_vector(1, Pp))
+    for it in range(ns):
+        ju, jp = stfem.stokes_block_index(nt, it, 0, 0), stfem.stokes_block_index(nt, it, 1, 0)
+        assert (ju, jp) == (2 * it, 2 * it + 1)
+        assert rel(dst[ju].download(), init[ju] + Gamma[ju] * ku.reshape(-1) + Zeta[ju] * mu.reshape(-1)) < TOL
+        assert rel(dst[jp].download(), init[jp] + Gamma[jp] * kp) < TOL
+
+
 # ---- weak (Nitsche) boundary faces: StokesMatrixFreeOperator with weak_boundary_ids (LoopType::Full) and
 # StokesNitscheMatrixFreeOperator (reference include/operators.h:1640-1741, 1768-1951)
 NITSCHE_FIXTURES = ["stokes_nitsche_cart_2x2x2", "stokes_nitsche_pert_2x3x2", "stokes_nitsche_pert_3x2x2"]

@@ -14,7 +14,8 @@
 // getting matrix entries, tests/tp_05dgp_support.cc:140-149) - no second implementation of the cell matrices.  Apply: the
 // MFMA class kernel of the scalar smoother (stfem_vanka_kernel.h) with a row table in place of its (block, node) arithmetic, rows
 // to a scratch array, then one collecting launch that sums every DoF's cells in a fixed order: two launches, no colours, no
-// atomics, bitwise reproducible.
+// atomics, bitwise reproducible.  Block classes, the flat cell list, the tile plan and the way from the probed matrices to the stored
+// inverse are the shared host steps of stfem_vanka_setup.h.
 #include "stfem_internal.h"
 
 #include <hip/hip_runtime.h>
@@ -24,11 +25,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "stfem_vanka_kernel.h"
+#include "stfem_vanka_setup.h"
+
+namespace vanka = stfem::vanka;
 
 namespace {
 
@@ -67,17 +71,7 @@ __global__ __launch_bounds__(256) void stokes_vanka_collect_kernel(const StokesC
     const long long node = i - (long long)comp * N;
     const int idx[3] = {int(node % nd[0]), int((node / nd[0]) % nd[1]), int(node / ((long long)nd[0] * nd[1]))};
     int cc[3][2], ll[3][2], cnt[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const int c0 = idx[d] / p, l0 = idx[d] - c0 * p;
-      cnt[d] = 0;
-      if (l0 == 0) {
-        if (c0 > 0) { cc[d][cnt[d]] = c0 - 1; ll[d][cnt[d]] = p; ++cnt[d]; }
-        if (c0 < P.nc[d]) { cc[d][cnt[d]] = c0; ll[d][cnt[d]] = 0; ++cnt[d]; }
-      } else {
-        cc[d][0] = c0; ll[d][0] = l0; cnt[d] = 1;
-      }
-    }
+    node_cells(idx, p, P.nc, cc, ll, cnt);
     const int rb = P.rowbase[b] + comp * 27;
     for (int kz = 0; kz < cnt[2]; ++kz)
       for (int ky = 0; ky < cnt[1]; ++ky)
@@ -89,35 +83,6 @@ __global__ __launch_bounds__(256) void stokes_vanka_collect_kernel(const StokesC
   }
   double *d = P.dst[b] + i;
   *d = P.accumulate ? *d + P.omega * s : P.omega * s;
-}
-
-bool invert_dense(int n, std::vector<double> &a) // Gauss-Jordan with partial pivoting (FullMatrix::gauss_jordan), in place
-{
-  std::vector<int> piv(n);
-  for (int k = 0; k < n; ++k) {
-    int r = k;
-    double best = std::fabs(a[size_t(k) * n + k]);
-    for (int i = k + 1; i < n; ++i)
-      if (std::fabs(a[size_t(i) * n + k]) > best) { best = std::fabs(a[size_t(i) * n + k]); r = i; }
-    if (!(best > 0.0)) return false;
-    piv[k] = r;
-    if (r != k)
-      for (int j = 0; j < n; ++j) std::swap(a[size_t(k) * n + j], a[size_t(r) * n + j]);
-    const double d = 1.0 / a[size_t(k) * n + k];
-    a[size_t(k) * n + k] = 1.0;
-    for (int j = 0; j < n; ++j) a[size_t(k) * n + j] *= d;
-    for (int i = 0; i < n; ++i)
-      if (i != k) {
-        const double f = a[size_t(i) * n + k];
-        if (f == 0.0) continue;
-        a[size_t(i) * n + k] = 0.0;
-        for (int j = 0; j < n; ++j) a[size_t(i) * n + j] -= f * a[size_t(k) * n + j];
-      }
-  }
-  for (int k = n - 1; k >= 0; --k)
-    if (piv[k] != k)
-      for (int i = 0; i < n; ++i) std::swap(a[size_t(i) * n + k], a[size_t(i) * n + piv[k]]);
-  return true;
 }
 
 template <int MT> const void *sv_kernel() { return reinterpret_cast<const void *>(&vanka_apply_kernel<double, 27, MT>); }
@@ -231,83 +196,21 @@ int probe_class(const stfem_stokes_desc &d, int key, int npl, std::vector<double
   return rc;
 }
 
-} // namespace
-
-extern "C" {
-
-const char *stfem_stokes_vanka_last_error(void) { return g_sv_err; }
-
-void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v)
+// The inverted block of every class: probed matrices, strong velocity constraints, valence, Alpha / Beta, Gauss-Jordan
+int build_class_blocks(stfem_stokes_vanka *v, const vanka::ClassTable &t, int npl, const double *Alpha, const double *Beta)
 {
-  if (!v) return;
-  (void)hipSetDevice(v->d.device);
-  if (v->d_blocks) (void)hipFree(v->d_blocks);
-  if (v->d_flat) (void)hipFree(v->d_flat);
-  if (v->d_rowtab) (void)hipFree(v->d_rowtab);
-  if (v->d_cellu) (void)hipFree(v->d_cellu);
-  if (v->d_cellp) (void)hipFree(v->d_cellp);
-  if (v->d_cls) (void)hipFree(v->d_cls);
-  if (v->d_slot) (void)hipFree(v->d_slot);
-  delete v;
-}
-
-int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v) { return v ? v->nclasses : 0; }
-
-int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta,
-                              stfem_stokes_vanka **out)
-{
-  if (!ctx || !block_variable || !Alpha || !Beta || !out || n_blocks < 1) return STFEM_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  if (n_blocks > VK_MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
-  stfem_stokes_vanka *v = new (std::nothrow) stfem_stokes_vanka;
-  if (!v) return STFEM_ERR_OUT_OF_MEMORY;
-  v->ctx = ctx;
-  int rc = stfem_stokes_internal_desc(ctx, &v->d);
   const stfem_stokes_desc &d = v->d;
-  if (rc == STFEM_OK && !d.cart) rc = STFEM_ERR_UNSUPPORTED; // (one block per cell on general meshes: not built for two variables)
-  if (rc != STFEM_OK) { delete v; return rc; }
-  const int npl = d.pspace ? 4 : 8, nl = 81 + npl;
-  v->nblk = n_blocks;
-  for (int i = 0; i < n_blocks; ++i) {
-    if (block_variable[i] < 0 || block_variable[i] > 1) { delete v; return STFEM_ERR_INVALID_ARGUMENT; }
-    v->var[i] = block_variable[i];
-    v->rowbase[i] = v->m;
-    v->m += block_variable[i] == 0 ? 81 : npl;
-  }
-  const int m = v->m;
-  if (m > VK_MAX_ROWS) { delete v; return STFEM_ERR_UNSUPPORTED; }
-  { // row tiles per workgroup: the split with the fewest padded tiles (fp64: at most six per workgroup)
-    const int tiles = (m + 15) / 16;
-    int best = 1 << 30;
-    for (int mtw : {4, 3, 6, 2, 1}) {
-      if (mtw > tiles && mtw != 1) continue;
-      const int parts = (tiles + mtw - 1) / mtw;
-      if (parts * mtw < best) { best = parts * mtw; v->mtw = mtw; v->parts = parts; }
-    }
-    v->mt = v->parts * v->mtw;
-    v->mpad = 16 * v->mt;
-    v->kpad = ((m + KS - 1) / KS) * KS;
-  }
-  SV_TRY(hipSetDevice(d.device));
-  // ---- classes: per direction bit 0 = has a lower neighbour, bit 1 = has an upper neighbour
-  auto dir_class = [&](int k, int c) { return (c > 0 ? 1 : 0) | (c < d.nc[k] - 1 ? 2 : 0); };
-  std::map<int, int> class_id;
-  std::vector<int> class_key;
-  for (int cz = 0; cz < d.nc[2]; ++cz)
-    for (int cy = 0; cy < d.nc[1]; ++cy)
-      for (int cx = 0; cx < d.nc[0]; ++cx) {
-        const int key = dir_class(0, cx) | (dir_class(1, cy) << 2) | (dir_class(2, cz) << 4);
-        if (!class_id.count(key)) { class_id[key] = int(class_key.size()); class_key.push_back(key); }
-      }
-  v->nclasses = int(class_key.size());
+  const int nl = 81 + npl, m = v->m;
   const size_t bsz = size_t(v->kpad) * v->mpad;
-  std::vector<double> all(bsz * v->nclasses, 0.0), A, Mu;
-  for (int ci = 0; ci < v->nclasses; ++ci) {
-    const int key = class_key[ci];
-    rc = probe_class(d, key, npl, A, Mu);
+  std::vector<double> all(bsz * t.key.size()), A, Mu, B;
+  std::vector<int> dof(m); // row -> DoF of the cell (81 velocity, then npl pressure)
+  for (int i = 0; i < v->nblk; ++i)
+    for (int k = 0; k < (v->var[i] ? npl : 81); ++k) dof[v->rowbase[i] + k] = (v->var[i] ? 81 : 0) + k;
+  for (size_t ci = 0; ci < t.key.size(); ++ci) {
+    const int key = t.key[ci];
+    const int rc = probe_class(d, key, npl, A, Mu);
     if (rc != STFEM_OK) {
       snprintf(g_sv_err, sizeof(g_sv_err), "probing the block of class %d: status %d (%s)", key, rc, stfem_stokes_last_hip_error());
-      stfem_stokes_vanka_destroy(v);
       return rc;
     }
     // valence and strong constraints of the cell's DoFs
@@ -330,45 +233,28 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
           if ((a[k] == 0 && (kk & 1)) || (a[k] == 1 && (kk & 2))) val[81 + n] *= 2.0;
         }
       }
-    for (int r = 0; r < 81; ++r)
-      if (con[r])
-        for (int s = 0; s < nl; ++s)
-          if (s != r) {
-            A[size_t(r) * nl + s] = A[size_t(s) * nl + r] = 0.0;
-            if (s < 81) Mu[size_t(r) * 81 + s] = Mu[size_t(s) * 81 + r] = 0.0;
-          }
-    std::vector<double> B(size_t(m) * m, 0.0);
-    for (int i = 0; i < n_blocks; ++i)
-      for (int j = 0; j < n_blocks; ++j) {
-        const int iv = v->var[i], jv = v->var[j];
-        const int ni = iv ? npl : 81, nj = jv ? npl : 81, ro = iv ? 81 : 0, co = jv ? 81 : 0;
-        const double al = Alpha[i * n_blocks + j], be = Beta[i * n_blocks + j];
-        for (int k = 0; k < ni; ++k)
-          for (int l = 0; l < nj; ++l) {
-            double e = 0.0;
-            if (be != 0.0 && iv == 0 && jv == 0) e += be * Mu[size_t(k) * 81 + l];                 // M_mask(0, 0) only
-            if (al != 0.0) e += al * A[size_t(ro + k) * nl + co + l];
-            B[size_t(v->rowbase[i] + k) * m + v->rowbase[j] + l] = val[ro + k] * e;
-          }
-      }
-    if (!invert_dense(m, B)) {
+    vanka::combine_two_variable(v->nblk, v->var, v->rowbase, m, 81, nl, Alpha, Beta, A, Mu, B);
+    if (!vanka::finish_block(m, B, dof, con, val, all.data() + bsz * ci, v->mpad, v->kpad)) {
       snprintf(g_sv_err, sizeof(g_sv_err), "singular cell block (class %d)", key);
-      stfem_stokes_vanka_destroy(v);
       return STFEM_ERR_INVALID_ARGUMENT;
     }
-    double *dstb = all.data() + bsz * ci;
-    for (int r = 0; r < m; ++r)
-      for (int k = 0; k < m; ++k) dstb[size_t(k) * v->mpad + r] = B[size_t(r) * m + k];
   }
+  return vk_upload(&v->d_blocks, all, g_sv_err);
+}
+
+// The row table, the flat cell list with the cells' first velocity and pressure DoFs, and the scratch array
+int build_tables(stfem_stokes_vanka *v, const vanka::ClassTable &t, int npl)
+{
+  const stfem_stokes_desc &d = v->d;
   // ---- row table: row -> (vector, variable, element offset from the cell's first DoF of the variable)
-  std::vector<int2> rowtab(m);
-  for (int i = 0; i < n_blocks; ++i) {
+  std::vector<int2> rowtab(v->m);
+  for (int i = 0; i < v->nblk; ++i) {
     if (v->var[i] == 0) {
       for (int c = 0; c < 3; ++c)
         for (int n = 0; n < 27; ++n) {
           const int a = n % 3, b = (n / 3) % 3, e = n / 9;
           const long long off = c * d.Nu + a + (long long)d.ndu[0] * (b + (long long)d.ndu[1] * e);
-          if (off > 0x7fffffffll) { stfem_stokes_vanka_destroy(v); return STFEM_ERR_UNSUPPORTED; }
+          if (off > 0x7fffffffll) return STFEM_ERR_UNSUPPORTED;
           rowtab[v->rowbase[i] + c * 27 + n] = make_int2(i, int(off));
         }
     } else {
@@ -379,43 +265,81 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
     }
   }
   // ---- cells grouped by class into batches of 16, four batches of one class per workgroup
-  const long long ncells = (long long)d.nc[0] * d.nc[1] * d.nc[2];
-  std::map<int, std::vector<int>> by_class;
+  std::vector<int> firstu(t.cls.size()), firstp(t.cls.size());
   for (int cz = 0; cz < d.nc[2]; ++cz)
     for (int cy = 0; cy < d.nc[1]; ++cy)
-      for (int cx = 0; cx < d.nc[0]; ++cx)
-        by_class[class_id[dir_class(0, cx) | (dir_class(1, cy) << 2) | (dir_class(2, cz) << 4)]].push_back(cx + d.nc[0] * (cy + d.nc[1] * cz));
-  std::vector<int> cellu, cellp, cls, slot(size_t(ncells), 0);
-  for (auto &kv : by_class) {
-    for (int cell : kv.second) {
-      const int cx = cell % d.nc[0], cy = (cell / d.nc[0]) % d.nc[1], cz = cell / (d.nc[0] * d.nc[1]);
-      slot[cell] = int(cellu.size());
-      cellu.push_back(2 * cx + d.ndu[0] * (2 * cy + d.ndu[1] * 2 * cz));
-      cellp.push_back(d.pspace ? 4 * cell : cx + d.ndp[0] * (cy + d.ndp[1] * cz));
-    }
-    cellu.resize(((cellu.size() + 63) / 64) * 64, -1);
-    cellp.resize(cellu.size(), 0);
-    while (cls.size() < cellu.size() / 64) cls.push_back(kv.first);
+      for (int cx = 0; cx < d.nc[0]; ++cx) {
+        const int cell = cx + d.nc[0] * (cy + d.nc[1] * cz);
+        firstu[cell] = 2 * cx + d.ndu[0] * (2 * cy + d.ndu[1] * 2 * cz);
+        firstp[cell] = d.pspace ? 4 * cell : cx + d.ndp[0] * (cy + d.ndp[1] * cz);
+      }
+  const vanka::CellList list = vanka::cell_list(t, -1);
+  v->nquad = int(list.cls.size());
+  int rc = vk_upload(&v->d_rowtab, rowtab, g_sv_err);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_cellu, vanka::gather_cells(list.order, firstu, -1), g_sv_err);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_cellp, vanka::gather_cells(list.order, firstp, 0), g_sv_err);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_cls, list.cls, g_sv_err);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_slot, list.slot, g_sv_err);
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&v->d_flat), list.order.size() * v->mpad * sizeof(double), g_sv_err);
+  return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+const char *stfem_stokes_vanka_last_error(void) { return g_sv_err; }
+
+void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v)
+{
+  if (!v) return;
+  (void)hipSetDevice(v->d.device);
+  (void)hipFree(v->d_blocks);
+  (void)hipFree(v->d_flat);
+  (void)hipFree(v->d_rowtab);
+  (void)hipFree(v->d_cellu);
+  (void)hipFree(v->d_cellp);
+  (void)hipFree(v->d_cls);
+  (void)hipFree(v->d_slot);
+  delete v;
+}
+
+int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v) { return v ? v->nclasses : 0; }
+
+int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta,
+                              stfem_stokes_vanka **out)
+{
+  if (!ctx || !block_variable || !Alpha || !Beta || !out || n_blocks < 1) return STFEM_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (n_blocks > VK_MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
+  stfem_stokes_desc d;
+  int rc = stfem_stokes_internal_desc(ctx, &d);
+  if (rc == STFEM_OK && !d.cart) rc = STFEM_ERR_UNSUPPORTED; // (one block per cell on general meshes: not built for two variables)
+  if (rc != STFEM_OK) return rc;
+  std::unique_ptr<stfem_stokes_vanka, void (*)(stfem_stokes_vanka *)> v(new (std::nothrow) stfem_stokes_vanka, stfem_stokes_vanka_destroy);
+  if (!v) return STFEM_ERR_OUT_OF_MEMORY;
+  v->ctx = ctx;
+  v->d = d;
+  const int npl = d.pspace ? 4 : 8;
+  v->nblk = n_blocks;
+  for (int i = 0; i < n_blocks; ++i) {
+    if (block_variable[i] < 0 || block_variable[i] > 1) return STFEM_ERR_INVALID_ARGUMENT;
+    v->var[i] = block_variable[i];
+    v->rowbase[i] = v->m;
+    v->m += block_variable[i] == 0 ? 81 : npl;
   }
-  v->nquad = int(cls.size());
-  if (hipMalloc(&v->d_blocks, all.size() * sizeof(double)) != hipSuccess || hipMalloc(&v->d_rowtab, rowtab.size() * sizeof(int2)) != hipSuccess ||
-      hipMalloc(&v->d_cellu, cellu.size() * sizeof(int)) != hipSuccess || hipMalloc(&v->d_cellp, cellp.size() * sizeof(int)) != hipSuccess ||
-      hipMalloc(&v->d_cls, cls.size() * sizeof(int)) != hipSuccess || hipMalloc(&v->d_slot, slot.size() * sizeof(int)) != hipSuccess ||
-      hipMalloc(&v->d_flat, cellu.size() * v->mpad * sizeof(double)) != hipSuccess) {
-    stfem_stokes_vanka_destroy(v);
-    return STFEM_ERR_OUT_OF_MEMORY;
-  }
-  if (hipMemcpy(v->d_blocks, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v->d_rowtab, rowtab.data(), rowtab.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v->d_cellu, cellu.data(), cellu.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v->d_cellp, cellp.data(), cellp.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v->d_cls, cls.data(), cls.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v->d_slot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-    stfem_stokes_vanka_destroy(v);
-    return STFEM_ERR_HIP;
-  }
-  *out = v;
-  return STFEM_OK;
+  if (v->m > VK_MAX_ROWS) return STFEM_ERR_UNSUPPORTED;
+  const vanka::TilePlan plan = vanka::stokes_tile_plan((v->m + 15) / 16);
+  v->mtw = plan.mtw; v->parts = plan.parts; v->mt = plan.parts * plan.mtw;
+  v->mpad = 16 * v->mt;
+  v->kpad = ((v->m + KS - 1) / KS) * KS;
+  SV_TRY(hipSetDevice(d.device));
+  const vanka::ClassTable t = vanka::class_table(d.nc, 0);
+  v->nclasses = int(t.key.size());
+  rc = build_class_blocks(v.get(), t, npl, Alpha, Beta);
+  if (rc == STFEM_OK) rc = build_tables(v.get(), t, npl);
+  if (rc == STFEM_OK) *out = v.release();
+  return rc;
 }
 
 // dst = (accumulate ? dst : 0) + omega * (sum over cells of scatter(B_c^-1 gather(src))); blocks in the order of the BlockSlice
@@ -448,11 +372,8 @@ int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, do
   (void)hipGetLastError();
   const void *k = sv_kernel(v->mtw);
   if (!k) return STFEM_ERR_UNSUPPORTED;
-  void *args[] = {&prm};
-  if (hipLaunchKernel(k, dim3(v->nquad, v->parts), dim3(256), args, 0, st) != hipSuccess) {
-    snprintf(g_sv_err, sizeof(g_sv_err), "vanka_apply_kernel: %s", hipGetErrorString(hipGetLastError()));
-    return STFEM_ERR_HIP;
-  }
+  const int rc = vk_launch(k, dim3(v->nquad, v->parts), &prm, st, "vanka_apply_kernel", g_sv_err);
+  if (rc != STFEM_OK) return rc;
   StokesCollectParams cp;
   std::memset(&cp, 0, sizeof(cp));
   for (int i = 0; i < v->nblk; ++i) { cp.dst[i] = dst_blocks[i]; cp.var[i] = v->var[i]; cp.rowbase[i] = v->rowbase[i]; }
@@ -460,13 +381,8 @@ int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, do
   for (int k3 = 0; k3 < 3; ++k3) { cp.nc[k3] = v->d.nc[k3]; cp.ndu[k3] = v->d.ndu[k3]; cp.ndp[k3] = v->d.ndp[k3]; }
   cp.Nu = v->d.Nu; cp.Np = v->d.Np; cp.omega = omega; cp.accumulate = accumulate;
   const long long big = std::max(3 * v->d.Nu, v->d.Np);
-  hipLaunchKernelGGL(stokes_vanka_collect_kernel, dim3((unsigned)((big + 255) / 256), v->nblk), dim3(256), 0, st, cp);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_sv_err, sizeof(g_sv_err), "stokes_vanka_collect_kernel: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  return STFEM_OK;
+  return vk_launch(reinterpret_cast<const void *>(&stokes_vanka_collect_kernel), dim3((unsigned)((big + 255) / 256), v->nblk), &cp, st,
+                   "stokes_vanka_collect_kernel", g_sv_err);
 }
 
 int stfem_stokes_vanka_vmult(stfem_stokes_vanka *v, double *const *dst_blocks, const double *const *src_blocks, void *stream)

@@ -15,8 +15,12 @@
 // with the gather and the scatter fused in: MFMA work (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32,
 // 125 kflop against 4 kB of DoF traffic per cell).  Cells are processed in eight colours (cells of one
 // colour share no DoF), so the scatter is plain load-add-store: no atomics, bitwise reproducible.
-// General meshes and coefficient tables get one block per cell (the reference's layout): set-up on the host
-// from device-computed cell matrices, apply = one HBM-bound block-times-vector per cell (vanka_apply_percell_kernel).
+// General meshes and coefficient tables get one block per cell (the reference's layout): set-up on the device (or, for
+// comparison, on the host from device-computed cell matrices), apply = one HBM-bound block-times-vector per cell
+// (vanka_apply_percell_kernel).  Meshes of up to 50 000 cells take two launches instead of eight: all cells at once, then
+// vanka_collect_kernel.
+// The host steps of the set-up - block classes, cell lists, tile plan, constrain / scale / invert / store - are in
+// stfem_vanka_setup.h, shared with the Stokes smoother; uploads and launches go through the helpers of stfem_vanka_kernel.h.
 #include "stfem_internal.h"
 
 #include <hip/hip_runtime.h>
@@ -26,12 +30,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <utility>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "stfem_vanka_kernel.h"
+#include "stfem_vanka_setup.h"
+
+namespace vanka = stfem::vanka;
 
 namespace {
 
@@ -164,20 +170,9 @@ template <typename T> __global__ __launch_bounds__(256) void vanka_collect_kerne
   if (i >= (long long)prm.nx * prm.ny * prm.nz) return;
   const int ix = int(i % prm.nx), iy = int((i / prm.nx) % prm.ny), iz = int(i / ((long long)prm.nx * prm.ny));
   const int p = prm.p, np = p + 1;
-  // per direction: the cells holding node i and its local index there (a vertex node: the cell below with index p, then the cell above with 0)
   int cc[3][2], ll[3][2], cnt[3];
   const int idx[3] = {ix, iy, iz}, nc[3] = {prm.ncx, prm.ncy, prm.ncz};
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const int c0 = idx[d] / p, l0 = idx[d] - c0 * p;
-    cnt[d] = 0;
-    if (l0 == 0) {
-      if (c0 > 0) { cc[d][cnt[d]] = c0 - 1; ll[d][cnt[d]] = p; ++cnt[d]; }
-      if (c0 < nc[d]) { cc[d][cnt[d]] = c0; ll[d][cnt[d]] = 0; ++cnt[d]; }
-    } else {
-      cc[d][0] = c0; ll[d][0] = l0; cnt[d] = 1;
-    }
-  }
+  node_cells(idx, p, nc, cc, ll, cnt);
   T acc[VK_MAX_BLOCKS];
 #pragma unroll
   for (int b = 0; b < VK_MAX_BLOCKS; ++b) acc[b] = T(0);
@@ -261,7 +256,7 @@ __global__ __launch_bounds__(256) void vanka_assemble_kernel(const VankaAssemble
   }
 }
 
-// In-place Gauss-Jordan inverse with partial pivoting (FullMatrix::gauss_jordan, stmg.h:828; the steps of invert() above), one
+// In-place Gauss-Jordan inverse with partial pivoting (FullMatrix::gauss_jordan, stmg.h:828; the steps of vanka::invert, stfem_vanka_setup.h), one
 // workgroup per m x m matrix in global memory, then the block in the apply's layout: out[k][r] = T(inverse(r, k)), row stride mpad.
 template <typename T>
 __global__ __launch_bounds__(256) void vanka_invert_kernel(double *__restrict__ Ball, T *__restrict__ out_all, int m, int mpad, int kpad,
@@ -341,39 +336,11 @@ __global__ __launch_bounds__(256) void vanka_invert_kernel(double *__restrict__ 
   }
 }
 
-// in-place Gauss-Jordan inverse with partial pivoting (FullMatrix::gauss_jordan, stmg.h:828)
-bool invert(int n, std::vector<double> &A)
-{
-  std::vector<int> piv(n);
-  for (int c = 0; c < n; ++c) {
-    int p = c;
-    double best = std::abs(A[size_t(c) * n + c]);
-    for (int r = c + 1; r < n; ++r)
-      if (std::abs(A[size_t(r) * n + c]) > best) { best = std::abs(A[size_t(r) * n + c]); p = r; }
-    if (best == 0.0) return false;
-    piv[c] = p;
-    if (p != c)
-      for (int k = 0; k < n; ++k) std::swap(A[size_t(c) * n + k], A[size_t(p) * n + k]);
-    const double inv = 1.0 / A[size_t(c) * n + c];
-    A[size_t(c) * n + c] = 1.0;
-    for (int k = 0; k < n; ++k) A[size_t(c) * n + k] *= inv;
-    for (int r = 0; r < n; ++r) {
-      if (r == c) continue;
-      const double f = A[size_t(r) * n + c];
-      if (f == 0.0) continue;
-      A[size_t(r) * n + c] = 0.0;
-      for (int k = 0; k < n; ++k) A[size_t(r) * n + k] -= f * A[size_t(c) * n + k];
-    }
-  }
-  for (int c = n - 1; c >= 0; --c)
-    if (piv[c] != c)
-      for (int r = 0; r < n; ++r) std::swap(A[size_t(r) * n + c], A[size_t(r) * n + piv[c]]);
-  return true;
-}
-
 thread_local char g_vanka_err[256] = "";
 
 } // namespace
+
+constexpr int VK_FLAT = 8; // the launch after the eight colours: all cells at once (two-phase apply)
 
 struct stfem_vanka {
   stfem_ctx *ctx = nullptr;
@@ -381,17 +348,18 @@ struct stfem_vanka {
   void *d_blocks = nullptr;
   void *d_blocks_base = nullptr; // allocation d_blocks points into (blocks built on an extended context: the ghost layers' come first)
   int *d_off = nullptr;
-  int *d_cell[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int *d_cls[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int nquad[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool per_cell = false; // one block per cell (general meshes, coefficient tables): d_blocks is [cell][kpad][mpad]
-  int ncol[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // cells per colour (d_cell[colour] = their numbers)
+  // the launches of an apply: colours 0 - 7, or VK_FLAT alone.  Class blocks: d_cell = first DoF per list entry, d_cls per quad
+  // of 64 entries, ngrid quads; per-cell blocks: d_cell = cell numbers (VK_FLAT: every cell, no list), ngrid cells.
+  int *d_cell[VK_FLAT + 1] = {}, *d_cls[VK_FLAT + 1] = {};
+  int ngrid[VK_FLAT + 1] = {};
   // two-phase apply (meshes of up to VK_FLAT_CELLS cells): all cells in ONE launch, rows to d_flat, then vanka_collect_kernel
   bool flat = false;
   void *d_flat = nullptr;
-  int *d_cell_all = nullptr, *d_cls_all = nullptr, *d_slot = nullptr;
-  int nquad_all = 0;
+  int *d_slot = nullptr;
 };
+using VankaPtr = std::unique_ptr<stfem_vanka, void (*)(stfem_vanka *)>; // (released only into *out)
+
 constexpr long long VK_FLAT_CELLS = 50000; // (36^3 cells: 45 us instead of 8 x 23; at 72^3 the scratch traffic costs more than the launches)
 static bool vanka_wants_flat(const stfem_ctx *c)
 {
@@ -408,6 +376,8 @@ static bool vanka_wants_flat(const stfem_ctx *c)
       return STFEM_ERR_HIP;                                                           \
     }                                                                                 \
   } while (0)
+// the float or double instantiation of kernel template K, by the context's Number type
+#define VK_TYPED(c, K) ((c)->prec ? reinterpret_cast<const void *>(&K<float>) : reinterpret_cast<const void *>(&K<double>))
 
 template <typename T, int NLOC> static const void *vanka_kernel(int mtw)
 {
@@ -431,14 +401,6 @@ template <typename T> static const void *vanka_kernel(int p, int mtw)
 }
 static const void *vanka_kernel(const stfem_ctx *c, int mtw) { return c->prec ? vanka_kernel<float>(c->p, mtw) : vanka_kernel<double>(c->p, mtw); }
 
-static int vanka_launch(const stfem_vanka *v, VankaParams &prm, int nquad, hipStream_t st)
-{
-  const void *k = vanka_kernel(v->ctx, v->mtw);
-  if (!k) return STFEM_ERR_UNSUPPORTED;
-  void *args[] = {&prm};
-  return hipLaunchKernel(k, dim3(nquad, v->parts), dim3(256), args, 0, st) == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
-}
-
 static int vanka_collect(const stfem_vanka *v, stfem_vec *dst, double omega, int accumulate, hipStream_t st)
 {
   const stfem_ctx *c = v->ctx;
@@ -450,76 +412,85 @@ static int vanka_collect(const stfem_vanka *v, stfem_vec *dst, double omega, int
   cp.nb = v->nb; cp.nloc = v->nloc; cp.p = c->p; cp.mpad = v->mpad;
   cp.ncx = c->nc[0]; cp.ncy = c->nc[1]; cp.ncz = c->nc[2]; cp.nx = c->nd[0]; cp.ny = c->nd[1]; cp.nz = c->nd[2];
   cp.omega = omega; cp.accumulate = accumulate;
-  const unsigned grid = (unsigned)((c->ndofs + 255) / 256);
-  if (c->prec) hipLaunchKernelGGL(vanka_collect_kernel<float>, dim3(grid), dim3(256), 0, st, cp);
-  else hipLaunchKernelGGL(vanka_collect_kernel<double>, dim3(grid), dim3(256), 0, st, cp);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_vanka_err, sizeof(g_vanka_err), "vanka_collect_kernel: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  return STFEM_OK;
+  return vk_launch(VK_TYPED(c, vanka_collect_kernel), dim3((unsigned)((c->ndofs + 255) / 256)), &cp, st, "vanka_collect_kernel", g_vanka_err);
 }
 
-// Row tiles (16 rows each) per workgroup: a cell block of `tiles` tiles is split into parts of mtw tiles, one
-// workgroup each (smaller parts: more workgroups per launch and per CU; larger: less set-up per MFMA).
-// Measured on cfg 1 (16 tiles; profiles/r2/vanka): fp64 1.16 / 1.25 ms with 4 / 8 tiles per workgroup, fp32 0.74 / 0.69;
-// two or four 16-cell column batches per wave (one staged slab and one LDS read for 2 - 4 MFMAs) 1.19 - 1.47 ms: slower;
-// capping the resident workgroups per CU changes nothing.
-static void vanka_plan(stfem_vanka *v, int tiles)
+// a new smoother on context c, nothing built yet
+static VankaPtr vanka_new(stfem_ctx *c, int nb)
 {
-  int env_tiles = 0;
-  if (const char *e = getenv("STFEM_VANKA_TILES")) env_tiles = atoi(e); // (experiments)
-  double best = 1e30;
-  const int cand64[] = {4, 8, 6, 3, 2, 1}, cand32[] = {8, 4, 6, 3, 2, 1};
-  for (int mtw : (v->ctx->prec ? cand32 : cand64)) {
-    if (tiles <= 4 ? mtw != tiles : mtw > tiles) continue; // small blocks: one part
-    if (env_tiles && mtw != env_tiles) continue;
-    if (!vanka_kernel(v->ctx, mtw)) continue;
-    const int parts = (tiles + mtw - 1) / mtw;
-    const double cost = double(parts * mtw) / tiles * (mtw >= 4 ? 1.0 : 1.1); // padded row tiles are computed too
-    if (cost < best - 1e-9) {
-      best = cost;
-      v->mtw = mtw; v->parts = parts; v->mt = parts * mtw;
-    }
+  VankaPtr v(new (std::nothrow) stfem_vanka, stfem_vanka_destroy);
+  if (v) {
+    const int n = c->p + 1;
+    v->ctx = c; v->nb = nb; v->nloc = n * n * n; v->m = nb * v->nloc;
   }
+  return v;
 }
 
-// DoF offsets of a cell and the cells of every colour (per-cell variant)
-static int vanka_per_cell_tables(stfem_vanka *v)
+// local node -> DoF offset from the cell's first node
+static int vanka_offset_table(stfem_vanka *v)
 {
-  stfem_ctx *c = v->ctx;
-  const int n = c->p + 1, nloc = v->nloc;
-  const int ncx = c->nc[0], ncy = c->nc[1], ncz = c->nc[2];
-  // ---- DoF offsets and the cells of every colour
-  std::vector<int> off(nloc);
+  const stfem_ctx *c = v->ctx;
+  const int n = c->p + 1;
+  std::vector<int> off(v->nloc);
   for (int kz = 0; kz < n; ++kz)
     for (int jy = 0; jy < n; ++jy)
       for (int ix = 0; ix < n; ++ix) off[ix + n * (jy + n * kz)] = ix + c->nd[0] * (jy + c->nd[1] * kz);
-  if (hipMalloc(&v->d_off, nloc * sizeof(int)) != hipSuccess ||
-      hipMemcpy(v->d_off, off.data(), nloc * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-    return STFEM_ERR_HIP;
-  for (int colour = 0; colour < 8; ++colour) {
+  return vk_upload(&v->d_off, off, g_vanka_err);
+}
+
+// per-cell variant: one block of mt row tiles per cell
+static void vanka_per_cell_shape(stfem_vanka *v)
+{
+  v->per_cell = true;
+  v->mt = (v->m + 15) / 16;
+  v->mpad = 16 * v->mt;
+  v->kpad = ((v->m + 3) / 4) * 4;
+}
+
+// The blocks on the host, in the context's Number type and the apply's layout [block][kpad][mpad], filled block by block from the
+// restricted assembled matrices K, M of a cell with its constrained nodes (con) and node valences (val): stmg.h:806-829
+namespace {
+struct VankaHostBlocks {
+  const stfem_vanka *v;
+  const double *Alpha, *Beta;
+  std::vector<float> f32;
+  std::vector<double> f64, B;
+  std::vector<int> dof; // row -> node
+  VankaHostBlocks(const stfem_vanka *v_, size_t count, const double *Alpha_, const double *Beta_) : v(v_), Alpha(Alpha_), Beta(Beta_), dof(v_->m)
+  {
+    if (v->ctx->prec) f32.resize(count * v->kpad * v->mpad);
+    else f64.resize(count * v->kpad * v->mpad);
+    for (int r = 0; r < v->m; ++r) dof[r] = r % v->nloc;
+  }
+  bool add(size_t index, const std::vector<double> &K, const std::vector<double> &M, const std::vector<char> &con, const std::vector<double> &val) // false: singular
+  {
+    const size_t at = index * v->kpad * v->mpad;
+    vanka::combine_scalar(v->nb, v->nloc, Alpha, Beta, K, M, B);
+    return v->ctx->prec ? vanka::finish_block(v->m, B, dof, con, val, f32.data() + at, v->mpad, v->kpad)
+                        : vanka::finish_block(v->m, B, dof, con, val, f64.data() + at, v->mpad, v->kpad);
+  }
+  int upload(stfem_vanka *to) const { return v->ctx->prec ? vk_upload(&to->d_blocks, f32, g_vanka_err) : vk_upload(&to->d_blocks, f64, g_vanka_err); }
+};
+} // namespace
+
+// per-cell variant: DoF offsets, the cells of every colour and, for the two-phase apply, the scratch array (slot = cell)
+static int vanka_per_cell_tables(stfem_vanka *v)
+{
+  stfem_ctx *c = v->ctx;
+  const int ncx = c->nc[0], ncy = c->nc[1], ncz = c->nc[2];
+  int rc = vanka_offset_table(v);
+  for (int colour = 0; colour < 8 && rc == STFEM_OK; ++colour) {
     std::vector<int> cells;
     for (int cz = colour >> 2; cz < ncz; cz += 2)
       for (int cy = (colour >> 1) & 1; cy < ncy; cy += 2)
         for (int cx = colour & 1; cx < ncx; cx += 2) cells.push_back(cx + ncx * (cy + ncy * cz));
-    v->ncol[colour] = int(cells.size());
-    if (cells.empty()) continue;
-    if (hipMalloc(&v->d_cell[colour], cells.size() * sizeof(int)) != hipSuccess ||
-        hipMemcpy(v->d_cell[colour], cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-      return STFEM_ERR_HIP;
+    v->ngrid[colour] = int(cells.size());
+    if (!cells.empty()) rc = vk_upload(&v->d_cell[colour], cells, g_vanka_err);
   }
-  return STFEM_OK;
-}
-
-// two-phase apply of the per-cell variant: the scratch array (slot = cell)
-static int vanka_flat_per_cell(stfem_vanka *v)
-{
-  if (!vanka_wants_flat(v->ctx)) return STFEM_OK;
-  if (hipMalloc(&v->d_flat, size_t(v->ctx->ncells) * v->mpad * v->ctx->es) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
+  if (rc != STFEM_OK || !vanka_wants_flat(c)) return rc;
+  v->ngrid[VK_FLAT] = int(c->ncells);
   v->flat = true;
-  return STFEM_OK;
+  return vk_alloc(&v->d_flat, size_t(c->ncells) * v->mpad * c->es, g_vanka_err);
 }
 
 // Set-up of the per-cell blocks (general meshes, coefficient tables): cell matrices on the device from the stored
@@ -530,11 +501,8 @@ static int vanka_flat_per_cell(stfem_vanka *v)
 static int vanka_create_per_cell_host(stfem_vanka *v, const double *Alpha, const double *Beta)
 {
   stfem_ctx *c = v->ctx;
-  const int p = c->p, n = p + 1, nloc = v->nloc, m = v->m, nb = v->nb;
-  v->per_cell = true;
-  v->mt = (m + 15) / 16;
-  v->mpad = 16 * v->mt;
-  v->kpad = ((m + 3) / 4) * 4;
+  const int p = c->p, n = p + 1, nloc = v->nloc;
+  vanka_per_cell_shape(v);
   const size_t bsz = size_t(v->kpad) * v->mpad;
   if (double(c->ncells) * double(bsz) * double(c->es) > 64e9) {
     snprintf(g_vanka_err, sizeof(g_vanka_err), "per-cell blocks of %lld cells need %.1f GB", (long long)c->ncells,
@@ -582,12 +550,9 @@ static int vanka_create_per_cell_host(stfem_vanka *v, const double *Alpha, const
   }
   // ---- blocks
   const int ncx = c->nc[0], ncy = c->nc[1], ncz = c->nc[2];
-  std::vector<double> Kr(size_t(nloc) * nloc), Mr(size_t(nloc) * nloc), B(size_t(m) * m), val(nloc);
+  std::vector<double> Kr(size_t(nloc) * nloc), Mr(size_t(nloc) * nloc), val(nloc);
   std::vector<char> cn(nloc);
-  std::vector<float> out32;
-  std::vector<double> out64;
-  if (c->prec) out32.assign(size_t(c->ncells) * bsz, 0.0f);
-  else out64.assign(size_t(c->ncells) * bsz, 0.0);
+  VankaHostBlocks blocks(v, size_t(c->ncells), Alpha, Beta);
   for (int cz = 0; cz < ncz; ++cz)
     for (int cy = 0; cy < ncy; ++cy)
       for (int cx = 0; cx < ncx; ++cx) {
@@ -632,32 +597,14 @@ static int vanka_create_per_cell_host(stfem_vanka *v, const double *Alpha, const
             Mr[size_t(a) * nloc + b] = ms;
           }
         }
-        for (int r = 0; r < nloc; ++r)
-          if (cn[r])
-            for (int q = 0; q < nloc; ++q)
-              if (q != r) {
-                Kr[size_t(r) * nloc + q] = Kr[size_t(q) * nloc + r] = 0.0;
-                Mr[size_t(r) * nloc + q] = Mr[size_t(q) * nloc + r] = 0.0;
-              }
-        for (int i = 0; i < nb; ++i)
-          for (int j = 0; j < nb; ++j)
-            for (int r = 0; r < nloc; ++r)
-              for (int q = 0; q < nloc; ++q)
-                B[size_t(i * nloc + r) * m + j * nloc + q] =
-                  val[r] * (Beta[i * nb + j] * Mr[size_t(r) * nloc + q] + Alpha[i * nb + j] * Kr[size_t(r) * nloc + q]);
-        if (!invert(m, B)) {
+        // from here on as for the class blocks: constraints, valence, Kronecker with Alpha / Beta, Gauss-Jordan
+        if (!blocks.add(cell, Kr, Mr, cn, val)) {
           snprintf(g_vanka_err, sizeof(g_vanka_err), "singular cell block (cell %zu)", cell);
           return STFEM_ERR_INVALID_ARGUMENT;
         }
-        for (int r = 0; r < m; ++r)
-          for (int k = 0; k < m; ++k) {
-            if (c->prec) out32[cell * bsz + size_t(k) * v->mpad + r] = float(B[size_t(r) * m + k]);
-            else out64[cell * bsz + size_t(k) * v->mpad + r] = B[size_t(r) * m + k];
-          }
       }
-  const void *hostp = c->prec ? static_cast<const void *>(out32.data()) : static_cast<const void *>(out64.data());
-  if (hipMalloc(&v->d_blocks, size_t(c->ncells) * bsz * c->es) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
-  if (hipMemcpy(v->d_blocks, hostp, size_t(c->ncells) * bsz * c->es, hipMemcpyHostToDevice) != hipSuccess) return STFEM_ERR_HIP;
+  rc = blocks.upload(v);
+  if (rc != STFEM_OK) return rc;
   v->nclasses = int(c->ncells);
   return vanka_per_cell_tables(v);
 }
@@ -669,10 +616,7 @@ static int vanka_create_per_cell_device(stfem_vanka *v, const double *Alpha, con
 {
   stfem_ctx *c = v->ctx;
   const int p = c->p, n = p + 1, nloc = v->nloc, m = v->m, nb = v->nb;
-  v->per_cell = true;
-  v->mt = (m + 15) / 16;
-  v->mpad = 16 * v->mt;
-  v->kpad = ((m + 3) / 4) * 4;
+  vanka_per_cell_shape(v);
   const size_t bsz = size_t(v->kpad) * v->mpad;
   const int ncx = c->nc[0], ncy = c->nc[1], ncz = c->nc[2];
   const size_t cpl = size_t(ncx) * ncy;
@@ -704,7 +648,8 @@ static int vanka_create_per_cell_device(stfem_vanka *v, const double *Alpha, con
   std::vector<double> tabs(2 * n * n);
   for (int i = 0; i < n * n; ++i) { tabs[i] = c->tab.S[i]; tabs[n * n + i] = c->tab.D[i]; }
   const size_t win_cells = cpl * size_t(std::min(ncz, L + 2));
-  if (hipMalloc(&v->d_blocks, size_t(c->ncells) * bsz * c->es) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
+  rc = vk_alloc(&v->d_blocks, size_t(c->ncells) * bsz * c->es, g_vanka_err);
+  if (rc != STFEM_OK) return rc;
   if (hipMalloc(&d_tab, tabs.size() * sizeof(double)) != hipSuccess || hipMalloc(&d_K, win_cells * nloc * nloc * sizeof(double)) != hipSuccess ||
       hipMalloc(&d_M, win_cells * nloc * nloc * sizeof(double)) != hipSuccess || hipMalloc(&d_B, cpl * L * size_t(m) * m * sizeof(double)) != hipSuccess ||
       hipMalloc(&d_flag, sizeof(int)) != hipSuccess) {
@@ -760,43 +705,17 @@ static int vanka_create_per_cell(stfem_vanka *v, const double *Alpha, const doub
   return (e && atoi(e) != 0) ? vanka_create_per_cell_host(v, Alpha, Beta) : vanka_create_per_cell_device(v, Alpha, Beta);
 }
 
-extern "C" {
-
-const char *stfem_vanka_last_error(void) { return g_vanka_err; }
-
-int stfem_vanka_create(stfem_ctx *c, int nb, const double *Alpha, const double *Beta, stfem_vanka **out)
+// Class variant: the block of every class from Kronecker products of restricted 1D matrices, inverted on the host in double
+static int build_class_blocks(stfem_vanka *v, const vanka::ClassTable &t, const double *Alpha, const double *Beta)
 {
-  return stfem_vanka_create_partitioned(c, nb, Alpha, Beta, 0, out);
-}
-
-int stfem_vanka_create_partitioned(stfem_ctx *c, int nb, const double *Alpha, const double *Beta, int neighbour_mask, stfem_vanka **out)
-{
-  if (!c || !Alpha || !Beta || !out || nb < 1 || nb > VK_MAX_BLOCKS || (neighbour_mask & ~63) || (neighbour_mask & c->dmask))
-    return STFEM_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  const int p = c->p, n = p + 1, nloc = n * n * n, m = nb * nloc;
-  if (m > VK_MAX_ROWS) return STFEM_ERR_UNSUPPORTED; // Q4 with more than 4 temporal blocks, Q5 with more than 2
-  VK_TRY(hipSetDevice(c->device));
-  stfem_vanka *v = new (std::nothrow) stfem_vanka;
-  if (!v) return STFEM_ERR_OUT_OF_MEMORY;
-  v->ctx = c; v->nb = nb; v->nloc = nloc; v->m = m;
-  // one block per neighbour pattern needs identical cells: axis-aligned uniform mesh, no coefficient tables;
-  // everything else gets one block per cell
-  if (!c->cartesian || c->coef_layout[0] != 0 || c->coef_layout[1] != 0) {
-    if (neighbour_mask) { // (the blocks of the interface cells need the cell matrices of the neighbour rank's cells)
-      delete v;
-      return STFEM_ERR_UNSUPPORTED;
-    }
-    int rc = vanka_create_per_cell(v, Alpha, Beta);
-    if (rc == STFEM_OK) rc = vanka_flat_per_cell(v);
-    if (rc != STFEM_OK) {
-      stfem_vanka_destroy(v);
-      return rc;
-    }
-    *out = v;
-    return STFEM_OK;
-  }
-
+  const stfem_ctx *c = v->ctx;
+  const int p = c->p, n = p + 1, nloc = v->nloc;
+  const vanka::TilePlan plan = vanka::scalar_tile_plan((v->m + 15) / 16, c->prec != 0);
+  if (plan.mtw == 0 || !vanka_kernel(c, plan.mtw)) return STFEM_ERR_UNSUPPORTED;
+  v->mtw = plan.mtw; v->parts = plan.parts; v->mt = plan.parts * plan.mtw;
+  v->mpad = 16 * v->mt;
+  v->kpad = ((v->m + KS - 1) / KS) * KS;
+  v->nclasses = int(t.key.size());
   // 1D nodal matrices of the reference cell: Mhat = S^T W S, Khat = D^T W D
   const stfem::ShapeTables &tab = c->tab;
   std::vector<double> Mh(n * n, 0.0), Kh(n * n, 0.0);
@@ -806,39 +725,11 @@ int stfem_vanka_create_partitioned(stfem_ctx *c, int nb, const double *Alpha, co
         Mh[a * n + b] += tab.wq[q] * tab.S[q * n + a] * tab.S[q * n + b];
         Kh[a * n + b] += tab.wq[q] * tab.D[q * n + a] * tab.D[q * n + b];
       }
-  // classes: per direction bit 0 = has a lower neighbour, bit 1 = has an upper neighbour - on this rank or, across a face of
-  // neighbour_mask, on the rank next to it (valence and assembled entries count those cells too; what they add to the shared
-  // DoFs arrives with the caller's add-exchange of the interface planes).  local_class: neighbours on this rank only - the
-  // first-touch rule of the scatter.
-  auto local_class = [&](int d, int cd) { return (cd > 0 ? 1 : 0) | (cd < c->nc[d] - 1 ? 2 : 0); };
-  auto dir_class = [&](int d, int cd) {
-    return local_class(d, cd) | ((cd == 0 && (neighbour_mask & (1 << (2 * d)))) ? 1 : 0) | ((cd == c->nc[d] - 1 && (neighbour_mask & (2 << (2 * d)))) ? 2 : 0);
-  };
-  std::map<int, int> class_id;
-  std::vector<int> class_key;
-  for (int cz = 0; cz < c->nc[2]; ++cz)
-    for (int cy = 0; cy < c->nc[1]; ++cy)
-      for (int cx = 0; cx < c->nc[0]; ++cx) {
-        const int key = dir_class(0, cx) | (dir_class(1, cy) << 2) | (dir_class(2, cz) << 4);
-        if (!class_id.count(key)) {
-          class_id[key] = int(class_key.size());
-          class_key.push_back(key);
-        }
-      }
-  v->nclasses = int(class_key.size());
-  {
-    vanka_plan(v, (m + 15) / 16);
-    if (v->mtw == 0) {
-      delete v;
-      return STFEM_ERR_UNSUPPORTED;
-    }
-    v->mpad = 16 * v->mt;
-    v->kpad = ((m + KS - 1) / KS) * KS;
-  }
-  const size_t bsz = size_t(v->kpad) * v->mpad;
-  std::vector<double> all(bsz * v->nclasses, 0.0);
+  VankaHostBlocks blocks(v, t.key.size(), Alpha, Beta);
+  std::vector<double> Kr(size_t(nloc) * nloc), Mr(size_t(nloc) * nloc), val(nloc);
+  std::vector<char> cn(nloc);
   for (int ci = 0; ci < v->nclasses; ++ci) {
-    const int key = class_key[ci];
+    const int key = t.key[ci];
     // restricted assembled 1D matrices: the end nodes also carry the neighbour's diagonal entry
     std::vector<double> M1[3], K1[3];
     bool con[3][8], shared[3][8];
@@ -858,8 +749,6 @@ int stfem_vanka_create_partitioned(stfem_ctx *c, int nb, const double *Alpha, co
         con[d][a] = (a == 0 && !(k & 1) && (c->dmask & (1 << (2 * d)))) || (a == p && !(k & 2) && (c->dmask & (2 << (2 * d))));
       }
     }
-    std::vector<double> Kr(size_t(nloc) * nloc), Mr(size_t(nloc) * nloc), val(nloc);
-    std::vector<char> cn(nloc);
     for (int kz = 0; kz < n; ++kz)
       for (int jy = 0; jy < n; ++jy)
         for (int ix = 0; ix < n; ++ix) {
@@ -876,106 +765,70 @@ int stfem_vanka_create_partitioned(stfem_ctx *c, int nb, const double *Alpha, co
                 Kr[size_t(r) * nloc + s] = mz * my * kx + mz * ky * mx + kz1 * my * mx;
               }
         }
-    // zero-boundary constraints: row and column dropped, the diagonal of the unconstrained assembly stays
-    for (int r = 0; r < nloc; ++r)
-      if (cn[r])
-        for (int s = 0; s < nloc; ++s)
-          if (s != r) {
-            Kr[size_t(r) * nloc + s] = Kr[size_t(s) * nloc + r] = 0.0;
-            Mr[size_t(r) * nloc + s] = Mr[size_t(s) * nloc + r] = 0.0;
-          }
-    std::vector<double> B(size_t(m) * m);
-    for (int i = 0; i < nb; ++i)
-      for (int j = 0; j < nb; ++j)
-        for (int r = 0; r < nloc; ++r)
-          for (int s = 0; s < nloc; ++s)
-            B[size_t(i * nloc + r) * m + j * nloc + s] =
-              val[r] * (Beta[i * nb + j] * Mr[size_t(r) * nloc + s] + Alpha[i * nb + j] * Kr[size_t(r) * nloc + s]);
-    if (!invert(m, B)) {
+    if (!blocks.add(ci, Kr, Mr, cn, val)) {
       snprintf(g_vanka_err, sizeof(g_vanka_err), "singular cell block (class %d)", key);
-      delete v;
       return STFEM_ERR_INVALID_ARGUMENT;
     }
-    double *dstb = all.data() + bsz * ci;
-    for (int r = 0; r < m; ++r)
-      for (int k = 0; k < m; ++k) dstb[size_t(k) * v->mpad + r] = B[size_t(r) * m + k];
   }
-  // upload in the context's Number type
-  if (c->prec) {
-    std::vector<float> f(all.size());
-    for (size_t i = 0; i < all.size(); ++i) f[i] = float(all[i]);
-    if (hipMalloc(&v->d_blocks, f.size() * sizeof(float)) != hipSuccess) { delete v; return STFEM_ERR_OUT_OF_MEMORY; }
-    if (hipMemcpy(v->d_blocks, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { stfem_vanka_destroy(v); return STFEM_ERR_HIP; }
+  return blocks.upload(v);
+}
+
+// Class variant: DoF offsets and the cell lists of the eight colour launches and, on small meshes, of the two-phase apply
+static int build_cell_lists(stfem_vanka *v, const vanka::ClassTable &t)
+{
+  const stfem_ctx *c = v->ctx;
+  const int p = c->p;
+  std::vector<int> first(size_t(c->ncells)); // first DoF of every cell
+  for (int cz = 0; cz < c->nc[2]; ++cz)
+    for (int cy = 0; cy < c->nc[1]; ++cy)
+      for (int cx = 0; cx < c->nc[0]; ++cx) first[cx + c->nc[0] * (cy + c->nc[1] * cz)] = p * cx + c->nd[0] * (p * cy + c->nd[1] * p * cz);
+  int rc = vanka_offset_table(v);
+  v->flat = vanka_wants_flat(c);
+  for (int l = 0; l <= (v->flat ? VK_FLAT : 7) && rc == STFEM_OK; ++l) {
+    const vanka::CellList list = vanka::cell_list(t, l == VK_FLAT ? -1 : l);
+    v->ngrid[l] = int(list.cls.size());
+    if (list.cls.empty()) continue;
+    rc = vk_upload(&v->d_cell[l], vanka::gather_cells(list.order, first, -1), g_vanka_err);
+    if (rc == STFEM_OK) rc = vk_upload(&v->d_cls[l], list.cls, g_vanka_err);
+    if (l != VK_FLAT) continue; // cell -> slot for the second phase, and the rows between the two
+    if (rc == STFEM_OK) rc = vk_upload(&v->d_slot, list.slot, g_vanka_err);
+    if (rc == STFEM_OK) rc = vk_alloc(&v->d_flat, list.order.size() * v->mpad * c->es, g_vanka_err);
+  }
+  return rc;
+}
+
+extern "C" {
+
+const char *stfem_vanka_last_error(void) { return g_vanka_err; }
+
+int stfem_vanka_create(stfem_ctx *c, int nb, const double *Alpha, const double *Beta, stfem_vanka **out)
+{
+  return stfem_vanka_create_partitioned(c, nb, Alpha, Beta, 0, out);
+}
+
+int stfem_vanka_create_partitioned(stfem_ctx *c, int nb, const double *Alpha, const double *Beta, int neighbour_mask, stfem_vanka **out)
+{
+  if (!c || !Alpha || !Beta || !out || nb < 1 || nb > VK_MAX_BLOCKS || (neighbour_mask & ~63) || (neighbour_mask & c->dmask))
+    return STFEM_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  const int n = c->p + 1;
+  if (nb * n * n * n > VK_MAX_ROWS) return STFEM_ERR_UNSUPPORTED; // Q4 with more than 4 temporal blocks, Q5 with more than 2
+  VK_TRY(hipSetDevice(c->device));
+  VankaPtr v = vanka_new(c, nb);
+  if (!v) return STFEM_ERR_OUT_OF_MEMORY;
+  int rc;
+  // one block per neighbour pattern needs identical cells: axis-aligned uniform mesh, no coefficient tables;
+  // everything else gets one block per cell
+  if (!c->cartesian || c->coef_layout[0] != 0 || c->coef_layout[1] != 0) {
+    if (neighbour_mask) return STFEM_ERR_UNSUPPORTED; // (the blocks of the interface cells need the cell matrices of the neighbour rank's cells)
+    rc = vanka_create_per_cell(v.get(), Alpha, Beta);
   } else {
-    if (hipMalloc(&v->d_blocks, all.size() * sizeof(double)) != hipSuccess) { delete v; return STFEM_ERR_OUT_OF_MEMORY; }
-    if (hipMemcpy(v->d_blocks, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { stfem_vanka_destroy(v); return STFEM_ERR_HIP; }
+    const vanka::ClassTable t = vanka::class_table(c->nc, neighbour_mask);
+    rc = build_class_blocks(v.get(), t, Alpha, Beta);
+    if (rc == STFEM_OK) rc = build_cell_lists(v.get(), t);
   }
-  std::vector<int> off(nloc);
-  for (int kz = 0; kz < n; ++kz)
-    for (int jy = 0; jy < n; ++jy)
-      for (int ix = 0; ix < n; ++ix) off[ix + n * (jy + n * kz)] = ix + c->nd[0] * (jy + c->nd[1] * kz);
-  if (hipMalloc(&v->d_off, nloc * sizeof(int)) != hipSuccess ||
-      hipMemcpy(v->d_off, off.data(), nloc * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-    stfem_vanka_destroy(v);
-    return STFEM_ERR_HIP;
-  }
-  // cell lists: per colour, grouped by class into batches of 16 cells, four batches of one class per workgroup
-  for (int colour = 0; colour < 8; ++colour) {
-    std::map<std::pair<int, int>, std::vector<int>> by_class; // (block class, local neighbour pattern) -> cells
-    for (int cz = colour >> 2; cz < c->nc[2]; cz += 2)
-      for (int cy = (colour >> 1) & 1; cy < c->nc[1]; cy += 2)
-        for (int cx = colour & 1; cx < c->nc[0]; cx += 2) {
-          const int key = dir_class(0, cx) | (dir_class(1, cy) << 2) | (dir_class(2, cz) << 4);
-          const int local = local_class(0, cx) | (local_class(1, cy) << 2) | (local_class(2, cz) << 4);
-          by_class[{class_id[key], local}].push_back(p * cx + c->nd[0] * (p * cy + c->nd[1] * p * cz));
-        }
-    std::vector<int> cells, cls;
-    for (auto &kv : by_class) {
-      std::vector<int> &l = kv.second;
-      l.resize(((l.size() + 63) / 64) * 64, -1);
-      for (size_t q = 0; q < l.size() / 64; ++q) cls.push_back(kv.first.first | (kv.first.second << 8));
-      cells.insert(cells.end(), l.begin(), l.end());
-    }
-    v->nquad[colour] = int(cls.size());
-    if (cls.empty()) continue;
-    if (hipMalloc(&v->d_cell[colour], cells.size() * sizeof(int)) != hipSuccess ||
-        hipMalloc(&v->d_cls[colour], cls.size() * sizeof(int)) != hipSuccess ||
-        hipMemcpy(v->d_cell[colour], cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(v->d_cls[colour], cls.data(), cls.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-      stfem_vanka_destroy(v);
-      return STFEM_ERR_HIP;
-    }
-  }
-  if (vanka_wants_flat(c)) { // two-phase apply: all cells in one launch, grouped by class; cell -> slot for the second phase
-    std::map<int, std::vector<std::pair<int, int>>> by_class; // class -> (first DoF, cell number)
-    for (int cz = 0; cz < c->nc[2]; ++cz)
-      for (int cy = 0; cy < c->nc[1]; ++cy)
-        for (int cx = 0; cx < c->nc[0]; ++cx) {
-          const int key = dir_class(0, cx) | (dir_class(1, cy) << 2) | (dir_class(2, cz) << 4);
-          by_class[class_id[key]].push_back({p * cx + c->nd[0] * (p * cy + c->nd[1] * p * cz), cx + c->nc[0] * (cy + c->nc[1] * cz)});
-        }
-    std::vector<int> cells, cls, slot(size_t(c->ncells), 0);
-    for (auto &kv : by_class) {
-      for (const auto &e : kv.second) {
-        slot[e.second] = int(cells.size());
-        cells.push_back(e.first);
-      }
-      cells.resize(((cells.size() + 63) / 64) * 64, -1);
-      while (cls.size() < cells.size() / 64) cls.push_back(kv.first);
-    }
-    v->nquad_all = int(cls.size());
-    if (hipMalloc(&v->d_cell_all, cells.size() * sizeof(int)) != hipSuccess || hipMalloc(&v->d_cls_all, cls.size() * sizeof(int)) != hipSuccess ||
-        hipMalloc(&v->d_slot, slot.size() * sizeof(int)) != hipSuccess || hipMalloc(&v->d_flat, cells.size() * v->mpad * c->es) != hipSuccess ||
-        hipMemcpy(v->d_cell_all, cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(v->d_cls_all, cls.data(), cls.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(v->d_slot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-      stfem_vanka_destroy(v);
-      return STFEM_ERR_HIP;
-    }
-    v->flat = true;
-  }
-  *out = v;
-  return STFEM_OK;
+  if (rc == STFEM_OK) *out = v.release();
+  return rc;
 }
 
 // One block per cell on a z-slab of a partitioned GENERAL mesh (perturbed cells, coefficient tables: BASELINE configs[2] on more
@@ -999,19 +852,14 @@ int stfem_vanka_create_partitioned_general(stfem_ctx *slab, stfem_ctx *extended,
   if ((extended->dmask & 15) != (slab->dmask & 15) || (glo && (extended->dmask & 16)) || (ghi && (extended->dmask & 32)) ||
       (!glo && (extended->dmask & 16) != (slab->dmask & 16)) || (!ghi && (extended->dmask & 32) != (slab->dmask & 32)))
     return STFEM_ERR_INVALID_ARGUMENT;
-  stfem_vanka *ve = nullptr;
-  int rc = stfem_vanka_create_partitioned(extended, nb, Alpha, Beta, 0, &ve);
+  stfem_vanka *built = nullptr;
+  int rc = stfem_vanka_create_partitioned(extended, nb, Alpha, Beta, 0, &built);
   if (rc != STFEM_OK) return rc;
-  if (!ve->per_cell) { // an axis-aligned uniform mesh: the class variant handles the partition by itself
-    stfem_vanka_destroy(ve);
+  VankaPtr ve(built, stfem_vanka_destroy);
+  if (!ve->per_cell) // an axis-aligned uniform mesh: the class variant handles the partition by itself
     return stfem_vanka_create_partitioned(slab, nb, Alpha, Beta, neighbour_mask, out);
-  }
-  stfem_vanka *v = new (std::nothrow) stfem_vanka;
-  if (!v) {
-    stfem_vanka_destroy(ve);
-    return STFEM_ERR_OUT_OF_MEMORY;
-  }
-  v->ctx = slab; v->nb = ve->nb; v->nloc = ve->nloc; v->m = ve->m;
+  VankaPtr v = vanka_new(slab, nb);
+  if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   v->mt = ve->mt; v->mtw = ve->mtw; v->parts = ve->parts; v->mpad = ve->mpad; v->kpad = ve->kpad;
   v->per_cell = true;
   v->nclasses = int(slab->ncells);
@@ -1020,32 +868,24 @@ int stfem_vanka_create_partitioned_general(stfem_ctx *slab, stfem_ctx *extended,
   ve->d_blocks = nullptr;
   const size_t bsz = size_t(v->kpad) * v->mpad;
   v->d_blocks = static_cast<char *>(v->d_blocks_base) + size_t(glo) * size_t(slab->nc[0]) * slab->nc[1] * bsz * slab->es;
-  stfem_vanka_destroy(ve);
+  ve.reset();
   VK_TRY(hipSetDevice(slab->device));
-  rc = vanka_per_cell_tables(v);
-  if (rc == STFEM_OK) rc = vanka_flat_per_cell(v);
-  if (rc != STFEM_OK) {
-    stfem_vanka_destroy(v);
-    return rc;
-  }
-  *out = v;
-  return STFEM_OK;
+  rc = vanka_per_cell_tables(v.get());
+  if (rc == STFEM_OK) *out = v.release();
+  return rc;
 }
 
 void stfem_vanka_destroy(stfem_vanka *v)
 {
   if (!v) return;
   (void)hipSetDevice(v->ctx->device);
-  if (v->d_blocks_base) (void)hipFree(v->d_blocks_base);
-  else if (v->d_blocks) (void)hipFree(v->d_blocks);
-  if (v->d_off) (void)hipFree(v->d_off);
-  if (v->d_flat) (void)hipFree(v->d_flat);
-  if (v->d_cell_all) (void)hipFree(v->d_cell_all);
-  if (v->d_cls_all) (void)hipFree(v->d_cls_all);
-  if (v->d_slot) (void)hipFree(v->d_slot);
-  for (int i = 0; i < 8; ++i) {
-    if (v->d_cell[i]) (void)hipFree(v->d_cell[i]);
-    if (v->d_cls[i]) (void)hipFree(v->d_cls[i]);
+  (void)hipFree(v->d_blocks_base ? v->d_blocks_base : v->d_blocks);
+  (void)hipFree(v->d_off);
+  (void)hipFree(v->d_flat);
+  (void)hipFree(v->d_slot);
+  for (int l = 0; l <= VK_FLAT; ++l) {
+    (void)hipFree(v->d_cell[l]);
+    (void)hipFree(v->d_cls[l]);
   }
   delete v;
 }
@@ -1076,77 +916,36 @@ int stfem_vanka_step(stfem_vanka *v, stfem_vec *dst, double omega, int accumulat
   stfem_ctx *c = v->ctx;
   VK_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // dst = 0 (stmg.h:836) is not a pass of its own: the first cell to touch a DoF stores (every DoF has one)
-  if (v->per_cell) {
-    VankaCellParams cp;
-    std::memset(&cp, 0, sizeof(cp));
-    for (int i = 0; i < v->nb; ++i) {
-      cp.src[i] = src->blk[i];
-      cp.dst[i] = dst->blk[i];
-    }
-    cp.blocks = v->d_blocks;
-    cp.off = v->d_off;
-    cp.m = v->m; cp.mpad = v->mpad; cp.kpad = v->kpad; cp.nloc = v->nloc; cp.p = c->p;
-    cp.ncx = c->nc[0]; cp.ncy = c->nc[1]; cp.ncz = c->nc[2]; cp.nx = c->nd[0]; cp.ny = c->nd[1];
-    cp.omega = omega; cp.accumulate = accumulate;
-    (void)hipGetLastError();
-    if (v->flat) {
-      cp.flat = v->d_flat;
-      if (c->prec) hipLaunchKernelGGL(vanka_apply_percell_kernel<float>, dim3((unsigned)c->ncells), dim3(256), 0, st, cp);
-      else hipLaunchKernelGGL(vanka_apply_percell_kernel<double>, dim3((unsigned)c->ncells), dim3(256), 0, st, cp);
-      return vanka_collect(v, dst, omega, accumulate, st);
-    }
-    for (int colour = 0; colour < 8; ++colour) {
-      if (v->ncol[colour] == 0) continue;
-      cp.cell = v->d_cell[colour];
-      cp.colour = colour;
-      if (c->prec) hipLaunchKernelGGL(vanka_apply_percell_kernel<float>, dim3(v->ncol[colour]), dim3(256), 0, st, cp);
-      else hipLaunchKernelGGL(vanka_apply_percell_kernel<double>, dim3(v->ncol[colour]), dim3(256), 0, st, cp);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) {
-        snprintf(g_vanka_err, sizeof(g_vanka_err), "vanka_apply_percell_kernel: %s", hipGetErrorString(e));
-        return STFEM_ERR_HIP;
-      }
-    }
-    return STFEM_OK;
-  }
+  // the parameters of both kernels; a launch changes the cell list and the colour only
   VankaParams prm;
+  VankaCellParams cp;
   std::memset(&prm, 0, sizeof(prm));
+  std::memset(&cp, 0, sizeof(cp));
   for (int i = 0; i < v->nb; ++i) {
-    prm.src[i] = src->blk[i];
-    prm.dst[i] = dst->blk[i];
+    prm.src[i] = cp.src[i] = src->blk[i];
+    prm.dst[i] = cp.dst[i] = dst->blk[i];
   }
-  prm.blocks = v->d_blocks;
-  prm.off = v->d_off;
-  prm.m = v->m; prm.mpad = v->mpad; prm.kpad = v->kpad;
-  prm.p = c->p;
-  prm.omega = omega; prm.accumulate = accumulate;
+  prm.blocks = cp.blocks = v->d_blocks;
+  prm.off = cp.off = v->d_off;
+  prm.m = cp.m = v->m; prm.mpad = cp.mpad = v->mpad; prm.kpad = cp.kpad = v->kpad; prm.p = cp.p = c->p;
+  cp.nloc = v->nloc; cp.ncx = c->nc[0]; cp.ncy = c->nc[1]; cp.ncz = c->nc[2]; cp.nx = c->nd[0]; cp.ny = c->nd[1];
+  prm.flat = cp.flat = v->flat ? v->d_flat : nullptr;
+  prm.omega = cp.omega = omega; prm.accumulate = cp.accumulate = accumulate;
+  const void *kernel = v->per_cell ? VK_TYPED(c, vanka_apply_percell_kernel) : vanka_kernel(c, v->mtw);
+  if (!kernel) return STFEM_ERR_UNSUPPORTED;
   (void)hipGetLastError();
-  if (v->flat) {
-    prm.cell = v->d_cell_all;
-    prm.cls = v->d_cls_all;
-    prm.nquad = v->nquad_all;
-    prm.flat = v->d_flat;
-    const int rc = vanka_launch(v, prm, prm.nquad, st);
-    if (rc != STFEM_OK) {
-      snprintf(g_vanka_err, sizeof(g_vanka_err), "vanka_apply_kernel: %s", hipGetErrorString(hipGetLastError()));
-      return rc;
-    }
-    return vanka_collect(v, dst, omega, accumulate, st);
+  // dst = 0 (stmg.h:836) is not a pass of its own: the first cell to touch a DoF stores (every DoF has one)
+  for (int l = v->flat ? VK_FLAT : 0; l <= (v->flat ? VK_FLAT : 7); ++l) {
+    if (v->ngrid[l] == 0) continue;
+    prm.cell = cp.cell = v->d_cell[l];
+    prm.cls = v->d_cls[l];
+    prm.nquad = v->ngrid[l];
+    prm.colour = cp.colour = l & 7;
+    const int rc = v->per_cell ? vk_launch(kernel, dim3(v->ngrid[l]), &cp, st, "vanka_apply_percell_kernel", g_vanka_err)
+                               : vk_launch(kernel, dim3(v->ngrid[l], v->parts), &prm, st, "vanka_apply_kernel", g_vanka_err);
+    if (rc != STFEM_OK) return rc;
   }
-  for (int colour = 0; colour < 8; ++colour) {
-    if (v->nquad[colour] == 0) continue;
-    prm.cell = v->d_cell[colour];
-    prm.cls = v->d_cls[colour];
-    prm.nquad = v->nquad[colour];
-    prm.colour = colour;
-    const int rc = vanka_launch(v, prm, prm.nquad, st);
-    if (rc != STFEM_OK) {
-      snprintf(g_vanka_err, sizeof(g_vanka_err), "vanka_apply_kernel: %s", hipGetErrorString(hipGetLastError()));
-      return rc;
-    }
-  }
-  return STFEM_OK;
+  return v->flat ? vanka_collect(v, dst, omega, accumulate, st) : STFEM_OK;
 }
 
 } // extern "C"

@@ -1,7 +1,13 @@
 // The class-block apply kernel of the cell-patch smoothers (stfem_vanka.hip: scalar systems; stfem_stokes_vanka.hip: the
-// two-variable Stokes system), shared by the two translation units.  Not part of the boundary.
+// two-variable Stokes system), shared by the two translation units, with their device helpers: uploads, launches and the
+// node -> cells rule of the collecting kernels.  Not part of the boundary.
 #pragma once
+#include "../../include/stfem.h"
+
 #include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <vector>
 
 namespace {
 
@@ -28,6 +34,53 @@ struct VankaParams {
   const int2 *rowtab;
   const int *cell2;
 };
+
+// ---- host helpers: a failure leaves its reason in the caller's last-error string `err` ----
+inline int vk_alloc(void **dev, size_t bytes, char (&err)[256])
+{
+  if (hipMalloc(dev, bytes) == hipSuccess) return STFEM_OK;
+  (void)hipGetLastError();
+  snprintf(err, sizeof(err), "device allocation of %zu bytes failed", bytes);
+  return STFEM_ERR_OUT_OF_MEMORY;
+}
+// a new device allocation holding a copy of host
+template <typename D, typename T> int vk_upload(D **dev, const std::vector<T> &host, char (&err)[256])
+{
+  const size_t bytes = host.size() * sizeof(T);
+  const int rc = vk_alloc(reinterpret_cast<void **>(dev), bytes, err);
+  if (rc != STFEM_OK) return rc;
+  const hipError_t e = hipMemcpy(*dev, host.data(), bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) return STFEM_OK;
+  snprintf(err, sizeof(err), "upload of %zu bytes: %s", bytes, hipGetErrorString(e));
+  return STFEM_ERR_HIP;
+}
+// one launch of 256-thread workgroups with the parameter struct prm
+inline int vk_launch(const void *kernel, dim3 grid, void *prm, hipStream_t st, const char *name, char (&err)[256])
+{
+  void *args[] = {prm};
+  const hipError_t e = hipLaunchKernel(kernel, grid, dim3(256), args, 0, st); // (returns what a launch statement leaves to hipGetLastError)
+  if (e == hipSuccess) return STFEM_OK;
+  snprintf(err, sizeof(err), "%s: %s", name, hipGetErrorString(e));
+  (void)hipGetLastError();
+  return STFEM_ERR_HIP;
+}
+
+// The cells holding node idx of a Q_p mesh of nc cells and its local index there, per direction (a vertex node: the cell below
+// with index p, then the cell above with 0).  The collecting kernels sum over cc[2] x cc[1] x cc[0] in this order.
+__device__ __forceinline__ void node_cells(const int idx[3], int p, const int nc[3], int (&cc)[3][2], int (&ll)[3][2], int (&cnt)[3])
+{
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const int c0 = idx[d] / p, l0 = idx[d] - c0 * p;
+    cnt[d] = 0;
+    if (l0 == 0) {
+      if (c0 > 0) { cc[d][cnt[d]] = c0 - 1; ll[d][cnt[d]] = p; ++cnt[d]; }
+      if (c0 < nc[d]) { cc[d][cnt[d]] = c0; ll[d][cnt[d]] = 0; ++cnt[d]; }
+    } else {
+      cc[d][0] = c0; ll[d][0] = l0; cnt[d] = 1;
+    }
+  }
+}
 
 template <typename T> struct Mfma;
 template <> struct Mfma<double> {

@@ -972,13 +972,15 @@ template <typename T>
 static int tensorproduct_add_t(stfem_ctx *c, int nrows, int ncols, const double *A, stfem_vec *cv, const stfem_vec *b,
                                hipStream_t st)
 {
+  for (int i = 0; i < nrows; ++i) // a refused call modifies nothing: every row is checked before the first launch
+    for (int j = 0; j < ncols; ++j)
+      if (A[size_t(i) * ncols + j] != 0.0 && cv->blk[i] == b->blk[j]) return STFEM_ERR_ALIAS;
   for (int i = 0; i < nrows; ++i)
     for (int j0 = 0; j0 < ncols; j0 += MAX_BLOCKS) {
       AxpyArgs<T> a;
       a.n = 0;
       for (int j = j0; j < std::min(ncols, j0 + MAX_BLOCKS); ++j)
         if (A[size_t(i) * ncols + j] != 0.0) { // operators.h:246
-          if (cv->blk[i] == b->blk[j]) return STFEM_ERR_ALIAS;
           a.x[a.n] = static_cast<const T *>(b->blk[j]);
           a.coef[a.n++] = T(A[size_t(i) * ncols + j]);
         }
@@ -994,7 +996,7 @@ static int tensorproduct_add_t(stfem_ctx *c, int nrows, int ncols, const double 
 int stfem_tensorproduct_add(stfem_ctx *c, int nrows, int ncols, const double *A, stfem_vec *cv,
                             const stfem_vec *b, void *stream)
 {
-  if (!c || !A || !cv || !b) return STFEM_ERR_INVALID_ARGUMENT;
+  if (!c || !A || !cv || !b || cv->ctx != c || b->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   if (cv->nb != nrows || b->nb != ncols) return STFEM_ERR_SHAPE_MISMATCH;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1087,6 +1089,8 @@ template <typename T> __global__ __launch_bounds__(256) void multi_axpy_kernel(i
 static int multi_dot_device(stfem_ctx *c, int k, const stfem_vec *const *as, const stfem_vec *b, int64_t n_own, double *d_out, hipStream_t st)
 {
   if (b->nb > MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
+  for (int i = 0; i < k; ++i)
+    if (!as[i] || as[i]->nb != b->nb || as[i]->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   const int grid = (int)std::min<int64_t>((n_own + 255) / 256, DOT_GRID);
   double *partial = c->d_scratch + 256; // [DOT_VECS][DOT_GRID]
   (void)hipGetLastError();
@@ -1096,10 +1100,8 @@ static int multi_dot_device(stfem_ctx *c, int k, const stfem_vec *const *as, con
     args.nvec = std::min(DOT_VECS, k - k0);
     args.nblk = b->nb;
     for (int j = 0; j < b->nb; ++j) args.b[j] = b->blk[j];
-    for (int v = 0; v < args.nvec; ++v) {
-      if (!as[k0 + v] || as[k0 + v]->nb != b->nb || as[k0 + v]->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
+    for (int v = 0; v < args.nvec; ++v)
       for (int j = 0; j < b->nb; ++j) args.a[v][j] = as[k0 + v]->blk[j];
-    }
     if (c->prec) hipLaunchKernelGGL(multi_dot_kernel<float>, dim3(grid), dim3(256), 0, st, n_own, args, partial);
     else hipLaunchKernelGGL(multi_dot_kernel<double>, dim3(grid), dim3(256), 0, st, n_own, args, partial);
     hipLaunchKernelGGL(dot_finish_kernel, dim3(1), dim3(256), 0, st, args.nvec, grid, partial, d_out + k0);
@@ -1111,7 +1113,7 @@ static int multi_dot_device(stfem_ctx *c, int k, const stfem_vec *const *as, con
 
 int stfem_dot(stfem_ctx *c, const stfem_vec *a, const stfem_vec *b, int64_t n_own, double *out, void *stream)
 {
-  if (!c || !a || !b || !out || a->nb != b->nb) return STFEM_ERR_INVALID_ARGUMENT;
+  if (!c || !a || !b || !out || a->nb != b->nb || a->ctx != c || b->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   if (n_own <= 0 || n_own > c->ndofs) n_own = c->ndofs;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1155,6 +1157,8 @@ int stfem_multi_axpy(stfem_ctx *c, int k, const double *coef, const stfem_vec *c
 {
   if (!c || !coef || !xs || !y || k < 1 || y->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   if (y->nb > MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
+  for (int i = 0; i < k; ++i) // a refused call modifies nothing: every vector is checked before the first launch
+    if (!xs[i] || xs[i]->nb != y->nb || xs[i]->ctx != c || xs[i] == y) return STFEM_ERR_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = (unsigned)std::min<int64_t>((c->ndofs + 255) / 256, 2048);
@@ -1166,7 +1170,6 @@ int stfem_multi_axpy(stfem_ctx *c, int k, const double *coef, const stfem_vec *c
     args.sign = 1.0;
     for (int j = 0; j < y->nb; ++j) args.y[j] = y->blk[j];
     for (int v = 0; v < args.nvec; ++v) {
-      if (!xs[k0 + v] || xs[k0 + v]->nb != y->nb || xs[k0 + v]->ctx != c || xs[k0 + v] == y) return STFEM_ERR_INVALID_ARGUMENT;
       args.coef[v] = coef[k0 + v];
       for (int j = 0; j < y->nb; ++j) args.x[v][j] = xs[k0 + v]->blk[j];
     }
@@ -1183,6 +1186,10 @@ int stfem_orthogonalize(stfem_ctx *c, int k, const stfem_vec *const *vs, stfem_v
 {
   if (!c || !vs || !w || !h_out || k < 1 || k > 256 - 9 || w->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   if (w->nb > MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
+  for (int i = 0; i < k; ++i) { // a refused call modifies nothing: every vector is checked before the first launch
+    if (!vs[i] || vs[i]->nb != w->nb || vs[i]->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
+    if (vs[i] == w) return STFEM_ERR_ALIAS;
+  }
   if (n_own <= 0 || n_own > c->ndofs) n_own = c->ndofs;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1199,10 +1206,8 @@ int stfem_orthogonalize(stfem_ctx *c, int k, const stfem_vec *const *vs, stfem_v
     args.sign = -1.0;
     args.dcoef = c->d_scratch + k0;
     for (int j = 0; j < w->nb; ++j) args.y[j] = w->blk[j];
-    for (int v = 0; v < args.nvec; ++v) {
-      if (vs[k0 + v] == w) return STFEM_ERR_ALIAS;
+    for (int v = 0; v < args.nvec; ++v)
       for (int j = 0; j < w->nb; ++j) args.x[v][j] = vs[k0 + v]->blk[j];
-    }
     if (c->prec) hipLaunchKernelGGL(multi_axpy_kernel<float>, dim3(grid, w->nb), dim3(256), 0, st, c->ndofs, args);
     else hipLaunchKernelGGL(multi_axpy_kernel<double>, dim3(grid, w->nb), dim3(256), 0, st, c->ndofs, args);
   }

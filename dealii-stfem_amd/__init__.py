@@ -166,6 +166,11 @@ SIGNATURES = {
                                         C.POINTER(_vp), _vp]),
     "stfem_stokes_st_vmult_slice_add": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(_vp),
                                                   _vp, _vp, _vp]),
+    "stfem_stokes_vmult_convection": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "stfem_stokes_st_vmult_convection": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(_vp),
+                                                   C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    "stfem_stokes_st_vmult_slice_add_convection": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(_vp),
+                                                             _vp, _vp, _vp, _vp]),
     "stfem_stokes_last_hip_error": (C.c_char_p, []),
     "stfem_stokes_set_weak_boundaries": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double]),
     "stfem_stokes_n_face_points": (C.c_int64, [_vp]),
@@ -750,10 +755,17 @@ def get_fe_time_weights_stokes(type_, r, time_step_size, n_timesteps_at_once=1):
     return Alpha, Beta, Gamma, Zeta
 
 
+# The Navier-Stokes modes of StokesMatrixFreeOperator (OperatorMode::form / jacobian, operators.h:1288-1297): the `mode` of vmult,
+# st_vmult and st_vmult_slice_add; 0 is the linear operator
+CONVECTION_NONE, CONVECTION_FORM, CONVECTION_JACOBIAN = 0, 1, 2
+
+
 class StokesMatrixFreeOperator:
     """StokesMatrixFreeOperator + SystemMatrixStokes of the reference (include/operators.h:1193-1575,
     666-868) for the cell loop, FE_Q(2)^3 x FE_Q(1).  Vectors are device pointers (e.g.
-    torch.Tensor.data_ptr()): velocity 3 * n_velocity doubles (component-major), pressure n_pressure."""
+    torch.Tensor.data_ptr()): velocity 3 * n_velocity doubles (component-major), pressure n_pressure.
+    vmult / st_vmult / st_vmult_slice_add take the convection mode (CONVECTION_FORM / CONVECTION_JACOBIAN) and the linearisation
+    velocity `lin` that the reference's set_data hands in; with the defaults they are the linear operator."""
 
     def __init__(self, ncell, vertices=None, lower=(0, 0, 0), upper=(1, 1, 1), dirichlet_mask=63,
                  viscosity=1.0, velocity_degree=2, device=0, weak_boundary_ids=(), outflow_boundary_ids=(),
@@ -806,24 +818,35 @@ class StokesMatrixFreeOperator:
         """Device vector of `variable` (0 velocity, 1 pressure) as a StokesVector; optionally filled."""
         return StokesVector(self, variable, host)
 
-    def vmult(self, dst_u, dst_p, src_u, src_p, stream=None):
+    def vmult(self, dst_u, dst_p, src_u, src_p, stream=None, lin=None, mode=0):
         dst_u, dst_p, src_u, src_p = (getattr(v, "ptr", v) for v in (dst_u, dst_p, src_u, src_p))
-        _check(lib().stfem_stokes_vmult(self._h, dst_u, dst_p, src_u, src_p, stream), "stfem_stokes_vmult")
+        if mode == 0 and lin is None:
+            _check(lib().stfem_stokes_vmult(self._h, dst_u, dst_p, src_u, src_p, stream), "stfem_stokes_vmult")
+            return
+        _check(lib().stfem_stokes_vmult_convection(self._h, int(mode), dst_u, dst_p, src_u, src_p, getattr(lin, "ptr", lin), stream),
+               "stfem_stokes_vmult_convection")
 
     def mass_vmult(self, dst_u, src_u, stream=None):
         dst_u, src_u = getattr(dst_u, "ptr", dst_u), getattr(src_u, "ptr", src_u)
         _check(lib().stfem_stokes_mass_vmult(self._h, dst_u, src_u, stream), "stfem_stokes_mass_vmult")
 
     def st_vmult(self, Alpha, Beta, n_timesteps_at_once, n_timedofs, dst_blocks, src_blocks,
-                 variable_major=True, stream=None):
-        """SystemMatrixStokes::vmult; dst_blocks / src_blocks: device pointers in BlockSlice order."""
+                 variable_major=True, stream=None, lin=None, mode=0):
+        """SystemMatrixStokes::vmult; dst_blocks / src_blocks: device pointers in BlockSlice order.  lin: the linearisation vector in
+        the same order (only its velocity entries are read; pressure entries may be None)."""
         nb = 2 * n_timesteps_at_once * n_timedofs
         A = np.ascontiguousarray(Alpha, dtype=np.float64); B = np.ascontiguousarray(Beta, dtype=np.float64)
         assert A.shape == (nb, nb) and B.shape == (nb, nb) and len(dst_blocks) == nb and len(src_blocks) == nb
         d = (_vp * nb)(*[getattr(v, "ptr", v) for v in dst_blocks])
         s_ = (_vp * nb)(*[getattr(v, "ptr", v) for v in src_blocks])
-        _check(lib().stfem_stokes_st_vmult(self._h, n_timesteps_at_once, n_timedofs, int(variable_major),
-                                           _p(A), _p(B), d, s_, stream), "stfem_stokes_st_vmult")
+        if mode == 0 and lin is None:
+            _check(lib().stfem_stokes_st_vmult(self._h, n_timesteps_at_once, n_timedofs, int(variable_major),
+                                               _p(A), _p(B), d, s_, stream), "stfem_stokes_st_vmult")
+            return
+        assert lin is None or len(lin) == nb
+        l_ = None if lin is None else (_vp * nb)(*[getattr(v, "ptr", v) for v in lin])
+        _check(lib().stfem_stokes_st_vmult_convection(self._h, int(mode), n_timesteps_at_once, n_timedofs, int(variable_major),
+                                                      _p(A), _p(B), d, s_, l_, stream), "stfem_stokes_st_vmult_convection")
 
     def st_Tvmult(self, Alpha, Beta, n_timesteps_at_once, n_timedofs, dst_blocks, src_blocks, variable_major=True, stream=None):
         """SystemMatrixStokes::Tvmult AS THE REFERENCE HAS IT (operators.h:708-745): its scatter overload (operators.h:111-123)
@@ -847,17 +870,23 @@ class StokesMatrixFreeOperator:
         self.st_vmult(Ae, Be, ns, nt, dst_blocks, src_blocks, variable_major, stream)
 
     def st_vmult_slice_add(self, Gamma, Zeta, n_timesteps_at_once, n_timedofs, dst_blocks, src_u, src_p,
-                           variable_major=True, stream=None):
+                           variable_major=True, stream=None, lin=None, mode=0):
         """SystemMatrixStokes::vmult_slice_add (n x 1 right-hand-side case); dst is accumulated into."""
         nb = 2 * n_timesteps_at_once * n_timedofs
         g = np.ascontiguousarray(Gamma, dtype=np.float64).reshape(-1)
         z = np.ascontiguousarray(Zeta, dtype=np.float64).reshape(-1)
         assert g.size == nb and z.size == nb and len(dst_blocks) == nb
         d = (_vp * nb)(*[getattr(v, "ptr", v) for v in dst_blocks])
-        _check(lib().stfem_stokes_st_vmult_slice_add(self._h, n_timesteps_at_once, n_timedofs, int(variable_major),
-                                                     _p(g), _p(z), d, getattr(src_u, "ptr", src_u),
-                                                     getattr(src_p, "ptr", src_p), stream),
-               "stfem_stokes_st_vmult_slice_add")
+        if mode == 0 and lin is None:
+            _check(lib().stfem_stokes_st_vmult_slice_add(self._h, n_timesteps_at_once, n_timedofs, int(variable_major),
+                                                         _p(g), _p(z), d, getattr(src_u, "ptr", src_u),
+                                                         getattr(src_p, "ptr", src_p), stream),
+                   "stfem_stokes_st_vmult_slice_add")
+            return
+        _check(lib().stfem_stokes_st_vmult_slice_add_convection(self._h, int(mode), n_timesteps_at_once, n_timedofs,
+                                                                int(variable_major), _p(g), _p(z), d, getattr(src_u, "ptr", src_u),
+                                                                getattr(src_p, "ptr", src_p), getattr(lin, "ptr", lin), stream),
+               "stfem_stokes_st_vmult_slice_add_convection")
 
     @property
     def n_cells(self):

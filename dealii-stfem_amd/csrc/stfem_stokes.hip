@@ -4,7 +4,8 @@
 // components as the blocks of the scalar FE_Q(2) pencil sweep (csrc/stfem_pencil.hip), for one time dof with the pressure gradient
 // term folded into that sweep, and the coupling kernels of stfem_stokes_coupling.hip, the divergence as a marching gather kernel.
 // General meshes: the cell kernel (stfem_stokes_cell.hip).  On top of either: the weak (Nitsche) boundary faces
-// (stfem_stokes_boundary.hip).  The helpers of the pressure space the solver around the operator needs: stfem_stokes_pressure.hip.
+// (stfem_stokes_boundary.hip), and with a convection mode (form / jacobian of the Navier-Stokes operator) the convection launches
+// (stfem_stokes_convection.hip).  The helpers of the pressure space the solver around the operator needs: stfem_stokes_pressure.hip.
 // Every entry point describes its launches in ONE form, StokesParams (stfem_stokes_internal.h), put together by StokesLaunch below.
 #include "stfem_stokes_internal.h"
 
@@ -253,16 +254,22 @@ int stfem_stokes_vector_download(stfem_stokes_ctx *c, int variable, const double
 
 namespace {
 
-int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st);
+int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double *const *lin, hipStream_t st);
 
 // One set of launches in the making: the sources first, then the destination pairs with their weights per source.
 struct StokesLaunch {
   stfem_stokes_ctx *c;
   hipStream_t st;
   StokesParams prm;
-  StokesLaunch(stfem_stokes_ctx *c_, hipStream_t st_) : c(c_), st(st_), prm(c_->base) { prm.nsrc = prm.nout = 0; }
-  void add_source(const double *u, const double *p) // (p == nullptr: mass only)
+  int mode;                  // STFEM_CONVECTION_*: what follows the launches of the linear operator
+  const double *lin[MAXSRC]; // the linearisation velocity of every source (mode != none)
+  StokesLaunch(stfem_stokes_ctx *c_, hipStream_t st_, int mode_ = STFEM_CONVECTION_NONE) : c(c_), st(st_), prm(c_->base), mode(mode_)
   {
+    prm.nsrc = prm.nout = 0;
+  }
+  void add_source(const double *u, const double *p, const double *b = nullptr) // (p == nullptr: mass only; b: linearisation velocity)
+  {
+    lin[prm.nsrc] = b;
     prm.us[prm.nsrc] = u;
     prm.ps[prm.nsrc++] = p;
   }
@@ -294,7 +301,7 @@ struct StokesLaunch {
   int flush()
   {
     if (prm.nout == 0) return STFEM_OK;
-    const int rc = stokes_launch(c, prm, st);
+    const int rc = stokes_launch(c, prm, mode, lin, st);
     prm.nout = 0;
     return rc;
   }
@@ -408,7 +415,9 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
   return STFEM_OK;
 }
 
-int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st)
+// In this fixed order: the linear part (Kronecker path or cell kernel), its boundary launches, then - with a convection mode - the
+// convection colours 0..7 and the inflow colours (stfem_stokes_convection.hip), which add to what the linear part has written.
+int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double *const *lin, hipStream_t st)
 {
   // axis-aligned uniform mesh: the Kronecker path; otherwise the cell kernel
   const int rc = c->scalar ? stokes_cart_launch(c, prm, st) : stokes_cell_launch(c, prm, st);
@@ -417,7 +426,11 @@ int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st)
   bool k_part = false;
   for (int o = 0; o < prm.nout; ++o)
     for (int q = 0; q < prm.nsrc; ++q) k_part = k_part || prm.wKu[q][o] != 0.0 || prm.wKp[q][o] != 0.0;
-  if (c->weak_mask && k_part) return stokes_boundary_launch(c, prm, nullptr, st);
+  if (c->weak_mask && k_part) {
+    const int rb = stokes_boundary_launch(c, prm, nullptr, st);
+    if (rb != STFEM_OK) return rb;
+  }
+  if (mode != STFEM_CONVECTION_NONE) return stokes_convection_launch(c, prm, lin, mode, st);
   return STFEM_OK;
 }
 
@@ -431,11 +444,20 @@ extern "C" {
 int stfem_stokes_vmult(stfem_stokes_ctx *c, double *dst_u, double *dst_p, const double *src_u,
                        const double *src_p, void *stream)
 {
+  return stfem_stokes_vmult_convection(c, STFEM_CONVECTION_NONE, dst_u, dst_p, src_u, src_p, nullptr, stream);
+}
+
+int stfem_stokes_vmult_convection(stfem_stokes_ctx *c, int mode, double *dst_u, double *dst_p, const double *src_u,
+                                  const double *src_p, const double *lin_u, void *stream)
+{
   if (!c || !dst_u || !dst_p || !src_u || !src_p) return STFEM_ERR_INVALID_ARGUMENT;
+  if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_u))
+    return STFEM_ERR_INVALID_ARGUMENT;
   if (dst_u == src_u || dst_p == src_p) return STFEM_ERR_ALIAS;
+  if (mode != STFEM_CONVECTION_NONE && (lin_u == dst_u || lin_u == dst_p)) return STFEM_ERR_ALIAS;
   STOKES_TRY(hipSetDevice(c->device));
-  StokesLaunch launch(c, static_cast<hipStream_t>(stream));
-  launch.add_source(src_u, src_p);
+  StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
+  launch.add_source(src_u, src_p, lin_u);
   const double one = 1.0, zero = 0.0;
   char written[2] = {0, 0}; // dst is overwritten
   const int rc = launch.add_destination(dst_u, dst_p, &one, &one, &zero, &written[0], &written[1]);
@@ -459,15 +481,35 @@ int stfem_stokes_st_vmult(stfem_stokes_ctx *c, int n_timesteps_at_once, int n_ti
                           const double *Alpha, const double *Beta, double *const *dst_blocks,
                           const double *const *src_blocks, void *stream)
 {
+  return stfem_stokes_st_vmult_convection(c, STFEM_CONVECTION_NONE, n_timesteps_at_once, n_timedofs, variable_major, Alpha, Beta,
+                                          dst_blocks, src_blocks, nullptr, stream);
+}
+
+int stfem_stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timesteps_at_once, int n_timedofs, int variable_major,
+                                     const double *Alpha, const double *Beta, double *const *dst_blocks,
+                                     const double *const *src_blocks, const double *const *lin_blocks, void *stream)
+{
   if (!c || !Alpha || !Beta || !dst_blocks || !src_blocks || n_timesteps_at_once < 1 || n_timedofs < 1)
     return STFEM_ERR_INVALID_ARGUMENT;
+  if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_blocks))
+    return STFEM_ERR_INVALID_ARGUMENT;
+  const bool navier = mode != STFEM_CONVECTION_NONE;
   const int nt = n_timedofs, ns = n_timesteps_at_once, nb = 2 * nt * ns;
   auto index = [&](int it, int v, int d) { return block_index(nt, variable_major, it, v, d); };
+  if (navier)
+    for (int it = 0; it < ns; ++it)
+      for (int d = 0; d < nt; ++d)
+        if (!lin_blocks[index(it, 0, d)]) return STFEM_ERR_INVALID_ARGUMENT; // (only the velocity entries are read)
   for (int j = 0; j < nb; ++j) {
     if (!dst_blocks[j] || !src_blocks[j]) return STFEM_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < nb; ++i)
       if (dst_blocks[j] == src_blocks[i]) return STFEM_ERR_ALIAS;
   }
+  if (navier)
+    for (int j = 0; j < nb; ++j)
+      for (int it = 0; it < ns; ++it)
+        for (int d = 0; d < nt; ++d)
+          if (dst_blocks[j] == lin_blocks[index(it, 0, d)]) return STFEM_ERR_ALIAS;
   STOKES_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // dst = 0.0 (operators.h:833): the first launch that reaches a block overwrites it; blocks no launch
@@ -481,8 +523,10 @@ int stfem_stokes_st_vmult(stfem_stokes_ctx *c, int n_timesteps_at_once, int n_ti
   }();
   const int group = (fused_ok && ns * nt <= MAXSRC) ? ns * nt : 1;
   for (int s0 = 0; s0 < ns * nt; s0 += group) {
-    StokesLaunch launch(c, st);
-    for (int s = s0; s < s0 + group; ++s) launch.add_source(src_blocks[index(s / nt, 0, s % nt)], src_blocks[index(s / nt, 1, s % nt)]);
+    StokesLaunch launch(c, st, mode);
+    for (int s = s0; s < s0 + group; ++s)
+      launch.add_source(src_blocks[index(s / nt, 0, s % nt)], src_blocks[index(s / nt, 1, s % nt)],
+                        navier ? lin_blocks[index(s / nt, 0, s % nt)] : nullptr);
     for (int jt = 0; jt < ns; ++jt)
       for (int jd = 0; jd < nt; ++jd) {
         const int ju = index(jt, 0, jd), jp = index(jt, 1, jd);
@@ -512,16 +556,28 @@ int stfem_stokes_st_vmult_slice_add(stfem_stokes_ctx *c, int n_timesteps_at_once
                                     const double *Gamma, const double *Zeta, double *const *dst_blocks,
                                     const double *src_u, const double *src_p, void *stream)
 {
+  return stfem_stokes_st_vmult_slice_add_convection(c, STFEM_CONVECTION_NONE, n_timesteps_at_once, n_timedofs, variable_major, Gamma,
+                                                    Zeta, dst_blocks, src_u, src_p, nullptr, stream);
+}
+
+int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, int n_timesteps_at_once, int n_timedofs,
+                                               int variable_major, const double *Gamma, const double *Zeta,
+                                               double *const *dst_blocks, const double *src_u, const double *src_p,
+                                               const double *lin_u, void *stream)
+{
   if (!c || !Gamma || !Zeta || !dst_blocks || !src_u || !src_p || n_timesteps_at_once < 1 || n_timedofs < 1)
+    return STFEM_ERR_INVALID_ARGUMENT;
+  if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_u))
     return STFEM_ERR_INVALID_ARGUMENT;
   const int nt = n_timedofs, ns = n_timesteps_at_once, nb = 2 * nt * ns;
   for (int j = 0; j < nb; ++j) {
     if (!dst_blocks[j]) return STFEM_ERR_INVALID_ARGUMENT;
     if (dst_blocks[j] == src_u || dst_blocks[j] == src_p) return STFEM_ERR_ALIAS;
+    if (mode != STFEM_CONVECTION_NONE && dst_blocks[j] == lin_u) return STFEM_ERR_ALIAS;
   }
   STOKES_TRY(hipSetDevice(c->device));
-  StokesLaunch launch(c, static_cast<hipStream_t>(stream));
-  launch.add_source(src_u, src_p);
+  StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
+  launch.add_source(src_u, src_p, lin_u);
   for (int it = 0; it < ns; ++it)
     for (int id = 0; id < nt; ++id) {
       const int ju = block_index(nt, variable_major, it, 0, id), jp = block_index(nt, variable_major, it, 1, id);

@@ -1,5 +1,5 @@
 // What the translation units of the Stokes two-field operator share (stfem_stokes.hip and stfem_stokes_{cell,coupling,boundary,
-// pressure}.hip): the description of a launch, the context and the launchers.  Not part of the boundary.
+// pressure,convection}.hip): the description of a launch, the context and the launchers.  Not part of the boundary.
 #pragma once
 #include "stfem_internal.h"
 
@@ -67,6 +67,32 @@ struct BoundaryParams {
   double Eu[6], EDu[6], Ep[4]; // end-point tables [s * n + a]: FE_Q(2) values / derivatives, FE_Q(1) values at 0 and 1
 };
 
+// The convection launches of the Navier-Stokes modes (stfem_stokes_convection.hip): a description of their own, so that StokesParams,
+// the by-value argument of every kernel of the linear operator, stays what it is.
+//   out_u[o] += sum_s wKu[s][o] C(b_s, u_s),   C = C_form(b, u) (form) or C_form(b, u) + C_form(u, b) (jacobian),
+//   C_form(b, u)(v) = - int (u (x) b) : grad v  - int_{weak faces} min(b.n, 0) u.v
+// Geometry, tables and the weights are copied from the StokesParams of the same set; only destinations with a non-zero wKu are listed.
+struct ConvectionParams {
+  const double *vertices;
+  int ncx, ncy, ncz;
+  int ndu[3];
+  long long Nu;
+  int dmask;
+  int nsrc;
+  const double *us[MAXSRC], *bs[MAXSRC]; // source and linearisation velocity of every source
+  int nout;
+  double *out_u[MAXOUT];
+  double wKu[MAXSRC][MAXOUT];
+  double Su[9], Du[9];
+  double xq[3], wq[3];
+  int interleave, colour, cart;
+  double hinv[3], detJ;
+  // the inflow term on the weak faces
+  int weak_mask;
+  int foff[7];
+  double Eu[6];
+};
+
 struct stfem_stokes_ctx {
   int device = 0;
   int nc[3] = {0, 0, 0};
@@ -100,7 +126,8 @@ struct stfem_stokes_ctx {
   std::vector<double> h_vertices;
 };
 
-__device__ __forceinline__ bool constrained_u(const StokesParams &prm, int ix, int iy, int iz)
+template <typename Params> // (StokesParams or ConvectionParams)
+__device__ __forceinline__ bool constrained_u(const Params &prm, int ix, int iy, int iz)
 {
   return ((prm.dmask & 1) && ix == 0) || ((prm.dmask & 2) && ix == prm.ndu[0] - 1) ||
          ((prm.dmask & 4) && iy == 0) || ((prm.dmask & 8) && iy == prm.ndu[1] - 1) ||
@@ -126,6 +153,10 @@ void stokes_grad_launch(const CouplingParams &k, hipStream_t st);
 void stokes_div_launch(const CouplingParams &k, long long Np, hipStream_t st);
 // The eight colour launches of the boundary kernel (stfem_stokes_boundary.hip); d_g: the Dirichlet data of the rhs mode, or nullptr
 int stokes_boundary_launch(stfem_stokes_ctx *c, StokesParams &prm, const double *d_g, hipStream_t st);
+// The convection launches after those of `prm` (stfem_stokes_convection.hip): eight colour launches of the cell kernel, then, with weak
+// faces, eight of the inflow-face kernel.  mode: STFEM_CONVECTION_FORM / _JACOBIAN; lin[s]: the linearisation velocity of source s.
+// Nothing is launched when all wKu of the set are zero.
+int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *lin, int mode, hipStream_t st);
 #pragma GCC visibility pop
 
 #define STOKES_TRY(call)                                                   \

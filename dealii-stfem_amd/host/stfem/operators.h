@@ -333,8 +333,12 @@ private:
 // include/operators.h:1953-2050 PDE<>: the nonlinear-solver face of an operator.  residual = rhs - form(src);
 // form falls back to vmult for operators without one (internal::has_form, 1999-2004); vmult applies the
 // Jacobian operator (the same object unless given separately).
-template <int dim, typename Number, typename PDEOperator, typename JacOperator = PDEOperator> class PDE {
-  using BlockVectorType = BlockVectorT<Number>;
+// BlockVector: the block vector type of the operators (the scalar systems' BlockVectorT; the Stokes systems' vector of StokesVector,
+// whose rhs_minus is in stokes.h).
+template <typename Number> void rhs_minus(BlockVectorT<Number> &dst, const BlockVectorT<Number> &rhs);
+template <int dim, typename Number, typename PDEOperator, typename JacOperator = PDEOperator, typename BlockVector = BlockVectorT<Number>>
+class PDE {
+  using BlockVectorType = BlockVector;
 
   template <typename Op, typename = void> struct has_form : std::false_type {};
   template <typename Op>
@@ -366,21 +370,11 @@ public:
     rhs = &rhs_;
     residual(dst, src);
   }
-  // rhs - form(src): dst = -form(src) + rhs through the block BLAS-1 of the boundary
+  // rhs - form(src): dst = -form(src) + rhs through the block BLAS-1 of the boundary (rhs_minus of the block vector type)
   void residual(BlockVectorType &dst, const BlockVectorType &src) const
   {
     form(dst, src);
-    const unsigned n = dst.n_blocks();
-    FullMatrix<Number> minus_two(n, n), one(n, n);
-    for (unsigned i = 0; i < n; ++i) {
-      minus_two(i, i) = Number(-2); // dst += -2 dst  ->  -form
-      one(i, i) = Number(1);
-    }
-    BlockVectorType tmp;
-    tmp.reinit(dst.context(), n);
-    tensorproduct_add_impl(dst.context(), tmp, one, dst);       // tmp = form
-    tensorproduct_add_impl(dst.context(), dst, minus_two, tmp); // dst = form - 2 form
-    tensorproduct_add_impl(dst.context(), dst, one, *rhs);      // dst = rhs - form
+    rhs_minus(dst, *rhs);
   }
   void form(BlockVectorType &dst, const BlockVectorType &src) const
   {
@@ -396,20 +390,30 @@ public:
   {
     pde_operator->initialize_dof_vector(vec);
   }
+  template <typename Vector> void initialize_dof_vector(Vector &vec) const { pde_operator->initialize_dof_vector(vec); }
 
 private:
-  static void tensorproduct_add_impl(const std::shared_ptr<Context> &ctx, BlockVectorType &c, const FullMatrix<Number> &A,
-                                     const BlockVectorType &b)
-  {
-    std::vector<double> a(size_t(A.m()) * A.n());
-    for (size_t i = 0; i < a.size(); ++i) a[i] = double(A.data()[i]);
-    check(stfem_tensorproduct_add(ctx->h, int(A.m()), int(A.n()), a.data(), c.handle(), b.handle(), nullptr),
-          "PDE::residual");
-  }
   mutable const BlockVectorType *rhs = nullptr;
   const PDEOperator *pde_operator = nullptr;
   const JacOperator *jac_operator = nullptr;
 };
+
+// dst = rhs - dst for the block vectors of the scalar systems (PDE::residual)
+template <typename Number> void rhs_minus(BlockVectorT<Number> &dst, const BlockVectorT<Number> &rhs)
+{
+  const unsigned n = dst.n_blocks();
+  std::vector<double> minus_two(size_t(n) * n, 0.0), one(size_t(n) * n, 0.0);
+  for (unsigned i = 0; i < n; ++i) {
+    minus_two[size_t(i) * n + i] = -2.0; // dst += -2 dst  ->  -form
+    one[size_t(i) * n + i] = 1.0;
+  }
+  BlockVectorT<Number> tmp;
+  tmp.reinit(dst.context(), n);
+  stfem_ctx *h = dst.context()->h;
+  check(stfem_tensorproduct_add(h, int(n), int(n), one.data(), tmp.handle(), dst.handle(), nullptr), "PDE::residual");       // tmp = form
+  check(stfem_tensorproduct_add(h, int(n), int(n), minus_two.data(), dst.handle(), tmp.handle(), nullptr), "PDE::residual"); // dst = form - 2 form
+  check(stfem_tensorproduct_add(h, int(n), int(n), one.data(), dst.handle(), rhs.handle(), nullptr), "PDE::residual");       // dst = rhs - form
+}
 
 // operators.h:211-283 tensorproduct_add: c_i += A(i,j) b_j
 template <typename Number>

@@ -1,7 +1,8 @@
 // Host-side mirror of the reference's Stokes operators (include/operators.h:666-868
 // SystemMatrixStokes, 1193-1766 StokesMatrixFreeOperator, 1768-1951 StokesNitscheMatrixFreeOperator;
 // include/fe_time.h:901-1221 BlockSlice, 1242-1285 get_fe_time_weights_stokes) on the C-ABI (stfem_stokes_*):
-// cell loop and, for weak boundary ids, the boundary-face loop of the linear operator.
+// cell loop and, for weak boundary ids, the boundary-face loop; with a NonlinearTreatment the convection modes of the Navier-Stokes
+// operator (OperatorMode::form / jacobian) and the NavierStokesOperator alias over PDE<> (operators.h:2052-2063).
 #pragma once
 #include "fe_time.h"
 #include "operators.h"
@@ -91,6 +92,7 @@ public:
   ~StokesVector() { if (d_) stfem_stokes_vector_destroy(c_, d_); }
   double *data() const { return d_; }
   size_t size() const { return n_; }
+  stfem_stokes_ctx *context() const { return c_; }
   void copy_from_host(const std::vector<double> &h)
   {
     if (h.size() != n_) throw std::invalid_argument("StokesVector size mismatch");
@@ -113,8 +115,29 @@ private:
 // boundary ids of the structured block: 2 d + s (direction d, side s), as deal.II colorizes a hyper_rectangle
 using boundary_id = unsigned;
 
-// operators.h:1193-1766, linear operator: cell loop + boundary-face loop for the weak (Nitsche) ids.  Same constructor
-// arguments after the mesh as the reference (1199-1212); delta0 != 0 (CIP interior faces) and the nonlinear treatments throw.
+// dst = rhs - dst, block by block in one launch (PDE::residual on the Stokes block vectors)
+inline void rhs_minus(std::vector<StokesVector> &dst, const std::vector<StokesVector> &rhs)
+{
+  const size_t nb = dst.size();
+  if (rhs.size() != nb) throw Error(STFEM_ERR_SHAPE_MISMATCH, "PDE::residual: blocks");
+  if (nb == 0) return;
+  std::vector<int64_t> len(nb);
+  std::vector<const void *> px(nb);
+  std::vector<void *> py(nb);
+  for (size_t i = 0; i < nb; ++i) {
+    if (rhs[i].size() != dst[i].size()) throw Error(STFEM_ERR_SHAPE_MISMATCH, "PDE::residual: block sizes");
+    len[i] = int64_t(dst[i].size());
+    px[i] = rhs[i].data();
+    py[i] = dst[i].data();
+  }
+  stfem_ctx *pc = nullptr; // (any scalar context of the device serves the vector arithmetic: the pressure space's is at hand)
+  check(stfem_stokes_pressure_ctx(dst[0].context(), &pc), "stfem_stokes_pressure_ctx");
+  check(stfem_axpby_many(pc, int(nb), len.data(), 1.0, px.data(), -1.0, py.data(), nullptr), "PDE::residual");
+}
+
+// operators.h:1193-1766: cell loop + boundary-face loop for the weak (Nitsche) ids.  Same constructor arguments after the mesh as
+// the reference (1199-1213), with dg_pressure before the nonlinear treatment; delta0 != 0 (CIP interior faces) throws, and so does a
+// nonlinear treatment together with outflow_penalty != 0 (the outflow faces' value term, 1705-1709, is not built).
 template <int dim, typename Number> class StokesMatrixFreeOperator {
   static_assert(dim == 3 && std::is_same<Number, double>::value, "3D, fp64");
 
@@ -123,11 +146,15 @@ public:
 
   StokesMatrixFreeOperator(const Mesh &mesh, unsigned velocity_degree, Number viscosity, const std::set<boundary_id> &weak_boundary_ids = {},
                            const std::set<boundary_id> &outflow_boundary_ids = {}, Number penalty1 = 20, Number penalty2 = 10,
-                           Number /*outflow_penalty*/ = 0.0, Number delta0 = 0.0, Number /*delta1*/ = 0.0, bool dg_pressure = false)
+                           Number outflow_penalty = 0.0, Number delta0 = 0.0, Number /*delta1*/ = 0.0, bool dg_pressure = false,
+                           NonlinearTreatment nonlinear_treatment_ = NonlinearTreatment::None)
+    : nonlinear_treatment(nonlinear_treatment_), nonlinear(nonlinear_treatment_ != NonlinearTreatment::None)
   {
     // dg_pressure: FE_DGP(degree - 1) instead of FE_Q(degree - 1) for the pressure (the reference chooses the element of its
     // second DoFHandler, tests/tp_03stokes.cc:83-86: dGPressure)
     if (delta0 != 0.0) throw Error(STFEM_ERR_UNSUPPORTED, "StokesMatrixFreeOperator: the CIP face term (delta0 != 0) is not built");
+    if (nonlinear && outflow_penalty != 0.0)
+      throw Error(STFEM_ERR_UNSUPPORTED, "StokesMatrixFreeOperator: outflow_penalty != 0 with a nonlinear treatment is not built");
     create(mesh, velocity_degree, viscosity, dg_pressure);
     int weak = 0, outflow = 0;
     for (boundary_id f : weak_boundary_ids) weak |= 1 << f;
@@ -162,11 +189,25 @@ public:
   }
   void initialize_dof_vector(StokesVector &vec, unsigned variable) const { vec = StokesVector(h_, int(variable)); }
 
-  void vmult(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const
+  // operators.h:1288-1297: none / form (Explicit) / jacobian (Implicit)
+  void vmult(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const { apply(vmult_mode(), dst, src, stream); }
+  // operators.h:1279-1286: the nonlinear weak form; the linear operator without a nonlinear treatment
+  void form(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const { apply(form_mode(), dst, src, stream); }
+  // operators.h:1333-1342: the linearisation state, {velocity, pressure} (only the velocity is read) or the velocity alone; it is
+  // referred to, not copied
+  void set_data(const BlockVectorType &data) const { set_data(data.at(0)); }
+  void set_data(const StokesVector &velocity) const
   {
-    check(stfem_stokes_vmult(h_, dst.at(0).data(), dst.at(1).data(), src.at(0).data(), src.at(1).data(), stream),
-          "StokesMatrixFreeOperator::vmult");
+    if (!nonlinear) throw Error(STFEM_ERR_INVALID_ARGUMENT, "StokesMatrixFreeOperator::set_data: not allowed without a nonlinear treatment");
+    lin_ = velocity.data();
   }
+  // the STFEM_CONVECTION_* mode behind vmult / form
+  int vmult_mode() const
+  {
+    return nonlinear_treatment == NonlinearTreatment::None ? STFEM_CONVECTION_NONE
+           : nonlinear_treatment == NonlinearTreatment::Explicit ? STFEM_CONVECTION_FORM : STFEM_CONVECTION_JACOBIAN;
+  }
+  int form_mode() const { return nonlinear ? STFEM_CONVECTION_FORM : STFEM_CONVECTION_NONE; }
   // the MassMatrixType of SystemMatrixStokes (vector mass)
   void mass_vmult(StokesVector &dst, const StokesVector &src, void *stream = nullptr) const
   {
@@ -176,7 +217,16 @@ public:
   stfem_stokes_ctx *handle() const { return h_; }
 
 private:
+  void apply(int mode, BlockVectorType &dst, const BlockVectorType &src, void *stream) const
+  {
+    if (mode != STFEM_CONVECTION_NONE && !lin_) throw Error(STFEM_ERR_INVALID_ARGUMENT, "StokesMatrixFreeOperator: no linearization set");
+    check(stfem_stokes_vmult_convection(h_, mode, dst.at(0).data(), dst.at(1).data(), src.at(0).data(), src.at(1).data(), lin_, stream),
+          "StokesMatrixFreeOperator::vmult");
+  }
   stfem_stokes_ctx *h_ = nullptr;
+  NonlinearTreatment nonlinear_treatment;
+  bool nonlinear;
+  mutable const double *lin_ = nullptr; // data_lin[0]
 };
 
 // operators.h:1768-1951: the right-hand-side functional of the weakly imposed Dirichlet data.  It shares the geometry
@@ -220,8 +270,9 @@ public:
   using BlockVectorType = std::vector<StokesVector>;
 
   SystemMatrixStokes(const StokesMatrixFreeOperator<dim, Number> &K, const FullMatrix<Number> &Alpha_,
-                     const FullMatrix<Number> &Beta_, const BlockSlice &blk_slice_)
-    : K(K), Alpha(Alpha_), Beta(Beta_), blk_slice(blk_slice_)
+                     const FullMatrix<Number> &Beta_, const BlockSlice &blk_slice_,
+                     NonlinearTreatment nonlinear_treatment_ = NonlinearTreatment::None)
+    : K(K), Alpha(Alpha_), Beta(Beta_), blk_slice(blk_slice_), nonlinear(nonlinear_treatment_ != NonlinearTreatment::None)
   {
     if (Alpha.m() != blk_slice.n_blocks() || (Alpha.n() != Alpha.m() && Alpha.n() != 1) || Beta.m() != Alpha.m() ||
         Beta.n() != Alpha.n())
@@ -232,17 +283,50 @@ public:
     vec.clear();
     for (unsigned i = 0; i < blk_slice.n_blocks(); ++i) vec.emplace_back(K.handle(), int(blk_slice.decompose(i)[1]));
   }
-  void vmult(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const
+  // operators.h:385-388: the linearisation vector, in BlockSlice order (n x 1 systems: one {velocity, pressure} pair); referred to,
+  // not copied.  Source time dof (it, id) is linearised about its block index(it, 0, id) (473-484, 843-846).
+  void set_data(const BlockVectorType &solution_linearization_) const { solution_linearization = &solution_linearization_; }
+  void vmult(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const // 696-700
+  {
+    tensorproduct_eval(dst, src, K.vmult_mode(), stream);
+  }
+  void form(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const // 702-706
+  {
+    tensorproduct_eval(dst, src, K.form_mode(), stream);
+  }
+
+private:
+  // the velocity blocks of the linearisation vector for the operator's mode (pressure entries stay null)
+  std::vector<const double *> linearization(int mode, unsigned n_expected, const char *what) const
+  {
+    std::vector<const double *> l;
+    if (mode == STFEM_CONVECTION_NONE) return l;
+    if (!nonlinear || !solution_linearization) throw Error(STFEM_ERR_INVALID_ARGUMENT, std::string(what) + ": no linearization set");
+    if (solution_linearization->size() != n_expected) throw Error(STFEM_ERR_SHAPE_MISMATCH, std::string(what) + ": linearization blocks");
+    l.assign(n_expected, nullptr);
+    return l;
+  }
+  void tensorproduct_eval(BlockVectorType &dst, const BlockVectorType &src, int mode, void *stream) const // 819-867
   {
     const unsigned nb = blk_slice.n_blocks();
     if (dst.size() != nb || src.size() != nb) throw Error(STFEM_ERR_SHAPE_MISMATCH, "SystemMatrixStokes::vmult");
     std::vector<double *> d(nb);
     std::vector<const double *> s(nb);
     for (unsigned i = 0; i < nb; ++i) { d[i] = dst[i].data(); s[i] = src[i].data(); }
-    check(stfem_stokes_st_vmult(K.handle(), int(blk_slice.n_timesteps_at_once()), int(blk_slice.n_timedofs()),
-                                blk_slice.variable_major() ? 1 : 0, Alpha.data(), Beta.data(), d.data(), s.data(), stream),
+    std::vector<const double *> l = linearization(mode, nb, "SystemMatrixStokes::vmult");
+    if (!l.empty())
+      for (unsigned it = 0; it < blk_slice.n_timesteps_at_once(); ++it)
+        for (unsigned id = 0; id < blk_slice.n_timedofs(); ++id) {
+          const unsigned i = blk_slice.index(it, 0, id);
+          l[i] = (*solution_linearization)[i].data();
+        }
+    check(stfem_stokes_st_vmult_convection(K.handle(), mode, int(blk_slice.n_timesteps_at_once()), int(blk_slice.n_timedofs()),
+                                           blk_slice.variable_major() ? 1 : 0, Alpha.data(), Beta.data(), d.data(), s.data(),
+                                           l.empty() ? nullptr : l.data(), stream),
           "SystemMatrixStokes::vmult");
   }
+
+public:
   // operators.h:708-745, as the reference has it: its scatter overload (operators.h:111-123) reads j = index(it, v, id),
   // i = index(jt, v, jd) - the result of source time dof (it, id) only reaches the destination blocks of the SAME time dof,
   // weighted with the entries of row j summed over (jt, jd).  Not a transpose; reproduced as one vmult with those matrices.
@@ -279,9 +363,13 @@ public:
     if (dst.size() != nb || src.size() != 2 || Alpha.n() != 1) throw Error(STFEM_ERR_SHAPE_MISMATCH, "vmult_slice_add");
     std::vector<double *> d(nb);
     for (unsigned i = 0; i < nb; ++i) d[i] = dst[i].data();
-    check(stfem_stokes_st_vmult_slice_add(K.handle(), int(blk_slice.n_timesteps_at_once()), int(blk_slice.n_timedofs()),
-                                          blk_slice.variable_major() ? 1 : 0, Alpha.data(), Beta.data(), d.data(),
-                                          src[0].data(), src[1].data(), stream),
+    // (759-761: set_linearization_data_slice - one linearisation pair for the one source pair)
+    const int mode = K.vmult_mode();
+    const std::vector<const double *> l = linearization(mode, 2, "SystemMatrixStokes::vmult_slice_add");
+    check(stfem_stokes_st_vmult_slice_add_convection(K.handle(), mode, int(blk_slice.n_timesteps_at_once()), int(blk_slice.n_timedofs()),
+                                                     blk_slice.variable_major() ? 1 : 0, Alpha.data(), Beta.data(), d.data(),
+                                                     src[0].data(), src[1].data(), l.empty() ? nullptr : (*solution_linearization)[0].data(),
+                                                     stream),
           "SystemMatrixStokes::vmult_slice_add");
   }
   unsigned long long m() const { return (unsigned long long)(blk_slice.n_blocks() / 2) * K.m(); }
@@ -291,7 +379,15 @@ private:
   const FullMatrix<Number> &Alpha;
   const FullMatrix<Number> &Beta;
   BlockSlice blk_slice;
+  bool nonlinear;
+  mutable const BlockVectorType *solution_linearization = nullptr;
 };
+
+// operators.h:2052-2063: the nonlinear-solver face of the space-time Navier-Stokes system: residual = rhs - form(src), vmult = the
+// Jacobian (or, with the Explicit treatment, the form), set_data = the linearisation vector
+template <int dim, typename Number>
+using NavierStokesOperator =
+  PDE<dim, Number, SystemMatrixStokes<dim, Number>, SystemMatrixStokes<dim, Number>, std::vector<StokesVector>>;
 
 // PreconditionVanka in its block form (include/stmg.h:626-738, 832-872) as tests/tp_03stokes.cc:537-540, 714-726 creates it for the
 // Stokes levels: the assembled Stokes and mass matrices restricted to every cell's velocity and pressure DoFs, combined with

@@ -34,6 +34,10 @@ inline void check(int status, const char *what)
   if (status != STFEM_OK) throw Error(status, what);
 }
 
+// include/types.h:115-120: how an operator treats the convection term (None: the linear operator; Explicit: vmult evaluates the
+// nonlinear form; Implicit: vmult applies the Jacobian); the enumerators carry the reference's values
+enum class NonlinearTreatment : unsigned int { None = 0, Explicit = 2, Implicit = 1 };
+
 // minimal stand-in for dealii::FullMatrix<Number> (row-major)
 template <typename Number> class FullMatrix {
 public:

@@ -382,8 +382,9 @@ int stfem_coefficient_per_cell(const int32_t ncell[3], const double *vertices, d
                                const double lower[3], const double upper[3], double *out);
 
 /* ---- Stokes two-field operator (BASELINE configs[4]): the cell loop (LoopType::Cell, include/operators.h:1228-1229) and,
- * after stfem_stokes_set_weak_boundaries below, the weak (Nitsche) boundary faces of operators.h:1662-1751; the CIP interior-face
- * term (delta0 != 0, 1603-1638) and the convection modes are not built.  Velocity FE_Q(2)^3, pressure FE_Q(1) (stfem_stokes_create)
+ * after stfem_stokes_set_weak_boundaries below, the weak (Nitsche) boundary faces of operators.h:1662-1751; the convection modes of the
+ * Navier-Stokes operator (OperatorMode::form / jacobian) through the *_convection entry points below.  Not built: the CIP
+ * interior-face term (delta0 != 0, 1603-1638) and the outflow penalty (beta, 1705-1709).  Velocity FE_Q(2)^3, pressure FE_Q(1) (stfem_stokes_create)
  * or FE_DGP(1) (stfem_stokes_create_ex), QGauss(3), MappingQ1 on the mesh of `mesh`; mesh->dirichlet_mask constrains the velocity
  * (homogeneous), the pressure is unconstrained.  fp64.
  * Layout: a velocity vector is 3 * n_velocity_dofs doubles, component-major, every component in
@@ -437,6 +438,30 @@ int stfem_stokes_st_vmult_slice_add(stfem_stokes_ctx *ctx, int n_timesteps_at_on
                                     int variable_major, const double *Gamma, const double *Zeta,
                                     double *const *dst_blocks, const double *src_u,
                                     const double *src_p, void *stream);
+/* The Navier-Stokes modes of the same operator (NonlinearTreatment, OperatorMode::form / jacobian): what
+ * StokesMatrixFreeOperator::vmult dispatches to (operators.h:1288-1297), form() (1279-1286) and set_data() (1333-1342) become.
+ * lin_u is the linearisation velocity b that set_data hands in (a velocity vector; entries on strongly constrained DoFs read as 0,
+ * like those of the source).  On top of the linear operator, at its own 3 x 3 x 3 Gauss points (operators.h:1554-1567, 1738-1743):
+ *   STFEM_CONVECTION_FORM:      dst_u += - int (u (x) b) : grad v                  - int_{weak faces} min(b.n, 0) u.v
+ *   STFEM_CONVECTION_JACOBIAN:  dst_u += - int (b (x) u + u (x) b) : grad v        - int_{weak faces} min(b.n, 0) u.v
+ * dst_p is that of the linear operator.  Mode STFEM_CONVECTION_NONE ignores lin_u and is stfem_stokes_vmult, launch for launch.
+ * lin_u may be src_u (Picard: form with b = u); lin_u equal to a destination is STFEM_ERR_ALIAS; a mode outside 0..2 or a null
+ * lin_u with a mode other than 0 is STFEM_ERR_INVALID_ARGUMENT, decided before anything touches the device. */
+enum { STFEM_CONVECTION_NONE = 0, STFEM_CONVECTION_FORM = 1, STFEM_CONVECTION_JACOBIAN = 2 };
+int stfem_stokes_vmult_convection(stfem_stokes_ctx *ctx, int mode, double *dst_u, double *dst_p, const double *src_u,
+                                  const double *src_p, const double *lin_u, void *stream);
+/* SystemMatrixStokes::vmult / form with a linearisation state (operators.h:473-500, 820-867): lin_blocks in BlockSlice order like
+ * src_blocks; source time dof (it, id) is linearised about lin_blocks[index(it, 0, id)] (835-866); only the velocity entries are
+ * read, the pressure entries may be null.  The convective result rides with nu K u - B^T p: the same Alpha weights and skip rule. */
+int stfem_stokes_st_vmult_convection(stfem_stokes_ctx *ctx, int mode, int n_timesteps_at_once, int n_timedofs,
+                                     int variable_major, const double *Alpha, const double *Beta,
+                                     double *const *dst_blocks, const double *const *src_blocks,
+                                     const double *const *lin_blocks, void *stream);
+/* SystemMatrixStokes::vmult_slice_add (operators.h:748-781) with one linearisation velocity for the one source pair */
+int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *ctx, int mode, int n_timesteps_at_once, int n_timedofs,
+                                               int variable_major, const double *Gamma, const double *Zeta,
+                                               double *const *dst_blocks, const double *src_u,
+                                               const double *src_p, const double *lin_u, void *stream);
 /* Weak boundary conditions of StokesMatrixFreeOperator (reference include/operators.h:1206-1211, 1220-1221, 1640-1741) and
  * StokesNitscheMatrixFreeOperator (1768-1951), linear operator (NonlinearTreatment::None).
  * Faces are numbered f = 2 d + s (direction d, side s: 0 = lower, 1 = upper; bit f of the masks) - the boundary ids of deal.II's
@@ -450,7 +475,9 @@ int stfem_stokes_st_vmult_slice_add(stfem_stokes_ctx *ctx, int n_timesteps_at_on
  *       evaluated (velocity.quadrature_point(q), operators.h:1911-1914).
  *   nitsche_rhs: StokesNitscheMatrixFreeOperator::vmult(dst): the boundary functional of the Dirichlet data g (host array
  *       [point][3] in that order) is ADDED to dst_u / dst_p (device).  Synchronises `stream` once (upload of g).
- * Not built: the CIP interior-face term (delta0 != 0, operators.h:1603-1638) and the convection modes (form / jacobian). */
+ * With a convection mode (the *_convection entry points) the weak faces also get the inflow term - min(b.n, 0) u (1738-1743); the
+ * outflow faces still add nothing: their back-flow term carries a factor 0.0 and their value term the outflow penalty.
+ * Not built: the CIP interior-face term (delta0 != 0, operators.h:1603-1638) and outflow_penalty (beta). */
 int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *ctx, int weak_mask, int outflow_mask, double penalty1, double penalty2);
 int64_t stfem_stokes_n_face_points(const stfem_stokes_ctx *ctx);
 int stfem_stokes_face_points(const stfem_stokes_ctx *ctx, double *out);

@@ -183,6 +183,8 @@ SIGNATURES = {
     "stfem_stokes_dgp_prolongate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "stfem_stokes_dgp_restrict": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "stfem_stokes_vanka_create": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.POINTER(_vp)]),
+    "stfem_stokes_vanka_create_linearised": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.c_int, C.POINTER(_vp), C.POINTER(_vp)]),
+    "stfem_stokes_vanka_update": (C.c_int, [_vp, C.POINTER(_vp)]),
     "stfem_stokes_vanka_destroy": (None, [_vp]),
     "stfem_stokes_vanka_n_classes": (C.c_int, [_vp]),
     "stfem_stokes_vanka_vmult": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
@@ -931,19 +933,40 @@ def stokes_dgp_restrict(fine, coarse, dst, src, add=False, stream=None):
 class StokesPreconditionVanka:
     """PreconditionVanka over a two-variable BlockSlice (stmg.h:626-738, 832-872, as tests/tp_03stokes.cc:714-726 creates it).
     block_variable[i] = 0 (velocity) / 1 (pressure) for the blocks in BlockSlice order; Alpha, Beta: the matrices of
-    get_fe_time_weights_stokes."""
+    get_fe_time_weights_stokes.  per_cell=True or a convection mode builds one block per cell from the operator linearised about
+    `lin` (reinit_asm, stmg.h:929-965): device vectors in BlockSlice order like those of st_vmult, only the velocity entries are read
+    (pressure entries may be None); update(lin) rebuilds the blocks for new states.  The defaults are the class blocks of a box (one
+    block per cell on a general mesh)."""
 
-    def __init__(self, op, block_variable, Alpha, Beta):
+    def __init__(self, op, block_variable, Alpha, Beta, lin=None, mode=0, per_cell=False):
         self.op = op
         self.nb = len(block_variable)
         bv = (C.c_int32 * self.nb)(*[int(v) for v in block_variable])
         A = np.ascontiguousarray(Alpha, dtype=np.float64); B = np.ascontiguousarray(Beta, dtype=np.float64)
         assert A.shape == (self.nb, self.nb) and B.shape == (self.nb, self.nb)
         h = _vp()
-        rc = lib().stfem_stokes_vanka_create(op._h, self.nb, bv, _p(A), _p(B), C.byref(h))
+        if per_cell or mode != 0:
+            rc = lib().stfem_stokes_vanka_create_linearised(op._h, self.nb, bv, _p(A), _p(B), int(mode), self._lin(lin), C.byref(h))
+            what = "stfem_stokes_vanka_create_linearised: "
+        else:
+            rc = lib().stfem_stokes_vanka_create(op._h, self.nb, bv, _p(A), _p(B), C.byref(h))
+            what = "stfem_stokes_vanka_create: "
         if rc != 0:
-            raise StfemError(rc, "stfem_stokes_vanka_create: " + lib().stfem_stokes_vanka_last_error().decode())
+            assert not h.value
+            raise StfemError(rc, what + lib().stfem_stokes_vanka_last_error().decode())
         self._h = h
+
+    def _lin(self, lin):
+        if lin is None:
+            return None
+        assert len(lin) == self.nb
+        return (_vp * self.nb)(*[getattr(v, "ptr", v) for v in lin])
+
+    def update(self, lin):
+        """the blocks again, linearised about `lin` (same mode, same storage)"""
+        rc = lib().stfem_stokes_vanka_update(self._h, self._lin(lin))
+        if rc != 0:
+            raise StfemError(rc, "stfem_stokes_vanka_update: " + lib().stfem_stokes_vanka_last_error().decode())
 
     def __del__(self):
         if getattr(self, "_h", None):

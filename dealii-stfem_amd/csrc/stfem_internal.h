@@ -68,3 +68,24 @@ struct stfem_stokes_desc {
   double lower[3], upper[3], nu, penalty1, penalty2;
 };
 int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *out);
+
+#pragma GCC visibility push(hidden)
+// stfem_vanka.hip: vanka_invert_kernel<double> on `count` m x m matrices at B (row-major, destroyed), the inverses in the apply's
+// layout [kpad][mpad] from block cell0 of out; *singular (device) is set to 1 by a matrix without a pivot.  `stream`: a hipStream_t.
+int stfem_vanka_invert_launch(double *B, double *out, int m, int mpad, int kpad, long long cell0, unsigned count, int *singular, void *stream);
+
+// stfem_stokes_vanka_cell.hip: one block per cell of the two-variable Stokes system (stfem_stokes_vanka_create_linearised)
+struct stokes_cell_vanka_desc {
+  int nblk, m, mpad, kpad, mode;
+  int var[8];                 // 0 velocity / 1 pressure, in BlockSlice order
+  double Alpha[64], Beta[64]; // nblk x nblk, row-major
+};
+struct stokes_cell_vanka;
+// row table: nblk-block rows -> (vector | variable << 8, element offset from the cell's first DoF of the variable), m entries of two ints
+int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &d, const int *rowtab_xy, const double *const *lin,
+                             stokes_cell_vanka **out, char (&err)[256]);
+int stokes_cell_vanka_update(stokes_cell_vanka *v, const double *const *lin, char (&err)[256]);
+// rows of y = B_c^-1 gather(src) of every cell to the scratch array [cell][mpad], returned in *rows
+int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_blocks, const double **rows, void *stream, char (&err)[256]);
+void stokes_cell_vanka_destroy(stokes_cell_vanka *v);
+#pragma GCC visibility pop

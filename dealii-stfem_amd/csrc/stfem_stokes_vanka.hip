@@ -8,8 +8,10 @@
 // weak boundary faces) and M = the assembled vector mass, both restricted to the cell (compute_block_matrix.h:50-139) with the
 // strong velocity constraints (row and column dropped, diagonal kept), inverted by Gauss-Jordan;
 //     vmult: dst = sum over cells of scatter(B_c^-1 gather(src)).
-// Axis-aligned uniform meshes only (the Kronecker path of csrc/stfem_stokes.hip): there the block of a cell depends only on which
-// neighbours it has - at most 27 blocks per mesh.  Set-up: every class block is read off the device operator itself, applied to
+// Axis-aligned uniform meshes (the Kronecker path of csrc/stfem_stokes.hip): there the block of a cell depends only on which
+// neighbours it has - at most 27 blocks per mesh; general meshes and the linearised operator (stfem_stokes_vanka_create_linearised)
+// hold one block per cell: set-up and streaming apply in stfem_stokes_vanka_cell.hip, the collecting launch is the one below.  Set-up
+// of the class blocks: every class block is read off the device operator itself, applied to
 // unit vectors on a mesh of 1 - 3 cells per direction with the cell in the position of its class (the reference's own method of
 // getting matrix entries, tests/tp_05dgp_support.cc:140-149) - no second implementation of the cell matrices.  Apply: the
 // MFMA class kernel of the scalar smoother (stfem_vanka_kernel.h) with a row table in place of its (block, node) arithmetic, rows
@@ -41,7 +43,7 @@ thread_local char g_sv_err[256] = "";
 struct StokesCollectParams {
   double *dst[VK_MAX_BLOCKS];
   const double *y;   // [slot][mpad]
-  const int *slot;   // cell -> slot
+  const int *slot;   // cell -> slot (nullptr: slot = cell, the one-block-per-cell layout)
   int nblk, mpad, pdg;
   int var[VK_MAX_BLOCKS], rowbase[VK_MAX_BLOCKS];
   int nc[3], ndu[3], ndp[3];
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(256) void stokes_vanka_collect_kernel(const StokesC
   double s = 0.0;
   if (var == 1 && P.pdg) {
     const long long cell = i >> 2;
-    s = P.y[size_t(P.slot[cell]) * P.mpad + P.rowbase[b] + int(i & 3)];
+    s = P.y[size_t(P.slot ? P.slot[cell] : cell) * P.mpad + P.rowbase[b] + int(i & 3)];
   } else {
     const int p = var == 0 ? 2 : 1, np = p + 1;
     const int *nd = var == 0 ? P.ndu : P.ndp;
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(256) void stokes_vanka_collect_kernel(const StokesC
         for (int kx = 0; kx < cnt[0]; ++kx) {
           const int cell = cc[0][kx] + P.nc[0] * (cc[1][ky] + P.nc[1] * cc[2][kz]);
           const int n = ll[0][kx] + np * (ll[1][ky] + np * ll[2][kz]);
-          s += P.y[size_t(P.slot[cell]) * P.mpad + rb + n];
+          s += P.y[size_t(P.slot ? P.slot[cell] : cell) * P.mpad + rb + n];
         }
   }
   double *d = P.dst[b] + i;
@@ -108,6 +110,8 @@ struct stfem_stokes_vanka {
   double *d_blocks = nullptr, *d_flat = nullptr;
   int2 *d_rowtab = nullptr;
   int *d_cellu = nullptr, *d_cellp = nullptr, *d_cls = nullptr, *d_slot = nullptr;
+  int mode = 0;                      // convection mode of the per-cell blocks
+  stokes_cell_vanka *cell = nullptr; // one block per cell (stfem_stokes_vanka_cell.hip): none of the class arrays above
 };
 
 #define SV_TRY(call)                                                                \
@@ -242,12 +246,11 @@ int build_class_blocks(stfem_stokes_vanka *v, const vanka::ClassTable &t, int np
   return vk_upload(&v->d_blocks, all, g_sv_err);
 }
 
-// The row table, the flat cell list with the cells' first velocity and pressure DoFs, and the scratch array
-int build_tables(stfem_stokes_vanka *v, const vanka::ClassTable &t, int npl)
+// The row table: row -> (vector, variable, element offset from the cell's first DoF of the variable)
+int row_table(const stfem_stokes_vanka *v, int npl, std::vector<int2> &rowtab)
 {
   const stfem_stokes_desc &d = v->d;
-  // ---- row table: row -> (vector, variable, element offset from the cell's first DoF of the variable)
-  std::vector<int2> rowtab(v->m);
+  rowtab.resize(v->m);
   for (int i = 0; i < v->nblk; ++i) {
     if (v->var[i] == 0) {
       for (int c = 0; c < 3; ++c)
@@ -264,6 +267,16 @@ int build_tables(stfem_stokes_vanka *v, const vanka::ClassTable &t, int npl)
       }
     }
   }
+  return STFEM_OK;
+}
+
+// The row table, the flat cell list with the cells' first velocity and pressure DoFs, and the scratch array
+int build_tables(stfem_stokes_vanka *v, const vanka::ClassTable &t, int npl)
+{
+  const stfem_stokes_desc &d = v->d;
+  std::vector<int2> rowtab;
+  int rc = row_table(v, npl, rowtab);
+  if (rc != STFEM_OK) return rc;
   // ---- cells grouped by class into batches of 16, four batches of one class per workgroup
   std::vector<int> firstu(t.cls.size()), firstp(t.cls.size());
   for (int cz = 0; cz < d.nc[2]; ++cz)
@@ -275,7 +288,7 @@ int build_tables(stfem_stokes_vanka *v, const vanka::ClassTable &t, int npl)
       }
   const vanka::CellList list = vanka::cell_list(t, -1);
   v->nquad = int(list.cls.size());
-  int rc = vk_upload(&v->d_rowtab, rowtab, g_sv_err);
+  rc = vk_upload(&v->d_rowtab, rowtab, g_sv_err);
   if (rc == STFEM_OK) rc = vk_upload(&v->d_cellu, vanka::gather_cells(list.order, firstu, -1), g_sv_err);
   if (rc == STFEM_OK) rc = vk_upload(&v->d_cellp, vanka::gather_cells(list.order, firstp, 0), g_sv_err);
   if (rc == STFEM_OK) rc = vk_upload(&v->d_cls, list.cls, g_sv_err);
@@ -301,10 +314,24 @@ void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v)
   (void)hipFree(v->d_cellp);
   (void)hipFree(v->d_cls);
   (void)hipFree(v->d_slot);
+  stokes_cell_vanka_destroy(v->cell);
   delete v;
 }
 
 int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v) { return v ? v->nclasses : 0; }
+
+// the rows of the cell block: block i holds the 81 velocity or the npl pressure DoFs of the cell from row rowbase[i]
+static int block_rows(stfem_stokes_vanka *v, int n_blocks, const int32_t *block_variable, int npl)
+{
+  v->nblk = n_blocks;
+  for (int i = 0; i < n_blocks; ++i) {
+    if (block_variable[i] < 0 || block_variable[i] > 1) return STFEM_ERR_INVALID_ARGUMENT;
+    v->var[i] = block_variable[i];
+    v->rowbase[i] = v->m;
+    v->m += block_variable[i] == 0 ? 81 : npl;
+  }
+  return v->m > VK_MAX_ROWS ? STFEM_ERR_UNSUPPORTED : STFEM_OK;
+}
 
 int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta,
                               stfem_stokes_vanka **out)
@@ -314,21 +341,16 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
   if (n_blocks > VK_MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
   stfem_stokes_desc d;
   int rc = stfem_stokes_internal_desc(ctx, &d);
-  if (rc == STFEM_OK && !d.cart) rc = STFEM_ERR_UNSUPPORTED; // (one block per cell on general meshes: not built for two variables)
   if (rc != STFEM_OK) return rc;
+  // one block per neighbour pattern needs identical cells; a general mesh gets one block per cell
+  if (!d.cart) return stfem_stokes_vanka_create_linearised(ctx, n_blocks, block_variable, Alpha, Beta, STFEM_CONVECTION_NONE, nullptr, out);
   std::unique_ptr<stfem_stokes_vanka, void (*)(stfem_stokes_vanka *)> v(new (std::nothrow) stfem_stokes_vanka, stfem_stokes_vanka_destroy);
   if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   v->ctx = ctx;
   v->d = d;
   const int npl = d.pspace ? 4 : 8;
-  v->nblk = n_blocks;
-  for (int i = 0; i < n_blocks; ++i) {
-    if (block_variable[i] < 0 || block_variable[i] > 1) return STFEM_ERR_INVALID_ARGUMENT;
-    v->var[i] = block_variable[i];
-    v->rowbase[i] = v->m;
-    v->m += block_variable[i] == 0 ? 81 : npl;
-  }
-  if (v->m > VK_MAX_ROWS) return STFEM_ERR_UNSUPPORTED;
+  rc = block_rows(v.get(), n_blocks, block_variable, npl);
+  if (rc != STFEM_OK) return rc;
   const vanka::TilePlan plan = vanka::stokes_tile_plan((v->m + 15) / 16);
   v->mtw = plan.mtw; v->parts = plan.parts; v->mt = plan.parts * plan.mtw;
   v->mpad = 16 * v->mt;
@@ -340,6 +362,63 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
   if (rc == STFEM_OK) rc = build_tables(v.get(), t, npl);
   if (rc == STFEM_OK) *out = v.release();
   return rc;
+}
+
+// One block per cell, on every mesh, of the operator linearised about lin_blocks (reinit_asm, stmg.h:929-965: set_data, then the
+// assembled matrix of compute_matrix_helper<OperatorMode::jacobian>, operators.h:1310-1318, and one inverted block per cell from it,
+// stmg.h:704-742, compute_block_matrix.h:50-139).  Every refusal is decided before anything touches the device.
+int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta,
+                                         int mode, const double *const *lin_blocks, stfem_stokes_vanka **out)
+{
+  if (!out) return STFEM_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (!ctx || !block_variable || !Alpha || !Beta || n_blocks < 1) return STFEM_ERR_INVALID_ARGUMENT;
+  if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_blocks)) return STFEM_ERR_INVALID_ARGUMENT;
+  if (n_blocks > VK_MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
+  stfem_stokes_desc d;
+  int rc = stfem_stokes_internal_desc(ctx, &d);
+  if (rc != STFEM_OK) return rc;
+  std::unique_ptr<stfem_stokes_vanka, void (*)(stfem_stokes_vanka *)> v(new (std::nothrow) stfem_stokes_vanka, stfem_stokes_vanka_destroy);
+  if (!v) return STFEM_ERR_OUT_OF_MEMORY;
+  v->ctx = ctx;
+  v->d = d;
+  const int npl = d.pspace ? 4 : 8;
+  rc = block_rows(v.get(), n_blocks, block_variable, npl);
+  if (rc != STFEM_OK) return rc;
+  if (mode != STFEM_CONVECTION_NONE) // (only the velocity entries are read: operators.h:835-866)
+    for (int i = 0; i < n_blocks; ++i)
+      if (v->var[i] == 0 && !lin_blocks[i]) return STFEM_ERR_INVALID_ARGUMENT;
+  v->mt = (v->m + 15) / 16;
+  v->mpad = 16 * v->mt;
+  v->kpad = ((v->m + 3) / 4) * 4;
+  v->nclasses = int((long long)d.nc[0] * d.nc[1] * d.nc[2]);
+  std::vector<int2> rowtab;
+  rc = row_table(v.get(), npl, rowtab);
+  if (rc != STFEM_OK) return rc;
+  stokes_cell_vanka_desc cd;
+  std::memset(&cd, 0, sizeof(cd));
+  v->mode = mode;
+  cd.nblk = n_blocks; cd.m = v->m; cd.mpad = v->mpad; cd.kpad = v->kpad; cd.mode = mode;
+  for (int i = 0; i < n_blocks; ++i) cd.var[i] = v->var[i];
+  for (int i = 0; i < n_blocks * n_blocks; ++i) { cd.Alpha[i] = Alpha[i]; cd.Beta[i] = Beta[i]; }
+  SV_TRY(hipSetDevice(d.device));
+  rc = stokes_cell_vanka_create(ctx, cd, &rowtab[0].x, lin_blocks, &v->cell, g_sv_err);
+  if (rc == STFEM_OK) *out = v.release();
+  return rc;
+}
+
+// The blocks of a smoother of stfem_stokes_vanka_create_linearised again, for new linearisation states: same mode, same storage
+int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_blocks)
+{
+  if (!v) return STFEM_ERR_INVALID_ARGUMENT;
+  if (!v->cell) return STFEM_ERR_UNSUPPORTED; // (class blocks hold the linear operator only)
+  if (v->mode != STFEM_CONVECTION_NONE) {
+    if (!lin_blocks) return STFEM_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < v->nblk; ++i)
+      if (v->var[i] == 0 && !lin_blocks[i]) return STFEM_ERR_INVALID_ARGUMENT;
+  }
+  SV_TRY(hipSetDevice(v->d.device));
+  return stokes_cell_vanka_update(v->cell, lin_blocks, g_sv_err);
 }
 
 // dst = (accumulate ? dst : 0) + omega * (sum over cells of scatter(B_c^-1 gather(src))); blocks in the order of the BlockSlice
@@ -359,25 +438,31 @@ int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, do
   } scope;
   SV_TRY(hipSetDevice(v->d.device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  VankaParams prm;
-  std::memset(&prm, 0, sizeof(prm));
-  for (int i = 0; i < v->nblk; ++i) {
-    prm.src[i] = src_blocks[i];
-    prm.dst[i] = dst_blocks[i];
-  }
-  prm.blocks = v->d_blocks;
-  prm.cell = v->d_cellu; prm.cell2 = v->d_cellp; prm.cls = v->d_cls; prm.rowtab = v->d_rowtab;
-  prm.nquad = v->nquad; prm.m = v->m; prm.mpad = v->mpad; prm.kpad = v->kpad; prm.p = 2;
-  prm.flat = v->d_flat; prm.omega = 1.0;
+  const double *rows = v->d_flat;
   (void)hipGetLastError();
-  const void *k = sv_kernel(v->mtw);
-  if (!k) return STFEM_ERR_UNSUPPORTED;
-  const int rc = vk_launch(k, dim3(v->nquad, v->parts), &prm, st, "vanka_apply_kernel", g_sv_err);
-  if (rc != STFEM_OK) return rc;
+  if (v->cell) { // one block per cell: every block streamed once, rows to the scratch array
+    const int rc = stokes_cell_vanka_apply(v->cell, src_blocks, &rows, st, g_sv_err);
+    if (rc != STFEM_OK) return rc;
+  } else {
+    VankaParams prm;
+    std::memset(&prm, 0, sizeof(prm));
+    for (int i = 0; i < v->nblk; ++i) {
+      prm.src[i] = src_blocks[i];
+      prm.dst[i] = dst_blocks[i];
+    }
+    prm.blocks = v->d_blocks;
+    prm.cell = v->d_cellu; prm.cell2 = v->d_cellp; prm.cls = v->d_cls; prm.rowtab = v->d_rowtab;
+    prm.nquad = v->nquad; prm.m = v->m; prm.mpad = v->mpad; prm.kpad = v->kpad; prm.p = 2;
+    prm.flat = v->d_flat; prm.omega = 1.0;
+    const void *k = sv_kernel(v->mtw);
+    if (!k) return STFEM_ERR_UNSUPPORTED;
+    const int rc = vk_launch(k, dim3(v->nquad, v->parts), &prm, st, "vanka_apply_kernel", g_sv_err);
+    if (rc != STFEM_OK) return rc;
+  }
   StokesCollectParams cp;
   std::memset(&cp, 0, sizeof(cp));
   for (int i = 0; i < v->nblk; ++i) { cp.dst[i] = dst_blocks[i]; cp.var[i] = v->var[i]; cp.rowbase[i] = v->rowbase[i]; }
-  cp.y = v->d_flat; cp.slot = v->d_slot; cp.nblk = v->nblk; cp.mpad = v->mpad; cp.pdg = v->d.pspace;
+  cp.y = rows; cp.slot = v->d_slot; cp.nblk = v->nblk; cp.mpad = v->mpad; cp.pdg = v->d.pspace;
   for (int k3 = 0; k3 < 3; ++k3) { cp.nc[k3] = v->d.nc[k3]; cp.ndu[k3] = v->d.ndu[k3]; cp.ndp[k3] = v->d.ndp[k3]; }
   cp.Nu = v->d.Nu; cp.Np = v->d.Np; cp.omega = omega; cp.accumulate = accumulate;
   const long long big = std::max(3 * v->d.Nu, v->d.Np);

@@ -1,0 +1,528 @@
+// Cell-patch Vanka smoother of the two-variable Stokes system with ONE BLOCK PER CELL: general (perturbed) meshes and the linearised
+// Navier-Stokes operator (stfem_stokes_vanka_create_linearised).
+//
+// Replaces the two steps of the reference's reinit_asm (include/stmg.h:929-965): space_operator_mf->set_data(mg_data[l]) followed by
+// the assembly of the linearised matrix (compute_matrix_helper<OperatorMode::jacobian>, operators.h:1310-1318), and the construction of
+// one inverted block per cell from that matrix (stmg.h:704-742, compute_block_matrix.h:50-139).  The block is the one of the header
+// comment of stfem_stokes_vanka.hip with K = the assembled A(b_j) of the column block's linearisation state b_j (operators.h:835-866):
+//   A(b) = [[nu K, -B^T], [B, 0]] + Nitsche terms of the weak faces + C_form(b, .) (form) / C_form(b, .) + C_form(., b) (jacobian),
+//   C_form(b, u)(v) = - int (u (x) b) : grad v - int_{weak faces} min(b.n, 0) u.v            (operators.h:1554-1567, 1738-1743).
+// Set-up on the device, a few cell layers at a time, in the stages of the scalar smoother (stfem_vanka.hip):
+//   stokes_cell_matrices_kernel   the cell's own (81 + npl)^2 matrix of A(b) and its 27 x 27 scalar mass, in plain matrix form
+//   stokes_vanka_assemble_kernel  restriction of the assembled matrices to the cell's DoFs, constraints, valence, Alpha / Beta
+//   vanka_invert_kernel<double>   (stfem_vanka.hip) Gauss-Jordan, straight into the apply's layout
+// Apply: stokes_vanka_apply_percell_kernel streams every block from HBM once and leaves the rows in the scratch array; the collecting
+// launch of stfem_stokes_vanka.hip sums them per DoF: two launches, no colours, no atomics, fixed summation order.
+#include "stfem_stokes_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "stfem_vanka_kernel.h"
+#include "stfem_vanka_setup.h"
+
+namespace vanka = stfem::vanka;
+
+namespace {
+
+struct StokesCellMatParams {
+  const double *vertices; // (nc + 1)^3 x 3
+  const double *b;        // linearisation velocity (3 Nu, component-major); nullptr: none
+  double *Ac, *Mc;        // [cell of the window][nl][nl], [cell of the window][27][27] (nullptr: not wanted)
+  int nc[3], ndu[3];
+  long long Nu, cell0;    // first cell of the window
+  int dmask, weak_mask, mode;
+  double nu, gamma1, gamma2;
+  double xq[3], wq[3];
+};
+
+// FE_Q(2) on the nodes 0, 1/2, 1 and FE_Q(1), value and derivative of node n at x
+__device__ __forceinline__ double q2v(int n, double x) { return n == 0 ? (2 * x - 1) * (x - 1) : (n == 1 ? 4 * x * (1 - x) : x * (2 * x - 1)); }
+__device__ __forceinline__ double q2d(int n, double x) { return n == 0 ? 4 * x - 3 : (n == 1 ? 4 - 8 * x : 4 * x - 1); }
+__device__ __forceinline__ double q1v(int n, double x) { return n == 0 ? 1 - x : x; }
+
+// One workgroup per cell; a thread takes entries (row, column) of the cell matrix.  Phase 0: the cell term at the operator's 3 x 3 x 3
+// Gauss points (MappingQ1 Jacobian from the eight vertices); phases 1 - 6: the Nitsche and inflow terms of the cell's weak faces at
+// their 3 x 3 points, h = sqrt(face area) (get_h_face, operators.h:184-209).  Set-up code: plain matrix form, not tuned.
+template <bool PDG>
+__global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesCellMatParams P)
+{
+  constexpr int NPL = PDG ? 4 : 8, NL = 81 + NPL;
+  __shared__ double G[27][27][3]; // physical gradient of velocity node n at point q
+  __shared__ double PH[27][27];   // its value
+  __shared__ double PS[27][NPL];  // pressure functions
+  __shared__ double JI[27][9], W[27], NR[9][3], BQ[27][3], INF[9];
+  __shared__ double bl[81], V[8][3];
+  const int tid = threadIdx.x;
+  const long long cell = P.cell0 + blockIdx.x;
+  const int cx = int(cell % P.nc[0]), cy = int((cell / P.nc[0]) % P.nc[1]), cz = int(cell / ((long long)P.nc[0] * P.nc[1]));
+  const int cc[3] = {cx, cy, cz};
+  double *Ac = P.Ac + (size_t)blockIdx.x * NL * NL;
+  if (tid < 24) {
+    const int v = tid / 3, d = tid % 3;
+    const long long nvx = P.nc[0] + 1, nvy = P.nc[1] + 1;
+    V[v][d] = P.vertices[3 * ((cx + (v & 1)) + nvx * ((cy + ((v >> 1) & 1)) + nvy * (long long)(cz + (v >> 2)))) + d];
+  }
+  if (tid < 81) { // read_dof_values: entries on strongly constrained DoFs read as 0
+    const int comp = tid / 27, n = tid % 27;
+    const int ix = 2 * cx + n % 3, iy = 2 * cy + (n / 3) % 3, iz = 2 * cz + n / 9;
+    const bool con = ((P.dmask & 1) && ix == 0) || ((P.dmask & 2) && ix == P.ndu[0] - 1) || ((P.dmask & 4) && iy == 0) ||
+                     ((P.dmask & 8) && iy == P.ndu[1] - 1) || ((P.dmask & 16) && iz == 0) || ((P.dmask & 32) && iz == P.ndu[2] - 1);
+    bl[tid] = (P.b && P.mode && !con) ? P.b[comp * P.Nu + ix + (long long)P.ndu[0] * (iy + (long long)P.ndu[1] * iz)] : 0.0;
+  }
+  __syncthreads();
+  for (int phase = 0; phase < 7; ++phase) {
+    const int f = phase - 1, fd = f >> 1, fs = f & 1; // the face of phases 1 - 6
+    if (phase > 0 && !((P.weak_mask >> f & 1) && cc[fd] == (fs ? P.nc[fd] - 1 : 0))) continue; // (uniform)
+    const int npts = phase == 0 ? 27 : 9;
+    const int t1 = fd == 0 ? 1 : 0;
+    // reference coordinates of point q
+    auto point = [&](int q, double (&xi)[3]) {
+      if (phase == 0) {
+        xi[0] = P.xq[q % 3]; xi[1] = P.xq[(q / 3) % 3]; xi[2] = P.xq[q / 9];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xi[k] = k == fd ? double(fs) : P.xq[k == t1 ? q % 3 : q / 3];
+      }
+    };
+    // ---- geometry of the points
+    if (tid < npts) {
+      double xi[3];
+      point(tid, xi);
+      const double fx[2] = {1 - xi[0], xi[0]}, fy[2] = {1 - xi[1], xi[1]}, fz[2] = {1 - xi[2], xi[2]}, dd[2] = {-1.0, 1.0};
+      double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+      for (int k = 0; k < 2; ++k)
+        for (int j = 0; j < 2; ++j)
+          for (int i = 0; i < 2; ++i)
+            for (int d = 0; d < 3; ++d) {
+              const double Vd = V[i + 2 * j + 4 * k][d];
+              J[d][0] += Vd * dd[i] * fy[j] * fz[k];
+              J[d][1] += Vd * fx[i] * dd[j] * fz[k];
+              J[d][2] += Vd * fx[i] * fy[j] * dd[k];
+            }
+      const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
+                         J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+      const double id = 1.0 / det;
+      double *Ji = JI[tid]; // Ji[3 e + d] = d xi_e / d x_d
+      Ji[0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
+      Ji[1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
+      Ji[2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
+      Ji[3] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
+      Ji[4] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
+      Ji[5] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
+      Ji[6] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
+      Ji[7] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
+      Ji[8] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+      if (phase == 0) {
+        W[tid] = det * P.wq[tid % 3] * P.wq[(tid / 3) % 3] * P.wq[tid / 9];
+      } else {
+        double mm[3], len = 0.0;
+        for (int k = 0; k < 3; ++k) {
+          mm[k] = (fs ? 1.0 : -1.0) * Ji[3 * fd + k];
+          len += mm[k] * mm[k];
+        }
+        len = sqrt(len);
+        for (int k = 0; k < 3; ++k) NR[tid][k] = mm[k] / len;
+        W[tid] = fabs(det) * len * P.wq[tid % 3] * P.wq[tid / 3];
+      }
+    }
+    __syncthreads();
+    // ---- the functions at the points
+    for (int e = tid; e < npts * 27; e += 256) {
+      const int q = e / 27, n = e % 27, a = n % 3, b = (n / 3) % 3, c = n / 9;
+      double xi[3];
+      point(q, xi);
+      const double sx = q2v(a, xi[0]), sy = q2v(b, xi[1]), sz = q2v(c, xi[2]);
+      const double gr[3] = {q2d(a, xi[0]) * sy * sz, sx * q2d(b, xi[1]) * sz, sx * sy * q2d(c, xi[2])};
+      const double *Ji = JI[q];
+      PH[q][n] = sx * sy * sz;
+      for (int d = 0; d < 3; ++d) G[q][n][d] = gr[0] * Ji[d] + gr[1] * Ji[3 + d] + gr[2] * Ji[6 + d];
+    }
+    for (int e = tid; e < npts * NPL; e += 256) {
+      const int q = e / NPL, l = e % NPL;
+      double xi[3];
+      point(q, xi);
+      // FE_DGP(1): deal.II's basis 1, l(xi), l(eta), l(zeta), l(x) = sqrt 3 (2 x - 1)
+      if (PDG) PS[q][l] = l == 0 ? 1.0 : 1.7320508075688772 * (2.0 * xi[l - 1] - 1.0);
+      else PS[q][l] = q1v(l & 1, xi[0]) * q1v((l >> 1) & 1, xi[1]) * q1v(l >> 2, xi[2]);
+    }
+    __syncthreads();
+    if (tid < npts * 3) {
+      const int q = tid / 3, comp = tid % 3;
+      double s = 0.0;
+      for (int n = 0; n < 27; ++n) s += PH[q][n] * bl[comp * 27 + n];
+      BQ[q][comp] = s;
+    }
+    __syncthreads();
+    double h = 1.0;
+    if (phase > 0) {
+      double area = 0.0;
+      for (int q = 0; q < 9; ++q) area += W[q];
+      h = sqrt(area);
+      if (tid < 9) INF[tid] = P.mode ? -fmin(BQ[tid][0] * NR[tid][0] + BQ[tid][1] * NR[tid][1] + BQ[tid][2] * NR[tid][2], 0.0) * W[tid] : 0.0;
+      __syncthreads();
+    }
+    const double g1h = P.gamma1 / h, g2h = P.gamma2 / h;
+    // ---- the entries
+    for (int e = tid; e < NL * NL; e += 256) {
+      const int r = e / NL, c = e % NL;
+      double acc = 0.0;
+      if (r < 81 && c < 81) {
+        const int ci = r / 27, a = r % 27, cj = c / 27, b = c % 27;
+        for (int q = 0; q < npts; ++q) {
+          const double *ga = G[q][a], *gb = G[q][b];
+          const double pa = PH[q][a], pb = PH[q][b];
+          double t = 0.0;
+          if (phase == 0) {
+            if (ci == cj) {
+              t = P.nu * (ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2]);
+              if (P.mode) t -= pb * (BQ[q][0] * ga[0] + BQ[q][1] * ga[1] + BQ[q][2] * ga[2]); // - (u (x) b) : grad v
+            }
+            if (P.mode == 2) t -= BQ[q][ci] * pb * ga[cj];                                    // - (b (x) u) : grad v
+            acc += W[q] * t;
+          } else {
+            const double *n = NR[q];
+            if (ci == cj) {
+              const double dna = ga[0] * n[0] + ga[1] * n[1] + ga[2] * n[2], dnb = gb[0] * n[0] + gb[1] * n[1] + gb[2] * n[2];
+              t = -P.nu * dnb * pa + g1h * pa * pb - P.nu * pb * dna;
+            }
+            t += g2h * n[ci] * n[cj] * pa * pb;
+            acc += W[q] * t;
+            if (ci == cj) acc += INF[q] * pa * pb; // - min(b.n, 0) u.v
+          }
+        }
+      } else if (r < 81) { // - p div v; faces: p n.v
+        const int ci = r / 27, a = r % 27, l = c - 81;
+        for (int q = 0; q < npts; ++q)
+          acc += phase == 0 ? -W[q] * PS[q][l] * G[q][a][ci] : W[q] * PS[q][l] * NR[q][ci] * PH[q][a];
+      } else if (c < 81) { // q div u; faces: - q u.n
+        const int cj = c / 27, b = c % 27, l = r - 81;
+        for (int q = 0; q < npts; ++q)
+          acc += phase == 0 ? W[q] * PS[q][l] * G[q][b][cj] : -W[q] * PS[q][l] * NR[q][cj] * PH[q][b];
+      }
+      if (phase == 0) Ac[e] = acc;
+      else Ac[e] += acc; // (the same thread wrote the entry in the phases before)
+    }
+    if (phase == 0 && P.Mc) {
+      double *Mc = P.Mc + (size_t)blockIdx.x * 729;
+      for (int e = tid; e < 729; e += 256) {
+        const int a = e / 27, b = e % 27;
+        double s = 0.0;
+        for (int q = 0; q < 27; ++q) s += W[q] * PH[q][a] * PH[q][b];
+        Mc[e] = s;
+      }
+    }
+    __syncthreads(); // the next phase rewrites the tables
+  }
+}
+
+struct StokesAssembleParams {
+  const double *Ac, *Mc;    // cell matrices of the cell layers [zw0, ...): Ac[state][cell of the window][nl][nl], Mc[cell][27][27]
+  size_t state_stride;      // doubles between the states of Ac
+  double *B;                // [cell of the batch][m][m]
+  const int *nbr, *face;    // vanka::CellDofTables
+  const int *rowblk, *rowdof;
+  int nc[3], dmask, nl, m, nblk;
+  int zw0, z0;
+  int var[VK_MAX_BLOCKS], sel[VK_MAX_BLOCKS];
+  double Alpha[VK_MAX_BLOCKS * VK_MAX_BLOCKS], Beta[VK_MAX_BLOCKS * VK_MAX_BLOCKS];
+};
+
+// One workgroup per cell: entry (r, s) of the block = valence(r) (Alpha(i, j) A_j(k, l) + [velocity, velocity] Beta(i, j) M(k, l)) with the
+// ASSEMBLED matrices restricted to the cell's DoFs k, l: the cell's own matrix + what the neighbours holding both DoFs add
+// (compute_block_matrix.h:50-139; cells in z, y, x order); a strongly constrained DoF keeps only the entries with itself.
+__global__ __launch_bounds__(256) void stokes_vanka_assemble_kernel(const StokesAssembleParams P)
+{
+  __shared__ double s_val[96];
+  __shared__ int s_con[96];
+  const int lc = blockIdx.x, cpl = P.nc[0] * P.nc[1];
+  const int cz = P.z0 + lc / cpl, cy = (lc % cpl) / P.nc[0], cx = lc % P.nc[0];
+  const int cc[3] = {cx, cy, cz};
+  auto has_cell = [&](int s) { // the neighbour at shift s exists
+    const int sh[3] = {s % 3 - 1, (s / 3) % 3 - 1, s / 9 - 1};
+    return cx + sh[0] >= 0 && cx + sh[0] < P.nc[0] && cy + sh[1] >= 0 && cy + sh[1] < P.nc[1] && cz + sh[2] >= 0 && cz + sh[2] < P.nc[2];
+  };
+  for (int k = threadIdx.x; k < P.nl; k += 256) {
+    int val = 0;
+    for (int s = 0; s < 27; ++s)
+      if (P.nbr[k * 27 + s] >= 0 && has_cell(s)) ++val;
+    bool con = false;
+    for (int d = 0; d < 3; ++d) {
+      if ((P.face[k] >> (2 * d) & 1) && cc[d] == 0 && (P.dmask >> (2 * d) & 1)) con = true;
+      if ((P.face[k] >> (2 * d + 1) & 1) && cc[d] == P.nc[d] - 1 && (P.dmask >> (2 * d + 1) & 1)) con = true;
+    }
+    s_val[k] = double(val);
+    s_con[k] = con;
+  }
+  __syncthreads();
+  double *B = P.B + (size_t)lc * P.m * P.m;
+  const size_t nl2 = size_t(P.nl) * P.nl;
+  for (int e = threadIdx.x; e < P.m * P.m; e += 256) {
+    const int r = e / P.m, s = e % P.m;
+    const int i = P.rowblk[r], j = P.rowblk[s], a = P.rowdof[r], b = P.rowdof[s];
+    double out = 0.0;
+    if (a == b || !(s_con[a] || s_con[b])) {
+      const bool mass = a < 81 && b < 81 && a / 27 == b / 27;
+      const double *A = P.Ac + size_t(P.sel[j]) * P.state_stride;
+      double ks = 0.0, ms = 0.0;
+      for (int sh = 0; sh < 27; ++sh) {
+        const int a2 = P.nbr[a * 27 + sh], b2 = P.nbr[b * 27 + sh];
+        if (a2 < 0 || b2 < 0 || !has_cell(sh)) continue;
+        const size_t c2 = size_t(cx + sh % 3 - 1) + size_t(P.nc[0]) * (size_t(cy + (sh / 3) % 3 - 1) + size_t(P.nc[1]) * size_t(cz + sh / 9 - 1 - P.zw0));
+        ks += A[c2 * nl2 + size_t(a2) * P.nl + b2];
+        if (mass) ms += P.Mc[c2 * 729 + (a2 % 27) * 27 + b2 % 27];
+      }
+      const double al = P.Alpha[i * P.nblk + j], be = P.Beta[i * P.nblk + j];
+      if (be != 0.0 && P.var[i] == 0 && P.var[j] == 0) out += be * ms; // M_mask(0, 0) only
+      if (al != 0.0) out += al * ks;
+      out *= s_val[a];
+    }
+    B[e] = out;
+  }
+}
+
+struct StokesCellApplyParams {
+  const double *src[VK_MAX_BLOCKS];
+  const double *blocks; // [cell][kpad][mpad], element (row r, column k) of the cell's inverse at [k][r]
+  double *flat;         // Y[cell][mpad]
+  const int2 *rowtab;   // row -> (vector | variable << 8, element offset from the cell's first DoF of the variable)
+  int m, mpad, kpad, pdg;
+  int nc[3], ndu[3], ndp[3];
+};
+
+typedef double double2_t __attribute__((ext_vector_type(2)));
+
+// y = B_c^-1 gather(src) per cell, the block streamed from HBM once (the reference's apply: stmg.h:845-867): one workgroup per cell.
+// HBM-bound: kpad * mpad doubles per cell (70 kB at m = 89) against 2 m of DoF traffic.  A thread holds a PAIR of rows (one 16-byte
+// load per k) and the threads are dealt over 256 / (mpad / 2) groups that split k between them - at m = 89 five groups of 48 threads,
+// 240 of 256 busy, each step of the k loop reading 5 consecutive k rows = 3840 contiguous bytes (thread r = row r with 8-byte loads,
+// the scalar kernel's shape, would leave 167 threads idle there).  Four loads of a thread are in flight at a time.  The partial sums
+// of the groups meet in LDS and are added in ascending group order: reproducible.
+__global__ __launch_bounds__(256) void stokes_vanka_apply_percell_kernel(const StokesCellApplyParams P)
+{
+  __shared__ double xs[VK_MAX_ROWS];
+  __shared__ double part[VK_MAX_ROWS]; // [group][mpad], groups * mpad <= 512
+  const int tid = threadIdx.x;
+  const long long cell = blockIdx.x;
+  const int cx = int(cell % P.nc[0]), cy = int((cell / P.nc[0]) % P.nc[1]), cz = int(cell / ((long long)P.nc[0] * P.nc[1]));
+  const long long firstu = 2 * cx + (long long)P.ndu[0] * (2 * cy + (long long)P.ndu[1] * 2 * cz);
+  const long long firstp = P.pdg ? 4 * cell : cx + (long long)P.ndp[0] * (cy + (long long)P.ndp[1] * cz);
+  for (int r = tid; r < P.kpad; r += 256) {
+    double v = 0.0;
+    if (r < P.m) {
+      const int2 e = P.rowtab[r];
+      const int blk = e.x & 255;
+      const double *sp = P.src[0];
+#pragma unroll
+      for (int b = 1; b < VK_MAX_BLOCKS; ++b)
+        if (b == blk) sp = P.src[b];
+      v = sp[((e.x >> 8) ? firstp : firstu) + e.y];
+    }
+    xs[r] = v;
+  }
+  __syncthreads();
+  const int RP = P.mpad >> 1, KG = 256 / RP; // row pairs, k groups
+  const int rp = tid % RP, kg = tid / RP;
+  if (kg < KG) {
+    const double2_t *B = reinterpret_cast<const double2_t *>(P.blocks + (size_t)cell * P.kpad * P.mpad) + rp;
+    double2_t a0 = {0, 0}, a1 = {0, 0}, a2 = {0, 0}, a3 = {0, 0};
+    int k = kg;
+    for (; k + 3 * KG < P.kpad; k += 4 * KG) {
+      const double2_t b0 = __builtin_nontemporal_load(B + (size_t)k * RP);
+      const double2_t b1 = __builtin_nontemporal_load(B + (size_t)(k + KG) * RP);
+      const double2_t b2 = __builtin_nontemporal_load(B + (size_t)(k + 2 * KG) * RP);
+      const double2_t b3 = __builtin_nontemporal_load(B + (size_t)(k + 3 * KG) * RP);
+      a0 += b0 * xs[k];
+      a1 += b1 * xs[k + KG];
+      a2 += b2 * xs[k + 2 * KG];
+      a3 += b3 * xs[k + 3 * KG];
+    }
+    for (; k < P.kpad; k += KG) a0 += __builtin_nontemporal_load(B + (size_t)k * RP) * xs[k];
+    const double2_t s = (a0 + a1) + (a2 + a3);
+    part[kg * P.mpad + 2 * rp] = s.x;
+    part[kg * P.mpad + 2 * rp + 1] = s.y;
+  }
+  __syncthreads();
+  for (int r = tid; r < P.m; r += 256) {
+    double s = part[r];
+    for (int g = 1; g < KG; ++g) s += part[g * P.mpad + r];
+    P.flat[(size_t)cell * P.mpad + r] = s;
+  }
+}
+
+} // namespace
+
+struct stokes_cell_vanka {
+  stfem_stokes_ctx *ctx = nullptr;
+  stokes_cell_vanka_desc d;
+  int nl = 0, npl = 0;
+  double *d_blocks = nullptr, *d_flat = nullptr;
+  int2 *d_rowtab = nullptr;
+  int *d_nbr = nullptr, *d_face = nullptr, *d_rowblk = nullptr, *d_rowdof = nullptr;
+};
+
+namespace {
+
+// Stages 1 - 3 into v->d_blocks, a few cell layers at a time with a window of cell matrices (the batch's layers and one on either
+// side), as vanka_create_per_cell_device does it.  fresh: the blocks are not allocated yet - they must fit beside the scratch.
+int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh, char (&err)[256])
+{
+  stfem_stokes_ctx *c = v->ctx;
+  const stokes_cell_vanka_desc &d = v->d;
+  const int nl = v->nl, m = d.m;
+  const int ncx = c->nc[0], ncy = c->nc[1], ncz = c->nc[2];
+  const size_t cpl = size_t(ncx) * ncy, ncells = cpl * ncz, bsz = size_t(d.kpad) * d.mpad;
+  int sel[VK_MAX_BLOCKS];
+  const double *state[VK_MAX_BLOCKS];
+  const int nstates = vanka::distinct_states(d.nblk, d.var, d.mode ? lin : nullptr, sel, state);
+  const size_t nl2 = size_t(nl) * nl;
+  const size_t km_layer = (size_t(nstates) * nl2 + 729) * cpl * sizeof(double), b_layer = cpl * size_t(m) * m * sizeof(double);
+  if (hipSetDevice(c->device) != hipSuccess) return STFEM_ERR_HIP;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+  const double need = double(ncells) * double(bsz) * sizeof(double);
+  // scratch of one batch of L cell layers: (L + 2) layers of cell matrices + L layers of blocks; at most 6 GB, and never more than
+  // what is left beside the blocks themselves
+  const double budget = std::min(6e9, 0.9 * double(free_b) - (fresh ? need : 0.0));
+  if (budget < 3.0 * double(km_layer) + double(b_layer)) {
+    snprintf(err, sizeof(err), "per-cell Stokes blocks of %zu cells need %.2f GB and %.2f GB of set-up scratch (%.2f GB free)", ncells, need * 1e-9,
+             (3.0 * double(km_layer) + double(b_layer)) * 1e-9, double(free_b) * 1e-9);
+    return STFEM_ERR_OUT_OF_MEMORY;
+  }
+  int L = int((budget - 2.0 * double(km_layer)) / double(km_layer + b_layer));
+  L = std::max(1, std::min(L, ncz));
+  if (fresh) {
+    const int rc = vk_alloc(reinterpret_cast<void **>(&v->d_blocks), ncells * bsz * sizeof(double), err);
+    if (rc != STFEM_OK) return rc;
+  }
+  const size_t win_cells = cpl * size_t(std::min(ncz, L + 2));
+  double *d_A = nullptr, *d_M = nullptr, *d_B = nullptr;
+  int *d_flag = nullptr;
+  auto cleanup = [&]() {
+    (void)hipFree(d_A);
+    (void)hipFree(d_M);
+    (void)hipFree(d_B);
+    (void)hipFree(d_flag);
+  };
+  int rc = vk_alloc(reinterpret_cast<void **>(&d_A), size_t(nstates) * win_cells * nl2 * sizeof(double), err);
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_M), win_cells * 729 * sizeof(double), err);
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_B), cpl * L * size_t(m) * m * sizeof(double), err);
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_flag), sizeof(int), err);
+  if (rc != STFEM_OK) {
+    cleanup();
+    return rc;
+  }
+  hipError_t e = hipMemset(d_flag, 0, sizeof(int));
+  StokesCellMatParams mp;
+  std::memset(&mp, 0, sizeof(mp));
+  mp.vertices = c->d_vertices;
+  for (int k = 0; k < 3; ++k) { mp.nc[k] = c->nc[k]; mp.ndu[k] = c->ndu[k]; mp.xq[k] = c->base.xq[k]; mp.wq[k] = c->base.wq[k]; }
+  mp.Nu = c->Nu; mp.dmask = c->dmask; mp.weak_mask = c->weak_mask; mp.mode = d.mode;
+  mp.nu = c->nu; mp.gamma1 = c->nu * c->penalty1; mp.gamma2 = c->penalty2;
+  StokesAssembleParams ap;
+  std::memset(&ap, 0, sizeof(ap));
+  ap.Ac = d_A; ap.Mc = d_M; ap.state_stride = win_cells * nl2; ap.B = d_B;
+  ap.nbr = v->d_nbr; ap.face = v->d_face; ap.rowblk = v->d_rowblk; ap.rowdof = v->d_rowdof;
+  for (int k = 0; k < 3; ++k) ap.nc[k] = c->nc[k];
+  ap.dmask = c->dmask; ap.nl = nl; ap.m = m; ap.nblk = d.nblk;
+  for (int i = 0; i < d.nblk; ++i) { ap.var[i] = d.var[i]; ap.sel[i] = sel[i]; }
+  for (int i = 0; i < d.nblk * d.nblk; ++i) { ap.Alpha[i] = d.Alpha[i]; ap.Beta[i] = d.Beta[i]; }
+  const void *cellk = c->pspace ? reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<false>);
+  (void)hipGetLastError();
+  for (int z0 = 0; z0 < ncz && e == hipSuccess && rc == STFEM_OK; z0 += L) {
+    const int z1 = std::min(ncz, z0 + L), zw0 = std::max(0, z0 - 1), zw1 = std::min(ncz, z1 + 1);
+    const size_t wcells = cpl * size_t(zw1 - zw0), bcells = cpl * size_t(z1 - z0);
+    mp.cell0 = (long long)cpl * zw0;
+    for (int s = 0; s < nstates && rc == STFEM_OK; ++s) {
+      mp.b = state[s];
+      mp.Ac = d_A + size_t(s) * ap.state_stride;
+      mp.Mc = s == 0 ? d_M : nullptr;
+      rc = vk_launch(cellk, dim3((unsigned)wcells), &mp, nullptr, "stokes_cell_matrices_kernel", err);
+    }
+    ap.zw0 = zw0; ap.z0 = z0;
+    if (rc == STFEM_OK) rc = vk_launch(reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel), dim3((unsigned)bcells), &ap, nullptr, "stokes_vanka_assemble_kernel", err);
+    if (rc == STFEM_OK) {
+      rc = stfem_vanka_invert_launch(d_B, v->d_blocks, m, d.mpad, d.kpad, (long long)cpl * z0, (unsigned)bcells, d_flag, nullptr);
+      if (rc != STFEM_OK) snprintf(err, sizeof(err), "vanka_invert_kernel: launch failed");
+    }
+    if (rc == STFEM_OK) e = hipDeviceSynchronize(); // (the next batch reuses the scratch)
+  }
+  int flag = 0;
+  if (rc == STFEM_OK && e == hipSuccess) e = hipMemcpy(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost);
+  cleanup();
+  if (rc != STFEM_OK) return rc;
+  if (e != hipSuccess) {
+    snprintf(err, sizeof(err), "per-cell Stokes block set-up: %s", hipGetErrorString(e));
+    return STFEM_ERR_HIP;
+  }
+  if (flag) {
+    snprintf(err, sizeof(err), "singular cell block");
+    return STFEM_ERR_INVALID_ARGUMENT;
+  }
+  return STFEM_OK;
+}
+
+} // namespace
+
+void stokes_cell_vanka_destroy(stokes_cell_vanka *v)
+{
+  if (!v) return;
+  (void)hipFree(v->d_blocks);
+  (void)hipFree(v->d_flat);
+  (void)hipFree(v->d_rowtab);
+  (void)hipFree(v->d_nbr);
+  (void)hipFree(v->d_face);
+  (void)hipFree(v->d_rowblk);
+  (void)hipFree(v->d_rowdof);
+  delete v;
+}
+
+int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &d, const int *rowtab_xy, const double *const *lin,
+                             stokes_cell_vanka **out, char (&err)[256])
+{
+  *out = nullptr;
+  stokes_cell_vanka *v = new (std::nothrow) stokes_cell_vanka;
+  if (!v) return STFEM_ERR_OUT_OF_MEMORY;
+  v->ctx = c;
+  v->d = d;
+  v->npl = c->pspace ? 4 : 8;
+  v->nl = 81 + v->npl;
+  const vanka::CellDofTables t = vanka::stokes_cell_dof_tables(c->pspace != 0);
+  std::vector<int> rowblk, rowdof;
+  vanka::stokes_row_dofs(d.nblk, d.var, v->npl, rowblk, rowdof);
+  std::vector<int2> rowtab(d.m);
+  for (int r = 0; r < d.m; ++r) rowtab[r] = make_int2(rowtab_xy[2 * r], rowtab_xy[2 * r + 1]);
+  const size_t ncells = size_t(c->nc[0]) * c->nc[1] * c->nc[2];
+  int rc = vk_upload(&v->d_nbr, t.nbr, err);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_face, t.face, err);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_rowblk, rowblk, err);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_rowdof, rowdof, err);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_rowtab, rowtab, err);
+  if (rc == STFEM_OK) rc = build_blocks(v, lin, true, err);
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&v->d_flat), ncells * d.mpad * sizeof(double), err);
+  if (rc != STFEM_OK) {
+    stokes_cell_vanka_destroy(v);
+    return rc;
+  }
+  *out = v;
+  return STFEM_OK;
+}
+
+int stokes_cell_vanka_update(stokes_cell_vanka *v, const double *const *lin, char (&err)[256]) { return build_blocks(v, lin, false, err); }
+
+int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_blocks, const double **rows, void *stream, char (&err)[256])
+{
+  const stfem_stokes_ctx *c = v->ctx;
+  StokesCellApplyParams p;
+  std::memset(&p, 0, sizeof(p));
+  for (int i = 0; i < v->d.nblk; ++i) p.src[i] = src_blocks[i];
+  p.blocks = v->d_blocks; p.flat = v->d_flat; p.rowtab = v->d_rowtab;
+  p.m = v->d.m; p.mpad = v->d.mpad; p.kpad = v->d.kpad; p.pdg = c->pspace;
+  for (int k = 0; k < 3; ++k) { p.nc[k] = c->nc[k]; p.ndu[k] = c->ndu[k]; p.ndp[k] = c->ndp[k]; }
+  *rows = v->d_flat;
+  const size_t ncells = size_t(c->nc[0]) * c->nc[1] * c->nc[2];
+  return vk_launch(reinterpret_cast<const void *>(&stokes_vanka_apply_percell_kernel), dim3((unsigned)ncells), &p, static_cast<hipStream_t>(stream),
+                   "stokes_vanka_apply_percell_kernel", err);
+}

@@ -340,6 +340,14 @@ thread_local char g_vanka_err[256] = "";
 
 } // namespace
 
+// vanka_invert_kernel<double> for the other translation units (the per-cell Stokes blocks, stfem_stokes_vanka_cell.hip)
+int stfem_vanka_invert_launch(double *B, double *out, int m, int mpad, int kpad, long long cell0, unsigned count, int *singular, void *stream)
+{
+  if (m < 1 || m > VK_MAX_ROWS || count == 0) return STFEM_ERR_INVALID_ARGUMENT;
+  hipLaunchKernelGGL(vanka_invert_kernel<double>, dim3(count), dim3(256), 0, static_cast<hipStream_t>(stream), B, out, m, mpad, kpad, cell0, singular);
+  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
+}
+
 constexpr int VK_FLAT = 8; // the launch after the eight colours: all cells at once (two-phase apply)
 
 struct stfem_vanka {

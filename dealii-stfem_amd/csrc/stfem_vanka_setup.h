@@ -1,6 +1,7 @@
 // Host-side set-up steps shared by the cell-patch smoothers (stfem_vanka.hip: scalar systems; stfem_stokes_vanka.hip: the
 // two-variable Stokes system): block classes of an axis-aligned uniform mesh, cell lists of the apply launches, tile plans, and
-// the way from a combined cell matrix to the stored inverse.  Plain C++17, no HIP: csrc/test_vanka_setup.cpp runs it on the CPU.
+// the way from a combined cell matrix to the stored inverse, and the index tables of the one-block-per-cell Stokes layout
+// (stfem_stokes_vanka_cell.hip).  Plain C++17, no HIP: csrc/test_vanka_setup.cpp and csrc/test_stokes_vanka_setup.cpp run it on the CPU.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -204,6 +205,77 @@ bool finish_block(int m, std::vector<double> &B, const std::vector<int> &dof, co
   for (int k = 0; k < kpad; ++k)
     for (int r = 0; r < mpad; ++r) out[size_t(k) * mpad + r] = (k < m && r < m) ? T(B[size_t(r) * m + k]) : T(0);
   return true;
+}
+
+// ---- one block per cell of the two-variable (Stokes) system: the cell's DoFs and the cells that share them ----
+// Cell DoF k: 0 .. 80 velocity (component k / 27, node k % 27 = a + 3 b + 9 e of the FE_Q(2) cell), 81 .. the pressure DoFs:
+// FE_Q(1) vertices a + 2 b + 4 e, or the four FE_DGP(1) functions of the cell, which no other cell holds.
+struct CellDofTables {
+  int nl = 0;            // 81 + pressure DoFs of a cell
+  std::vector<int> nbr;  // [nl][27]: the DoF's index in the neighbour cell at shift (sx + 1) + 3 (sy + 1) + 9 (sz + 1), -1: not held there
+  std::vector<int> face; // [nl]: bit 2 d / 2 d + 1: a velocity DoF on the cell's lower / upper face of direction d (strong constraints)
+};
+inline CellDofTables stokes_cell_dof_tables(bool pdg)
+{
+  CellDofTables t;
+  const int npl = pdg ? 4 : 8;
+  t.nl = 81 + npl;
+  t.nbr.assign(size_t(t.nl) * 27, -1);
+  t.face.assign(t.nl, 0);
+  for (int k = 0; k < t.nl; ++k) {
+    const bool vel = k < 81;
+    if (!vel && pdg) { // a cell function: the cell itself only
+      t.nbr[size_t(k) * 27 + 13] = k;
+      continue;
+    }
+    const int n1 = vel ? 3 : 2, top = n1 - 1, n = vel ? k % 27 : k - 81, base = vel ? k - n : 81;
+    const int idx[3] = {n % n1, (n / n1) % n1, n / (n1 * n1)};
+    for (int d = 0; d < 3; ++d)
+      if (vel) t.face[k] |= (idx[d] == 0 ? 1 << (2 * d) : 0) | (idx[d] == top ? 2 << (2 * d) : 0);
+    for (int s = 0; s < 27; ++s) {
+      const int sh[3] = {s % 3 - 1, (s / 3) % 3 - 1, s / 9 - 1};
+      int n2 = 0, mul = 1;
+      bool held = true;
+      for (int d = 0; d < 3; ++d) {
+        // the cell below holds the DoFs of this cell's lower face on its upper face, and the other way round
+        if (sh[d] == -1 && idx[d] != 0) held = false;
+        if (sh[d] == 1 && idx[d] != top) held = false;
+        n2 += (sh[d] == -1 ? top : (sh[d] == 1 ? 0 : idx[d])) * mul;
+        mul *= n1;
+      }
+      if (held) t.nbr[size_t(k) * 27 + s] = base + n2;
+    }
+  }
+  return t;
+}
+// row of the cell block -> (block of the BlockSlice, cell DoF): block i holds the 81 velocity or the npl pressure DoFs, the blocks
+// one after the other
+inline void stokes_row_dofs(int nblk, const int *var, int npl, std::vector<int> &rowblk, std::vector<int> &rowdof)
+{
+  rowblk.clear();
+  rowdof.clear();
+  for (int i = 0; i < nblk; ++i)
+    for (int k = 0; k < (var[i] ? npl : 81); ++k) {
+      rowblk.push_back(i);
+      rowdof.push_back((var[i] ? 81 : 0) + k);
+    }
+}
+// The distinct linearisation states of the velocity column blocks: sel[j] = position of lin[j] among the distinct pointers, in the
+// order the blocks meet them (pressure blocks and a null `lin`: 0); returns their number (at least 1)
+inline int distinct_states(int nblk, const int *var, const double *const *lin, int *sel, const double **state)
+{
+  int n = 0;
+  for (int j = 0; j < nblk; ++j) {
+    sel[j] = 0;
+    if (var[j] != 0 || !lin) continue;
+    int at = -1;
+    for (int s = 0; s < n; ++s)
+      if (state[s] == lin[j]) at = s;
+    if (at < 0) { state[n] = lin[j]; at = n++; }
+    sel[j] = at;
+  }
+  if (n == 0) { state[0] = nullptr; n = 1; }
+  return n;
 }
 
 } // namespace vanka

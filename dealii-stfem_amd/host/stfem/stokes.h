@@ -392,7 +392,8 @@ using NavierStokesOperator =
 // PreconditionVanka in its block form (include/stmg.h:626-738, 832-872) as tests/tp_03stokes.cc:537-540, 714-726 creates it for the
 // Stokes levels: the assembled Stokes and mass matrices restricted to every cell's velocity and pressure DoFs, combined with
 // Alpha / Beta over the blocks of the BlockSlice (K_mask empty, M_mask(0, 0) only), inverted.  The assembled matrices and DoF
-// handlers of the reference's constructor are not needed: the blocks follow from the operator (stfem_stokes_vanka_create).
+// handlers of the reference's constructor are not needed: the blocks follow from the operator (stfem_stokes_vanka_create; one block
+// per neighbour pattern on a box, one per cell on a general mesh and, second constructor, for the linearised operator).
 template <typename Number> class PreconditionVankaStokes {
   static_assert(std::is_same<Number, double>::value, "fp64");
 
@@ -401,7 +402,7 @@ public:
   template <int dim>
   PreconditionVankaStokes(const StokesMatrixFreeOperator<dim, Number> &K, const FullMatrix<Number> &Alpha, const FullMatrix<Number> &Beta,
                           const BlockSlice &blk_slice)
-    : nb_(blk_slice.n_blocks())
+    : nb_(blk_slice.n_blocks()), slice_(blk_slice)
   {
     if (Alpha.m() != nb_ || Alpha.n() != nb_ || Beta.m() != nb_ || Beta.n() != nb_) throw std::invalid_argument("Alpha/Beta do not match the block slice");
     std::vector<int32_t> var(nb_);
@@ -410,6 +411,33 @@ public:
     const int rc = stfem_stokes_vanka_create(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), &v);
     if (rc != STFEM_OK) throw Error(rc, std::string("stfem_stokes_vanka_create: ") + stfem_stokes_vanka_last_error());
     v_.reset(v, stfem_stokes_vanka_destroy);
+  }
+  // The smoother of the LINEARISED operator, one block per cell (reinit_asm, stmg.h:929-965: set_data(mg_data[l]), the assembled
+  // matrix of compute_matrix_helper<OperatorMode::jacobian>, operators.h:1310-1318, and the blocks from it, stmg.h:704-742): the
+  // column blocks of time dof (it, id) are linearised about block index(it, 0, id) of solution_linearization (operators.h:835-866).
+  // NonlinearTreatment::None gives the plain Stokes blocks, Explicit the form, Implicit the jacobian (as the operator's vmult).
+  template <int dim>
+  PreconditionVankaStokes(const StokesMatrixFreeOperator<dim, Number> &K, const FullMatrix<Number> &Alpha, const FullMatrix<Number> &Beta,
+                          const BlockSlice &blk_slice, NonlinearTreatment nonlinear_treatment, const BlockVectorType &solution_linearization)
+    : nb_(blk_slice.n_blocks()), slice_(blk_slice)
+  {
+    if (Alpha.m() != nb_ || Alpha.n() != nb_ || Beta.m() != nb_ || Beta.n() != nb_) throw std::invalid_argument("Alpha/Beta do not match the block slice");
+    std::vector<int32_t> var(nb_);
+    for (unsigned i = 0; i < nb_; ++i) var[i] = int32_t(blk_slice.decompose(i)[1]);
+    const int mode = nonlinear_treatment == NonlinearTreatment::None ? STFEM_CONVECTION_NONE
+                     : nonlinear_treatment == NonlinearTreatment::Explicit ? STFEM_CONVECTION_FORM : STFEM_CONVECTION_JACOBIAN;
+    const std::vector<const double *> l = linearization(solution_linearization);
+    stfem_stokes_vanka *v = nullptr;
+    const int rc = stfem_stokes_vanka_create_linearised(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), mode, l.data(), &v);
+    if (rc != STFEM_OK) throw Error(rc, std::string("stfem_stokes_vanka_create_linearised: ") + stfem_stokes_vanka_last_error());
+    v_.reset(v, stfem_stokes_vanka_destroy);
+  }
+  // the blocks again for a new linearisation vector (same treatment, same storage): the next Newton / Picard step
+  void update(const BlockVectorType &solution_linearization)
+  {
+    const std::vector<const double *> l = linearization(solution_linearization);
+    const int rc = stfem_stokes_vanka_update(v_.get(), l.data());
+    if (rc != STFEM_OK) throw Error(rc, std::string("stfem_stokes_vanka_update: ") + stfem_stokes_vanka_last_error());
   }
   void vmult(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const { step(dst, 1.0, false, src, stream); }
   void smooth(BlockVectorType &u, const BlockVectorType &rhs) const { vmult(u, rhs); }
@@ -426,7 +454,17 @@ public:
   int n_classes() const { return stfem_stokes_vanka_n_classes(v_.get()); }
 
 private:
+  // the velocity blocks of the linearisation vector (pressure entries stay null)
+  std::vector<const double *> linearization(const BlockVectorType &lin) const
+  {
+    if (lin.size() != nb_) throw Error(STFEM_ERR_SHAPE_MISMATCH, "PreconditionVankaStokes: linearization blocks");
+    std::vector<const double *> l(nb_, nullptr);
+    for (unsigned i = 0; i < nb_; ++i)
+      if (slice_.decompose(i)[1] == 0) l[i] = lin[i].data();
+    return l;
+  }
   unsigned nb_;
+  BlockSlice slice_;
   std::shared_ptr<stfem_stokes_vanka> v_;
 };
 

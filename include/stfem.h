@@ -508,11 +508,31 @@ int stfem_stokes_dgp_restrict(stfem_stokes_ctx *fine, stfem_stokes_ctx *coarse, 
  * i, j = blocks of the BlockSlice, block_variable[i] = 0 (velocity) / 1 (pressure), K = the assembled Stokes matrix of the context
  * (weak boundary faces included; strong velocity constraints: row and column dropped, diagonal kept), M = the vector mass;
  * vmult / step: dst = (accumulate ? dst : 0) + omega * sum over cells of scatter(B_c^-1 gather(src)), blocks in BlockSlice order
- * (at most 8; velocity blocks 3 * n_velocity_dofs doubles, pressure blocks n_pressure_dofs).  Axis-aligned uniform meshes (<= 27
- * distinct blocks, read off the operator applied to unit vectors); general meshes: STFEM_ERR_UNSUPPORTED.  fp64. */
+ * (at most 8; velocity blocks 3 * n_velocity_dofs doubles, pressure blocks n_pressure_dofs).  Axis-aligned uniform meshes: <= 27
+ * distinct blocks, read off the operator applied to unit vectors; general meshes: one block per cell, as create_linearised with
+ * mode 0 builds them.  fp64. */
 typedef struct stfem_stokes_vanka stfem_stokes_vanka;
 int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta,
                               stfem_stokes_vanka **out);
+/* The smoother of the LINEARISED operator, one block per cell on every mesh (boxes included): what the reference's reinit_asm does
+ * in two steps (include/stmg.h:929-965): set_data(mg_data[l]) and the assembled matrix of compute_matrix_helper<OperatorMode::jacobian>
+ * (operators.h:1310-1318), then one inverted block per cell from that matrix (stmg.h:704-742, compute_block_matrix.h:50-139).  The block
+ * is the one above with K replaced by the assembled A(b_j): the column blocks of source time dof (it, id) use the linearisation
+ * velocity b = lin_blocks[index(it, 0, id)] (operators.h:835-866; BlockSlice order like stfem_stokes_st_vmult_convection, device
+ * pointers, only the velocity entries are read, entries on strongly constrained DoFs count as zero); equal pointers are evaluated
+ * once - the reference's single data_lin[0] is the same pointer everywhere.  mode: STFEM_CONVECTION_NONE (lin_blocks may be null: the
+ * plain Stokes blocks), _FORM (Stokes + C_form(b, .)) or _JACOBIAN (Stokes + C_form(b, .) + C_form(., b)), cell term and the inflow
+ * term - min(b.n, 0) u.v on the weak non-outflow faces; strong constraints, valence, Alpha / Beta and Gauss-Jordan as above.  Set-up on
+ * the device; the apply streams every block from HBM once (kpad * mpad * 8 bytes per cell: 70 kB at 89 rows).
+ * Refusals, decided before anything touches the device, *out = NULL: a mode outside 0..2 or a null lin_blocks (entry of a velocity
+ * block) with a mode other than 0: STFEM_ERR_INVALID_ARGUMENT; more than 8 blocks or 512 rows: STFEM_ERR_UNSUPPORTED.  Blocks that do
+ * not fit beside the free device memory: STFEM_ERR_OUT_OF_MEMORY, the sizes in stfem_stokes_vanka_last_error.
+ * update: stages the same set-up again into the existing block storage for new linearisation states (same mode);
+ * STFEM_ERR_UNSUPPORTED for the class blocks of stfem_stokes_vanka_create on a box.  n_classes: the cell count.  Not built: fp32
+ * blocks, the CIP term and outflow_penalty, slab partitioning of this layout. */
+int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha,
+                                         const double *Beta, int mode, const double *const *lin_blocks, stfem_stokes_vanka **out);
+int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_blocks);
 void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v);
 int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v);
 int stfem_stokes_vanka_vmult(stfem_stokes_vanka *v, double *const *dst_blocks, const double *const *src_blocks, void *stream);

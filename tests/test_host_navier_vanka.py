@@ -1,0 +1,33 @@
+"""The C++ mirror of the smoother of the linearised operator (host/stfem/stokes.h: PreconditionVankaStokes with a NonlinearTreatment
+and a linearisation vector, update, step) through its caller host/test_host_navier_vanka, against the values the caller computes with
+the same linearisation through the C-ABI (stfem_stokes_vanka_create_linearised / _step): the same kernels on the same data, so the
+two agree bit for bit."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "dealii-stfem_amd", "host")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", [(0, 2, 1), (1, 1, 2)])
+def test_cpp_navier_vanka_caller(case):
+    """(3, 2, 2) cells, perturbed, Implicit treatment: cG(2) with one step (four blocks, two linearisation states), dG(1) with two steps
+    (eight blocks, four states).  Created about one vector, updated to a second, one step: equal to a C-ABI smoother created about the
+    second; the update changed the blocks; NonlinearTreatment::None equals the first constructor; four refusals."""
+    ttype, r, ns = case
+    exe = os.path.join(HOST, "test_host_navier_vanka")
+    if not os.path.exists(exe):
+        subprocess.check_call(["make", "-C", HOST, "test_host_navier_vanka"], stdout=subprocess.DEVNULL)
+    res = subprocess.run([exe, "3", "2", "2", str(ttype), str(r), str(ns), "0.5"], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    out = dict(re.findall(r"(\w+)=(\S+)", res.stdout))
+    nt = r if ttype == 0 else r + 1
+    assert int(out["blocks"]) == 2 * nt * ns and int(out["cells"]) == 12
+    assert float(out["mirror_vs_capi"]) == 0.0
+    assert int(out["update_changed"]) == 1
+    assert float(out["none_vs_create"]) == 0.0
+    assert int(out["exceptions"]) == 4

@@ -180,6 +180,7 @@ SIGNATURES = {
     "stfem_stokes_pressure_mean_vectors": (C.c_int, [_vp, _dp, _dp, _dp]),
     "stfem_stokes_pressure_quadrature_points": (C.c_int, [_vp, C.c_int, _dp]),
     "stfem_stokes_pressure_difference": (C.c_int, [_vp, C.c_int, _vp, _dp, _dp, _vp]),
+    "stfem_stokes_divergence": (C.c_int, [_vp, _vp, _vp, _dp, _vp]),
     "stfem_stokes_dgp_prolongate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "stfem_stokes_dgp_restrict": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "stfem_stokes_vanka_create": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.POINTER(_vp)]),
@@ -909,6 +910,20 @@ class StokesMatrixFreeOperator:
         _check(lib().stfem_stokes_pressure_difference(self._h, nq, getattr(p, "ptr", p), _p(e), _p(out), stream),
                "stfem_stokes_pressure_difference")
         return out
+
+    def divergence(self, u, cells=False, stream=None):
+        """StokesMatrixFreeOperator::compute_divergence (operators.h:1391-1439): sqrt(sum_cells int (div u_h)^2) of the device
+        velocity vector u at the operator's Gauss points, the values read plain (constrained entries count as stored).
+        cells=True: (total, [n_cells] cell values, cells lexicographic); cells=<device pointer>: the cell values are written there."""
+        total = C.c_double(0.0)
+        scratch = None
+        if cells is True:  # (a pressure vector holds the cell values: either pressure space has at least one DoF per cell)
+            scratch = StokesVector(self, 1)
+            dptr = scratch.ptr
+        else:
+            dptr = None if cells is False or cells is None else getattr(cells, "ptr", cells)
+        _check(lib().stfem_stokes_divergence(self._h, getattr(u, "ptr", u), dptr, C.byref(total), stream), "stfem_stokes_divergence")
+        return (total.value, scratch.download()[:self.n_cells].copy()) if scratch is not None else total.value
 
     def pressure_mean_vectors(self):
         """(ones, weights, volume): coefficients of p = 1, (1, psi_j), and the volume: mean(p) = weights . p / volume"""

@@ -186,6 +186,7 @@ void stfem_stokes_destroy(stfem_stokes_ctx *c)
   if (c->pressure_space) stfem_ctx_destroy(c->pressure_space);
   if (c->d_pq) (void)hipFree(c->d_pq);
   if (c->d_pred) (void)hipFree(c->d_pred);
+  if (c->d_div) (void)hipFree(c->d_div);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   delete c;

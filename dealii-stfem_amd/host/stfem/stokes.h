@@ -175,10 +175,15 @@ private:
     md.dirichlet_mask = mesh.dirichlet_mask;
     md.device = mesh.device;
     check(stfem_stokes_create_ex(&md, int(velocity_degree), dg_pressure ? 1 : 0, viscosity, &h_), "stfem_stokes_create");
+    n_cells_ = size_t(mesh.ncell[0]) * size_t(mesh.ncell[1]) * size_t(mesh.ncell[2]);
   }
 
 public:
-  ~StokesMatrixFreeOperator() { stfem_stokes_destroy(h_); }
+  ~StokesMatrixFreeOperator()
+  {
+    cells_ = StokesVector(); // (freed through the context, so before it)
+    stfem_stokes_destroy(h_);
+  }
   StokesMatrixFreeOperator(const StokesMatrixFreeOperator &) = delete;
 
   void initialize_dof_vector(BlockVectorType &vec) const // operators.h:1254-1262
@@ -213,6 +218,28 @@ public:
   {
     check(stfem_stokes_mass_vmult(h_, dst.data(), src.data(), stream), "vector mass vmult");
   }
+  // operators.h:1391-1415: sqrt(sum_cells int (div u_h)^2) of the velocity of src, read plain; cell_vector (the reference's
+  // ReadWriteVector) receives the cell values, cells lexicographic
+  Number compute_divergence(const BlockVectorType &src, std::vector<Number> &cell_vector, void *stream = nullptr) const
+  {
+    return compute_divergence(src.at(0), cell_vector, stream);
+  }
+  Number compute_divergence(const StokesVector &velocity, std::vector<Number> &cell_vector, void *stream = nullptr) const
+  {
+    // (the cell values land in a pressure vector: either pressure space has at least one DoF per cell)
+    if (!cells_.data()) cells_ = StokesVector(h_, 1);
+    Number total = 0;
+    check(stfem_stokes_divergence(h_, velocity.data(), cells_.data(), &total, stream), "stfem_stokes_divergence");
+    const std::vector<double> h = cells_.copy_to_host();
+    cell_vector.assign(h.begin(), h.begin() + (long long)n_cells_);
+    return total;
+  }
+  Number compute_divergence(const StokesVector &velocity, void *stream = nullptr) const // (the total alone)
+  {
+    Number total = 0;
+    check(stfem_stokes_divergence(h_, velocity.data(), nullptr, &total, stream), "stfem_stokes_divergence");
+    return total;
+  }
   unsigned long long m() const { return 3ull * stfem_stokes_n_velocity_dofs(h_) + stfem_stokes_n_pressure_dofs(h_); }
   stfem_stokes_ctx *handle() const { return h_; }
 
@@ -227,6 +254,8 @@ private:
   NonlinearTreatment nonlinear_treatment;
   bool nonlinear;
   mutable const double *lin_ = nullptr; // data_lin[0]
+  size_t n_cells_ = 0;
+  mutable StokesVector cells_; // device cell values of compute_divergence, made on demand
 };
 
 // operators.h:1768-1951: the right-hand-side functional of the weakly imposed Dirichlet data.  It shares the geometry
@@ -359,12 +388,23 @@ public:
   // (velocity, pressure) pair; dst is accumulated into
   void vmult_slice_add(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const
   {
+    slice_add(dst, src, K.vmult_mode(), stream);
+  }
+  // the same with the nonlinear weak form (form in place of vmult): the previous-slab term of a Navier-Stokes slab, whose j = 0
+  // time dof is linearised about itself whatever the treatment of the system (set_data(src) first)
+  void form_slice_add(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const
+  {
+    slice_add(dst, src, K.form_mode(), stream);
+  }
+
+private:
+  void slice_add(BlockVectorType &dst, const BlockVectorType &src, int mode, void *stream) const
+  {
     const unsigned nb = blk_slice.n_blocks();
     if (dst.size() != nb || src.size() != 2 || Alpha.n() != 1) throw Error(STFEM_ERR_SHAPE_MISMATCH, "vmult_slice_add");
     std::vector<double *> d(nb);
     for (unsigned i = 0; i < nb; ++i) d[i] = dst[i].data();
     // (759-761: set_linearization_data_slice - one linearisation pair for the one source pair)
-    const int mode = K.vmult_mode();
     const std::vector<const double *> l = linearization(mode, 2, "SystemMatrixStokes::vmult_slice_add");
     check(stfem_stokes_st_vmult_slice_add_convection(K.handle(), mode, int(blk_slice.n_timesteps_at_once()), int(blk_slice.n_timedofs()),
                                                      blk_slice.variable_major() ? 1 : 0, Alpha.data(), Beta.data(), d.data(),
@@ -372,6 +412,8 @@ public:
                                                      stream),
           "SystemMatrixStokes::vmult_slice_add");
   }
+
+public:
   unsigned long long m() const { return (unsigned long long)(blk_slice.n_blocks() / 2) * K.m(); }
 
 private:

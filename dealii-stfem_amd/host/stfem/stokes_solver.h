@@ -165,6 +165,14 @@ public:
     if (spaces->q2->comm) // partitioned: dst.compress(add) on every block through its scalar view
       for (unsigned b = 0; b < dst.n_blocks(); ++b) compress_add(*dst.view(b).context(), dst.view(b).handle(), stream);
   }
+  // the nonlinear weak form (SystemMatrixStokes::form) and the linearisation vector of both (referred to, not copied)
+  void form(StokesBlockVector &dst, const StokesBlockVector &src, void *stream = nullptr) const
+  {
+    A.form(dst.blocks(), src.blocks(), stream);
+    if (spaces->q2->comm)
+      for (unsigned b = 0; b < dst.n_blocks(); ++b) compress_add(*dst.view(b).context(), dst.view(b).handle(), stream);
+  }
+  void set_data(const StokesBlockVector &lin) const { A.set_data(lin.blocks()); }
 
 private:
   const SystemMatrixStokes<dim, Number> &A;
@@ -189,6 +197,7 @@ public:
       P.step(dst.blocks(), omega, true, res.blocks(), stream);
     }
   }
+  void set_relaxation(double omega_) { omega = omega_; } // (a linearised operator: the damping follows the operator)
 
 private:
   const System &A;
@@ -219,15 +228,17 @@ public:
     bool variable = true;              // MGSmootherPrecondition variable: 2^(max_level - level) steps on level `level`
     unsigned smoothing_degree = 1;     // sweeps of PreconditionRelaxation per step
     double relaxation = 0.0;           // its omega; 0: estimated per level (20 power iterations on P^-1 A), as the reference's default
+    bool reestimate_relaxation = true; // linearised levels, relaxation == 0: a fresh estimate at every set_data (false: the first one is kept)
   };
   // the finest mesh has mesh.ncell cells; level l < n_levels - 1 has them halved n_levels - 1 - l times
   GMGStokes(const Mesh &mesh, unsigned n_levels, double viscosity, const FullMatrix<double> &Alpha, const FullMatrix<double> &Beta,
             const BlockSlice &slice, const AdditionalData &data = AdditionalData(), const std::set<boundary_id> &weak_boundary_ids = {},
-            bool dg_pressure = false)
+            bool dg_pressure = false, NonlinearTreatment treatment = NonlinearTreatment::None)
     : data_(data)
   {
     if (n_levels < 1) throw std::invalid_argument("GMGStokes: at least one level");
     dg_ = dg_pressure;
+    treatment_ = treatment;
     levels_.resize(n_levels);
     for (unsigned l = 0; l < n_levels; ++l) {
       levels_[l].halvings = n_levels - 1 - l;
@@ -243,9 +254,10 @@ public:
   // degree poly_time_sequence.back(), n_timesteps_at_once steps of size time_step_size per slab
   GMGStokes(const Mesh &mesh, const std::vector<MGType> &mg_type_level, const std::vector<unsigned> &poly_time_sequence, TimeStepType type,
             double time_step_size, unsigned n_timesteps_at_once, double viscosity, const AdditionalData &data = AdditionalData(),
-            const std::set<boundary_id> &weak_boundary_ids = {}, bool dg_pressure = false)
+            const std::set<boundary_id> &weak_boundary_ids = {}, bool dg_pressure = false, NonlinearTreatment treatment = NonlinearTreatment::None)
     : data_(data)
   {
+    if (treatment != NonlinearTreatment::None) throw std::invalid_argument("GMGStokes: the linearisation on k / tau levels is not built");
     dg_ = dg_pressure;
     const unsigned n_levels = unsigned(mg_type_level.size()) + 1;
     levels_.resize(n_levels);
@@ -275,6 +287,47 @@ public:
   const std::shared_ptr<StokesSpaces> &finest_spaces() const { return levels_.back().spaces; }
   double relaxation(unsigned level) const { return levels_.at(level).omega; }
   unsigned n_levels() const { return unsigned(levels_.size()); }
+  NonlinearTreatment nonlinear_treatment() const { return treatment_; }
+  // The hierarchy of the operator linearised about `lin` (the reference's set_data + reinit_asm(..., mg_data), include/stmg.h:929-965):
+  // the finest level refers to lin itself (only its velocity blocks are read; it has to outlive the cycles), every coarser level
+  // holds the nodal interpolation of the level above (MGTwoLevelTransfer::interpolate on the three components of every time dof:
+  // the reference's mg_data[l]), in storage made at the first call.  Then, level by level: the operator's set_data, the per-cell
+  // smoother of the linearised operator (made at the first call, update afterwards) and the damping of its relaxation.
+  void set_data(const StokesBlockVector &lin)
+  {
+    if (treatment_ == NonlinearTreatment::None) throw std::invalid_argument("GMGStokes::set_data: a hierarchy without a nonlinear treatment");
+    const unsigned top = unsigned(levels_.size()) - 1;
+    if (lin.n_blocks() != levels_[top].slice.n_blocks()) throw Error(STFEM_ERR_SHAPE_MISMATCH, "GMGStokes::set_data: blocks");
+    for (unsigned l = levels_.size(); l-- > 0;) {
+      Level &L = levels_[l];
+      if (l < top) {
+        const Level &F = levels_[l + 1];
+        if (L.lin.empty()) L.system->initialize_dof_vector(L.lin);
+        for (unsigned b = 0; b < L.slice.n_blocks(); ++b) {
+          if (L.slice.decompose(b)[1] != 0) continue;
+          // (the caller's vector may live on contexts of its own for the same mesh: viewed through this hierarchy's spaces)
+          const BlockVectorT<double> caller = l + 1 == top ? foreign_view(lin, b) : BlockVectorT<double>();
+          const stfem_vec *fine = l + 1 == top ? caller.handle() : F.lin.view(b).handle();
+          check(stfem_transfer_interpolate(F.tr_u->handle(), L.lin.view(b).handle(), fine, nullptr), "GMGStokes::set_data: interpolate");
+        }
+      }
+      const std::vector<StokesVector> &blocks = l == top ? lin.blocks() : L.lin.blocks();
+      L.A->set_data(blocks);
+      const bool first = !L.vanka;
+      if (first) L.vanka = std::make_unique<PreconditionVankaStokes<double>>(*L.K, L.Alpha, L.Beta, L.slice, treatment_, blocks);
+      else L.vanka->update(blocks);
+      if (data_.relaxation != 0.0) L.omega = data_.relaxation;
+      else if (first || data_.reestimate_relaxation) L.omega = estimate_relaxation_stokes(*L.system, *L.vanka, 20, 1.0);
+      if (first) L.relax = std::make_unique<PreconditionRelaxationStokes<StokesSystem<dim, double>>>(*L.system, *L.vanka, L.omega, data_.smoothing_degree);
+      else L.relax->set_relaxation(L.omega);
+    }
+  }
+  // the linearisation a level below the finest holds (set_data)
+  const StokesBlockVector &level_linearization(unsigned level) const
+  {
+    if (level + 1 >= levels_.size() || levels_[level].lin.empty()) throw std::invalid_argument("GMGStokes::level_linearization");
+    return levels_[level].lin;
+  }
   // STFEM_MG_TIMING=1: wall time per level (smoothing, residual + transfers), with a device synchronisation around every section -
   // the sections of the reference's TimerOutput ("gmg" and below); the synchronisations cost the overlap of launches and kernels
   void print_timing(FILE *f) const
@@ -289,6 +342,7 @@ public:
   {
     TraceRange scope("gmg");
     const unsigned top = unsigned(levels_.size()) - 1;
+    if (!levels_[top].relax) throw std::invalid_argument("GMGStokes::vmult: set_data first");
     // (the caller's vectors may live on contexts of their own for the same mesh: view their blocks through this level's spaces)
     const unsigned nb = levels_[top].slice.n_blocks();
     for (unsigned b = 0; b < nb; ++b) axpby(1.0, foreign_view(src, b), 0.0, levels_[top].defect.view(b));
@@ -317,6 +371,7 @@ private:
     std::unique_ptr<MGTwoLevelTransfer<double>> tr_u, tr_p; // to the level below
     double omega = 1.0;
     mutable StokesBlockVector defect, solution, t, tmp;
+    StokesBlockVector lin; // linearised levels below the finest: the interpolated linearisation (mg_data[l])
     mutable double t_smooth = 0.0, t_transfer = 0.0;
   };
   struct Section { // (times one section of the cycle when STFEM_MG_TIMING is set)
@@ -349,14 +404,17 @@ private:
         if (mesh.ncell[d] % f) throw std::invalid_argument("GMGStokes: the cell counts must be divisible by 2^(space levels - 1)");
         L.mesh.ncell[d] = mesh.ncell[d] / f;
       }
+      const bool linearised = treatment_ != NonlinearTreatment::None;
       L.K = std::make_unique<StokesMatrixFreeOperator<dim, double>>(L.mesh, 2, viscosity, weak_boundary_ids, std::set<boundary_id>(), 20.0, 10.0, 0.0, 0.0, 0.0,
-                                                                   dg_);
+                                                                   dg_, treatment_);
       L.spaces = std::make_shared<StokesSpaces>(L.mesh, L.K->handle());
-      L.A = std::make_unique<SystemMatrixStokes<dim, double>>(*L.K, L.Alpha, L.Beta, L.slice);
+      L.A = std::make_unique<SystemMatrixStokes<dim, double>>(*L.K, L.Alpha, L.Beta, L.slice, treatment_);
       L.system = std::make_unique<StokesSystem<dim, double>>(*L.A, L.spaces, L.K->handle(), L.slice);
-      L.vanka = std::make_unique<PreconditionVankaStokes<double>>(*L.K, L.Alpha, L.Beta, L.slice);
-      L.omega = data_.relaxation != 0.0 ? data_.relaxation : estimate_relaxation_stokes(*L.system, *L.vanka, 20, 1.0);
-      L.relax = std::make_unique<PreconditionRelaxationStokes<StokesSystem<dim, double>>>(*L.system, *L.vanka, L.omega, data_.smoothing_degree);
+      if (!linearised) { // (linearised levels: smoother and damping belong to a linearisation - set_data)
+        L.vanka = std::make_unique<PreconditionVankaStokes<double>>(*L.K, L.Alpha, L.Beta, L.slice);
+        L.omega = data_.relaxation != 0.0 ? data_.relaxation : estimate_relaxation_stokes(*L.system, *L.vanka, 20, 1.0);
+        L.relax = std::make_unique<PreconditionRelaxationStokes<StokesSystem<dim, double>>>(*L.system, *L.vanka, L.omega, data_.smoothing_degree);
+      }
       L.system->initialize_dof_vector(L.defect);
       L.system->initialize_dof_vector(L.solution);
       L.system->initialize_dof_vector(L.t);
@@ -484,6 +542,7 @@ private:
   mutable unsigned cycles_ = 0;
   AdditionalData data_;
   bool dg_ = false;
+  NonlinearTreatment treatment_ = NonlinearTreatment::None;
   std::vector<Level> levels_;
 };
 
@@ -654,6 +713,200 @@ private:
   bool zero_mean;
   std::vector<double> qpoints;
   BlockVectorT<double> load, weights, ones;
+  double volume = 1.0;
+};
+
+// PreconditionRelaxation around ONE per-cell Vanka smoother of the linearised operator (no multigrid): the smoother is made at the
+// first set_data and updated afterwards (PreconditionVankaStokes::update), the damping estimated for the current operator unless it
+// is given.  The preconditioner interface of TimeIntegratorNavierStokes beside GMGStokes.
+template <int dim> class PreconditionRelaxationLinearisedStokes {
+public:
+  PreconditionRelaxationLinearisedStokes(const StokesMatrixFreeOperator<dim, double> &K, const StokesSystem<dim, double> &system, const FullMatrix<double> &Alpha,
+                                         const FullMatrix<double> &Beta, const BlockSlice &slice, NonlinearTreatment treatment, unsigned n_iterations,
+                                         double relaxation = 0.0, bool reestimate_relaxation = true)
+    : K(K), system(system), Alpha(Alpha), Beta(Beta), slice(slice), treatment(treatment), n_iterations(n_iterations), relaxation_(relaxation),
+      reestimate(reestimate_relaxation)
+  {
+    if (treatment == NonlinearTreatment::None) throw std::invalid_argument("PreconditionRelaxationLinearisedStokes: a nonlinear treatment");
+  }
+  void set_data(const StokesBlockVector &lin)
+  {
+    const bool first = !vanka;
+    if (first) vanka = std::make_unique<PreconditionVankaStokes<double>>(K, Alpha, Beta, slice, treatment, lin.blocks());
+    else vanka->update(lin.blocks());
+    if (relaxation_ != 0.0) omega = relaxation_;
+    else if (first || reestimate) omega = estimate_relaxation_stokes(system, *vanka, 20, 1.0);
+    if (first) relax = std::make_unique<PreconditionRelaxationStokes<StokesSystem<dim, double>>>(system, *vanka, omega, n_iterations);
+    else relax->set_relaxation(omega);
+  }
+  void vmult(StokesBlockVector &dst, const StokesBlockVector &src, void *stream = nullptr) const
+  {
+    if (!relax) throw std::invalid_argument("PreconditionRelaxationLinearisedStokes::vmult: set_data first");
+    relax->vmult(dst, src, stream);
+  }
+  double relaxation() const { return omega; }
+
+private:
+  const StokesMatrixFreeOperator<dim, double> &K;
+  const StokesSystem<dim, double> &system;
+  const FullMatrix<double> &Alpha, &Beta;
+  BlockSlice slice;
+  NonlinearTreatment treatment;
+  unsigned n_iterations;
+  double relaxation_, omega = 1.0;
+  bool reestimate;
+  std::unique_ptr<PreconditionVankaStokes<double>> vanka;
+  std::unique_ptr<PreconditionRelaxationStokes<StokesSystem<dim, double>>> relax;
+};
+
+// The slab problem of the Navier-Stokes equations: TimeIntegratorStokes with a Newton / Picard iteration in place of the one linear
+// solve.  The reference prepares the interfaces (PDE<>::residual / form / vmult, set_data, reinit_asm(..., mg_data)) and has no
+// nonlinear loop (include/time_integrators.h:20-22); this is the loop they are prepared for.  Per time dof the nonlinear term is the
+// weak form linearised about that time dof's own velocity (include/operators.h:835-866), so the discrete problem is
+//     sum_j Alpha(i, j) F(x_j) + Beta(i, j) M u_j = rhs_i,   F(u, p) = (nu K u - B^T p + C(u, u), B u),
+// and the previous-slab term (j = 0 of the same sum, moved to the right) is rhs_matrix.form_slice_add about the previous end value.
+//   matrix (System): set_data(x), form(dst, x), vmult(dst, src) - a StokesSystem whose operator carries the treatment: Implicit
+//       applies the jacobian about x (Newton), Explicit the form about x (Picard), as in StokesMatrixFreeOperator::vmult;
+//   preconditioner: set_data(x), vmult - GMGStokes with the same treatment or PreconditionRelaxationLinearisedStokes.
+// Per slab: x = previous solution; r = rhs - form(x); until |r| <= max(abstol, reltol |r_0|) or max_nonlinear steps (reported by
+// converged(), not thrown): set_data(x) on both, FGMRES on J delta = r from zero, x += delta.
+template <int dim, typename System, typename Preconditioner> class TimeIntegratorNavierStokes {
+public:
+  TimeIntegratorNavierStokes(TimeStepType type, unsigned time_degree, const FullMatrix<double> &Alpha_1, const FullMatrix<double> &Gamma_1,
+                             double linear_tolerance, const System &matrix, Preconditioner &preconditioner,
+                             const SystemMatrixStokes<dim, double> &rhs_matrix, const VectorPointFunction &force, bool zero_mean_pressure,
+                             double nonlinear_reltol = 1e-12, double nonlinear_abstol = 1e-14, unsigned max_nonlinear = 30, double linear_abstol = 1e-16,
+                             unsigned max_steps = 400)
+    : type(type), time_degree(time_degree), quad_time(time_points(type, time_degree)), Alpha(Alpha_1), Gamma(Gamma_1),
+      solver(max_steps, linear_abstol, linear_tolerance, 200), preconditioner(preconditioner), matrix(matrix), rhs_matrix(rhs_matrix), force(force),
+      nt_dofs(type == TimeStepType::DG ? time_degree + 1 : time_degree), zero_mean(zero_mean_pressure), reltol(nonlinear_reltol),
+      abstol(nonlinear_abstol), max_nonlinear(max_nonlinear)
+  {
+    if (const char *e = std::getenv("STFEM_FGMRES_VERBOSE")) solver.verbose = unsigned(std::atoi(e));
+  }
+
+  // x, rhs: the slab's blocks; prev: one (velocity, pressure) pair (BlockSlice(1, 2, 1))
+  void solve(StokesBlockVector &x, const StokesBlockVector &prev, StokesBlockVector &rhs, double time, double time_step)
+  {
+    TraceRange scope("step");
+    const StokesSpaces &sp = *x.spaces();
+    const BlockSlice &slice = x.slice();
+    set_zero(rhs);
+    rhs_matrix.set_data(prev.blocks());
+    rhs_matrix.form_slice_add(rhs.blocks(), prev.blocks());
+    if (qpoints.empty()) { // assemble_force, as TimeIntegratorStokes
+      qpoints.resize(size_t(stfem_n_cells(sp.q2->h)) * 27 * 3);
+      check(stfem_quadrature_points(sp.q2->h, 3, qpoints.data()), "stfem_quadrature_points");
+      load.reinit(sp.q2, 3);
+    }
+    std::array<std::vector<double>, 3> fq;
+    for (unsigned j = 0; j < quad_time.size(); ++j) {
+      force(time + time_step * quad_time[j], qpoints, fq);
+      for (int c = 0; c < 3; ++c) check(stfem_integrate_rhs(sp.q2->h, 3, fq[c].data(), load.handle(), c, nullptr), "stfem_integrate_rhs");
+      auto add = [&](unsigned timedof, double w) { axpby(w, load, 1.0, rhs.view(slice.index(0, 0, timedof))); };
+      if (type == TimeStepType::DG) add(j, Alpha(j, j));
+      else if (j == 0)
+        for (unsigned i = 0; i < nt_dofs; ++i) add(i, -Gamma(i, 0));
+      else add(j - 1, Alpha(j - 1, j - 1));
+    }
+    for (unsigned i = 0; i < x.n_blocks(); ++i) axpby(1.0, prev.view(slice.decompose(i)[1]), 0.0, x.view(i));
+    reinit_like(residual, x);
+    reinit_like(delta, x);
+    nonlinear_steps_ = 0;
+    linear_steps_ = 0;
+    converged_ = false;
+    residuals_.clear();
+    double r0 = 0.0;
+    for (;;) {
+      double rn;
+      {
+        Clock c(residual_seconds_);
+        matrix.set_data(x);
+        matrix.form(residual, x);
+        axpby(1.0, rhs, -1.0, residual);
+        rn = norm(residual);
+      }
+      residuals_.push_back(rn);
+      if (nonlinear_steps_ == 0) r0 = rn;
+      if (rn <= std::max(abstol, reltol * r0)) {
+        converged_ = true;
+        break;
+      }
+      if (nonlinear_steps_ == max_nonlinear) break;
+      {
+        Clock c(set_data_seconds_);
+        preconditioner.set_data(x);
+      }
+      {
+        Clock c(solver_seconds_);
+        set_zero(delta);
+        solver.solve(matrix, delta, residual, preconditioner);
+        linear_steps_ += solver.last_step();
+      }
+      axpby(1.0, delta, 1.0, x);
+      ++nonlinear_steps_;
+    }
+    if (zero_mean) {
+      if (!weights.handle()) {
+        weights.reinit(sp.q1, 1);
+        ones.reinit(sp.q1, 1);
+        std::vector<std::vector<double>> h1(1, std::vector<double>(ones.block_size())), hw(1, std::vector<double>(ones.block_size()));
+        check(stfem_stokes_pressure_mean_vectors(sp.stokes, h1[0].data(), hw[0].data(), &volume), "stfem_stokes_pressure_mean_vectors");
+        ones.copy_from_host(h1);
+        weights.copy_from_host(hw);
+      }
+      for (unsigned a = 0; a < nt_dofs; ++a) {
+        BlockVectorT<double> &p = x.view(slice.index(0, 1, a));
+        axpby(-dot(weights, p) / volume, ones, 1.0, p);
+      }
+    }
+  }
+  // the last slab: Newton / Picard steps, FGMRES iterations over all of them, whether the tolerance was met, the residual norms
+  unsigned nonlinear_steps() const { return nonlinear_steps_; }
+  unsigned last_step() const { return linear_steps_; }
+  bool converged() const { return converged_; }
+  const std::vector<double> &residuals() const { return residuals_; }
+  // wall time so far, the device synchronised at the section edges: residual evaluations, set_data of the preconditioner (smoother
+  // update + relaxation estimate), Krylov solves
+  double residual_seconds() const { return residual_seconds_; }
+  double set_data_seconds() const { return set_data_seconds_; }
+  double solver_seconds() const { return solver_seconds_; }
+
+private:
+  struct Clock {
+    explicit Clock(double &acc) : acc(acc)
+    {
+      (void)stfem_stream_synchronize(nullptr);
+      t0 = std::chrono::steady_clock::now();
+    }
+    ~Clock()
+    {
+      (void)stfem_stream_synchronize(nullptr);
+      acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    double &acc;
+    std::chrono::steady_clock::time_point t0;
+  };
+  double residual_seconds_ = 0.0, set_data_seconds_ = 0.0, solver_seconds_ = 0.0;
+  TimeStepType type;
+  unsigned time_degree;
+  std::vector<double> quad_time;
+  const FullMatrix<double> &Alpha, &Gamma;
+  SolverFGMRES<double, StokesBlockVector> solver;
+  Preconditioner &preconditioner;
+  const System &matrix;
+  const SystemMatrixStokes<dim, double> &rhs_matrix;
+  VectorPointFunction force;
+  unsigned nt_dofs;
+  bool zero_mean;
+  double reltol, abstol;
+  unsigned max_nonlinear;
+  unsigned nonlinear_steps_ = 0, linear_steps_ = 0;
+  bool converged_ = false;
+  std::vector<double> residuals_;
+  std::vector<double> qpoints;
+  BlockVectorT<double> load, weights, ones;
+  StokesBlockVector residual, delta;
   double volume = 1.0;
 };
 

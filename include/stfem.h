@@ -383,7 +383,8 @@ int stfem_coefficient_per_cell(const int32_t ncell[3], const double *vertices, d
 
 /* ---- Stokes two-field operator (BASELINE configs[4]): the cell loop (LoopType::Cell, include/operators.h:1228-1229) and,
  * after stfem_stokes_set_weak_boundaries below, the weak (Nitsche) boundary faces of operators.h:1662-1751; the convection modes of the
- * Navier-Stokes operator (OperatorMode::form / jacobian) through the *_convection entry points below.  Not built: the CIP
+ * Navier-Stokes operator (OperatorMode::form / jacobian) through the *_convection entry points below; the divergence functional
+ * (compute_divergence) through stfem_stokes_divergence.  Not built: the CIP
  * interior-face term (delta0 != 0, 1603-1638) and the outflow penalty (beta, 1705-1709).  Velocity FE_Q(2)^3, pressure FE_Q(1) (stfem_stokes_create)
  * or FE_DGP(1) (stfem_stokes_create_ex), QGauss(3), MappingQ1 on the mesh of `mesh`; mesh->dirichlet_mask constrains the velocity
  * (homogeneous), the pressure is unconstrained.  fp64.
@@ -462,6 +463,14 @@ int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *ctx, int mode, 
                                                int variable_major, const double *Gamma, const double *Zeta,
                                                double *const *dst_blocks, const double *src_u,
                                                const double *src_p, const double *lin_u, void *stream);
+/* StokesMatrixFreeOperator::compute_divergence (operators.h:1391-1439): the divergence of a velocity vector u (device) at the operator's
+ * 3 x 3 x 3 Gauss points,
+ *   cell_out[cell] = sum_q (div u_h)^2 JxW   (device, n_cells entries, cell = cx + ncx (cy + ncy cz); may be NULL),
+ *   *total = sqrt(sum_cell cell_out[cell])    (host).
+ * The values are read PLAIN (read_dof_values_plain, 1430): entries on strongly constrained DoFs count as stored, not as zero.  One
+ * kernel for boxes and general meshes; the sums have a fixed order (no atomics): two calls agree bit for bit.  Synchronises `stream`.
+ * A null u or total is STFEM_ERR_INVALID_ARGUMENT, decided before anything touches the device. */
+int stfem_stokes_divergence(stfem_stokes_ctx *ctx, const double *u, double *cell_out, double *total, void *stream);
 /* Weak boundary conditions of StokesMatrixFreeOperator (reference include/operators.h:1206-1211, 1220-1221, 1640-1741) and
  * StokesNitscheMatrixFreeOperator (1768-1951), linear operator (NonlinearTreatment::None).
  * Faces are numbered f = 2 d + s (direction d, side s: 0 = lower, 1 = upper; bit f of the masks) - the boundary ids of deal.II's

@@ -9,6 +9,7 @@
 #include "time_integrators.h"
 
 #include <algorithm>
+#include <array>
 #include <memory>
 #include <variant>
 
@@ -309,32 +310,28 @@ private:
 
 // The largest eigenvalue of P^-1 A by deal.II's power iteration (what PreconditionRelaxation does when its
 // relaxation parameter is 0, as the reference leaves it: parameters.h:19, stmg.h:1207-1213): start vector
-// (i mod 11) - mean on every block, n_iterations steps; relaxation = 2 / (alpha + 1.2 lambda), alpha = min(1.08 lambda, 1) for
-// smoothing_range <= 1 (restated from deal.II's documentation of PreconditionRelaxation / PreconditionChebyshev; not checked against a build)
-template <typename Number, typename Operator, typename Precond> double estimate_max_eigenvalue(const Operator &A, const Precond &P, unsigned n_iterations);
-template <typename Number, typename Operator, typename Precond>
-double estimate_relaxation(const Operator &A, const Precond &P, unsigned n_iterations, double smoothing_range)
+// (i mod 11) - mean on every block, n_iterations steps.  VectorType: BlockVectorT<Number>, or any type with the free functions
+// axpby, dot, norm and power_iteration_start (host/stfem/stokes_solver.h: the two-variable block vector, each block of its own size)
+inline std::vector<double> power_iteration_start(size_t n)
 {
-  const double lambda = estimate_max_eigenvalue<Number>(A, P, n_iterations);
-  if (!(lambda > 0) || !std::isfinite(lambda)) return 1.0; // a level without free DoFs (one Q1 cell, all nodes constrained): nothing to relax
-  // internal::PreconditionChebyshevImplementation::estimate_eigenvalues with the power iteration: the tracker holds {1, lambda}, i.e. the
-  // lower estimate is 1 and the upper one carries the safety factor 1.2
-  const double beta = 1.2 * lambda, alpha = smoothing_range > 1.0 ? beta / smoothing_range : std::min(0.9 * beta, 1.0);
-  return 2.0 / (alpha + beta);
-}
-template <typename Number, typename Operator, typename Precond> double estimate_max_eigenvalue(const Operator &A, const Precond &P, unsigned n_iterations)
-{
-  BlockVectorT<Number> v, w, z;
-  A.initialize_dof_vector(v);
-  A.initialize_dof_vector(w);
-  A.initialize_dof_vector(z);
-  const size_t n = v.block_size();
   std::vector<double> guess(n);
   double mean = 0.0;
   for (size_t i = 0; i < n; ++i) mean += double(i % 11);
   mean /= double(n);
   for (size_t i = 0; i < n; ++i) guess[i] = double(i % 11) - mean;
-  v.copy_from_host(std::vector<std::vector<double>>(v.n_blocks(), guess));
+  return guess;
+}
+template <typename Number> void power_iteration_start(BlockVectorT<Number> &v)
+{
+  v.copy_from_host(std::vector<std::vector<double>>(v.n_blocks(), power_iteration_start(v.block_size())));
+}
+template <typename VectorType, typename Operator, typename Precond> double estimate_max_eigenvalue(const Operator &A, const Precond &P, unsigned n_iterations)
+{
+  VectorType v, w, z;
+  A.initialize_dof_vector(v);
+  A.initialize_dof_vector(w);
+  A.initialize_dof_vector(z);
+  power_iteration_start(v);
   axpby(0.0, v, 1.0 / norm(v), v);
   double lambda = 0.0;
   for (unsigned it = 0; it < n_iterations; ++it) {
@@ -347,6 +344,24 @@ template <typename Number, typename Operator, typename Precond> double estimate_
   }
   return std::abs(lambda);
 }
+// The interval {alpha, beta} the smoothers work on (internal::PreconditionChebyshevImplementation::estimate_eigenvalues with the power
+// iteration: the tracker holds {1, lambda}, i.e. the lower estimate is 1 and the upper one carries the safety factor 1.2): beta = 1.2 lambda,
+// alpha = min(0.9 beta, 1) for smoothing_range <= 1 (restated from deal.II's documentation of PreconditionRelaxation / PreconditionChebyshev;
+// not checked against a build)
+inline std::array<double, 2> smoothing_interval(double lambda, double smoothing_range)
+{
+  const double beta = 1.2 * lambda;
+  return {smoothing_range > 1.0 ? beta / smoothing_range : std::min(0.9 * beta, 1.0), beta};
+}
+// relaxation = 2 / (alpha + beta)
+template <typename VectorType, typename Operator, typename Precond>
+double estimate_relaxation(const Operator &A, const Precond &P, unsigned n_iterations, double smoothing_range)
+{
+  const double lambda = estimate_max_eigenvalue<VectorType>(A, P, n_iterations);
+  if (!(lambda > 0) || !std::isfinite(lambda)) return 1.0; // a level without free DoFs (one Q1 cell, all nodes constrained): nothing to relax
+  const auto [alpha, beta] = smoothing_interval(lambda, smoothing_range);
+  return 2.0 / (alpha + beta);
+}
 
 // deal.II PreconditionChebyshev<LevelMatrix, BlockVector, PreconditionVanka> as the reference's second smoother alternative
 // sets it up (stmg.h:1216-1227: degree = smoothing_steps, power iteration for the largest eigenvalue of P^-1 A, smoothing_range):
@@ -358,8 +373,7 @@ public:
   PreconditionChebyshev(const Operator &A, const PreconditionVanka<Number> &P, double lambda_max, double smoothing_range, unsigned degree)
     : A(A), P(P), degree(degree)
   {
-    const double beta = 1.2 * lambda_max; // deal.II's safety factor on the estimate; the lower estimate of the power iteration is 1
-    const double alpha = smoothing_range > 1.0 ? beta / smoothing_range : std::min(0.9 * beta, 1.0);
+    const auto [alpha, beta] = smoothing_interval(lambda_max, smoothing_range);
     theta = 0.5 * (beta + alpha);
     delta = 0.5 * (beta - alpha);
   }
@@ -480,14 +494,14 @@ public:
     for (unsigned l = 0; l < n_levels; ++l) {
       if (precondition_sequence[l] == unsigned(SupportedSmoothers::Identity)) continue;
       if (precondition_sequence[l] == unsigned(SupportedSmoothers::Chebyshev)) { // stmg.h:1216-1227
-        const double lambda = estimate_max_eigenvalue<Number>(*mg_operators[l], *precondition_vanka[l], additional_data.smoothing_eig_cg_n_iterations);
+        const double lambda = estimate_max_eigenvalue<BlockVectorType>(*mg_operators[l], *precondition_vanka[l], additional_data.smoothing_eig_cg_n_iterations);
         mg_smoother[l].initialize_chebyshev(*mg_operators[l], precondition_vanka[l], lambda > 0 && std::isfinite(lambda) ? lambda : 1.0,
                                             additional_data.smoothing_range, additional_data.smoothing_steps);
         continue;
       }
       double omega = additional_data.relaxation;
       if (omega == 0.0)
-        omega = estimate_relaxation<Number>(*mg_operators[l], *precondition_vanka[l], additional_data.smoothing_eig_cg_n_iterations,
+        omega = estimate_relaxation<BlockVectorType>(*mg_operators[l], *precondition_vanka[l], additional_data.smoothing_eig_cg_n_iterations,
                                             additional_data.smoothing_range);
       mg_smoother[l].initialize(*mg_operators[l], precondition_vanka[l], omega, additional_data.smoothing_steps);
     }
@@ -566,39 +580,18 @@ private:
     const double beta = norm(cv_[0]);
     if (!(beta > tol)) return;
     axpby(0.0, cv_[0], 1.0 / beta, cv_[0], stream_);
-    std::vector<double> H(size_t(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1, 0.0), hcol(m);
-    g[0] = beta;
-    unsigned j = 0;
-    for (; j < m;) {
+    HessenbergLeastSquares ls(m, beta);
+    std::vector<double> hcol(m);
+    for (unsigned j = 0; j < m; ++j) {
       mg_operators[0]->vmult(cw_, cv_[j], stream_);
       if (precondition_sequence[0] == unsigned(SupportedSmoothers::Identity)) axpby(1.0, cw_, 0.0, cv_[j + 1], stream_);
       else mg_smoother[0].vmult(cv_[j + 1], cw_, stream_);
       const double hn = orthogonalize(cv_, j + 1, cv_[j + 1], hcol.data());
-      for (unsigned i = 0; i <= j; ++i) H[i * m + j] = hcol[i];
-      H[(j + 1) * m + j] = hn;
       if (hn > 0) axpby(0.0, cv_[j + 1], 1.0 / hn, cv_[j + 1], stream_);
-      for (unsigned i = 0; i < j; ++i) {
-        const double t1 = cs[i] * H[i * m + j] + sn[i] * H[(i + 1) * m + j];
-        H[(i + 1) * m + j] = -sn[i] * H[i * m + j] + cs[i] * H[(i + 1) * m + j];
-        H[i * m + j] = t1;
-      }
-      const double d = std::hypot(H[j * m + j], H[(j + 1) * m + j]);
-      cs[j] = H[j * m + j] / d;
-      sn[j] = H[(j + 1) * m + j] / d;
-      H[j * m + j] = d;
-      H[(j + 1) * m + j] = 0.0;
-      g[j + 1] = -sn[j] * g[j];
-      g[j] = cs[j] * g[j];
-      ++j;
-      if (std::abs(g[j]) <= tol || !(hn > 0)) break;
+      if (ls.append_column(hcol, hn) <= tol || !(hn > 0)) break;
     }
-    std::vector<double> y(j);
-    for (int i = int(j) - 1; i >= 0; --i) {
-      double sum = g[i];
-      for (unsigned k = i + 1; k < j; ++k) sum -= H[i * m + k] * y[k];
-      y[i] = sum / H[i * m + i];
-    }
-    for (unsigned i = 0; i < j; ++i) axpby(y[i], cv_[i], 1.0, x, stream_);
+    const std::vector<double> y = ls.solve();
+    for (unsigned i = 0; i < y.size(); ++i) axpby(y[i], cv_[i], 1.0, x, stream_);
   }
   // One cycle = a fixed sequence of ~10^3 launches on the level vectors this object owns.  With STFEM_MG_GRAPH=1 the first
   // call runs it as it is (the operators allocate their scratch on first use), the second records it into a hipGraph

@@ -493,6 +493,9 @@ public:
     const int rc = stfem_stokes_vanka_step(v_.get(), d.data(), omega, accumulate ? 1 : 0, s.data(), stream);
     if (rc != STFEM_OK) throw Error(rc, std::string("PreconditionVankaStokes::vmult: ") + stfem_stokes_vanka_last_error());
   }
+  // the same on a vector that holds its blocks (StokesBlockVector): the smoother interface PreconditionRelaxation and the power iteration consume
+  template <typename V> void vmult(V &dst, const V &src, void *stream = nullptr) const { step(dst.blocks(), 1.0, false, src.blocks(), stream); }
+  template <typename V> void step(V &dst, double omega, bool accumulate, const V &src, void *stream = nullptr) const { step(dst.blocks(), omega, accumulate, src.blocks(), stream); }
   int n_classes() const { return stfem_stokes_vanka_n_classes(v_.get()); }
 
 private:

@@ -181,34 +181,86 @@ private:
   BlockSlice slice;
 };
 
-// PreconditionRelaxation around the two-variable Vanka smoother (stmg.h:1199-1238): n sweeps of x <- x + omega P^-1 (b - A x) from 0
-template <typename System> class PreconditionRelaxationStokes {
-public:
-  PreconditionRelaxationStokes(const System &A, const PreconditionVankaStokes<double> &P, double omega, unsigned n_iterations)
-    : A(A), P(P), omega(omega), n_iterations(n_iterations)
-  {}
-  void vmult(StokesBlockVector &dst, const StokesBlockVector &src, void *stream = nullptr) const
+// the start vector of the power iteration (estimate_max_eigenvalue in stmg.h): (i mod 11) - mean on every block, each of its own size
+inline void power_iteration_start(StokesBlockVector &v)
+{
+  for (StokesVector &b : v.blocks()) b.copy_from_host(power_iteration_start(b.size()));
+}
+
+// Wall time of a scope added to `acc`, the device synchronised at both edges; nothing at all when off
+struct SynchronisedTimer {
+  SynchronisedTimer(double &acc, bool on = true) : acc(acc), on(on)
   {
-    P.step(dst.blocks(), omega, false, src.blocks(), stream);
-    for (unsigned it = 1; it < n_iterations; ++it) {
-      reinit_like(res, src);
-      A.vmult(res, dst, stream);
-      axpby(1.0, src, -1.0, res, stream);
-      P.step(dst.blocks(), omega, true, res.blocks(), stream);
+    if (on) {
+      (void)stfem_stream_synchronize(nullptr);
+      t0 = std::chrono::steady_clock::now();
     }
   }
-  void set_relaxation(double omega_) { omega = omega_; } // (a linearised operator: the damping follows the operator)
-
-private:
-  const System &A;
-  const PreconditionVankaStokes<double> &P;
-  double omega;
-  unsigned n_iterations;
-  mutable StokesBlockVector res;
+  ~SynchronisedTimer()
+  {
+    if (on) {
+      (void)stfem_stream_synchronize(nullptr);
+      acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+  }
+  double &acc;
+  bool on;
+  std::chrono::steady_clock::time_point t0;
 };
 
-template <typename System>
-double estimate_relaxation_stokes(const System &A, const PreconditionVankaStokes<double> &P, unsigned n_iterations = 20, double smoothing_range = 1.0);
+// The smoother of one Stokes level, or of a single-level preconditioner: the two-variable Vanka smoother, its damping omega and
+// PreconditionRelaxation (stmg.h:1199-1238) around both.  Without a nonlinear treatment all three are made by the constructor.
+// With one they belong to a linearisation: the first set_data makes the per-cell smoother of the operator linearised about `lin`,
+// every later one updates its blocks (PreconditionVankaStokes::update), and the damping follows the operator.  relaxation == 0:
+// omega is estimated as the reference's default does (20 power iterations on P^-1 A), at the first set_data and - unless
+// reestimate_relaxation is false - at every later one.  The preconditioner interface of TimeIntegratorNavierStokes beside GMGStokes.
+template <int dim> class RelaxedVankaStokes {
+public:
+  RelaxedVankaStokes(const StokesMatrixFreeOperator<dim, double> &K, const StokesSystem<dim, double> &system, const FullMatrix<double> &Alpha,
+                     const FullMatrix<double> &Beta, const BlockSlice &slice, NonlinearTreatment treatment, unsigned n_iterations, double relaxation = 0.0,
+                     bool reestimate_relaxation = true)
+    : K(K), system(system), Alpha(Alpha), Beta(Beta), slice(slice), treatment(treatment), n_iterations(n_iterations), relaxation_(relaxation),
+      reestimate(reestimate_relaxation)
+  {
+    if (treatment != NonlinearTreatment::None) return;
+    vanka = std::make_unique<PreconditionVankaStokes<double>>(K, Alpha, Beta, slice);
+    relax_with_new_omega();
+  }
+  void set_data(const StokesBlockVector &lin)
+  {
+    if (treatment == NonlinearTreatment::None) throw std::invalid_argument("RelaxedVankaStokes::set_data: a smoother without a nonlinear treatment");
+    if (vanka) vanka->update(lin.blocks());
+    else vanka = std::make_unique<PreconditionVankaStokes<double>>(K, Alpha, Beta, slice, treatment, lin.blocks());
+    relax_with_new_omega();
+  }
+  void vmult(StokesBlockVector &dst, const StokesBlockVector &src, void *stream = nullptr) const
+  {
+    if (!relax) throw std::invalid_argument("RelaxedVankaStokes::vmult: set_data first");
+    relax->vmult(dst, src, stream);
+  }
+  bool ready() const { return bool(relax); }
+  double relaxation() const { return omega; }
+
+private:
+  using Relaxation = PreconditionRelaxation<double, StokesSystem<dim, double>, PreconditionVankaStokes<double>, StokesBlockVector>;
+  void relax_with_new_omega() // omega: given, the first estimate or a fresh one
+  {
+    if (relaxation_ != 0.0) omega = relaxation_;
+    else if (!relax || reestimate) omega = estimate_relaxation<StokesBlockVector>(system, *vanka, 20, 1.0);
+    if (relax) relax->set_relaxation(omega);
+    else relax = std::make_unique<Relaxation>(system, *vanka, omega, n_iterations);
+  }
+  const StokesMatrixFreeOperator<dim, double> &K;
+  const StokesSystem<dim, double> &system;
+  const FullMatrix<double> &Alpha, &Beta;
+  BlockSlice slice;
+  NonlinearTreatment treatment;
+  unsigned n_iterations;
+  double relaxation_, omega = 1.0;
+  bool reestimate;
+  std::unique_ptr<PreconditionVankaStokes<double>> vanka;
+  std::unique_ptr<Relaxation> relax;
+};
 
 // The geometric multigrid of the reference's Stokes runs (tests/tp_03stokes.cc:283-290, 484-770: coarsening sequence in space from
 // MGTransferGlobalCoarseningTools::create_geometric_coarsening_sequence, one StokesMatrixFreeOperator / SystemMatrixStokes /
@@ -285,14 +337,14 @@ public:
   const StokesSystem<dim, double> &finest_system() const { return *levels_.back().system; }
   const StokesMatrixFreeOperator<dim, double> &finest_operator() const { return *levels_.back().K; }
   const std::shared_ptr<StokesSpaces> &finest_spaces() const { return levels_.back().spaces; }
-  double relaxation(unsigned level) const { return levels_.at(level).omega; }
+  double relaxation(unsigned level) const { return levels_.at(level).smoother->relaxation(); }
   unsigned n_levels() const { return unsigned(levels_.size()); }
   NonlinearTreatment nonlinear_treatment() const { return treatment_; }
   // The hierarchy of the operator linearised about `lin` (the reference's set_data + reinit_asm(..., mg_data), include/stmg.h:929-965):
   // the finest level refers to lin itself (only its velocity blocks are read; it has to outlive the cycles), every coarser level
   // holds the nodal interpolation of the level above (MGTwoLevelTransfer::interpolate on the three components of every time dof:
   // the reference's mg_data[l]), in storage made at the first call.  Then, level by level: the operator's set_data, the per-cell
-  // smoother of the linearised operator (made at the first call, update afterwards) and the damping of its relaxation.
+  // smoother of the linearised operator and the damping of its relaxation (RelaxedVankaStokes::set_data).
   void set_data(const StokesBlockVector &lin)
   {
     if (treatment_ == NonlinearTreatment::None) throw std::invalid_argument("GMGStokes::set_data: a hierarchy without a nonlinear treatment");
@@ -311,15 +363,9 @@ public:
           check(stfem_transfer_interpolate(F.tr_u->handle(), L.lin.view(b).handle(), fine, nullptr), "GMGStokes::set_data: interpolate");
         }
       }
-      const std::vector<StokesVector> &blocks = l == top ? lin.blocks() : L.lin.blocks();
-      L.A->set_data(blocks);
-      const bool first = !L.vanka;
-      if (first) L.vanka = std::make_unique<PreconditionVankaStokes<double>>(*L.K, L.Alpha, L.Beta, L.slice, treatment_, blocks);
-      else L.vanka->update(blocks);
-      if (data_.relaxation != 0.0) L.omega = data_.relaxation;
-      else if (first || data_.reestimate_relaxation) L.omega = estimate_relaxation_stokes(*L.system, *L.vanka, 20, 1.0);
-      if (first) L.relax = std::make_unique<PreconditionRelaxationStokes<StokesSystem<dim, double>>>(*L.system, *L.vanka, L.omega, data_.smoothing_degree);
-      else L.relax->set_relaxation(L.omega);
+      const StokesBlockVector &about = l == top ? lin : L.lin;
+      L.A->set_data(about.blocks());
+      L.smoother->set_data(about);
     }
   }
   // the linearisation a level below the finest holds (set_data)
@@ -342,7 +388,7 @@ public:
   {
     TraceRange scope("gmg");
     const unsigned top = unsigned(levels_.size()) - 1;
-    if (!levels_[top].relax) throw std::invalid_argument("GMGStokes::vmult: set_data first");
+    if (!levels_[top].smoother->ready()) throw std::invalid_argument("GMGStokes::vmult: set_data first");
     // (the caller's vectors may live on contexts of their own for the same mesh: view their blocks through this level's spaces)
     const unsigned nb = levels_[top].slice.n_blocks();
     for (unsigned b = 0; b < nb; ++b) axpby(1.0, foreign_view(src, b), 0.0, levels_[top].defect.view(b));
@@ -366,32 +412,11 @@ private:
     std::shared_ptr<StokesSpaces> spaces;
     std::unique_ptr<SystemMatrixStokes<dim, double>> A;
     std::unique_ptr<StokesSystem<dim, double>> system;
-    std::unique_ptr<PreconditionVankaStokes<double>> vanka;
-    std::unique_ptr<PreconditionRelaxationStokes<StokesSystem<dim, double>>> relax;
+    std::unique_ptr<RelaxedVankaStokes<dim>> smoother; // (linearised levels: smoother and damping belong to a linearisation - set_data)
     std::unique_ptr<MGTwoLevelTransfer<double>> tr_u, tr_p; // to the level below
-    double omega = 1.0;
     mutable StokesBlockVector defect, solution, t, tmp;
     StokesBlockVector lin; // linearised levels below the finest: the interpolated linearisation (mg_data[l])
     mutable double t_smooth = 0.0, t_transfer = 0.0;
-  };
-  struct Section { // (times one section of the cycle when STFEM_MG_TIMING is set)
-    Section(bool on, double &acc) : on(on), acc(acc)
-    {
-      if (on) {
-        (void)stfem_stream_synchronize(nullptr);
-        t0 = std::chrono::steady_clock::now();
-      }
-    }
-    ~Section()
-    {
-      if (on) {
-        (void)stfem_stream_synchronize(nullptr);
-        acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      }
-    }
-    bool on;
-    double &acc;
-    std::chrono::steady_clock::time_point t0;
   };
   void build(const Mesh &mesh, double viscosity, const std::set<boundary_id> &weak_boundary_ids, TimeStepType type)
   {
@@ -404,17 +429,13 @@ private:
         if (mesh.ncell[d] % f) throw std::invalid_argument("GMGStokes: the cell counts must be divisible by 2^(space levels - 1)");
         L.mesh.ncell[d] = mesh.ncell[d] / f;
       }
-      const bool linearised = treatment_ != NonlinearTreatment::None;
       L.K = std::make_unique<StokesMatrixFreeOperator<dim, double>>(L.mesh, 2, viscosity, weak_boundary_ids, std::set<boundary_id>(), 20.0, 10.0, 0.0, 0.0, 0.0,
                                                                    dg_, treatment_);
       L.spaces = std::make_shared<StokesSpaces>(L.mesh, L.K->handle());
       L.A = std::make_unique<SystemMatrixStokes<dim, double>>(*L.K, L.Alpha, L.Beta, L.slice, treatment_);
       L.system = std::make_unique<StokesSystem<dim, double>>(*L.A, L.spaces, L.K->handle(), L.slice);
-      if (!linearised) { // (linearised levels: smoother and damping belong to a linearisation - set_data)
-        L.vanka = std::make_unique<PreconditionVankaStokes<double>>(*L.K, L.Alpha, L.Beta, L.slice);
-        L.omega = data_.relaxation != 0.0 ? data_.relaxation : estimate_relaxation_stokes(*L.system, *L.vanka, 20, 1.0);
-        L.relax = std::make_unique<PreconditionRelaxationStokes<StokesSystem<dim, double>>>(*L.system, *L.vanka, L.omega, data_.smoothing_degree);
-      }
+      L.smoother = std::make_unique<RelaxedVankaStokes<dim>>(*L.K, *L.system, L.Alpha, L.Beta, L.slice, treatment_, data_.smoothing_degree, data_.relaxation,
+                                                           data_.reestimate_relaxation);
       L.system->initialize_dof_vector(L.defect);
       L.system->initialize_dof_vector(L.solution);
       L.system->initialize_dof_vector(L.t);
@@ -478,14 +499,14 @@ private:
     const unsigned steps = data_.smoothing_steps * (data_.variable ? 1u << (unsigned(levels_.size()) - 1 - level) : 1u);
     unsigned i = 0;
     if (from_zero) {
-      L.relax->vmult(L.solution, L.defect);
+      L.smoother->vmult(L.solution, L.defect);
       i = 1;
     }
     for (; i < steps; ++i) {
       reinit_like(L.tmp, L.defect);
       L.system->vmult(L.t, L.solution);
       axpby(1.0, L.defect, -1.0, L.t);
-      L.relax->vmult(L.tmp, L.t);
+      L.smoother->vmult(L.tmp, L.t);
       axpby(1.0, L.tmp, 1.0, L.solution);
     }
   }
@@ -494,16 +515,16 @@ private:
   {
     const Level &L = levels_[level];
     if (level == 0) { // MGCoarseGridApplySmoother
-      Section sec(timing_, L.t_smooth);
+      SynchronisedTimer sec(L.t_smooth, timing_);
       smooth(0, true);
       return;
     }
     const Level &C = levels_[level - 1];
     {
-      Section sec(timing_, L.t_smooth);
+      SynchronisedTimer sec(L.t_smooth, timing_);
       smooth(level, true);
     }
-    std::unique_ptr<Section> down(new Section(timing_, L.t_transfer));
+    auto down = std::make_unique<SynchronisedTimer>(L.t_transfer, timing_);
     L.system->vmult(L.t, L.solution);
     axpby(1.0, L.defect, -1.0, L.t);
     set_zero(C.defect);
@@ -520,7 +541,7 @@ private:
     }
     down.reset();
     level_v_step(level - 1);
-    std::unique_ptr<Section> up(new Section(timing_, L.t_transfer));
+    auto up = std::make_unique<SynchronisedTimer>(L.t_transfer, timing_);
     if (in_time) time_transfer(L, L.solution, L.time_prolongation, C, C.solution);
     for (unsigned b = 0; b < slice.n_blocks() && !in_time; ++b) {
       if (slice.decompose(b)[1] == 1 && dg_) {
@@ -532,7 +553,7 @@ private:
       check(stfem_transfer_prolongate(tr.handle(), L.solution.view(b).handle(), C.solution.view(b).handle(), 1, nullptr), "GMGStokes: prolongate_and_add");
     }
     up.reset();
-    Section sec(timing_, L.t_smooth);
+    SynchronisedTimer sec(L.t_smooth, timing_);
     smooth(level, false);
   }
   bool timing_ = [] {
@@ -545,41 +566,6 @@ private:
   NonlinearTreatment treatment_ = NonlinearTreatment::None;
   std::vector<Level> levels_;
 };
-
-// The relaxation parameter of PreconditionRelaxation when the reference leaves it at 0 (parameters.h:19, stmg.h:1207-1213): deal.II
-// estimates the largest eigenvalue of P^-1 A with a power iteration and takes 2 / (alpha + beta), beta = 1.2 lambda, alpha =
-// min(0.9 beta, 1) for smoothing_range <= 1 (see estimate_relaxation in stmg.h); the same for the two-variable system.
-template <typename System>
-double estimate_relaxation_stokes(const System &A, const PreconditionVankaStokes<double> &P, unsigned n_iterations, double smoothing_range)
-{
-  StokesBlockVector v, w, z;
-  A.initialize_dof_vector(v);
-  A.initialize_dof_vector(w);
-  A.initialize_dof_vector(z);
-  for (unsigned b = 0; b < v.n_blocks(); ++b) {
-    const size_t n = v.blocks()[b].size();
-    std::vector<double> guess(n);
-    double mean = 0.0;
-    for (size_t i = 0; i < n; ++i) mean += double(i % 11);
-    mean /= double(n);
-    for (size_t i = 0; i < n; ++i) guess[i] = double(i % 11) - mean;
-    v.blocks()[b].copy_from_host(guess);
-  }
-  axpby(0.0, v, 1.0 / norm(v), v);
-  double lambda = 0.0;
-  for (unsigned it = 0; it < n_iterations; ++it) {
-    A.vmult(z, v);
-    P.vmult(w.blocks(), z.blocks());
-    lambda = dot(v, w);
-    const double nw = norm(w);
-    if (!(nw > 0)) break;
-    axpby(1.0 / nw, w, 0.0, v);
-  }
-  lambda = std::abs(lambda);
-  if (!(lambda > 0) || !std::isfinite(lambda)) return 1.0;
-  const double beta = 1.2 * lambda, alpha = smoothing_range > 1.0 ? beta / smoothing_range : std::min(0.9 * beta, 1.0);
-  return 2.0 / (alpha + beta);
-}
 
 // ErrorCalculator (include/exact_solution.h:503-649) for the pressure variable in either pressure space: the temporal Lagrange
 // combination of the pressure blocks (evaluate_numerical_solution), then stfem_stokes_pressure_difference with QGauss(nq)^3
@@ -633,31 +619,21 @@ private:
 // A vector function of (x, t) at a list of points: out[c][i] = f_c(points[3 i .. 3 i + 2], t)
 using VectorPointFunction = std::function<void(double time, const std::vector<double> &points, std::array<std::vector<double>, 3> &out)>;
 
-// include/time_integrators.h:30-336 for the two-variable system: rhs = rhs_matrix (prev_u, prev_p) + time quadrature of the velocity
-// force (assemble_force per variable, 73-111: the pressure load is zero), FGMRES on the slab system, the pressure of every time
-// dof shifted to zero mean afterwards (tests/tp_03stokes.cc:1047-1062).  Alpha_1 / Gamma_1: the ONE-step scalar temporal matrices.
-template <int dim, typename System, typename Preconditioner> class TimeIntegratorStokes {
+// What the slab solves of the two-variable system share (include/time_integrators.h:30-336): the time quadrature of the velocity
+// force (assemble_force per variable, 73-111: the pressure load is zero), the start value, and the shift of every time dof's pressure
+// to zero mean afterwards (tests/tp_03stokes.cc:1047-1062).  Alpha_1 / Gamma_1: the ONE-step scalar temporal matrices.  The device
+// vectors are made at the first use.
+class StokesSlab {
 public:
-  TimeIntegratorStokes(TimeStepType type, unsigned time_degree, const FullMatrix<double> &Alpha_1, const FullMatrix<double> &Gamma_1,
-                       double gmres_tolerance, const System &matrix, const Preconditioner &preconditioner,
-                       const SystemMatrixStokes<dim, double> &rhs_matrix, const VectorPointFunction &force, bool zero_mean_pressure,
-                       double abstol = 1e-12, unsigned max_steps = 400)
-    : type(type), time_degree(time_degree), quad_time(time_points(type, time_degree)), Alpha(Alpha_1), Gamma(Gamma_1),
-      solver(max_steps, abstol, gmres_tolerance, 200), preconditioner(preconditioner), matrix(matrix), rhs_matrix(rhs_matrix), force(force),
+  StokesSlab(TimeStepType type, unsigned time_degree, const FullMatrix<double> &Alpha_1, const FullMatrix<double> &Gamma_1, const VectorPointFunction &force,
+             bool zero_mean_pressure)
+    : type(type), quad_time(time_points(type, time_degree)), Alpha(Alpha_1), Gamma(Gamma_1), force(force),
       nt_dofs(type == TimeStepType::DG ? time_degree + 1 : time_degree), zero_mean(zero_mean_pressure)
+  {}
+  // rhs += the force's load vectors: Alpha is diagonal (time quadrature = support points)
+  void assemble_force(StokesBlockVector &rhs, double time, double time_step)
   {
-    if (const char *e = std::getenv("STFEM_FGMRES_VERBOSE")) solver.verbose = unsigned(std::atoi(e));
-  }
-
-  // x, rhs: the slab's blocks; prev: one (velocity, pressure) pair (BlockSlice(1, 2, 1))
-  void solve(StokesBlockVector &x, const StokesBlockVector &prev, StokesBlockVector &rhs, double time, double time_step)
-  {
-    TraceRange scope("step");
-    const StokesSpaces &sp = *x.spaces();
-    const BlockSlice &slice = x.slice();
-    set_zero(rhs);
-    rhs_matrix.vmult_slice_add(rhs.blocks(), prev.blocks());
-    // assemble_force: Alpha is diagonal (time quadrature = support points)
+    const StokesSpaces &sp = *rhs.spaces();
     if (qpoints.empty()) {
       qpoints.resize(size_t(stfem_n_cells(sp.q2->h)) * 27 * 3);
       check(stfem_quadrature_points(sp.q2->h, 3, qpoints.data()), "stfem_quadrature_points");
@@ -667,47 +643,41 @@ public:
     for (unsigned j = 0; j < quad_time.size(); ++j) {
       force(time + time_step * quad_time[j], qpoints, fq);
       for (int c = 0; c < 3; ++c) check(stfem_integrate_rhs(sp.q2->h, 3, fq[c].data(), load.handle(), c, nullptr), "stfem_integrate_rhs");
-      auto add = [&](unsigned timedof, double w) { axpby(w, load, 1.0, rhs.view(slice.index(0, 0, timedof))); };
+      auto add = [&](unsigned timedof, double w) { axpby(w, load, 1.0, rhs.view(rhs.slice().index(0, 0, timedof))); };
       if (type == TimeStepType::DG) add(j, Alpha(j, j));
       else if (j == 0)
         for (unsigned i = 0; i < nt_dofs; ++i) add(i, -Gamma(i, 0));
       else add(j - 1, Alpha(j - 1, j - 1));
     }
-    for (unsigned i = 0; i < x.n_blocks(); ++i) // extrapolate (time_integrators.h:184-194): every time dof starts from the previous solution
-      axpby(1.0, prev.view(slice.decompose(i)[1]), 0.0, x.view(i));
-    (void)dot(rhs.view(0), rhs.view(0)); // (synchronises: the clock below sees the Krylov solve alone)
-    const auto t0 = std::chrono::steady_clock::now();
-    solver.solve(matrix, x, rhs, preconditioner);
-    (void)dot(x.view(0), x.view(0));
-    solver_seconds_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (zero_mean) {
-      if (!weights.handle()) { // mean(p) = weights . p / |Omega|, p -= mean * ones (VectorTools::compute_mean_value / add_constant)
-        weights.reinit(sp.q1, 1);
-        ones.reinit(sp.q1, 1);
-        std::vector<std::vector<double>> h1(1, std::vector<double>(ones.block_size())), hw(1, std::vector<double>(ones.block_size()));
-        check(stfem_stokes_pressure_mean_vectors(sp.stokes, h1[0].data(), hw[0].data(), &volume), "stfem_stokes_pressure_mean_vectors");
-        ones.copy_from_host(h1);
-        weights.copy_from_host(hw);
-      }
-      for (unsigned a = 0; a < nt_dofs; ++a) {
-        BlockVectorT<double> &p = x.view(slice.index(0, 1, a));
-        axpby(-dot(weights, p) / volume, ones, 1.0, p);
-      }
+  }
+  // extrapolate (time_integrators.h:184-194): every time dof starts from the previous solution; prev: one (velocity, pressure) pair
+  void extrapolate(StokesBlockVector &x, const StokesBlockVector &prev) const
+  {
+    for (unsigned i = 0; i < x.n_blocks(); ++i) axpby(1.0, prev.view(x.slice().decompose(i)[1]), 0.0, x.view(i));
+  }
+  // mean(p) = weights . p / |Omega|, p -= mean * ones (VectorTools::compute_mean_value / add_constant); nothing unless asked for
+  void shift_pressure_to_zero_mean(StokesBlockVector &x)
+  {
+    if (!zero_mean) return;
+    const StokesSpaces &sp = *x.spaces();
+    if (!weights.handle()) {
+      weights.reinit(sp.q1, 1);
+      ones.reinit(sp.q1, 1);
+      std::vector<std::vector<double>> h1(1, std::vector<double>(ones.block_size())), hw(1, std::vector<double>(ones.block_size()));
+      check(stfem_stokes_pressure_mean_vectors(sp.stokes, h1[0].data(), hw[0].data(), &volume), "stfem_stokes_pressure_mean_vectors");
+      ones.copy_from_host(h1);
+      weights.copy_from_host(hw);
+    }
+    for (unsigned a = 0; a < nt_dofs; ++a) {
+      BlockVectorT<double> &p = x.view(x.slice().index(0, 1, a));
+      axpby(-dot(weights, p) / volume, ones, 1.0, p);
     }
   }
-  unsigned last_step() const { return solver.last_step(); }
-  double solver_seconds() const { return solver_seconds_; } // wall time of the FGMRES solves so far (without the right-hand sides)
 
 private:
-  double solver_seconds_ = 0.0;
   TimeStepType type;
-  unsigned time_degree;
   std::vector<double> quad_time;
   const FullMatrix<double> &Alpha, &Gamma;
-  SolverFGMRES<double, StokesBlockVector> solver;
-  const Preconditioner &preconditioner;
-  const System &matrix;
-  const SystemMatrixStokes<dim, double> &rhs_matrix;
   VectorPointFunction force;
   unsigned nt_dofs;
   bool zero_mean;
@@ -716,47 +686,45 @@ private:
   double volume = 1.0;
 };
 
-// PreconditionRelaxation around ONE per-cell Vanka smoother of the linearised operator (no multigrid): the smoother is made at the
-// first set_data and updated afterwards (PreconditionVankaStokes::update), the damping estimated for the current operator unless it
-// is given.  The preconditioner interface of TimeIntegratorNavierStokes beside GMGStokes.
-template <int dim> class PreconditionRelaxationLinearisedStokes {
+// The slab problem of the Stokes equations: rhs = rhs_matrix (prev_u, prev_p) + force, FGMRES on the slab system from the
+// extrapolated start value, zero-mean pressure.
+template <int dim, typename System, typename Preconditioner> class TimeIntegratorStokes {
 public:
-  PreconditionRelaxationLinearisedStokes(const StokesMatrixFreeOperator<dim, double> &K, const StokesSystem<dim, double> &system, const FullMatrix<double> &Alpha,
-                                         const FullMatrix<double> &Beta, const BlockSlice &slice, NonlinearTreatment treatment, unsigned n_iterations,
-                                         double relaxation = 0.0, bool reestimate_relaxation = true)
-    : K(K), system(system), Alpha(Alpha), Beta(Beta), slice(slice), treatment(treatment), n_iterations(n_iterations), relaxation_(relaxation),
-      reestimate(reestimate_relaxation)
+  TimeIntegratorStokes(TimeStepType type, unsigned time_degree, const FullMatrix<double> &Alpha_1, const FullMatrix<double> &Gamma_1,
+                       double gmres_tolerance, const System &matrix, const Preconditioner &preconditioner,
+                       const SystemMatrixStokes<dim, double> &rhs_matrix, const VectorPointFunction &force, bool zero_mean_pressure,
+                       double abstol = 1e-12, unsigned max_steps = 400)
+    : slab(type, time_degree, Alpha_1, Gamma_1, force, zero_mean_pressure), solver(max_steps, abstol, gmres_tolerance, 200),
+      preconditioner(preconditioner), matrix(matrix), rhs_matrix(rhs_matrix)
   {
-    if (treatment == NonlinearTreatment::None) throw std::invalid_argument("PreconditionRelaxationLinearisedStokes: a nonlinear treatment");
+    if (const char *e = std::getenv("STFEM_FGMRES_VERBOSE")) solver.verbose = unsigned(std::atoi(e));
   }
-  void set_data(const StokesBlockVector &lin)
+
+  // x, rhs: the slab's blocks; prev: one (velocity, pressure) pair (BlockSlice(1, 2, 1))
+  void solve(StokesBlockVector &x, const StokesBlockVector &prev, StokesBlockVector &rhs, double time, double time_step)
   {
-    const bool first = !vanka;
-    if (first) vanka = std::make_unique<PreconditionVankaStokes<double>>(K, Alpha, Beta, slice, treatment, lin.blocks());
-    else vanka->update(lin.blocks());
-    if (relaxation_ != 0.0) omega = relaxation_;
-    else if (first || reestimate) omega = estimate_relaxation_stokes(system, *vanka, 20, 1.0);
-    if (first) relax = std::make_unique<PreconditionRelaxationStokes<StokesSystem<dim, double>>>(system, *vanka, omega, n_iterations);
-    else relax->set_relaxation(omega);
+    TraceRange scope("step");
+    set_zero(rhs);
+    rhs_matrix.vmult_slice_add(rhs.blocks(), prev.blocks());
+    slab.assemble_force(rhs, time, time_step);
+    slab.extrapolate(x, prev);
+    (void)dot(rhs.view(0), rhs.view(0)); // (synchronises: the clock below sees the Krylov solve alone)
+    const auto t0 = std::chrono::steady_clock::now();
+    solver.solve(matrix, x, rhs, preconditioner);
+    (void)dot(x.view(0), x.view(0));
+    solver_seconds_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    slab.shift_pressure_to_zero_mean(x);
   }
-  void vmult(StokesBlockVector &dst, const StokesBlockVector &src, void *stream = nullptr) const
-  {
-    if (!relax) throw std::invalid_argument("PreconditionRelaxationLinearisedStokes::vmult: set_data first");
-    relax->vmult(dst, src, stream);
-  }
-  double relaxation() const { return omega; }
+  unsigned last_step() const { return solver.last_step(); }
+  double solver_seconds() const { return solver_seconds_; } // wall time of the FGMRES solves so far (without the right-hand sides)
 
 private:
-  const StokesMatrixFreeOperator<dim, double> &K;
-  const StokesSystem<dim, double> &system;
-  const FullMatrix<double> &Alpha, &Beta;
-  BlockSlice slice;
-  NonlinearTreatment treatment;
-  unsigned n_iterations;
-  double relaxation_, omega = 1.0;
-  bool reestimate;
-  std::unique_ptr<PreconditionVankaStokes<double>> vanka;
-  std::unique_ptr<PreconditionRelaxationStokes<StokesSystem<dim, double>>> relax;
+  double solver_seconds_ = 0.0;
+  StokesSlab slab;
+  SolverFGMRES<double, StokesBlockVector> solver;
+  const Preconditioner &preconditioner;
+  const System &matrix;
+  const SystemMatrixStokes<dim, double> &rhs_matrix;
 };
 
 // The slab problem of the Navier-Stokes equations: TimeIntegratorStokes with a Newton / Picard iteration in place of the one linear
@@ -767,7 +735,7 @@ private:
 // and the previous-slab term (j = 0 of the same sum, moved to the right) is rhs_matrix.form_slice_add about the previous end value.
 //   matrix (System): set_data(x), form(dst, x), vmult(dst, src) - a StokesSystem whose operator carries the treatment: Implicit
 //       applies the jacobian about x (Newton), Explicit the form about x (Picard), as in StokesMatrixFreeOperator::vmult;
-//   preconditioner: set_data(x), vmult - GMGStokes with the same treatment or PreconditionRelaxationLinearisedStokes.
+//   preconditioner: set_data(x), vmult - GMGStokes with the same treatment or RelaxedVankaStokes.
 // Per slab: x = previous solution; r = rhs - form(x); until |r| <= max(abstol, reltol |r_0|) or max_nonlinear steps (reported by
 // converged(), not thrown): set_data(x) on both, FGMRES on J delta = r from zero, x += delta.
 template <int dim, typename System, typename Preconditioner> class TimeIntegratorNavierStokes {
@@ -777,10 +745,9 @@ public:
                              const SystemMatrixStokes<dim, double> &rhs_matrix, const VectorPointFunction &force, bool zero_mean_pressure,
                              double nonlinear_reltol = 1e-12, double nonlinear_abstol = 1e-14, unsigned max_nonlinear = 30, double linear_abstol = 1e-16,
                              unsigned max_steps = 400)
-    : type(type), time_degree(time_degree), quad_time(time_points(type, time_degree)), Alpha(Alpha_1), Gamma(Gamma_1),
-      solver(max_steps, linear_abstol, linear_tolerance, 200), preconditioner(preconditioner), matrix(matrix), rhs_matrix(rhs_matrix), force(force),
-      nt_dofs(type == TimeStepType::DG ? time_degree + 1 : time_degree), zero_mean(zero_mean_pressure), reltol(nonlinear_reltol),
-      abstol(nonlinear_abstol), max_nonlinear(max_nonlinear)
+    : slab(type, time_degree, Alpha_1, Gamma_1, force, zero_mean_pressure), solver(max_steps, linear_abstol, linear_tolerance, 200),
+      preconditioner(preconditioner), matrix(matrix), rhs_matrix(rhs_matrix), reltol(nonlinear_reltol), abstol(nonlinear_abstol),
+      max_nonlinear(max_nonlinear)
   {
     if (const char *e = std::getenv("STFEM_FGMRES_VERBOSE")) solver.verbose = unsigned(std::atoi(e));
   }
@@ -789,27 +756,11 @@ public:
   void solve(StokesBlockVector &x, const StokesBlockVector &prev, StokesBlockVector &rhs, double time, double time_step)
   {
     TraceRange scope("step");
-    const StokesSpaces &sp = *x.spaces();
-    const BlockSlice &slice = x.slice();
     set_zero(rhs);
     rhs_matrix.set_data(prev.blocks());
     rhs_matrix.form_slice_add(rhs.blocks(), prev.blocks());
-    if (qpoints.empty()) { // assemble_force, as TimeIntegratorStokes
-      qpoints.resize(size_t(stfem_n_cells(sp.q2->h)) * 27 * 3);
-      check(stfem_quadrature_points(sp.q2->h, 3, qpoints.data()), "stfem_quadrature_points");
-      load.reinit(sp.q2, 3);
-    }
-    std::array<std::vector<double>, 3> fq;
-    for (unsigned j = 0; j < quad_time.size(); ++j) {
-      force(time + time_step * quad_time[j], qpoints, fq);
-      for (int c = 0; c < 3; ++c) check(stfem_integrate_rhs(sp.q2->h, 3, fq[c].data(), load.handle(), c, nullptr), "stfem_integrate_rhs");
-      auto add = [&](unsigned timedof, double w) { axpby(w, load, 1.0, rhs.view(slice.index(0, 0, timedof))); };
-      if (type == TimeStepType::DG) add(j, Alpha(j, j));
-      else if (j == 0)
-        for (unsigned i = 0; i < nt_dofs; ++i) add(i, -Gamma(i, 0));
-      else add(j - 1, Alpha(j - 1, j - 1));
-    }
-    for (unsigned i = 0; i < x.n_blocks(); ++i) axpby(1.0, prev.view(slice.decompose(i)[1]), 0.0, x.view(i));
+    slab.assemble_force(rhs, time, time_step);
+    slab.extrapolate(x, prev);
     reinit_like(residual, x);
     reinit_like(delta, x);
     nonlinear_steps_ = 0;
@@ -820,7 +771,7 @@ public:
     for (;;) {
       double rn;
       {
-        Clock c(residual_seconds_);
+        SynchronisedTimer c(residual_seconds_);
         matrix.set_data(x);
         matrix.form(residual, x);
         axpby(1.0, rhs, -1.0, residual);
@@ -834,11 +785,11 @@ public:
       }
       if (nonlinear_steps_ == max_nonlinear) break;
       {
-        Clock c(set_data_seconds_);
+        SynchronisedTimer c(set_data_seconds_);
         preconditioner.set_data(x);
       }
       {
-        Clock c(solver_seconds_);
+        SynchronisedTimer c(solver_seconds_);
         set_zero(delta);
         solver.solve(matrix, delta, residual, preconditioner);
         linear_steps_ += solver.last_step();
@@ -846,20 +797,7 @@ public:
       axpby(1.0, delta, 1.0, x);
       ++nonlinear_steps_;
     }
-    if (zero_mean) {
-      if (!weights.handle()) {
-        weights.reinit(sp.q1, 1);
-        ones.reinit(sp.q1, 1);
-        std::vector<std::vector<double>> h1(1, std::vector<double>(ones.block_size())), hw(1, std::vector<double>(ones.block_size()));
-        check(stfem_stokes_pressure_mean_vectors(sp.stokes, h1[0].data(), hw[0].data(), &volume), "stfem_stokes_pressure_mean_vectors");
-        ones.copy_from_host(h1);
-        weights.copy_from_host(hw);
-      }
-      for (unsigned a = 0; a < nt_dofs; ++a) {
-        BlockVectorT<double> &p = x.view(slice.index(0, 1, a));
-        axpby(-dot(weights, p) / volume, ones, 1.0, p);
-      }
-    }
+    slab.shift_pressure_to_zero_mean(x);
   }
   // the last slab: Newton / Picard steps, FGMRES iterations over all of them, whether the tolerance was met, the residual norms
   unsigned nonlinear_steps() const { return nonlinear_steps_; }
@@ -873,41 +811,18 @@ public:
   double solver_seconds() const { return solver_seconds_; }
 
 private:
-  struct Clock {
-    explicit Clock(double &acc) : acc(acc)
-    {
-      (void)stfem_stream_synchronize(nullptr);
-      t0 = std::chrono::steady_clock::now();
-    }
-    ~Clock()
-    {
-      (void)stfem_stream_synchronize(nullptr);
-      acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    double &acc;
-    std::chrono::steady_clock::time_point t0;
-  };
   double residual_seconds_ = 0.0, set_data_seconds_ = 0.0, solver_seconds_ = 0.0;
-  TimeStepType type;
-  unsigned time_degree;
-  std::vector<double> quad_time;
-  const FullMatrix<double> &Alpha, &Gamma;
+  StokesSlab slab;
   SolverFGMRES<double, StokesBlockVector> solver;
   Preconditioner &preconditioner;
   const System &matrix;
   const SystemMatrixStokes<dim, double> &rhs_matrix;
-  VectorPointFunction force;
-  unsigned nt_dofs;
-  bool zero_mean;
   double reltol, abstol;
   unsigned max_nonlinear;
   unsigned nonlinear_steps_ = 0, linear_steps_ = 0;
   bool converged_ = false;
   std::vector<double> residuals_;
-  std::vector<double> qpoints;
-  BlockVectorT<double> load, weights, ones;
   StokesBlockVector residual, delta;
-  double volume = 1.0;
 };
 
 } // namespace stfem

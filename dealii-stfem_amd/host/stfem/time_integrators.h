@@ -4,6 +4,7 @@
 // on top of the C-ABI.  Everything heavy - operator, smoother, load vectors, error norms, vector arithmetic -
 // runs on the device; this file is the control flow.
 #pragma once
+#include "hessenberg.h"
 #include "operators.h"
 
 #include <chrono>
@@ -93,30 +94,39 @@ struct PreconditionIdentity {
   template <typename V> void vmult(V &dst, const V &src) const { axpby(1.0, src, 0.0, dst); }
 };
 
-// PreconditionRelaxation (deal.II) with the Vanka smoother as inner preconditioner, as the multigrid levels of the
-// reference use it (stmg.h:1199-1238): n_iterations sweeps of x <- x + omega P^-1 (b - A x) from x = 0
-template <typename Number, typename Operator> class PreconditionRelaxation {
+template <typename Number> inline void reinit_like(BlockVectorT<Number> &v, const BlockVectorT<Number> &x)
+{
+  if (!v.handle()) v.reinit(x.context(), x.n_blocks());
+}
+
+// PreconditionRelaxation (deal.II) with a Vanka smoother as inner preconditioner, as the multigrid levels of the
+// reference use it (stmg.h:1199-1238): n_iterations sweeps of x <- x + omega P^-1 (b - A x) from x = 0.
+// Smoother / VectorType: PreconditionVanka on BlockVectorT, or PreconditionVankaStokes on the two-variable StokesBlockVector
+// (host/stfem/stokes_solver.h); the vector type brings the free functions axpby and reinit_like.
+template <typename Number, typename Operator, typename Smoother = PreconditionVanka<Number>, typename VectorType = BlockVectorT<Number>>
+class PreconditionRelaxation {
 public:
-  PreconditionRelaxation(const Operator &A, const PreconditionVanka<Number> &P, double omega, unsigned n_iterations)
+  PreconditionRelaxation(const Operator &A, const Smoother &P, double omega, unsigned n_iterations)
     : A(A), P(P), omega(omega), n_iterations(n_iterations)
   {}
-  void vmult(BlockVectorT<Number> &dst, const BlockVectorT<Number> &src, void *stream = nullptr) const
+  void vmult(VectorType &dst, const VectorType &src, void *stream = nullptr) const
   {
-    if (!res.handle() && n_iterations > 1) A.initialize_dof_vector(res);
     P.step(dst, omega, false, src, stream); // dst = omega P^-1 src (scaling and update ride in the smoother's scatter)
     for (unsigned it = 1; it < n_iterations; ++it) {
+      reinit_like(res, src);
       A.vmult(res, dst, stream);
       axpby(1.0, src, -1.0, res, stream); // res = src - A dst
       P.step(dst, omega, true, res, stream);
     }
   }
+  void set_relaxation(double omega_) { omega = omega_; } // (a linearised operator: the damping follows the operator)
 
 private:
   const Operator &A;
-  const PreconditionVanka<Number> &P;
+  const Smoother &P;
   double omega;
   unsigned n_iterations;
-  mutable BlockVectorT<Number> res;
+  mutable VectorType res;
 };
 
 // deal.II SolverFGMRES with ReductionControl(max_steps, abs_tol, reduce) as the reference sets it up
@@ -124,10 +134,6 @@ private:
 // right-preconditioned flexible GMRES, modified Gram-Schmidt, Givens rotations.
 // VectorType: BlockVectorT<Number>, or any type with the free functions axpby, norm, orthogonalize and reinit_like
 // (host/stfem/stokes_solver.h: the two-variable block vector of the Stokes systems).
-template <typename Number> inline void reinit_like(BlockVectorT<Number> &v, const BlockVectorT<Number> &x)
-{
-  if (!v.handle()) v.reinit(x.context(), x.n_blocks());
-}
 template <typename Number, typename VectorType = BlockVectorT<Number>> class SolverFGMRES {
 public:
   using V = VectorType;
@@ -160,49 +166,24 @@ public:
       if (steps >= max_steps) throw std::runtime_error("SolverFGMRES: no convergence");
       const unsigned m = std::min(restart, max_steps - steps);
       if (vs.size() < m + 1) { vs.resize(m + 1); zs.resize(m); }
-      std::vector<double> H(size_t(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1, 0.0);
+      HessenbergLeastSquares ls(m, beta);
       fresh(vs[0]);
       axpby(1.0 / beta, r, 0.0, vs[0]);
-      g[0] = beta;
-      unsigned j = 0;
-      for (; j < m; ++j) {
+      for (unsigned j = 0; j < m; ++j) {
         fresh(zs[j]);
         fresh(vs[j + 1]);
         P.vmult(zs[j], vs[j]);
         A.vmult(vs[j + 1], zs[j]);
         hcol.resize(j + 1);
         const double hn = orthogonalize(vs, j + 1, vs[j + 1], hcol.data());
-        for (unsigned i = 0; i <= j; ++i) H[i * m + j] = hcol[i];
-        H[(j + 1) * m + j] = hn;
         if (hn > 0) axpby(1.0 / hn, vs[j + 1], 0.0, vs[j + 1]);
-        for (unsigned i = 0; i < j; ++i) {
-          const double t = cs[i] * H[i * m + j] + sn[i] * H[(i + 1) * m + j];
-          H[(i + 1) * m + j] = -sn[i] * H[i * m + j] + cs[i] * H[(i + 1) * m + j];
-          H[i * m + j] = t;
-        }
-        const double d = std::hypot(H[j * m + j], H[(j + 1) * m + j]);
-        cs[j] = H[j * m + j] / d;
-        sn[j] = H[(j + 1) * m + j] / d;
-        H[j * m + j] = d;
-        H[(j + 1) * m + j] = 0.0;
-        g[j + 1] = -sn[j] * g[j];
-        g[j] = cs[j] * g[j];
+        value = ls.append_column(hcol, hn);
         ++steps;
-        value = std::abs(g[j + 1]);
         if (verbose && steps % verbose == 0) std::fprintf(stderr, "  FGMRES step %u residual %.3e (start %.3e)\n", steps, value, beta);
-        if (value <= tol || steps >= max_steps) {
-          ++j;
-          break;
-        }
+        if (value <= tol || steps >= max_steps) break;
       }
-      // x += Z y,  H y = g
-      std::vector<double> y(j);
-      for (int i = int(j) - 1; i >= 0; --i) {
-        double s = g[i];
-        for (unsigned k = i + 1; k < j; ++k) s -= H[i * m + k] * y[k];
-        y[i] = s / H[i * m + i];
-      }
-      for (unsigned i = 0; i < j; ++i) axpby(y[i], zs[i], 1.0, x);
+      const std::vector<double> y = ls.solve(); // x += Z y,  H y = g
+      for (unsigned i = 0; i < y.size(); ++i) axpby(y[i], zs[i], 1.0, x);
       if (value <= tol) return;
     }
   }

@@ -2,8 +2,7 @@
 // FE_Q(2)^3 x FE_Q(1) in space (BASELINE configs[4]), dG(k) / cG(k) in time, tau = 2^-(refinement + 1), one time step per solve,
 // homogeneous Dirichlet velocity on the whole boundary, pressure with zero mean, FGMRES (1e-12) preconditioned by relaxation sweeps
 // of the two-variable cell-patch Vanka smoother (the smoother of the reference's Stokes multigrid levels, tests/tp_03stokes.cc:714-726).
-// The reference's exact solution (include/exact_solution.h:199-325) is two-dimensional; this driver uses its 3D analogue: the
-// velocity is the curl of psi e_z, psi = sin t (sin pi x sin pi y sin pi z)^2, the pressure sin t cos pi x cos pi y cos pi z.
+// Exact solution and force: host/stokes_problem.h.
 // With mg=<levels> the preconditioner is one V-cycle of the geometric multigrid of the reference's Stokes runs (GMGStokes in
 // host/stfem/stokes_solver.h: <levels> space levels, relaxation sweeps of the Vanka smoother on every level, 2^(levels - 1 - l) smoothing
 // steps on level l); with stmg=1 in addition the levels in time of the reference's sequence (get_mg_sequence as tests/tp_03stokes.cc:294-312
@@ -12,42 +11,14 @@
 // Usage: stokes_convergence <type 0 = cG | 1 = dG> <k> <refinement> [vanka sweeps = 3] [omega = 0: estimated] [viscosity = 1] [cells per direction]
 //                           [end_time = 1] [mg=<levels>] [stmg=1] [coarsening=space_and_time] [dg=1]
 // Prints: cells u-dofs p-dofs t-dofs  u:Linf-Linf  u:L2-L2  u:L2-H1semi  p:L2-L2  gmres-iterations-per-solve
-#include "stfem/stokes_solver.h"
+#include "stokes_problem.h"
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 
 using namespace stfem;
-
-namespace {
-const double PI = 3.14159265358979323846;
-inline double A(double s) { const double q = std::sin(PI * s); return q * q; }
-inline double dA(double s) { return PI * std::sin(2 * PI * s); }
-inline double d2A(double s) { return 2 * PI * PI * std::cos(2 * PI * s); }
-inline double B(double s) { return 0.5 * std::sin(2 * PI * s); }
-inline double dB(double s) { return PI * std::cos(2 * PI * s); }
-inline double d2B(double s) { return -4 * PI * PI * B(s); }
-// the analytic functions are evaluated at up to 10^7 points per call (27 quadrature points per cell): the point loop in slices on
-// the host's cores (the reference evaluates its Functions inside the threaded cell loops of deal.II)
-template <typename Body> void for_points(size_t n, Body &&body)
-{
-  const unsigned nthreads = n < 65536 ? 1u : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (nthreads == 1) {
-    body(size_t(0), n);
-    return;
-  }
-  std::vector<std::thread> pool;
-  const size_t chunk = (n + nthreads - 1) / nthreads;
-  for (unsigned t = 0; t < nthreads; ++t) {
-    const size_t lo = std::min(n, t * chunk), hi = std::min(n, lo + chunk);
-    if (lo < hi) pool.emplace_back([&body, lo, hi] { body(lo, hi); });
-  }
-  for (auto &th : pool) th.join();
-}
-} // namespace
 
 int main(int argc_all, char **argv_all)
 {
@@ -91,57 +62,7 @@ int main(int argc_all, char **argv_all)
     const bool cgp = type == TimeStepType::CGP;
     SystemMatrixStokes<3, double> rhs_matrix(K, cgp ? w[2] : zero, cgp ? w[3] : w[2], slice);
     StokesSystem<3, double> system(matrix, spaces, K.handle(), slice);
-    PreconditionVankaStokes<double> vanka(K, w[0], w[1], slice);
-    const double omega = omega_arg != 0.0 ? omega_arg : estimate_relaxation_stokes(system, vanka);
-    PreconditionRelaxationStokes<StokesSystem<3, double>> preconditioner(system, vanka, omega, sweeps);
-
-    const VectorPointFunction force = [&](double t, const std::vector<double> &p, std::array<std::vector<double>, 3> &out) {
-      const size_t np = p.size() / 3;
-      const double st = std::sin(t), ct = std::cos(t);
-      for (auto &o : out) o.resize(np);
-      for_points(np, [&](size_t lo, size_t hi) {
-      for (size_t i = lo; i < hi; ++i) {
-        const double x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
-        const double lap1 = d2A(x) * B(y) * A(z) + A(x) * d2B(y) * A(z) + A(x) * B(y) * d2A(z);
-        const double lap2 = d2B(x) * A(y) * A(z) + B(x) * d2A(y) * A(z) + B(x) * A(y) * d2A(z);
-        const double sx = std::sin(PI * x), sy = std::sin(PI * y), sz = std::sin(PI * z), cx = std::cos(PI * x), cy = std::cos(PI * y), cz = std::cos(PI * z);
-        out[0][i] = 2 * PI * (ct * A(x) * B(y) * A(z) - nu * st * lap1) - PI * st * sx * cy * cz;
-        out[1][i] = -2 * PI * (ct * B(x) * A(y) * A(z) - nu * st * lap2) - PI * st * cx * sy * cz;
-        out[2][i] = -PI * st * cx * cy * sz;
-      }
-      });
-    };
-    auto exact_u = [&](int c) {
-      return PointFunction([c](double t, const std::vector<double> &p, std::vector<double> &out) {
-        out.resize(p.size() / 3);
-        const double a = 2 * PI * std::sin(t);
-        for_points(out.size(), [&](size_t lo, size_t hi) {
-          for (size_t i = lo; i < hi; ++i) {
-            const double x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
-            out[i] = c == 0 ? a * A(x) * B(y) * A(z) : (c == 1 ? -a * B(x) * A(y) * A(z) : 0.0);
-          }
-        });
-      });
-    };
-    auto exact_grad_u = [&](int c) {
-      return PointFunction([c](double t, const std::vector<double> &p, std::vector<double> &out) {
-        out.assign(p.size(), 0.0);
-        const double a = 2 * PI * std::sin(t);
-        for_points(p.size() / 3, [&](size_t lo, size_t hi) {
-          for (size_t i = lo; i < hi; ++i) {
-            const double x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
-            if (c == 0) { out[3 * i] = a * dA(x) * B(y) * A(z); out[3 * i + 1] = a * A(x) * dB(y) * A(z); out[3 * i + 2] = a * A(x) * B(y) * dA(z); }
-            if (c == 1) { out[3 * i] = -a * dB(x) * A(y) * A(z); out[3 * i + 1] = -a * B(x) * dA(y) * A(z); out[3 * i + 2] = -a * B(x) * A(y) * dA(z); }
-          }
-        });
-      });
-    };
-    const PointFunction exact_p = [](double t, const std::vector<double> &p, std::vector<double> &out) {
-      out.resize(p.size() / 3);
-      for_points(out.size(), [&](size_t lo, size_t hi) {
-        for (size_t i = lo; i < hi; ++i) out[i] = std::sin(t) * std::cos(PI * p[3 * i]) * std::cos(PI * p[3 * i + 1]) * std::cos(PI * p[3 * i + 2]);
-      });
-    };
+    RelaxedVankaStokes<3> preconditioner(K, system, w[0], w[1], slice, NonlinearTreatment::None, sweeps, omega_arg); // (omega 0: estimated)
 
     // the preconditioner behind one interface: relaxation sweeps on the finest level, or one V-cycle
     std::unique_ptr<GMGStokes<3>> gmg;
@@ -160,9 +81,9 @@ int main(int argc_all, char **argv_all)
       } else gmg = std::make_unique<GMGStokes<3>>(mesh, mg_levels, nu, w[0], w[1], slice, ad, std::set<boundary_id>(), dg_pressure);
       for (unsigned l = 0; l < gmg->n_levels(); ++l) std::fprintf(stderr, "level %u: relaxation %.4f\n", l, gmg->relaxation(l));
     } else
-      std::fprintf(stderr, "relaxation %.4f\n", omega);
+      std::fprintf(stderr, "relaxation %.4f\n", preconditioner.relaxation());
     struct Prec {
-      const PreconditionRelaxationStokes<StokesSystem<3, double>> *relax;
+      const RelaxedVankaStokes<3> *relax;
       const GMGStokes<3> *gmg;
       void vmult(StokesBlockVector &dst, const StokesBlockVector &src) const
       {
@@ -170,18 +91,15 @@ int main(int argc_all, char **argv_all)
         else relax->vmult(dst, src);
       }
     } prec{&preconditioner, gmg.get()};
-    TimeIntegratorStokes<3, StokesSystem<3, double>, Prec> step(type, k, Alpha_1, Gamma_1, 1e-12, system, prec, rhs_matrix, force, true);
-    // ErrorCalculator (exact_solution.h:503-649): QGauss(k + 1) in time; QGauss(3) per direction for the velocity components, QGauss(2) for the pressure
-    std::vector<ErrorCalculator<double>> err_u;
-    for (int c = 0; c < 3; ++c) err_u.emplace_back(type, k, 3, spaces->q2, exact_u(c), exact_grad_u(c));
-    PressureErrorCalculator err_p(type, k, 2, spaces, exact_p);
+    TimeIntegratorStokes<3, StokesSystem<3, double>, Prec> step(type, k, Alpha_1, Gamma_1, 1e-12, system, prec, rhs_matrix, stokes_problem::force(nu, false), true);
+    stokes_problem::SlabErrors err(type, k, spaces);
 
     StokesBlockVector x, rhs, prev;
     x.reinit(spaces, K.handle(), slice);
     rhs.reinit(spaces, K.handle(), slice);
     prev.reinit(spaces, K.handle(), slice1); // u(0) = 0, p(0) = 0
     const size_t nu_dofs = size_t(stfem_stokes_n_velocity_dofs(K.handle()));
-    double time = 0.0, l2 = 0.0, l8 = -1.0, h1 = 0.0, l2p = 0.0;
+    double time = 0.0;
     unsigned solves = 0, iterations = 0;
     double solve_seconds = 0.0;
     while (time < end_time - 1e-12) {
@@ -191,37 +109,15 @@ int main(int argc_all, char **argv_all)
       solve_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       iterations += step.last_step();
       ++solves;
-      // component c of the time dofs as a block vector of the scalar velocity space; the pressure blocks likewise
-      for (int c = 0; c < 3; ++c) {
-        std::vector<void *> ptrs(nt);
-        for (unsigned a = 0; a < nt; ++a) ptrs[a] = x.blocks()[slice.index(0, 0, a)].data() + c * nu_dofs;
-        BlockVectorT<double> xc, pc;
-        xc.wrap(spaces->q2, ptrs.data(), nt);
-        void *pp[1] = {prev.blocks()[0].data() + c * nu_dofs};
-        pc.wrap(spaces->q2, pp, 1);
-        const auto e = err_u[c].evaluate_error(time, tau, xc, pc, 1);
-        l2 += e[0];
-        l8 = std::max(l8, e[1]);
-        h1 += e[2];
-      }
-      {
-        std::vector<void *> ptrs(nt);
-        for (unsigned a = 0; a < nt; ++a) ptrs[a] = x.blocks()[slice.index(0, 1, a)].data();
-        BlockVectorT<double> xp, pp;
-        xp.wrap(spaces->q1, ptrs.data(), nt);
-        void *q[1] = {prev.blocks()[1].data()};
-        pp.wrap(spaces->q1, q, 1);
-        l2p += err_p.evaluate_error(time, tau, xp, pp)[0];
-      }
-      axpby(1.0, x.view(slice.index(0, 0, nt - 1)), 0.0, prev.view(0));
-      axpby(1.0, x.view(slice.index(0, 1, nt - 1)), 0.0, prev.view(1));
+      err.add(time, tau, x, prev);
+      err.advance(x, prev);
       time += tau;
     }
     std::fprintf(stderr, "%u slab solves: %.3f s (right-hand side on the host + FGMRES), FGMRES alone %.3f s for %u iterations = %.2f ms per iteration\n", solves,
                  solve_seconds, step.solver_seconds(), iterations, 1e3 * step.solver_seconds() / std::max(1u, iterations));
     if (gmg) gmg->print_timing(stderr);
-    std::printf("%d %lld %lld %u %.12e %.12e %.12e %.12e %.2f\n", n * n * n, 3ll * (long long)nu_dofs, (long long)stfem_stokes_n_pressure_dofs(K.handle()), nt, l8,
-                std::sqrt(l2), std::sqrt(h1), std::sqrt(l2p), double(iterations) / solves);
+    std::printf("%d %lld %lld %u %.12e %.12e %.12e %.12e %.2f\n", n * n * n, 3ll * (long long)nu_dofs, (long long)stfem_stokes_n_pressure_dofs(K.handle()), nt, err.l8,
+                std::sqrt(err.l2), std::sqrt(err.h1), std::sqrt(err.l2p), double(iterations) / solves);
     return 0;
   } catch (const std::exception &e) {
     std::fprintf(stderr, "error: %s\n", e.what());

@@ -125,6 +125,7 @@ SIGNATURES = {
     "stfem_transfer_restrict": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "stfem_transfer_interpolate": (C.c_int, [_vp, _vp, _vp, _vp]),
     "stfem_transfer_last_error": (C.c_char_p, []),
+    "stfem_transfer_last_path": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "stfem_transfer_line_matrices": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "stfem_vector_convert": (C.c_int, [_vp, _vp, _vp]),
     "stfem_stream_create": (C.c_int, [C.POINTER(_vp)]),
@@ -140,6 +141,7 @@ SIGNATURES = {
     "stfem_vanka_destroy": (None, [_vp]),
     "stfem_vanka_n_classes": (C.c_int, [_vp]),
     "stfem_vanka_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    "stfem_vanka_setup_batches": (C.c_int, [_vp]),
     "stfem_vanka_vmult": (C.c_int, [_vp, _vp, _vp, _vp]),
     "stfem_vanka_step": (C.c_int, [_vp, _vp, C.c_double, C.c_int, _vp, _vp]),
     "stfem_vanka_last_error": (C.c_char_p, []),
@@ -172,6 +174,7 @@ SIGNATURES = {
     "stfem_stokes_st_vmult_slice_add_convection": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(_vp),
                                                              _vp, _vp, _vp, _vp]),
     "stfem_stokes_last_hip_error": (C.c_char_p, []),
+    "stfem_stokes_last_sweep_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "stfem_stokes_set_weak_boundaries": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double]),
     "stfem_stokes_n_face_points": (C.c_int64, [_vp]),
     "stfem_stokes_face_points": (C.c_int, [_vp, _dp]),
@@ -188,12 +191,14 @@ SIGNATURES = {
     "stfem_stokes_vanka_update": (C.c_int, [_vp, C.POINTER(_vp)]),
     "stfem_stokes_vanka_destroy": (None, [_vp]),
     "stfem_stokes_vanka_n_classes": (C.c_int, [_vp]),
+    "stfem_stokes_vanka_setup_batches": (C.c_int, [_vp]),
     "stfem_stokes_vanka_vmult": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "stfem_stokes_vanka_step": (C.c_int, [_vp, C.POINTER(_vp), C.c_double, C.c_int, C.POINTER(_vp), _vp]),
     "stfem_stokes_vanka_last_error": (C.c_char_p, []),
     "stfem_strerror": (C.c_char_p, [C.c_int]),
     "stfem_last_hip_error": (C.c_char_p, []),
     "stfem_last_kernel_name": (C.c_char_p, [_vp]),
+    "stfem_last_sweep_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
 }
 
 
@@ -425,6 +430,13 @@ class MatrixFreeOperator:
     def last_kernel_name(self):
         return lib().stfem_last_kernel_name(self._h).decode()
 
+    @property
+    def last_sweep_plan(self):
+        """(tiles, workgroups launched) of the last pencil-sweep launch; (0, 0) after another kernel variant"""
+        out = (C.c_int32 * 2)()
+        _check(lib().stfem_last_sweep_plan(self._h, out), "stfem_last_sweep_plan")
+        return tuple(out)
+
 
 class PreconditionVanka:
     """stmg.h:619-907: cell-patch additive-Schwarz smoother of Alpha (x) K + Beta (x) M on one context."""
@@ -460,6 +472,11 @@ class PreconditionVanka:
         out = (C.c_int32 * 2)()
         _check(lib().stfem_vanka_plan(self._h, out), "stfem_vanka_plan")
         return tuple(out)
+
+    @property
+    def setup_batches(self):
+        """batches of cell layers the device set-up of the per-cell blocks took (0: class blocks, host set-up)"""
+        return lib().stfem_vanka_setup_batches(self._h)
 
     def vmult(self, dst, src, stream=None):
         _check(lib().stfem_vanka_vmult(self._h, dst._h, src._h, stream), "stfem_vanka_vmult")
@@ -623,8 +640,18 @@ class MGTwoLevelTransfer:
     def restrict_and_add(self, dst, src, stream=None):
         _check(lib().stfem_transfer_restrict(self._h, dst._h, src._h, 1, stream), "stfem_transfer_restrict")
 
+    def restrict(self, dst, src, stream=None):
+        _check(lib().stfem_transfer_restrict(self._h, dst._h, src._h, 0, stream), "stfem_transfer_restrict")
+
     def interpolate(self, dst, src, stream=None):
         _check(lib().stfem_transfer_interpolate(self._h, dst._h, src._h, stream), "stfem_transfer_interpolate")
+
+    @property
+    def last_path(self):
+        """(fused y-z kernel in the last prolongation, coarse cells one thread marched through in the last restriction along y, along z)"""
+        out = (C.c_int32 * 3)()
+        _check(lib().stfem_transfer_last_path(self._h, out), "stfem_transfer_last_path")
+        return tuple(out)
 
 
 def transfer_line_matrices(ncell_fine, degree_fine, ncell_coarse, degree_coarse):
@@ -829,6 +856,14 @@ class StokesMatrixFreeOperator:
         _check(lib().stfem_stokes_vmult_convection(self._h, int(mode), dst_u, dst_p, src_u, src_p, getattr(lin, "ptr", lin), stream),
                "stfem_stokes_vmult_convection")
 
+    @property
+    def last_sweep_plan(self):
+        """(tiles, workgroups launched, gradient added by the sweep itself) of the last vmult's velocity sweep (tiles and workgroups as
+        MatrixFreeOperator.last_sweep_plan of the scalar FE_Q(2) context)"""
+        out = (C.c_int32 * 3)()
+        _check(lib().stfem_stokes_last_sweep_plan(self._h, out), "stfem_stokes_last_sweep_plan")
+        return tuple(out)
+
     def mass_vmult(self, dst_u, src_u, stream=None):
         dst_u, src_u = getattr(dst_u, "ptr", dst_u), getattr(src_u, "ptr", src_u)
         _check(lib().stfem_stokes_mass_vmult(self._h, dst_u, src_u, stream), "stfem_stokes_mass_vmult")
@@ -991,6 +1026,11 @@ class StokesPreconditionVanka:
     @property
     def n_classes(self):
         return lib().stfem_stokes_vanka_n_classes(self._h)
+
+    @property
+    def setup_batches(self):
+        """batches of cell layers the last create / update of the per-cell blocks took (0: class blocks)"""
+        return lib().stfem_stokes_vanka_setup_batches(self._h)
 
     def step(self, dst_blocks, omega, accumulate, src_blocks, stream=None):
         d = (_vp * self.nb)(*[getattr(v, "ptr", v) for v in dst_blocks])

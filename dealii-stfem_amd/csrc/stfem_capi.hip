@@ -236,6 +236,13 @@ int stfem_n_dofs_1d(const stfem_ctx *c, int32_t nd[3])
 int stfem_is_cartesian(const stfem_ctx *c) { return c && c->cartesian ? 1 : 0; }
 int stfem_ctx_precision(const stfem_ctx *c) { return c ? c->prec : -1; }
 const char *stfem_last_kernel_name(const stfem_ctx *c) { return c ? c->last_kernel : ""; }
+int stfem_last_sweep_plan(const stfem_ctx *c, int32_t out[2])
+{
+  if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  out[0] = c->last_sweep[0];
+  out[1] = c->last_sweep[1];
+  return STFEM_OK;
+}
 
 int stfem_set_coefficient(stfem_ctx *c, int which, int layout, const double *host)
 {
@@ -619,6 +626,7 @@ static int apply_tiled_t(stfem_ctx *c, int nbo, int nbi, const std::vector<doubl
       if (atomic) {
         rc = PR::atomic(c->p, prm, st);
         c->last_kernel = PR::atomic_name();
+        c->last_sweep[0] = c->last_sweep[1] = 0;
       } else if (c->variant == 0 && !general && PR::pencil_geometry(c->p, std::max(tj, ti), pencil_ty, pp) == 0) {
         plan_pencil(c, pp);
         const int nbm = std::max(tj, ti);
@@ -666,6 +674,8 @@ static int apply_tiled_t(stfem_ctx *c, int nbo, int nbi, const std::vector<doubl
         }
         rc = PR::pencil(c->p, prm, pp, st);
         c->last_kernel = PR::pencil_name();
+        c->last_sweep[0] = int(ntiles);
+        c->last_sweep[1] = int(std::min<size_t>(ntiles, size_t(pp.grid))); // (launch_pencil_ty)
         if (c->env_timeline && rc == 0) {
           HIP_TRY(hipStreamSynchronize(st));
           std::vector<long long> h(ptl_n);
@@ -721,6 +731,7 @@ static int apply_tiled_t(stfem_ctx *c, int nbo, int nbi, const std::vector<doubl
         long long *tl_dev = c->d_timeline;
         rc = PR::tile(c->p, prm, tp, st);
         c->last_kernel = PR::tile_name(prm.metric != nullptr);
+        c->last_sweep[0] = c->last_sweep[1] = 0;
         if (tl_path && rc == 0) {
           HIP_TRY(hipStreamSynchronize(st));
           std::vector<long long> h(tl_n);

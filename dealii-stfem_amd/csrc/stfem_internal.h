@@ -23,6 +23,7 @@ struct stfem_ctx {
   int coef_layout[2] = {0, 0};
   double *d_scratch = nullptr; // reductions (always double)
   const char *last_kernel = "";
+  int last_sweep[2] = {0, 0}; // {tiles, workgroups} of the last pencil launch (stfem_last_sweep_plan)
   // tile variant: halo slabs (grown on demand)
   void *d_halo = nullptr;
   size_t halo_doubles = 0; // elements
@@ -85,6 +86,7 @@ struct stokes_cell_vanka;
 int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &d, const int *rowtab_xy, const double *const *lin,
                              stokes_cell_vanka **out, char (&err)[256]);
 int stokes_cell_vanka_update(stokes_cell_vanka *v, const double *const *lin, char (&err)[256]);
+int stokes_cell_vanka_setup_batches(const stokes_cell_vanka *v);
 // rows of y = B_c^-1 gather(src) of every cell to the scratch array [cell][mpad], returned in *rows
 int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_blocks, const double **rows, void *stream, char (&err)[256]);
 void stokes_cell_vanka_destroy(stokes_cell_vanka *v);

@@ -44,6 +44,13 @@ extern "C" {
 
 const char *stfem_stokes_last_hip_error(void) { return g_stokes_err; }
 
+int stfem_stokes_last_sweep_plan(const stfem_stokes_ctx *c, int32_t out[3])
+{
+  if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  out[2] = c->last_grad_in_sweep ? 1 : 0;
+  return stfem_last_sweep_plan(c->scalar, out); // the velocity sweeps run on the scalar FE_Q(2) context
+}
+
 int stfem_stokes_create(const stfem_mesh_desc *mesh, int velocity_degree, double viscosity, stfem_stokes_ctx **out)
 {
   return stfem_stokes_create_ex(mesh, velocity_degree, 0, viscosity, out);
@@ -405,6 +412,7 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
     STOKES_TRY(hipEventRecord(c->ev_join, c->side));
   }
   // ---- 3. out_u -= sum_q wKu B^T p_q
+  c->last_grad_in_sweep = grad_done;
   if (k_u && !grad_done) stokes_grad_launch(k, st);
   if (forked) STOKES_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
   else if (any_p) stokes_div_launch(k, c->Np, st);

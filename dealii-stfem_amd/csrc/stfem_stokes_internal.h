@@ -107,6 +107,7 @@ struct stfem_stokes_ctx {
   // axis-aligned uniform meshes: the scalar FE_Q(2) context whose pencil sweep applies nu K + wM M to the velocity components,
   // and the 1D tables of the coupling kernels
   stfem_ctx *scalar = nullptr;
+  bool last_grad_in_sweep = false; // the last vmult's velocity sweep added - B^T p itself (stfem_stokes_last_sweep_plan)
   CouplingParams coupling;
   // the divergence kernel reads the sources and writes the pressure destinations only: it runs beside the velocity sweep on the
   // side stream - ONE per device, shared by all Stokes contexts (stokes_side_stream), not owned - forked from and joined to the

@@ -319,6 +319,7 @@ void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v)
 }
 
 int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v) { return v ? v->nclasses : 0; }
+int stfem_stokes_vanka_setup_batches(const stfem_stokes_vanka *v) { return v ? stokes_cell_vanka_setup_batches(v->cell) : 0; }
 
 // the rows of the cell block: block i holds the 81 velocity or the npl pressure DoFs of the cell from row rowbase[i]
 static int block_rows(stfem_stokes_vanka *v, int n_blocks, const int32_t *block_variable, int npl)

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 
@@ -358,6 +359,7 @@ struct stokes_cell_vanka {
   stfem_stokes_ctx *ctx = nullptr;
   stokes_cell_vanka_desc d;
   int nl = 0, npl = 0;
+  int setup_batches = 0; // batches of cell layers the last build_blocks took
   double *d_blocks = nullptr, *d_flat = nullptr;
   int2 *d_rowtab = nullptr;
   int *d_nbr = nullptr, *d_face = nullptr, *d_rowblk = nullptr, *d_rowdof = nullptr;
@@ -393,6 +395,8 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh, cha
   }
   int L = int((budget - 2.0 * double(km_layer)) / double(km_layer + b_layer));
   L = std::max(1, std::min(L, ncz));
+  if (const char *e = getenv("STFEM_VANKA_SETUP_LAYERS")) // at most this many cell layers per batch (tests: the batch loop on small meshes)
+    if (atoi(e) > 0) L = std::min(L, atoi(e));
   if (fresh) {
     const int rc = vk_alloc(reinterpret_cast<void **>(&v->d_blocks), ncells * bsz * sizeof(double), err);
     if (rc != STFEM_OK) return rc;
@@ -431,7 +435,9 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh, cha
   for (int i = 0; i < d.nblk * d.nblk; ++i) { ap.Alpha[i] = d.Alpha[i]; ap.Beta[i] = d.Beta[i]; }
   const void *cellk = c->pspace ? reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<false>);
   (void)hipGetLastError();
+  v->setup_batches = 0;
   for (int z0 = 0; z0 < ncz && e == hipSuccess && rc == STFEM_OK; z0 += L) {
+    ++v->setup_batches;
     const int z1 = std::min(ncz, z0 + L), zw0 = std::max(0, z0 - 1), zw1 = std::min(ncz, z1 + 1);
     const size_t wcells = cpl * size_t(zw1 - zw0), bcells = cpl * size_t(z1 - z0);
     mp.cell0 = (long long)cpl * zw0;
@@ -511,6 +517,7 @@ int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &
 }
 
 int stokes_cell_vanka_update(stokes_cell_vanka *v, const double *const *lin, char (&err)[256]) { return build_blocks(v, lin, false, err); }
+int stokes_cell_vanka_setup_batches(const stokes_cell_vanka *v) { return v ? v->setup_batches : 0; }
 
 int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_blocks, const double **rows, void *stream, char (&err)[256])
 {

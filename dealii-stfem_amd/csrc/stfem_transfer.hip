@@ -347,6 +347,9 @@ struct stfem_transfer {
   int pc[3] = {0, 0, 0}, Rn[3] = {0, 0, 0}, ncc[3] = {0, 0, 0}, flags[3] = {0, 0, 0};
   void *d_tmp[2] = {nullptr, nullptr};
   size_t tmp_elems = 0;
+  // diagnostics (stfem_transfer_last_path): fused y-z kernel in the last prolongation; most coarse cells one thread marched through in
+  // the last restriction along y and z (0: table-driven pass)
+  int last_path[3] = {0, 0, 0};
 };
 
 namespace {
@@ -386,7 +389,8 @@ static int march_segments = [] {
 }();
 
 template <typename T, int PC, int R>
-int launch_cell_t(bool prolongate, T *out, const T *in, long long S, int ncell, long long total, const double *L, int flags, int add, hipStream_t s)
+int launch_cell_t(bool prolongate, T *out, const T *in, long long S, int ncell, long long total, const double *L, int flags, int add, hipStream_t s,
+                  int *marched)
 {
   CellMat<T> m;
   for (int i = 0; i < 9 * 5; ++i) m.L[i] = T(L[i]);
@@ -400,7 +404,11 @@ int launch_cell_t(bool prolongate, T *out, const T *in, long long S, int ncell, 
     const long long tot = lines * nseg;
     const int bl = int(std::min<long long>((tot + 255) / 256, 1 << 20));
     cell_restrict_march_kernel<T, PC, R><<<bl, 256, 0, s>>>(out, in, S, ncell, nseg, tot, m, flags, add);
-  } else cell_restrict_kernel<T, PC, R><<<blocks, 256, 0, s>>>(out, in, S, ncell, total, m, flags, add);
+    *marched = (ncell + nseg - 1) / nseg; // the longest segment [ncell seg / nseg, ncell (seg + 1) / nseg)
+  } else {
+    cell_restrict_kernel<T, PC, R><<<blocks, 256, 0, s>>>(out, in, S, ncell, total, m, flags, add);
+    *marched = 1;
+  }
   TR_TRY(hipGetLastError());
   return STFEM_OK;
 }
@@ -408,10 +416,10 @@ int launch_cell_t(bool prolongate, T *out, const T *in, long long S, int ncell, 
 // returns 1 if there is no instantiation for (pc, R): the caller falls back to the table-driven kernel
 template <typename T>
 int launch_cell(bool prolongate, int pc, int R, T *out, const T *in, long long S, int ncell, long long total, const double *L, int flags, int add,
-                hipStream_t s)
+                hipStream_t s, int *marched)
 {
 #define STFEM_CELL_CASE(PC_, R_) \
-  if (pc == PC_ && R == R_) return launch_cell_t<T, PC_, R_>(prolongate, out, in, S, ncell, total, L, flags, add, s);
+  if (pc == PC_ && R == R_) return launch_cell_t<T, PC_, R_>(prolongate, out, in, S, ncell, total, L, flags, add, s, marched);
   STFEM_CELL_CASE(1, 2) STFEM_CELL_CASE(1, 3) STFEM_CELL_CASE(1, 4) STFEM_CELL_CASE(1, 6) STFEM_CELL_CASE(1, 8)
   STFEM_CELL_CASE(2, 3) STFEM_CELL_CASE(2, 4) STFEM_CELL_CASE(2, 6) STFEM_CELL_CASE(2, 8)
   STFEM_CELL_CASE(3, 4) STFEM_CELL_CASE(3, 6) STFEM_CELL_CASE(3, 8)
@@ -463,6 +471,7 @@ int apply3(stfem_transfer *t, const Band B[3], void *out, const void *in, const 
     int st = launch_axis<T>(mid, cur, dims, 0, B[0], 0, s);
     if (st != STFEM_OK) return st;
     st = launch_cell_yz<T>(t->pc[1], t->Rn[1], static_cast<T *>(out), mid, dims[0], t->ncc[1], t->ncc[2], t->L[1], t->flags[1], t->flags[2], add, s);
+    if (st == STFEM_OK) t->last_path[0] = 1;
     if (st <= 0) return st;
     dims[0] = B[0].n_in; // no instantiation: the three-pass form below
   }
@@ -474,8 +483,10 @@ int apply3(stfem_transfer *t, const Band B[3], void *out, const void *in, const 
     if (cell && ax > 0 && t->Rn[ax] > t->pc[ax] && !(cell == 2 && ax == 2 && !t->cell_restrict_z)) { // (an axis with the same cells and degree on both levels is a copy: table-driven)
       const long long S = ax == 1 ? dims[0] : (long long)dims[0] * dims[1];
       const long long total = S * t->ncc[ax] * (ax == 1 ? dims[2] : 1);
-      st = launch_cell<T>(cell == 1, t->pc[ax], t->Rn[ax], dst, cur, S, t->ncc[ax], total, t->L[ax], t->flags[ax], step == 2 ? add : 0, s);
+      int marched = 0;
+      st = launch_cell<T>(cell == 1, t->pc[ax], t->Rn[ax], dst, cur, S, t->ncc[ax], total, t->L[ax], t->flags[ax], step == 2 ? add : 0, s, &marched);
       if (st < 0) return st;
+      if (st == STFEM_OK && cell == 2) t->last_path[ax] = marched;
     }
     if (st == 1) st = launch_axis<T>(dst, cur, dims, ax, B[ax], step == 2 ? add : 0, s);
     if (st != STFEM_OK) return st;
@@ -588,15 +599,26 @@ void stfem_transfer_destroy(stfem_transfer *t)
 
 int stfem_transfer_prolongate(stfem_transfer *t, stfem_vec *dst_fine, const stfem_vec *src_coarse, int add, void *stream)
 {
-  return t ? run(t, t->P, t->fine, t->coarse, dst_fine, src_coarse, true, add, stream, t->cell_form ? 1 : 0) : STFEM_ERR_INVALID_ARGUMENT;
+  if (!t) return STFEM_ERR_INVALID_ARGUMENT;
+  t->last_path[0] = 0;
+  return run(t, t->P, t->fine, t->coarse, dst_fine, src_coarse, true, add, stream, t->cell_form ? 1 : 0);
 }
 int stfem_transfer_restrict(stfem_transfer *t, stfem_vec *dst_coarse, const stfem_vec *src_fine, int add, void *stream)
 {
-  return t ? run(t, t->R, t->coarse, t->fine, dst_coarse, src_fine, false, add, stream, t->cell_form ? 2 : 0) : STFEM_ERR_INVALID_ARGUMENT;
+  if (!t) return STFEM_ERR_INVALID_ARGUMENT;
+  t->last_path[1] = t->last_path[2] = 0;
+  return run(t, t->R, t->coarse, t->fine, dst_coarse, src_fine, false, add, stream, t->cell_form ? 2 : 0);
 }
 int stfem_transfer_interpolate(stfem_transfer *t, stfem_vec *dst_coarse, const stfem_vec *src_fine, void *stream)
 {
   return t ? run(t, t->I, t->coarse, t->fine, dst_coarse, src_fine, false, 0, stream) : STFEM_ERR_INVALID_ARGUMENT;
+}
+
+int stfem_transfer_last_path(const stfem_transfer *t, int32_t out[3])
+{
+  if (!t || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < 3; ++i) out[i] = t->last_path[i];
+  return STFEM_OK;
 }
 
 int stfem_transfer_line_matrices(int ncell_fine, int degree_fine, int ncell_coarse, int degree_coarse, double *P, double *I)

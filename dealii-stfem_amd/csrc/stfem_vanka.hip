@@ -353,6 +353,7 @@ constexpr int VK_FLAT = 8; // the launch after the eight colours: all cells at o
 struct stfem_vanka {
   stfem_ctx *ctx = nullptr;
   int nb = 0, nloc = 0, m = 0, mt = 0, mtw = 0, parts = 0, mpad = 0, kpad = 0, nclasses = 0;
+  int setup_batches = 0; // batches of cell layers the device set-up of the per-cell blocks took (stfem_vanka_setup_batches)
   void *d_blocks = nullptr;
   void *d_blocks_base = nullptr; // allocation d_blocks points into (blocks built on an extended context: the ghost layers' come first)
   int *d_off = nullptr;
@@ -641,6 +642,8 @@ static int vanka_create_per_cell_device(stfem_vanka *v, const double *Alpha, con
   }
   int L = int((budget - 2.0 * double(km_layer)) / double(km_layer + b_layer));
   L = std::max(1, std::min(L, ncz));
+  if (const char *e = getenv("STFEM_VANKA_SETUP_LAYERS")) // at most this many cell layers per batch (tests: the batch loop on small meshes)
+    if (atoi(e) > 0) L = std::min(L, atoi(e));
   const void *metric = nullptr;
   int rc = stfem_internal_metric(c, &metric, nullptr);
   if (rc != STFEM_OK) return rc;
@@ -671,7 +674,9 @@ static int vanka_create_per_cell_device(stfem_vanka *v, const double *Alpha, con
   ap.ncx = ncx; ap.ncy = ncy; ap.ncz = ncz; ap.p = p; ap.nb = nb; ap.dmask = c->dmask;
   for (int i = 0; i < nb * nb; ++i) { ap.Alpha[i] = Alpha[i]; ap.Beta[i] = Beta[i]; }
   const size_t lds = (size_t(nloc) * 7 + 2 * n * n) * sizeof(double);
+  v->setup_batches = 0;
   for (int z0 = 0; z0 < ncz && e == hipSuccess; z0 += L) {
+    ++v->setup_batches;
     const int z1 = std::min(ncz, z0 + L), zw0 = std::max(0, z0 - 1), zw1 = std::min(ncz, z1 + 1);
     const size_t wcells = cpl * size_t(zw1 - zw0), bcells = cpl * size_t(z1 - z0);
     const size_t moff = cpl * size_t(zw0) * nloc * 8; // metric records [cell][q][8]
@@ -905,6 +910,8 @@ int stfem_vanka_plan(const stfem_vanka *v, int32_t out[2])
   out[0] = v->mtw; out[1] = v->parts;
   return STFEM_OK;
 }
+
+int stfem_vanka_setup_batches(const stfem_vanka *v) { return v ? v->setup_batches : 0; }
 
 int stfem_vanka_vmult(stfem_vanka *v, stfem_vec *dst, const stfem_vec *src, void *stream) { return stfem_vanka_step(v, dst, 1.0, 0, src, stream); }
 

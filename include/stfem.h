@@ -267,6 +267,9 @@ int stfem_transfer_prolongate(stfem_transfer *t, stfem_vec *dst_fine, const stfe
 int stfem_transfer_restrict(stfem_transfer *t, stfem_vec *dst_coarse, const stfem_vec *src_fine, int add, void *stream);
 int stfem_transfer_interpolate(stfem_transfer *t, stfem_vec *dst_coarse, const stfem_vec *src_fine, void *stream);
 const char *stfem_transfer_last_error(void);
+/* diagnostics: {the last prolongation ran its y and z passes as one fused kernel (0 / 1), most coarse cells one thread marched
+ * through in the last restriction along y, the same along z (0: table-driven pass)} */
+int stfem_transfer_last_path(const stfem_transfer *t, int32_t out[3]);
 /* the 1D factors a transfer is the Kronecker product of, without constraints (host only, for checks):
  * P [n_f x n_c] embedding, I [n_c x n_f] nodal interpolation, n = degree * ncell + 1; either may be NULL */
 int stfem_transfer_line_matrices(int ncell_fine, int degree_fine, int ncell_coarse, int degree_coarse, double *P, double *I);
@@ -317,6 +320,8 @@ void stfem_vanka_destroy(stfem_vanka *v);
 int stfem_vanka_n_classes(const stfem_vanka *v); /* distinct cell blocks held */
 /* diagnostics: {row tiles (16 rows) per workgroup, parts per cell block} */
 int stfem_vanka_plan(const stfem_vanka *v, int32_t out[2]);
+/* diagnostics: batches of cell layers the device set-up of the per-cell blocks took (0: class blocks, host set-up) */
+int stfem_vanka_setup_batches(const stfem_vanka *v);
 int stfem_vanka_vmult(stfem_vanka *v, stfem_vec *dst, const stfem_vec *src, void *stream);
 /* dst = (accumulate ? dst : 0) + omega * V src: the step x <- x + omega P^-1 r of PreconditionRelaxation around the smoother
  * (include/stmg.h:1199-1238) fused into the smoother's scatter - no temporary vector, no separate update pass. */
@@ -492,6 +497,9 @@ int64_t stfem_stokes_n_face_points(const stfem_stokes_ctx *ctx);
 int stfem_stokes_face_points(const stfem_stokes_ctx *ctx, double *out);
 int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *ctx, const double *g_at_face_points, double *dst_u, double *dst_p, void *stream);
 const char *stfem_stokes_last_hip_error(void);
+/* diagnostics: {tiles, workgroups} as stfem_last_sweep_plan of the last velocity sweep (pencil sweep of the scalar FE_Q(2) context:
+ * box meshes), and whether that sweep of the last vmult added the pressure gradient itself (1) or the gradient kernel ran (0) */
+int stfem_stokes_last_sweep_plan(const stfem_stokes_ctx *ctx, int32_t out[3]);
 
 /* The pressure space by itself - what the solver around the operator needs of it (tests/tp_03stokes.cc:404-425, 1047-1062;
  * include/exact_solution.h:503-649; the pressure transfer of the Stokes multigrid levels, include/stmg.h:557-600).
@@ -544,6 +552,8 @@ int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, co
 int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_blocks);
 void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v);
 int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v);
+/* diagnostics: batches of cell layers the last set-up (create or update) of the per-cell blocks took (0: class blocks) */
+int stfem_stokes_vanka_setup_batches(const stfem_stokes_vanka *v);
 int stfem_stokes_vanka_vmult(stfem_stokes_vanka *v, double *const *dst_blocks, const double *const *src_blocks, void *stream);
 int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, double omega, int accumulate, const double *const *src_blocks,
                             void *stream);
@@ -559,6 +569,9 @@ void stfem_trace_push(const char *name);
 void stfem_trace_pop(void);
 /* name of the kernel variant the last stfem_st_vmult on this ctx dispatched to (for profiles) */
 const char *stfem_last_kernel_name(const stfem_ctx *ctx);
+/* diagnostics: {tiles, workgroups launched} of the last pencil-sweep launch of stfem_st_vmult on this ctx (a persistent kernel:
+ * with more tiles than workgroups a workgroup takes several); {0, 0} after another kernel variant */
+int stfem_last_sweep_plan(const stfem_ctx *ctx, int32_t out[2]);
 
 #ifdef __cplusplus
 }

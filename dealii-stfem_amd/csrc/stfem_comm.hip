@@ -13,7 +13,7 @@
 // fused in one ncclGroupStart/End.  RCCL is bound at run time (dlopen): the library also loads on a
 // box without RCCL, where stfem_comm_create reports STFEM_ERR_UNSUPPORTED.  If the process already
 // carries an RCCL (e.g. PyTorch's) that copy is used, so that one process never runs two of them.
-#include "../../include/stfem.h"
+#include "stfem_internal.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and enums only: no link-time dependency
@@ -92,14 +92,6 @@ struct stfem_comm {
   size_t plane_bytes = 0; // of all blocks
 };
 
-#define COMM_HIP(call)                                                                    \
-  do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess) {                                                               \
-      snprintf(g_comm_err, sizeof(g_comm_err), "%s: %s", #call, hipGetErrorString(e_));   \
-      return STFEM_ERR_HIP;                                                               \
-    }                                                                                     \
-  } while (0)
 #define COMM_NCCL(call)                                                                   \
   do {                                                                                    \
     ncclResult_t r_ = (call);                                                             \
@@ -151,7 +143,7 @@ int stfem_comm_create(const void *id, int rank, int world, int device, stfem_com
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return STFEM_ERR_NO_DEVICE;
   if (device < 0 || device >= ndev) return STFEM_ERR_INVALID_ARGUMENT;
-  COMM_HIP(hipSetDevice(device));
+  STFEM_TRY(g_comm_err, hipSetDevice(device));
   stfem_comm *c = new (std::nothrow) stfem_comm;
   if (!c) return STFEM_ERR_OUT_OF_MEMORY;
   c->rank = rank; c->world = world; c->device = device;
@@ -211,8 +203,8 @@ static int plane_geometry(stfem_ctx *ctx, const stfem_vec *v, size_t &plane_byte
 static int ensure_buffers(stfem_comm *c, size_t plane_bytes)
 {
   if (c->buf_bytes >= 4 * plane_bytes) return STFEM_OK;
-  COMM_HIP(hipStreamSynchronize(c->stream));
-  if (c->buf) COMM_HIP(hipFree(c->buf));
+  STFEM_TRY(g_comm_err, hipStreamSynchronize(c->stream));
+  if (c->buf) STFEM_TRY(g_comm_err, hipFree(c->buf));
   c->buf = nullptr;
   c->buf_bytes = 0;
   if (hipMalloc(&c->buf, 4 * plane_bytes) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
@@ -250,15 +242,15 @@ int stfem_halo_begin_split(stfem_comm *c, stfem_ctx *ctx_lo, stfem_vec *v_lo, st
     c->pending = true;
     return STFEM_OK;
   }
-  COMM_HIP(hipSetDevice(c->device));
+  STFEM_TRY(g_comm_err, hipSetDevice(c->device));
   if ((rc = ensure_buffers(c, pb)) != STFEM_OK) return rc;
   char *ts = static_cast<char *>(c->buf), *bs = ts + pb, *tr = bs + pb, *br = tr + pb;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // this rank's partial sums of its two interface planes
   if (upper >= 0 && (rc = stfem_plane_pack(ctx_hi, v_hi, nz - 1, ts, st)) != STFEM_OK) return rc;
   if (lower >= 0 && (rc = stfem_plane_pack(ctx_lo, v_lo, 0, bs, st)) != STFEM_OK) return rc;
-  COMM_HIP(hipEventRecord(c->packed, st));
-  COMM_HIP(hipStreamWaitEvent(c->stream, c->packed, 0));
+  STFEM_TRY(g_comm_err, hipEventRecord(c->packed, st));
+  STFEM_TRY(g_comm_err, hipStreamWaitEvent(c->stream, c->packed, 0));
   const ncclDataType_t dt = stfem_ctx_precision(ctx) ? ncclFloat : ncclDouble;
   const size_t count = pb / (stfem_ctx_precision(ctx) ? sizeof(float) : sizeof(double));
   COMM_NCCL(rccl().GroupStart());
@@ -271,7 +263,7 @@ int stfem_halo_begin_split(stfem_comm *c, stfem_ctx *ctx_lo, stfem_vec *v_lo, st
     COMM_NCCL_IN_GROUP(rccl().Recv(br, count, dt, lower, c->comm, c->stream));
   }
   COMM_NCCL(rccl().GroupEnd());
-  COMM_HIP(hipEventRecord(c->arrived, c->stream));
+  STFEM_TRY(g_comm_err, hipEventRecord(c->arrived, c->stream));
   c->lower = lower; c->upper = upper; c->plane_bytes = pb; // (only a successful begin leaves an exchange pending)
   c->pending = true;
   return STFEM_OK;
@@ -286,15 +278,15 @@ int stfem_halo_end(stfem_ctx *ctx, stfem_comm *c, stfem_vec *v, void *stream)
   int nz;
   int rc = plane_geometry(ctx, v, pb, nz);
   if (rc != STFEM_OK || pb != c->plane_bytes) return STFEM_ERR_SHAPE_MISMATCH;
-  COMM_HIP(hipSetDevice(c->device));
+  STFEM_TRY(g_comm_err, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  COMM_HIP(hipStreamWaitEvent(st, c->arrived, 0));
+  STFEM_TRY(g_comm_err, hipStreamWaitEvent(st, c->arrived, 0));
   char *tr = static_cast<char *>(c->buf) + 2 * pb, *br = tr + pb;
   if (c->upper >= 0 && (rc = stfem_plane_unpack(ctx, v, nz - 1, tr, 1, st)) != STFEM_OK) return rc;
   if (c->lower >= 0 && (rc = stfem_plane_unpack(ctx, v, 0, br, 1, st)) != STFEM_OK) return rc;
   // the buffers are reused by the next exchange: it must not start before these adds have read them
-  COMM_HIP(hipEventRecord(c->packed, st));
-  COMM_HIP(hipStreamWaitEvent(c->stream, c->packed, 0));
+  STFEM_TRY(g_comm_err, hipEventRecord(c->packed, st));
+  STFEM_TRY(g_comm_err, hipStreamWaitEvent(c->stream, c->packed, 0));
   return STFEM_OK;
 }
 
@@ -307,25 +299,25 @@ int stfem_ghost_update(stfem_ctx *ctx, stfem_comm *c, stfem_vec *v, int lower, i
   int nz;
   int rc = plane_geometry(ctx, v, pb, nz);
   if (rc != STFEM_OK) return rc;
-  COMM_HIP(hipSetDevice(c->device));
+  STFEM_TRY(g_comm_err, hipSetDevice(c->device));
   if ((rc = ensure_buffers(c, pb)) != STFEM_OK) return rc;
   char *bs = static_cast<char *>(c->buf) + pb, *tr = bs + pb;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // the owner of an interface plane is the upper rank (its bottom plane); the lower rank's top plane is the ghost
   if (lower >= 0 && (rc = stfem_plane_pack(ctx, v, 0, bs, st)) != STFEM_OK) return rc;
-  COMM_HIP(hipEventRecord(c->packed, st));
-  COMM_HIP(hipStreamWaitEvent(c->stream, c->packed, 0));
+  STFEM_TRY(g_comm_err, hipEventRecord(c->packed, st));
+  STFEM_TRY(g_comm_err, hipStreamWaitEvent(c->stream, c->packed, 0));
   const ncclDataType_t dt = stfem_ctx_precision(ctx) ? ncclFloat : ncclDouble;
   const size_t count = pb / (stfem_ctx_precision(ctx) ? sizeof(float) : sizeof(double));
   COMM_NCCL(rccl().GroupStart());
   if (lower >= 0) COMM_NCCL_IN_GROUP(rccl().Send(bs, count, dt, lower, c->comm, c->stream));
   if (upper >= 0) COMM_NCCL_IN_GROUP(rccl().Recv(tr, count, dt, upper, c->comm, c->stream));
   COMM_NCCL(rccl().GroupEnd());
-  COMM_HIP(hipEventRecord(c->arrived, c->stream));
-  COMM_HIP(hipStreamWaitEvent(st, c->arrived, 0));
+  STFEM_TRY(g_comm_err, hipEventRecord(c->arrived, c->stream));
+  STFEM_TRY(g_comm_err, hipStreamWaitEvent(st, c->arrived, 0));
   if (upper >= 0 && (rc = stfem_plane_unpack(ctx, v, nz - 1, tr, 0, st)) != STFEM_OK) return rc;
-  COMM_HIP(hipEventRecord(c->packed, st));
-  COMM_HIP(hipStreamWaitEvent(c->stream, c->packed, 0));
+  STFEM_TRY(g_comm_err, hipEventRecord(c->packed, st));
+  STFEM_TRY(g_comm_err, hipStreamWaitEvent(c->stream, c->packed, 0));
   return STFEM_OK;
 }
 
@@ -340,11 +332,11 @@ int stfem_dot_global(stfem_ctx *ctx, stfem_comm *c, const stfem_vec *a, const st
     *out = local;
     return STFEM_OK;
   }
-  COMM_HIP(hipSetDevice(c->device));
-  COMM_HIP(hipMemcpyAsync(c->d_red, &local, sizeof(double), hipMemcpyHostToDevice, c->stream));
+  STFEM_TRY(g_comm_err, hipSetDevice(c->device));
+  STFEM_TRY(g_comm_err, hipMemcpyAsync(c->d_red, &local, sizeof(double), hipMemcpyHostToDevice, c->stream));
   COMM_NCCL(rccl().AllReduce(c->d_red, c->d_red, 1, ncclDouble, ncclSum, c->comm, c->stream));
-  COMM_HIP(hipMemcpyAsync(out, c->d_red, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  COMM_HIP(hipStreamSynchronize(c->stream));
+  STFEM_TRY(g_comm_err, hipMemcpyAsync(out, c->d_red, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  STFEM_TRY(g_comm_err, hipStreamSynchronize(c->stream));
   return STFEM_OK;
 }
 

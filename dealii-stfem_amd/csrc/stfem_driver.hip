@@ -1,5 +1,5 @@
-// What the slab driver needs around the operator: load vectors, nodal interpolation points,
-// error norms and a block axpby.  None of it is on the vmult hot path; the kernels are plain (one workgroup
+// What the slab driver needs around the operator: load vectors, nodal interpolation points
+// and error norms.  None of it is on the vmult hot path; the kernels are plain (one workgroup
 // per cell, the MappingQ1 Jacobian from the eight cell vertices on the fly).
 //
 // Replaces, for the structured meshes of this library:
@@ -9,7 +9,7 @@
 //       -> stfem_support_points + stfem_vector_upload
 //   VectorTools::integrate_difference (L2, Linfty, H1-seminorm) of ErrorCalculator::evaluate_error
 //       (include/exact_solution.h:534-600)                                                -> stfem_integrate_difference
-//   the vector arithmetic of SolverFGMRES / TimeIntegrator (add, sadd, equ)               -> stfem_vector_axpby
+//   the vector arithmetic of SolverFGMRES / TimeIntegrator (add, sadd, equ)               -> stfem_vector_axpby (stfem_vector.hip)
 #include "stfem_internal.h"
 
 #include <hip/hip_runtime.h>
@@ -20,17 +20,9 @@
 #include <cstring>
 #include <vector>
 
-namespace {
-
 thread_local char g_driver_err[256] = "";
-#define DRV_TRY(call)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      snprintf(g_driver_err, sizeof(g_driver_err), "%s: %s", #call, hipGetErrorString(e_)); \
-      return STFEM_ERR_HIP;                                                                 \
-    }                                                                                       \
-  } while (0)
+
+namespace {
 
 // vertices of the structured block on the host (the context keeps them for general meshes only)
 std::vector<double> host_vertices(const stfem_ctx *c)
@@ -246,52 +238,6 @@ __global__ __launch_bounds__(256) void integrate_difference_kernel(const CellGeo
   if (threadIdx.x == 0) { out[cell * 3] = red[0]; out[cell * 3 + 1] = red[256]; out[cell * 3 + 2] = red[512]; }
 }
 
-// y = a x + b y on up to eight blocks per launch (blockIdx.y = block).  A zero factor means "not read": a = 0 never
-// touches x, b = 0 never touches y's old content (0 * NaN and 0 * Inf would survive otherwise, where deal.II's
-// `dst = 0.` / equ() assign); x and y may be the same vector (no __restrict__).
-struct AxpbyBlocks {
-  const void *x[8];
-  void *y[8];
-};
-template <typename T>
-__global__ __launch_bounds__(256) void axpby_kernel(int64_t n, T a, T b, const AxpbyBlocks blocks)
-{
-  const T *x = static_cast<const T *>(blocks.x[blockIdx.y]);
-  T *y = static_cast<T *>(blocks.y[blockIdx.y]);
-  const int64_t i0 = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, stride = int64_t(gridDim.x) * blockDim.x;
-  if (a == T(0) && b == T(0))
-    for (int64_t i = i0; i < n; i += stride) y[i] = T(0);
-  else if (a == T(0))
-    for (int64_t i = i0; i < n; i += stride) y[i] = b * y[i];
-  else if (b == T(0))
-    for (int64_t i = i0; i < n; i += stride) y[i] = a * x[i];
-  else
-    for (int64_t i = i0; i < n; i += stride) y[i] = a * x[i] + b * y[i];
-}
-
-// the same on arrays of different lengths in one launch (the blocks of a two-variable vector: velocity and pressure blocks)
-struct AxpbyMany {
-  const void *x[8];
-  void *y[8];
-  long long len[8];
-};
-template <typename T>
-__global__ __launch_bounds__(256) void axpby_many_kernel(T a, T b, const AxpbyMany v)
-{
-  const T *x = static_cast<const T *>(v.x[blockIdx.y]);
-  T *y = static_cast<T *>(v.y[blockIdx.y]);
-  const int64_t n = v.len[blockIdx.y];
-  const int64_t i0 = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, stride = int64_t(gridDim.x) * blockDim.x;
-  if (a == T(0) && b == T(0))
-    for (int64_t i = i0; i < n; i += stride) y[i] = T(0);
-  else if (a == T(0))
-    for (int64_t i = i0; i < n; i += stride) y[i] = b * y[i];
-  else if (b == T(0))
-    for (int64_t i = i0; i < n; i += stride) y[i] = a * x[i];
-  else
-    for (int64_t i = i0; i < n; i += stride) y[i] = a * x[i] + b * y[i];
-}
-
 // device copies of the geometry and of the tables of QGauss(nq) against the context's nodal basis
 struct GeomUpload {
   double *d = nullptr;
@@ -370,7 +316,7 @@ int stfem_quadrature_points(const stfem_ctx *c, int nq, double *out)
 static int integrate_rhs_impl(stfem_ctx *c, int nq, const double *f_at_points, const ProductFn pf, stfem_vec *dst, int block, void *stream)
 {
   if (!c || (!f_at_points && !pf.on) || !dst || dst->ctx != c || block < 0 || block >= dst->nb || nq < 1 || nq > 8) return STFEM_ERR_INVALID_ARGUMENT;
-  DRV_TRY(hipSetDevice(c->device));
+  STFEM_TRY(g_driver_err, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   GeomUpload geo;
   int rc = geo.build(c, nq);
@@ -388,10 +334,10 @@ static int integrate_rhs_impl(stfem_ctx *c, int nq, const double *f_at_points, c
   for (int par = 0; par < 8 && e == hipSuccess; ++par) { // fixed sequence on one stream: see the kernel
     const long long nblk = (long long)((c->nc[0] - (par & 1) + 1) / 2) * ((c->nc[1] - ((par >> 1) & 1) + 1) / 2) * ((c->nc[2] - (par >> 2) + 1) / 2);
     if (nblk == 0) continue;
-    if (c->prec)
-      hipLaunchKernelGGL(integrate_rhs_kernel<float>, dim3((unsigned)nblk), dim3(256), lds, st, geo.g, d_f, static_cast<float *>(dst->blk[block]), pf, par);
-    else
-      hipLaunchKernelGGL(integrate_rhs_kernel<double>, dim3((unsigned)nblk), dim3(256), lds, st, geo.g, d_f, static_cast<double *>(dst->blk[block]), pf, par);
+    stfem_by_prec(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(integrate_rhs_kernel<T>, dim3((unsigned)nblk), dim3(256), lds, st, geo.g, d_f, static_cast<T *>(dst->blk[block]), pf, par);
+    });
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -417,7 +363,7 @@ static int integrate_difference_impl(stfem_ctx *c, int nq, const stfem_vec *u, i
 {
   if (!c || !u || u->ctx != c || block < 0 || block >= u->nb || (!exact_at_points && !pf.on) || !out || nq < 1 || nq > 8)
     return STFEM_ERR_INVALID_ARGUMENT;
-  DRV_TRY(hipSetDevice(c->device));
+  STFEM_TRY(g_driver_err, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   GeomUpload geo;
   int rc = geo.build(c, nq);
@@ -442,12 +388,11 @@ static int integrate_difference_impl(stfem_ctx *c, int nq, const stfem_vec *u, i
     const int n = c->p + 1;
     const size_t lds = (size_t(n) * n * n + 3 * 256) * sizeof(double);
     (void)hipGetLastError();
-    if (c->prec)
-      hipLaunchKernelGGL(integrate_difference_kernel<float>, dim3((unsigned)c->ncells), dim3(256), lds, st, geo.g,
-                         static_cast<const float *>(u->blk[block]), d_e, d_g, d_out, pf);
-    else
-      hipLaunchKernelGGL(integrate_difference_kernel<double>, dim3((unsigned)c->ncells), dim3(256), lds, st, geo.g,
-                         static_cast<const double *>(u->blk[block]), d_e, d_g, d_out, pf);
+    stfem_by_prec(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(integrate_difference_kernel<T>, dim3((unsigned)c->ncells), dim3(256), lds, st, geo.g,
+                         static_cast<const T *>(u->blk[block]), d_e, d_g, d_out, pf);
+    });
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_out, part.size() * sizeof(double), hipMemcpyDeviceToHost, st);
@@ -475,81 +420,6 @@ int stfem_integrate_difference_product(stfem_ctx *c, int nq, const stfem_vec *u,
                                        void *stream)
 {
   return integrate_difference_impl(c, nq, u, block, nullptr, nullptr, ProductFn{1, amplitude, frequency}, out, stream);
-}
-
-int stfem_gauss_rule(int n, double *points, double *weights)
-{
-  if (n < 1 || n > 16 || !points || !weights) return STFEM_ERR_INVALID_ARGUMENT;
-  std::vector<double> x, w;
-  stfem::gauss_rule(n, x, w);
-  std::copy(x.begin(), x.end(), points);
-  std::copy(w.begin(), w.end(), weights);
-  return STFEM_OK;
-}
-
-int stfem_fe_time_points(int type, int r, double *points)
-{
-  if ((type != 0 && type != 1) || r < 0 || r > 8 || !points) return STFEM_ERR_INVALID_ARGUMENT;
-  // get_time_quad (fe_time.cc:152-161): QGaussLobatto(r + 1) for cG(r), QGaussRadau(r + 1, right) for dG(r)
-  if (type == 0 && r < 1) return STFEM_ERR_INVALID_ARGUMENT;
-  const std::vector<double> x = type == 0 ? stfem::lobatto_points(r + 1) : stfem::radau_right_points(r + 1);
-  std::copy(x.begin(), x.end(), points);
-  return STFEM_OK;
-}
-
-int stfem_vector_axpby(stfem_ctx *c, double a, const stfem_vec *x, double b, stfem_vec *y, void *stream)
-{
-  if (!c || !x || !y || x->ctx != c || y->ctx != c || x->nb != y->nb) return STFEM_ERR_INVALID_ARGUMENT;
-  DRV_TRY(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned grid = (unsigned)std::min<int64_t>((c->ndofs + 255) / 256, 4096);
-  (void)hipGetLastError();
-  for (int b0 = 0; b0 < x->nb; b0 += 8) {
-    const int nb = std::min(8, x->nb - b0);
-    AxpbyBlocks bl{};
-    for (int j = 0; j < nb; ++j) {
-      bl.x[j] = x->blk[b0 + j];
-      bl.y[j] = y->blk[b0 + j];
-    }
-    if (c->prec) hipLaunchKernelGGL(axpby_kernel<float>, dim3(grid, nb), dim3(256), 0, st, c->ndofs, float(a), float(b), bl);
-    else hipLaunchKernelGGL(axpby_kernel<double>, dim3(grid, nb), dim3(256), 0, st, c->ndofs, a, b, bl);
-  }
-  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
-}
-
-int stfem_axpby_many(stfem_ctx *c, int n_arrays, const int64_t *len, double a, const void *const *x, double b, void *const *y, void *stream)
-{
-  if (!c || n_arrays < 0 || (n_arrays > 0 && (!len || !y || (a != 0.0 && !x)))) return STFEM_ERR_INVALID_ARGUMENT;
-  for (int j = 0; j < n_arrays; ++j)
-    if (len[j] < 0 || !y[j] || (a != 0.0 && !x[j])) return STFEM_ERR_INVALID_ARGUMENT;
-  DRV_TRY(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  (void)hipGetLastError();
-  for (int b0 = 0; b0 < n_arrays; b0 += 8) {
-    const int nb = std::min(8, n_arrays - b0);
-    AxpbyMany v{};
-    long long longest = 0;
-    for (int j = 0; j < nb; ++j) {
-      v.x[j] = a != 0.0 ? x[b0 + j] : nullptr;
-      v.y[j] = y[b0 + j];
-      v.len[j] = len[b0 + j];
-      longest = std::max<long long>(longest, len[b0 + j]);
-    }
-    if (longest == 0) continue;
-    const unsigned grid = (unsigned)std::min<long long>((longest + 255) / 256, 4096);
-    if (c->prec) hipLaunchKernelGGL(axpby_many_kernel<float>, dim3(grid, nb), dim3(256), 0, st, float(a), float(b), v);
-    else hipLaunchKernelGGL(axpby_many_kernel<double>, dim3(grid, nb), dim3(256), 0, st, a, b, v);
-  }
-  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
-}
-
-int stfem_vector_set_zero(stfem_ctx *c, stfem_vec *y, void *stream)
-{
-  if (!c || !y || y->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
-  DRV_TRY(hipSetDevice(c->device));
-  const size_t bytes = size_t(c->ndofs) * (c->prec ? sizeof(float) : sizeof(double));
-  for (int j = 0; j < y->nb; ++j) DRV_TRY(hipMemsetAsync(y->blk[j], 0, bytes, static_cast<hipStream_t>(stream)));
-  return STFEM_OK;
 }
 
 } // extern "C"

@@ -1,12 +1,34 @@
-// Internal layout of the opaque handles of include/stfem.h, shared by the translation units of the
-// library (stfem_capi.hip, stfem_vanka.hip; the Stokes operator's own: stfem_stokes_internal.h).  Not part of the boundary.
+// Internal layout of the opaque handles of include/stfem.h and the few helpers shared by the host-side translation
+// units of the library (context and operator: stfem_capi.hip, vectors: stfem_vector.hip, smoothers, transfers, driver,
+// communicator; the Stokes operator's own: stfem_stokes_internal.h).  Not part of the boundary.
 #pragma once
 #include "../../include/stfem.h"
 
 #include "host_tables.h"
 
+#include <hip/hip_runtime_api.h>
+
 #include <cstdint>
+#include <cstdio>
 #include <vector>
+
+// Returns STFEM_ERR_HIP from the calling function if a HIP runtime call fails, leaving "<call>: <reason>" in `err`, the
+// thread-local char array behind the calling unit's exported *_last_error accessor.
+#define STFEM_TRY(err, call)                                                \
+  do {                                                                      \
+    hipError_t e_ = (call);                                                 \
+    if (e_ != hipSuccess) {                                                 \
+      snprintf(err, sizeof(err), "%s: %s", #call, hipGetErrorString(e_));   \
+      return STFEM_ERR_HIP;                                                 \
+    }                                                                       \
+  } while (0)
+
+namespace stfem {
+// stfem_ctx::d_scratch (always double): the results of the reductions, then the stage-1 partial sums of up to DOT_VECS inner
+// products from at most DOT_GRID workgroups each (stfem_vector.hip)
+constexpr int DOT_VECS = 8, DOT_GRID = 512, DOT_RESULTS = 256;
+constexpr size_t SCRATCH_DOUBLES = DOT_RESULTS + size_t(DOT_VECS) * DOT_GRID;
+} // namespace stfem
 
 struct stfem_ctx {
   int p = 0, device = 0, n_cu = 0;
@@ -21,7 +43,7 @@ struct stfem_ctx {
   size_t es = sizeof(double);  // element size
   void *d_coef[2] = {nullptr, nullptr}; // [0] mass, [1] laplace
   int coef_layout[2] = {0, 0};
-  double *d_scratch = nullptr; // reductions (always double)
+  double *d_scratch = nullptr; // reductions: [DOT_RESULTS] results, [DOT_VECS][DOT_GRID] partial sums
   const char *last_kernel = "";
   int last_sweep[2] = {0, 0}; // {tiles, workgroups} of the last pencil launch (stfem_last_sweep_plan)
   // tile variant: halo slabs (grown on demand)
@@ -56,6 +78,14 @@ struct stfem_vec {
   std::vector<void *> blk; // device arrays of the context's element type
 };
 
+// calls f with a value of the context's Number type: stfem_by_prec(c, [&](auto t) { using T = decltype(t); ... })
+template <class F> auto stfem_by_prec(const stfem_ctx *c, F &&f) { return c->prec ? f(float()) : f(double()); }
+
+// a named trace range around a scope (stfem_host_helpers.cpp: roctx, bound at run time)
+struct TraceScope {
+  explicit TraceScope(const char *name) { stfem_trace_push(name); }
+  ~TraceScope() { stfem_trace_pop(); }
+};
 
 // stfem_capi.hip: (re)builds the per-quadrature-point metric records [cell][qz][qy][qx][8] =
 // (Gxx,Gxy,Gxz,Gyy,Gyz,Gzz,Mq,pad) with the coefficient tables in force; element type = the context's Number
@@ -71,6 +101,11 @@ struct stfem_stokes_desc {
 int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *out);
 
 #pragma GCC visibility push(hidden)
+// the text behind stfem_last_hip_error (stfem_capi.hip; written by stfem_vector.hip too) and behind stfem_driver_last_error
+// (stfem_driver.hip; written by the vector arithmetic that came from there)
+extern thread_local char g_hip_error[256], g_driver_err[256];
+int hip_fail(hipError_t e, const char *what); // "<what>: <reason>" to g_hip_error, returns STFEM_ERR_HIP
+
 // stfem_vanka.hip: vanka_invert_kernel<double> on `count` m x m matrices at B (row-major, destroyed), the inverses in the apply's
 // layout [kpad][mpad] from block cell0 of out; *singular (device) is set to 1 by a matrix without a pivot.  `stream`: a hipStream_t.
 int stfem_vanka_invert_launch(double *B, double *out, int m, int mpad, int kpad, long long cell0, unsigned count, int *singular, void *stream);

@@ -1,5 +1,5 @@
 // Kernel parameter blocks and launch entry points shared by the device translation units and
-// stfem_capi.hip.  Everything precision-dependent lives in stfem_kernels_decl.h, instantiated
+// stfem_capi.hip (which drives them through the traits of stfem_prec_decl.h).  Everything precision-dependent lives in stfem_kernels_decl.h, instantiated
 // for fp64 (namespace stfem::f64, the solver precision) and fp32 (stfem::f32, the precision of
 // the reference's multigrid levels, tests/tp_01.cc:780,801-806).
 #pragma once

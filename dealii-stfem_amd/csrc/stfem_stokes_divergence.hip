@@ -162,7 +162,7 @@ extern "C" {
 int stfem_stokes_divergence(stfem_stokes_ctx *c, const double *u, double *cell_out, double *total, void *stream)
 {
   if (!c || !u || !total) return STFEM_ERR_INVALID_ARGUMENT; // (before anything touches the device)
-  STOKES_TRY(hipSetDevice(c->device));
+  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long ncells = (long long)c->nc[0] * c->nc[1] * c->nc[2];
   if (!c->d_div) {
@@ -191,8 +191,8 @@ int stfem_stokes_divergence(stfem_stokes_ctx *c, const double *u, double *cell_o
     return STFEM_ERR_HIP;
   }
   double sum = 0.0;
-  STOKES_TRY(hipMemcpyAsync(&sum, c->d_div + ncells, sizeof(double), hipMemcpyDeviceToHost, st));
-  STOKES_TRY(hipStreamSynchronize(st));
+  STFEM_TRY(g_stokes_err, hipMemcpyAsync(&sum, c->d_div + ncells, sizeof(double), hipMemcpyDeviceToHost, st));
+  STFEM_TRY(g_stokes_err, hipStreamSynchronize(st));
   *total = std::sqrt(sum);
   return STFEM_OK;
 }

@@ -161,11 +161,3 @@ int stokes_boundary_launch(stfem_stokes_ctx *c, StokesParams &prm, const double 
 int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *lin, int mode, hipStream_t st);
 #pragma GCC visibility pop
 
-#define STOKES_TRY(call)                                                   \
-  do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      snprintf(g_stokes_err, sizeof(g_stokes_err), "%s: %s", #call, hipGetErrorString(e_)); \
-      return STFEM_ERR_HIP;                                                \
-    }                                                                      \
-  } while (0)

@@ -114,15 +114,6 @@ struct stfem_stokes_vanka {
   stokes_cell_vanka *cell = nullptr; // one block per cell (stfem_stokes_vanka_cell.hip): none of the class arrays above
 };
 
-#define SV_TRY(call)                                                                \
-  do {                                                                              \
-    hipError_t e_ = (call);                                                         \
-    if (e_ != hipSuccess) {                                                         \
-      snprintf(g_sv_err, sizeof(g_sv_err), "%s: %s", #call, hipGetErrorString(e_)); \
-      return STFEM_ERR_HIP;                                                         \
-    }                                                                               \
-  } while (0)
-
 namespace {
 
 // The restricted assembled matrices of one block class, read off the operator on a mesh of 1 - 3 cells per direction:
@@ -356,7 +347,7 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
   v->mtw = plan.mtw; v->parts = plan.parts; v->mt = plan.parts * plan.mtw;
   v->mpad = 16 * v->mt;
   v->kpad = ((v->m + KS - 1) / KS) * KS;
-  SV_TRY(hipSetDevice(d.device));
+  STFEM_TRY(g_sv_err, hipSetDevice(d.device));
   const vanka::ClassTable t = vanka::class_table(d.nc, 0);
   v->nclasses = int(t.key.size());
   rc = build_class_blocks(v.get(), t, npl, Alpha, Beta);
@@ -402,7 +393,7 @@ int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, co
   cd.nblk = n_blocks; cd.m = v->m; cd.mpad = v->mpad; cd.kpad = v->kpad; cd.mode = mode;
   for (int i = 0; i < n_blocks; ++i) cd.var[i] = v->var[i];
   for (int i = 0; i < n_blocks * n_blocks; ++i) { cd.Alpha[i] = Alpha[i]; cd.Beta[i] = Beta[i]; }
-  SV_TRY(hipSetDevice(d.device));
+  STFEM_TRY(g_sv_err, hipSetDevice(d.device));
   rc = stokes_cell_vanka_create(ctx, cd, &rowtab[0].x, lin_blocks, &v->cell, g_sv_err);
   if (rc == STFEM_OK) *out = v.release();
   return rc;
@@ -418,7 +409,7 @@ int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_bl
     for (int i = 0; i < v->nblk; ++i)
       if (v->var[i] == 0 && !lin_blocks[i]) return STFEM_ERR_INVALID_ARGUMENT;
   }
-  SV_TRY(hipSetDevice(v->d.device));
+  STFEM_TRY(g_sv_err, hipSetDevice(v->d.device));
   return stokes_cell_vanka_update(v->cell, lin_blocks, g_sv_err);
 }
 
@@ -433,11 +424,8 @@ int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, do
     for (int j = 0; j < v->nblk; ++j)
       if (dst_blocks[i] == src_blocks[j]) return STFEM_ERR_ALIAS;
   }
-  struct Scope { // the reference's TimerOutput scope "vanka" (stmg.h:835)
-    Scope() { stfem_trace_push("vanka"); }
-    ~Scope() { stfem_trace_pop(); }
-  } scope;
-  SV_TRY(hipSetDevice(v->d.device));
+  TraceScope scope("vanka"); // the reference's TimerOutput scope "vanka" (stmg.h:835)
+  STFEM_TRY(g_sv_err, hipSetDevice(v->d.device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const double *rows = v->d_flat;
   (void)hipGetLastError();

@@ -27,14 +27,6 @@
 namespace {
 
 thread_local char g_transfer_err[256] = "";
-#define TR_TRY(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess) {                                                                     \
-      snprintf(g_transfer_err, sizeof(g_transfer_err), "%s: %s", #call, hipGetErrorString(e_)); \
-      return STFEM_ERR_HIP;                                                                     \
-    }                                                                                           \
-  } while (0)
 
 // one banded 1D matrix in row-compressed form: row o = sum_k w[off[o] + k] * in[first[o] + k], k < off[o+1] - off[o]
 struct Band {
@@ -356,12 +348,12 @@ namespace {
 
 int upload(Band &b)
 {
-  TR_TRY(hipMalloc(&b.d_first, b.first.size() * sizeof(int)));
-  TR_TRY(hipMalloc(&b.d_off, b.off.size() * sizeof(int)));
-  TR_TRY(hipMalloc(&b.d_w, b.w.size() * sizeof(double)));
-  TR_TRY(hipMemcpy(b.d_first, b.first.data(), b.first.size() * sizeof(int), hipMemcpyHostToDevice));
-  TR_TRY(hipMemcpy(b.d_off, b.off.data(), b.off.size() * sizeof(int), hipMemcpyHostToDevice));
-  TR_TRY(hipMemcpy(b.d_w, b.w.data(), b.w.size() * sizeof(double), hipMemcpyHostToDevice));
+  STFEM_TRY(g_transfer_err, hipMalloc(&b.d_first, b.first.size() * sizeof(int)));
+  STFEM_TRY(g_transfer_err, hipMalloc(&b.d_off, b.off.size() * sizeof(int)));
+  STFEM_TRY(g_transfer_err, hipMalloc(&b.d_w, b.w.size() * sizeof(double)));
+  STFEM_TRY(g_transfer_err, hipMemcpy(b.d_first, b.first.data(), b.first.size() * sizeof(int), hipMemcpyHostToDevice));
+  STFEM_TRY(g_transfer_err, hipMemcpy(b.d_off, b.off.data(), b.off.size() * sizeof(int), hipMemcpyHostToDevice));
+  STFEM_TRY(g_transfer_err, hipMemcpy(b.d_w, b.w.data(), b.w.size() * sizeof(double), hipMemcpyHostToDevice));
   return STFEM_OK;
 }
 void release(Band &b)
@@ -377,7 +369,7 @@ int launch_axis(T *out, const T *in, const int dims[3], int axis, const Band &b,
   const long long total = (long long)dims[0] * dims[1] * dims[2];
   const int blocks = int(std::min<long long>((total + 255) / 256, 1 << 20));
   axis_apply_kernel<T><<<blocks, 256, 0, s>>>(out, in, dims[0], dims[1], dims[2], axis, b.n_in, b.d_first, b.d_off, b.d_w, add);
-  TR_TRY(hipGetLastError());
+  STFEM_TRY(g_transfer_err, hipGetLastError());
   return STFEM_OK;
 }
 
@@ -409,7 +401,7 @@ int launch_cell_t(bool prolongate, T *out, const T *in, long long S, int ncell, 
     cell_restrict_kernel<T, PC, R><<<blocks, 256, 0, s>>>(out, in, S, ncell, total, m, flags, add);
     *marched = 1;
   }
-  TR_TRY(hipGetLastError());
+  STFEM_TRY(g_transfer_err, hipGetLastError());
   return STFEM_OK;
 }
 
@@ -438,7 +430,7 @@ int launch_cell_yz(int pc, int R, T *out, const T *in, int nx, int ncy, int ncz,
 #define STFEM_CELL_CASE(PC_, R_)                                                                                              \
   if (pc == PC_ && R == R_) {                                                                                                 \
     cell_prolongate_yz_kernel<T, PC_, R_><<<blocks, 256, 0, s>>>(out, in, nx, ncy, ncz, total, m, flags_y, flags_z, add);     \
-    TR_TRY(hipGetLastError());                                                                                                \
+    STFEM_TRY(g_transfer_err, hipGetLastError());                                                                                                \
     return STFEM_OK;                                                                                                          \
   }
   STFEM_CELL_CASE(1, 2) STFEM_CELL_CASE(2, 4) STFEM_CELL_CASE(3, 6) STFEM_CELL_CASE(4, 8) // h-transfers
@@ -504,8 +496,7 @@ int run(stfem_transfer *t, const Band B[3], stfem_ctx *to, stfem_ctx *from, stfe
   const int up[3] = {0, 1, 2}, down[3] = {2, 1, 0};
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int b = 0; b < dst->nb; ++b) {
-    const int st = to->prec == 0 ? apply3<double>(t, B, dst->blk[b], src->blk[b], expanding ? up : down, add, cell, s)
-                                 : apply3<float>(t, B, dst->blk[b], src->blk[b], expanding ? up : down, add, cell, s);
+    const int st = stfem_by_prec(to, [&](auto n) { return apply3<decltype(n)>(t, B, dst->blk[b], src->blk[b], expanding ? up : down, add, cell, s); });
     if (st != STFEM_OK) return st;
   }
   return STFEM_OK;
@@ -531,7 +522,7 @@ int stfem_transfer_create_partitioned(stfem_ctx *fine, stfem_ctx *coarse, int ne
     if (!same && !twice) return STFEM_ERR_SHAPE_MISMATCH;
   }
   if (coarse->p > fine->p) return STFEM_ERR_SHAPE_MISMATCH;
-  TR_TRY(hipSetDevice(fine->device));
+  STFEM_TRY(g_transfer_err, hipSetDevice(fine->device));
   stfem_transfer *t = new stfem_transfer;
   t->fine = fine;
   t->coarse = coarse;
@@ -641,11 +632,11 @@ int stfem_vector_convert(stfem_vec *dst, const stfem_vec *src, void *stream)
   const int blocks = int(std::min<long long>((n + 255) / 256, 1 << 16));
   for (int b = 0; b < dst->nb; ++b) {
     const int pd = dst->ctx->prec, ps = src->ctx->prec;
-    if (pd == ps) TR_TRY(hipMemcpyAsync(dst->blk[b], src->blk[b], size_t(n) * dst->ctx->es, hipMemcpyDeviceToDevice, s));
+    if (pd == ps) STFEM_TRY(g_transfer_err, hipMemcpyAsync(dst->blk[b], src->blk[b], size_t(n) * dst->ctx->es, hipMemcpyDeviceToDevice, s));
     else if (pd == 1) convert_kernel<float, double><<<blocks, 256, 0, s>>>(static_cast<float *>(dst->blk[b]), static_cast<const double *>(src->blk[b]), n);
     else convert_kernel<double, float><<<blocks, 256, 0, s>>>(static_cast<double *>(dst->blk[b]), static_cast<const float *>(src->blk[b]), n);
   }
-  TR_TRY(hipGetLastError());
+  STFEM_TRY(g_transfer_err, hipGetLastError());
   return STFEM_OK;
 }
 
@@ -659,7 +650,7 @@ int stfem_stream_create(void **stream_out)
 {
   if (!stream_out) return STFEM_ERR_INVALID_ARGUMENT;
   hipStream_t s = nullptr;
-  TR_TRY(hipStreamCreate(&s)); // a blocking stream: ordered against the legacy default stream the other calls use
+  STFEM_TRY(g_transfer_err, hipStreamCreate(&s)); // a blocking stream: ordered against the legacy default stream the other calls use
   *stream_out = s;
   return STFEM_OK;
 }
@@ -669,13 +660,13 @@ void stfem_stream_destroy(void *stream)
 }
 int stfem_stream_synchronize(void *stream)
 {
-  TR_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+  STFEM_TRY(g_transfer_err, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
   return STFEM_OK;
 }
 int stfem_graph_begin(void *stream)
 {
   if (!stream) return STFEM_ERR_INVALID_ARGUMENT; // the legacy default stream cannot be captured
-  TR_TRY(hipStreamBeginCapture(static_cast<hipStream_t>(stream), hipStreamCaptureModeThreadLocal));
+  STFEM_TRY(g_transfer_err, hipStreamBeginCapture(static_cast<hipStream_t>(stream), hipStreamCaptureModeThreadLocal));
   return STFEM_OK;
 }
 int stfem_graph_end(void *stream, stfem_graph **out)
@@ -683,7 +674,7 @@ int stfem_graph_end(void *stream, stfem_graph **out)
   if (!stream || !out) return STFEM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
   hipGraph_t g = nullptr;
-  TR_TRY(hipStreamEndCapture(static_cast<hipStream_t>(stream), &g));
+  STFEM_TRY(g_transfer_err, hipStreamEndCapture(static_cast<hipStream_t>(stream), &g));
   stfem_graph *r = new stfem_graph;
   const hipError_t e = hipGraphInstantiate(&r->exec, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
@@ -698,7 +689,7 @@ int stfem_graph_end(void *stream, stfem_graph **out)
 int stfem_graph_launch(stfem_graph *g, void *stream)
 {
   if (!g || !g->exec) return STFEM_ERR_INVALID_ARGUMENT;
-  TR_TRY(hipGraphLaunch(g->exec, static_cast<hipStream_t>(stream)));
+  STFEM_TRY(g_transfer_err, hipGraphLaunch(g->exec, static_cast<hipStream_t>(stream)));
   return STFEM_OK;
 }
 void stfem_graph_destroy(stfem_graph *g)

@@ -377,14 +377,6 @@ static bool vanka_wants_flat(const stfem_ctx *c)
   return c->ncells <= VK_FLAT_CELLS;
 }
 
-#define VK_TRY(call)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      snprintf(g_vanka_err, sizeof(g_vanka_err), "%s: %s", #call, hipGetErrorString(e_)); \
-      return STFEM_ERR_HIP;                                                           \
-    }                                                                                 \
-  } while (0)
 // the float or double instantiation of kernel template K, by the context's Number type
 #define VK_TYPED(c, K) ((c)->prec ? reinterpret_cast<const void *>(&K<float>) : reinterpret_cast<const void *>(&K<double>))
 
@@ -408,7 +400,7 @@ template <typename T> static const void *vanka_kernel(int p, int mtw)
     default: return nullptr;
   }
 }
-static const void *vanka_kernel(const stfem_ctx *c, int mtw) { return c->prec ? vanka_kernel<float>(c->p, mtw) : vanka_kernel<double>(c->p, mtw); }
+static const void *vanka_kernel(const stfem_ctx *c, int mtw) { return stfem_by_prec(c, [&](auto t) { return vanka_kernel<decltype(t)>(c->p, mtw); }); }
 
 static int vanka_collect(const stfem_vanka *v, stfem_vec *dst, double omega, int accumulate, hipStream_t st)
 {
@@ -541,12 +533,11 @@ static int vanka_create_per_cell_host(stfem_vanka *v, const double *Alpha, const
     hipError_t e = hipMemcpy(d_tab, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice);
     const size_t lds = (size_t(nloc) * 7 + 2 * n * n) * sizeof(double);
     if (e == hipSuccess) {
-      if (c->prec)
-        hipLaunchKernelGGL(vanka_cell_matrices_kernel<float>, dim3((unsigned)c->ncells), dim3(256), lds, 0, n,
-                           static_cast<const float *>(metric), d_tab, d_tab + n * n, d_K, d_M);
-      else
-        hipLaunchKernelGGL(vanka_cell_matrices_kernel<double>, dim3((unsigned)c->ncells), dim3(256), lds, 0, n,
-                           static_cast<const double *>(metric), d_tab, d_tab + n * n, d_K, d_M);
+      stfem_by_prec(c, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(vanka_cell_matrices_kernel<T>, dim3((unsigned)c->ncells), dim3(256), lds, 0, n, static_cast<const T *>(metric), d_tab,
+                           d_tab + n * n, d_K, d_M);
+      });
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(Kc.data(), d_K, nmat * sizeof(double), hipMemcpyDeviceToHost);
@@ -680,20 +671,18 @@ static int vanka_create_per_cell_device(stfem_vanka *v, const double *Alpha, con
     const int z1 = std::min(ncz, z0 + L), zw0 = std::max(0, z0 - 1), zw1 = std::min(ncz, z1 + 1);
     const size_t wcells = cpl * size_t(zw1 - zw0), bcells = cpl * size_t(z1 - z0);
     const size_t moff = cpl * size_t(zw0) * nloc * 8; // metric records [cell][q][8]
-    if (c->prec)
-      hipLaunchKernelGGL(vanka_cell_matrices_kernel<float>, dim3((unsigned)wcells), dim3(256), lds, 0, n, static_cast<const float *>(metric) + moff, d_tab,
+    stfem_by_prec(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(vanka_cell_matrices_kernel<T>, dim3((unsigned)wcells), dim3(256), lds, 0, n, static_cast<const T *>(metric) + moff, d_tab,
                          d_tab + n * n, d_K, d_M);
-    else
-      hipLaunchKernelGGL(vanka_cell_matrices_kernel<double>, dim3((unsigned)wcells), dim3(256), lds, 0, n, static_cast<const double *>(metric) + moff, d_tab,
-                         d_tab + n * n, d_K, d_M);
+    });
     ap.zw0 = zw0; ap.z0 = z0; ap.ncells_batch = int(bcells);
     hipLaunchKernelGGL(vanka_assemble_kernel, dim3((unsigned)bcells), dim3(256), 0, 0, ap);
     const long long cell0 = (long long)cpl * z0;
-    if (c->prec)
-      hipLaunchKernelGGL(vanka_invert_kernel<float>, dim3((unsigned)bcells), dim3(256), 0, 0, d_B, static_cast<float *>(v->d_blocks), m, v->mpad, v->kpad, cell0, d_flag);
-    else
-      hipLaunchKernelGGL(vanka_invert_kernel<double>, dim3((unsigned)bcells), dim3(256), 0, 0, d_B, static_cast<double *>(v->d_blocks), m, v->mpad, v->kpad, cell0,
-                         d_flag);
+    stfem_by_prec(c, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(vanka_invert_kernel<T>, dim3((unsigned)bcells), dim3(256), 0, 0, d_B, static_cast<T *>(v->d_blocks), m, v->mpad, v->kpad, cell0, d_flag);
+    });
     e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize(); // (the next batch reuses the scratch)
   }
@@ -826,7 +815,7 @@ int stfem_vanka_create_partitioned(stfem_ctx *c, int nb, const double *Alpha, co
   *out = nullptr;
   const int n = c->p + 1;
   if (nb * n * n * n > VK_MAX_ROWS) return STFEM_ERR_UNSUPPORTED; // Q4 with more than 4 temporal blocks, Q5 with more than 2
-  VK_TRY(hipSetDevice(c->device));
+  STFEM_TRY(g_vanka_err, hipSetDevice(c->device));
   VankaPtr v = vanka_new(c, nb);
   if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   int rc;
@@ -882,7 +871,7 @@ int stfem_vanka_create_partitioned_general(stfem_ctx *slab, stfem_ctx *extended,
   const size_t bsz = size_t(v->kpad) * v->mpad;
   v->d_blocks = static_cast<char *>(v->d_blocks_base) + size_t(glo) * size_t(slab->nc[0]) * slab->nc[1] * bsz * slab->es;
   ve.reset();
-  VK_TRY(hipSetDevice(slab->device));
+  STFEM_TRY(g_vanka_err, hipSetDevice(slab->device));
   rc = vanka_per_cell_tables(v.get());
   if (rc == STFEM_OK) *out = v.release();
   return rc;
@@ -920,16 +909,13 @@ int stfem_vanka_vmult(stfem_vanka *v, stfem_vec *dst, const stfem_vec *src, void
 int stfem_vanka_step(stfem_vanka *v, stfem_vec *dst, double omega, int accumulate, const stfem_vec *src, void *stream)
 {
   if (!v || !dst || !src) return STFEM_ERR_INVALID_ARGUMENT;
-  struct Scope { // the reference's TimerOutput scope "vanka" (stmg.h:835)
-    Scope() { stfem_trace_push("vanka"); }
-    ~Scope() { stfem_trace_pop(); }
-  } scope;
+  TraceScope scope("vanka"); // the reference's TimerOutput scope "vanka" (stmg.h:835)
   if (dst->ctx != v->ctx || src->ctx != v->ctx || dst->nb != v->nb || src->nb != v->nb) return STFEM_ERR_SHAPE_MISMATCH;
   for (int i = 0; i < v->nb; ++i)
     for (int j = 0; j < v->nb; ++j)
       if (dst->blk[i] == src->blk[j]) return STFEM_ERR_ALIAS;
   stfem_ctx *c = v->ctx;
-  VK_TRY(hipSetDevice(c->device));
+  STFEM_TRY(g_vanka_err, hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // the parameters of both kernels; a launch changes the cell list and the colour only
   VankaParams prm;

@@ -13,7 +13,7 @@ Precision of the reference.  Nothing here depends on np.longdouble.
    quantity every rounding-error bound of tests/test_gpu_krylov_kernels.py is proportional to.
 
 The second half emulates, in double precision, the ORDER in which the kernels add (multi_dot_kernel and dot_finish_kernel of
-csrc/stfem_capi.hip: per-thread strided sums over the blocks, the 64-lane tree, four waves, per-thread strided sum of the
+csrc/stfem_vector.hip: per-thread strided sums over the blocks, the 64-lane tree, four waves, per-thread strided sum of the
 partials, the 256-wide tree) and the roundings of multi_axpy_kernel and axpy_kernel.  tests/test_krylov_oracle_cpu.py uses it to
 show that such a summation satisfies the bounds before the device is asked to; the GPU tests do not use it."""
 import collections
@@ -23,7 +23,7 @@ import numpy as np
 
 Exact = collections.namedtuple("Exact", "value residual magnitude")
 
-# launch geometry of csrc/stfem_capi.hip
+# launch geometry of csrc/stfem_vector.hip (DOT_VECS, DOT_GRID: csrc/stfem_internal.h)
 DOT_VECS, DOT_GRID, WORKGROUP, MAX_BLOCKS = 8, 512, 256, 8
 
 

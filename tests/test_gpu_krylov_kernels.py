@@ -41,7 +41,7 @@ pytestmark = pytest.mark.gpu
 NUMBERS = ["double", "float"]
 INVALID, UNSUPPORTED, SHAPE_MISMATCH, ALIAS = -1, -2, -5, -6
 U64, U32 = 2.0 ** -53, 2.0 ** -24
-# DOT_GRID and the workgroup size of multi_dot_kernel (csrc/stfem_capi.hip): the inner-product bound depends on them
+# DOT_GRID (csrc/stfem_internal.h) and the workgroup size of multi_dot_kernel (csrc/stfem_vector.hip): the inner-product bound depends on them
 DOT_GRID, WORKGROUP = 512, 256
 
 MESHES = {  # name: (degree, cells): DoFs per block, purpose

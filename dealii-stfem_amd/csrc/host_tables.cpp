@@ -866,4 +866,41 @@ std::vector<int> precondition_stmg_types(const std::string &seq, int coarsening_
   return ret;
 }
 
+// ---- 1D factors of the space transfers (csrc/stfem_transfer.hip) ----
+void cell_of(int i, int p, int n, int &cell, int &j)
+{
+  if (i == p * n) {
+    cell = n - 1;
+    j = p;
+  } else {
+    cell = i / p;
+    j = i % p;
+  }
+}
+
+void line_matrices(int nc_f, int p_f, int nc_c, int p_c, std::vector<double> &P, std::vector<double> &I)
+{
+  const int r = nc_f / nc_c, n_f = p_f * nc_f + 1, n_c = p_c * nc_c + 1;
+  const std::vector<double> gf = lobatto_points(p_f + 1), gc = lobatto_points(p_c + 1);
+  P.assign(size_t(n_f) * n_c, 0.0);
+  I.assign(size_t(n_c) * n_f, 0.0);
+  Mat V, G;
+  for (int f = 0; f < n_f; ++f) {
+    int cell, j;
+    cell_of(f, p_f, nc_f, cell, j);
+    const int ec = cell / r;
+    const double xi = (double(cell % r) + gf[j]) / r;
+    lagrange_tables(gc, {xi}, V, G);
+    for (int a = 0; a <= p_c; ++a) P[size_t(f) * n_c + ec * p_c + a] = std::abs(V[a]) < 1e-15 ? 0.0 : V[a];
+  }
+  for (int c = 0; c < n_c; ++c) {
+    int cell, j;
+    cell_of(c, p_c, nc_c, cell, j);
+    const double t = gc[j] * r;
+    const int sub = std::min(int(t), r - 1);
+    lagrange_tables(gf, {t - sub}, V, G);
+    for (int a = 0; a <= p_f; ++a) I[size_t(c) * n_f + (cell * r + sub) * p_f + a] = std::abs(V[a]) < 1e-15 ? 0.0 : V[a];
+  }
+}
+
 } // namespace stfem

@@ -67,6 +67,13 @@ std::string mg_sequence(int n_sp_lvl, int n_k, int n_p, int n_timesteps_at_once,
 // get_precondition_stmg_types: one smoother id per level (0 = identity)
 std::vector<int> precondition_stmg_types(const std::string &mg_type_level, int coarsening_type, bool time_before_space, int smoother);
 
+// ---- 1D factors of the space transfers ----
+// line index -> (cell, local node) of a 1D FE_Q(p) line with n cells
+void cell_of(int i, int p, int n, int &cell, int &j);
+// 1D embedding P[n_f x n_c] (coarse nodal values -> fine nodal values of the same function) and the nodal
+// interpolation I[n_c x n_f] (the fine function at the coarse nodes); nc_f / nc_c = fine cells per coarse cell
+void line_matrices(int nc_f, int p_f, int nc_c, int p_c, std::vector<double> &P, std::vector<double> &I);
+
 // ---- mesh / coefficient ----
 void mesh_vertices(const int32_t gn[3], const double lo[3], const double up[3], double distort,
                    uint64_t seed, int32_t z0, int32_t z1, double *out);

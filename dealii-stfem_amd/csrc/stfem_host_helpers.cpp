@@ -1,5 +1,6 @@
-// The entry points of include/stfem.h that need no device: the temporal matrices, the 1D rules, the mesh and coefficient
-// helpers (host_tables.h behind the C-ABI) and the named trace ranges.  (C linkage: through the declarations in the header.)
+// The entry points of include/stfem.h that need no device: the temporal matrices, the 1D rules, the 1D factors of the space
+// transfers, the level schedule of the multigrid, the mesh and coefficient helpers (host_tables.h behind the C-ABI) and the
+// named trace ranges.  (C linkage: through the declarations in the header.)
 #include "../../include/stfem.h"
 
 #include "host_tables.h"
@@ -136,6 +137,49 @@ int stfem_fe_time_points(int type, int r, double *points)
   if (type == 0 && r < 1) return STFEM_ERR_INVALID_ARGUMENT;
   const std::vector<double> x = type == 0 ? lobatto_points(r + 1) : radau_right_points(r + 1);
   std::copy(x.begin(), x.end(), points);
+  return STFEM_OK;
+}
+
+// ---- space-time multigrid: the 1D factors of a space transfer and the level schedule (fe_time.cc:17-150)
+int stfem_transfer_line_matrices(int ncell_fine, int degree_fine, int ncell_coarse, int degree_coarse, double *P, double *I)
+{
+  if (ncell_coarse < 1 || degree_coarse < 1 || degree_fine < degree_coarse || (ncell_fine != ncell_coarse && ncell_fine != 2 * ncell_coarse))
+    return STFEM_ERR_INVALID_ARGUMENT;
+  std::vector<double> p, i;
+  line_matrices(ncell_fine, degree_fine, ncell_coarse, degree_coarse, p, i);
+  if (P) std::copy(p.begin(), p.end(), P);
+  if (I) std::copy(i.begin(), i.end(), I);
+  return STFEM_OK;
+}
+
+int stfem_poly_mg_sequence(int k_max, int k_min, int sequence_type, int32_t *out, int32_t *n_out)
+{
+  if (!n_out || k_min < 0 || k_max < k_min) return STFEM_ERR_INVALID_ARGUMENT;
+  const std::vector<int> s = poly_mg_sequence(k_max, k_min, sequence_type);
+  if (s.empty()) return STFEM_ERR_INVALID_ARGUMENT;
+  if (out) std::copy(s.begin(), s.end(), out);
+  *n_out = int32_t(s.size());
+  return STFEM_OK;
+}
+
+int stfem_mg_sequence(int n_sp_lvl, int n_k, int n_p, int n_timesteps_at_once, int n_timesteps_at_once_min, char lower_lvl, int coarsening_type,
+                      int time_before_space, int use_p_multigrid_space, int zip_from_back, char *out, int32_t *n_out)
+{
+  if (!n_out || n_sp_lvl < 1 || n_k < 1 || (use_p_multigrid_space && n_p < 1) || n_timesteps_at_once < 1 || n_timesteps_at_once_min < 1 ||
+      (lower_lvl != 'k' && lower_lvl != 't'))
+    return STFEM_ERR_INVALID_ARGUMENT;
+  const std::string s = mg_sequence(n_sp_lvl, n_k, n_p, n_timesteps_at_once, n_timesteps_at_once_min, lower_lvl, coarsening_type,
+                                    time_before_space != 0, use_p_multigrid_space != 0, zip_from_back != 0);
+  if (out) std::copy(s.begin(), s.end(), out);
+  *n_out = int32_t(s.size());
+  return STFEM_OK;
+}
+
+int stfem_precondition_stmg_types(const char *mg_type_level, int n, int coarsening_type, int time_before_space, int smoother, int32_t *out)
+{
+  if (!mg_type_level || !out || n < 0) return STFEM_ERR_INVALID_ARGUMENT;
+  const std::vector<int> r = precondition_stmg_types(std::string(mg_type_level, size_t(n)), coarsening_type, time_before_space != 0, smoother);
+  std::copy(r.begin(), r.end(), out);
   return STFEM_OK;
 }
 

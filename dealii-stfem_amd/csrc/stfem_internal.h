@@ -1,6 +1,7 @@
 // Internal layout of the opaque handles of include/stfem.h and the few helpers shared by the host-side translation
-// units of the library (context and operator: stfem_capi.hip, vectors: stfem_vector.hip, smoothers, transfers, driver,
-// communicator; the Stokes operator's own: stfem_stokes_internal.h).  Not part of the boundary.
+// units of the library (context and operator: stfem_capi.hip, vectors: stfem_vector.hip, space transfers: stfem_transfer.hip,
+// streams and captured graphs: stfem_stream.hip, smoothers, driver, communicator; the Stokes operator's own:
+// stfem_stokes_internal.h).  Not part of the boundary.
 #pragma once
 #include "../../include/stfem.h"
 
@@ -102,8 +103,9 @@ int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *out
 
 #pragma GCC visibility push(hidden)
 // the text behind stfem_last_hip_error (stfem_capi.hip; written by stfem_vector.hip too) and behind stfem_driver_last_error
-// (stfem_driver.hip; written by the vector arithmetic that came from there)
-extern thread_local char g_hip_error[256], g_driver_err[256];
+// (stfem_driver.hip; written by the vector arithmetic that came from there) and behind stfem_transfer_last_error
+// (stfem_transfer.hip; written by stfem_vector_convert and by the stream and graph calls of stfem_stream.hip too)
+extern thread_local char g_hip_error[256], g_driver_err[256], g_transfer_err[256];
 int hip_fail(hipError_t e, const char *what); // "<what>: <reason>" to g_hip_error, returns STFEM_ERR_HIP
 
 // stfem_vanka.hip: vanka_invert_kernel<double> on `count` m x m matrices at B (row-major, destroyed), the inverses in the apply's

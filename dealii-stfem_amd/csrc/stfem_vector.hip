@@ -1,5 +1,6 @@
 // Vectors of the space-time operator (include/stfem.h): storage, the block arithmetic of the Krylov solvers and the
-// time integrators (tensorproduct_add, axpby, inner products, Gram-Schmidt) and the DoF-plane copies of the z-slab exchange.
+// time integrators (tensorproduct_add, axpby, inner products, Gram-Schmidt), the precision change of the multigrid and the
+// DoF-plane copies of the z-slab exchange.
 // (The entry points have C linkage through their declarations in the header.)
 #include "stfem_internal.h"
 #include "stfem_kernels.h"
@@ -490,6 +491,32 @@ int stfem_vector_set_zero(stfem_ctx *c, stfem_vec *y, void *stream)
   STFEM_TRY(g_driver_err, hipSetDevice(c->device));
   const size_t bytes = size_t(c->ndofs) * c->es;
   for (int j = 0; j < y->nb; ++j) STFEM_TRY(g_driver_err, hipMemsetAsync(y->blk[j], 0, bytes, static_cast<hipStream_t>(stream)));
+  return STFEM_OK;
+}
+
+// the precision change between the solver's vectors and the multigrid's (GMG::vmult, stmg.h:1330-1343: copy_locally_owned_data_from);
+// errors: stfem_transfer_last_error
+namespace {
+template <typename TD, typename TS> __global__ void convert_kernel(TD *__restrict__ d, const TS *__restrict__ s, long long n)
+{
+  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) d[t] = TD(s[t]);
+}
+} // namespace
+
+int stfem_vector_convert(stfem_vec *dst, const stfem_vec *src, void *stream)
+{
+  if (!dst || !src) return STFEM_ERR_INVALID_ARGUMENT;
+  if (dst->nb != src->nb || dst->ctx->ndofs != src->ctx->ndofs) return STFEM_ERR_SHAPE_MISMATCH;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long n = dst->ctx->ndofs;
+  const int blocks = int(std::min<long long>((n + 255) / 256, 1 << 16));
+  for (int b = 0; b < dst->nb; ++b) {
+    const int pd = dst->ctx->prec, ps = src->ctx->prec;
+    if (pd == ps) STFEM_TRY(g_transfer_err, hipMemcpyAsync(dst->blk[b], src->blk[b], size_t(n) * dst->ctx->es, hipMemcpyDeviceToDevice, s));
+    else if (pd == 1) convert_kernel<float, double><<<blocks, 256, 0, s>>>(static_cast<float *>(dst->blk[b]), static_cast<const double *>(src->blk[b]), n);
+    else convert_kernel<double, float><<<blocks, 256, 0, s>>>(static_cast<double *>(dst->blk[b]), static_cast<const float *>(src->blk[b]), n);
+  }
+  STFEM_TRY(g_transfer_err, hipGetLastError());
   return STFEM_OK;
 }
 

@@ -1,5 +1,6 @@
 """The space-transfer paths that only larger meshes select (csrc/stfem_transfer.hip), against tests/transfer_line_reference.py:
-  * cell_prolongate_yz_kernel, taken when fine nx x coarse ncy x coarse ncz >= 150000 (and not for the fp64 Q4 h-transfer),
+  * cell_prolongate_yz_kernel, taken when fine nx x coarse ncy x coarse ncz >= 150000 (and not for the fp64 Q4 h-transfer, nor
+    for a shape it is not instantiated for: three passes, the x pass once),
   * cell_restrict_march_kernel with segments of several coarse cells (nseg = min(ncell, ceil(262144 / lines), 64) < ncell): the
     carry of w[] and u0 from one cell to the next, segments of unequal length,
   * stfem_transfer_restrict with add = 0 (no caller elsewhere).  The restriction runs z, y, x and hands `add` to its last pass only,
@@ -36,6 +37,8 @@ CASES = {
     "p_q3_q2":     (3, (60, 37, 37), 2, (60, 37, 37), MIXED_A, True, True, True),      # (2, 3): 247 789
     "p_q3_q1":     (3, (40, 47, 47), 1, (40, 47, 47), 63, True, True, True),           # (1, 3): 267 289
     "p_q2_q1":     (2, (33, 49, 49), 1, (33, 49, 49), 0, True, True, False),           # (1, 2): 160 867; only z marches several cells
+    # (1, 6): 172 040 threads would fuse, but cell_prolongate_yz_kernel has no such instantiation: three passes are planned
+    "hp_q3_q1":    (3, (130, 40, 44), 1, (65, 20, 22), MIXED_A, False, False, False),
 }
 
 

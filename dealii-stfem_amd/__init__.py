@@ -199,6 +199,7 @@ SIGNATURES = {
     "stfem_last_hip_error": (C.c_char_p, []),
     "stfem_last_kernel_name": (C.c_char_p, [_vp]),
     "stfem_last_sweep_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    "stfem_last_tile_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
 }
 
 
@@ -435,6 +436,14 @@ class MatrixFreeOperator:
         """(tiles, workgroups launched) of the last pencil-sweep launch; (0, 0) after another kernel variant"""
         out = (C.c_int32 * 2)()
         _check(lib().stfem_last_sweep_plan(self._h, out), "stfem_last_sweep_plan")
+        return tuple(out)
+
+    @property
+    def last_tile_plan(self):
+        """(x-tiles, y-tiles, z-chunks, cell layers of the longest chunk) of the last tile-sweep launch; zeros after another
+        kernel variant"""
+        out = (C.c_int32 * 4)()
+        _check(lib().stfem_last_tile_plan(self._h, out), "stfem_last_tile_plan")
         return tuple(out)
 
 

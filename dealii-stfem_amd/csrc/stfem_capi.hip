@@ -191,6 +191,12 @@ int stfem_last_sweep_plan(const stfem_ctx *c, int32_t out[2])
   out[1] = c->last_sweep[1];
   return STFEM_OK;
 }
+int stfem_last_tile_plan(const stfem_ctx *c, int32_t out[4])
+{
+  if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < 4; ++i) out[i] = c->last_tile[i];
+  return STFEM_OK;
+}
 
 int stfem_set_coefficient(stfem_ctx *c, int which, int layout, const double *host)
 {
@@ -492,6 +498,7 @@ template <class PR> static int launch_atomic_panel(stfem_ctx *c, const typename 
   const int rc = PR::atomic(c->p, prm, st);
   c->last_kernel = PR::atomic_name();
   c->last_sweep[0] = c->last_sweep[1] = 0;
+  std::fill(c->last_tile, c->last_tile + 4, 0);
   return launch_status(rc);
 }
 
@@ -531,6 +538,7 @@ static int launch_pencil_panel(stfem_ctx *c, typename PR::Sweep &prm, typename P
   c->last_kernel = PR::pencil_name();
   c->last_sweep[0] = int(ntiles);
   c->last_sweep[1] = int(std::min<size_t>(ntiles, size_t(pp.grid))); // (launch_pencil_ty)
+  std::fill(c->last_tile, c->last_tile + 4, 0);
   if (launched == 0) rc = timeline_dump(c, tl_n, (long long)ntiles, 4, (long long)pp.lz * pp.ty, 8, st);
   return rc != STFEM_OK ? rc : launch_status(launched);
 }
@@ -563,6 +571,10 @@ static int launch_tile_panel(stfem_ctx *c, const typename PR::Sweep &prm, bool g
   const int launched = PR::tile(c->p, prm, tp, st);
   c->last_kernel = PR::tile_name(prm.metric != nullptr);
   c->last_sweep[0] = c->last_sweep[1] = 0;
+  c->last_tile[0] = tp.ntx;
+  c->last_tile[1] = tp.nty;
+  c->last_tile[2] = tp.ntc;
+  c->last_tile[3] = tp.lz;
   if (launched == 0) rc = timeline_dump(c, tl_n, (long long)ntiles, 4 * tp.wx, tp.lz, 16, st);
   return rc != STFEM_OK ? rc : launch_status(launched);
 }

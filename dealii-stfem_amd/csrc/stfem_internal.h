@@ -47,6 +47,7 @@ struct stfem_ctx {
   double *d_scratch = nullptr; // reductions: [DOT_RESULTS] results, [DOT_VECS][DOT_GRID] partial sums
   const char *last_kernel = "";
   int last_sweep[2] = {0, 0}; // {tiles, workgroups} of the last pencil launch (stfem_last_sweep_plan)
+  int last_tile[4] = {0, 0, 0, 0}; // {ntx, nty, ntc, lz} of the last tile launch (stfem_last_tile_plan)
   // tile variant: halo slabs (grown on demand)
   void *d_halo = nullptr;
   size_t halo_doubles = 0; // elements

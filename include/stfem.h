@@ -572,6 +572,9 @@ const char *stfem_last_kernel_name(const stfem_ctx *ctx);
 /* diagnostics: {tiles, workgroups launched} of the last pencil-sweep launch of stfem_st_vmult on this ctx (a persistent kernel:
  * with more tiles than workgroups a workgroup takes several); {0, 0} after another kernel variant */
 int stfem_last_sweep_plan(const stfem_ctx *ctx, int32_t out[2]);
+/* diagnostics: {x-tiles, y-tiles, z-chunks, cell layers of the longest chunk} of the last tile-sweep launch of stfem_st_vmult on
+ * this ctx (a workgroup marches through the layers of its chunk); {0, 0, 0, 0} after another kernel variant */
+int stfem_last_tile_plan(const stfem_ctx *ctx, int32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -179,6 +179,8 @@ SIGNATURES = {
     "stfem_stokes_n_face_points": (C.c_int64, [_vp]),
     "stfem_stokes_face_points": (C.c_int, [_vp, _dp]),
     "stfem_stokes_nitsche_rhs": (C.c_int, [_vp, _dp, _vp, _vp, _vp]),
+    "stfem_stokes_set_cip": (C.c_int, [_vp, C.c_double, C.c_int]),
+    "stfem_stokes_cip_add": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, _vp]),
     "stfem_stokes_pressure_ctx": (C.c_int, [_vp, C.POINTER(_vp)]),
     "stfem_stokes_pressure_mean_vectors": (C.c_int, [_vp, _dp, _dp, _dp]),
     "stfem_stokes_pressure_quadrature_points": (C.c_int, [_vp, C.c_int, _dp]),
@@ -797,6 +799,9 @@ def get_fe_time_weights_stokes(type_, r, time_step_size, n_timesteps_at_once=1):
 # The Navier-Stokes modes of StokesMatrixFreeOperator (OperatorMode::form / jacobian, operators.h:1288-1297): the `mode` of vmult,
 # st_vmult and st_vmult_slice_add; 0 is the linear operator
 CONVECTION_NONE, CONVECTION_FORM, CONVECTION_JACOBIAN = 0, 1, 2
+# Whose velocity weighs the CIP interior-face term (StokesMatrixFreeOperator.set_cip): the source of the vmult (the reference's
+# behaviour: cubic in the source), or - with a convection mode - the linearisation velocity (linear in the source)
+CIP_WEIGHT_SOURCE, CIP_WEIGHT_LINEARISATION = 0, 1
 
 
 class StokesMatrixFreeOperator:
@@ -804,11 +809,12 @@ class StokesMatrixFreeOperator:
     666-868) for the cell loop, FE_Q(2)^3 x FE_Q(1).  Vectors are device pointers (e.g.
     torch.Tensor.data_ptr()): velocity 3 * n_velocity doubles (component-major), pressure n_pressure.
     vmult / st_vmult / st_vmult_slice_add take the convection mode (CONVECTION_FORM / CONVECTION_JACOBIAN) and the linearisation
-    velocity `lin` that the reference's set_data hands in; with the defaults they are the linear operator."""
+    velocity `lin` that the reference's set_data hands in; with the defaults they are the linear operator.  delta0 != 0 adds the
+    CIP interior-face stabilisation (operators.h:1605-1633) to all of them, see set_cip."""
 
     def __init__(self, ncell, vertices=None, lower=(0, 0, 0), upper=(1, 1, 1), dirichlet_mask=63,
                  viscosity=1.0, velocity_degree=2, device=0, weak_boundary_ids=(), outflow_boundary_ids=(),
-                 penalty1=20.0, penalty2=10.0, dg_pressure=False):
+                 penalty1=20.0, penalty2=10.0, dg_pressure=False, delta0=0.0, cip_weight=CIP_WEIGHT_SOURCE):
         """weak_boundary_ids / outflow_boundary_ids: boundary ids 0..5 (face 2 d + s) as in the reference's constructor
         (operators.h:1206-1211); penalty1 / penalty2: its Nitsche penalties (gamma1 = viscosity penalty1, gamma2 = penalty2)."""
         m = _MeshDesc()
@@ -834,6 +840,21 @@ class StokesMatrixFreeOperator:
         if self.weak_mask or self.outflow_mask:
             _check(lib().stfem_stokes_set_weak_boundaries(h, self.weak_mask, self.outflow_mask, penalty1, penalty2),
                    "stfem_stokes_set_weak_boundaries")
+        self.delta0, self.cip_weight = 0.0, CIP_WEIGHT_SOURCE
+        if delta0 != 0.0 or cip_weight != CIP_WEIGHT_SOURCE:
+            self.set_cip(delta0, cip_weight)
+
+    def set_cip(self, delta0, weight=CIP_WEIGHT_SOURCE):
+        """The CIP gradient-jump term sum_F int_F delta0 h_F^2 / 2^3.5 (w.n)^2 [d_n u].[d_n v] on the interior faces in every later
+        vmult / st_vmult / st_vmult_slice_add (not mass_vmult, not the Vanka blocks).  weight: CIP_WEIGHT_SOURCE (w = the source, as
+        the reference has it) or CIP_WEIGHT_LINEARISATION (w = `lin` where a convection mode is given).  delta0 = 0: no launch."""
+        _check(lib().stfem_stokes_set_cip(self._h, float(delta0), int(weight)), "stfem_stokes_set_cip")
+        self.delta0, self.cip_weight = float(delta0), int(weight)
+
+    def cip_add(self, dst_u, src_u, weight_u, delta0, stream=None):
+        """dst_u += C(weight_u; src_u): the CIP term by itself with the given delta0, independent of set_cip"""
+        dst_u, src_u, weight_u = (getattr(v, "ptr", v) for v in (dst_u, src_u, weight_u))
+        _check(lib().stfem_stokes_cip_add(self._h, dst_u, src_u, weight_u, float(delta0), stream), "stfem_stokes_cip_add")
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:

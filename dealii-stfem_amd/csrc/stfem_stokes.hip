@@ -5,7 +5,7 @@
 // term folded into that sweep, and the coupling kernels of stfem_stokes_coupling.hip, the divergence as a marching gather kernel.
 // General meshes: the cell kernel (stfem_stokes_cell.hip).  On top of either: the weak (Nitsche) boundary faces
 // (stfem_stokes_boundary.hip), and with a convection mode (form / jacobian of the Navier-Stokes operator) the convection launches
-// (stfem_stokes_convection.hip).  The helpers of the pressure space the solver around the operator needs: stfem_stokes_pressure.hip.
+// (stfem_stokes_convection.hip), and with delta0 != 0 the CIP interior-face launches (stfem_stokes_cip.hip).  The helpers of the pressure space the solver around the operator needs: stfem_stokes_pressure.hip.
 // Every entry point describes its launches in ONE form, StokesParams (stfem_stokes_internal.h), put together by StokesLaunch below.
 #include "stfem_stokes_internal.h"
 
@@ -425,7 +425,8 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
 }
 
 // In this fixed order: the linear part (Kronecker path or cell kernel), its boundary launches, then - with a convection mode - the
-// convection colours 0..7 and the inflow colours (stfem_stokes_convection.hip), which add to what the linear part has written.
+// convection colours 0..7 and the inflow colours (stfem_stokes_convection.hip), which add to what the linear part has written, then -
+// with delta0 != 0 - the CIP colours 0..7 (stfem_stokes_cip.hip).
 int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double *const *lin, hipStream_t st)
 {
   // axis-aligned uniform mesh: the Kronecker path; otherwise the cell kernel
@@ -439,7 +440,16 @@ int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double
     const int rb = stokes_boundary_launch(c, prm, nullptr, st);
     if (rb != STFEM_OK) return rb;
   }
-  if (mode != STFEM_CONVECTION_NONE) return stokes_convection_launch(c, prm, lin, mode, st);
+  if (mode != STFEM_CONVECTION_NONE) {
+    const int rv = stokes_convection_launch(c, prm, lin, mode, st);
+    if (rv != STFEM_OK) return rv;
+  }
+  if (c->cip_delta0 != 0.0) { // last: the CIP interior faces (stfem_stokes_set_cip); without it exactly the launches above
+    const double *w[MAXSRC];
+    const bool from_lin = c->cip_weight == STFEM_CIP_WEIGHT_LINEARISATION && mode != STFEM_CONVECTION_NONE;
+    for (int s = 0; s < prm.nsrc; ++s) w[s] = from_lin && lin[s] ? lin[s] : prm.us[s];
+    return stokes_cip_launch(c, prm, w, c->cip_delta0, st);
+  }
   return STFEM_OK;
 }
 

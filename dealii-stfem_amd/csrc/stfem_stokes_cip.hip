@@ -1,0 +1,370 @@
+// Stokes two-field operator: the CIP (continuous interior penalty) gradient-jump stabilisation on the interior faces, what
+//   StokesMatrixFreeOperator::do_face_integral_local (reference include/operators.h:1605-1633) adds when delta0 != 0:
+//   C(w; u)(v) = sum_F int_F delta_F(w) [d_n u] . [d_n v] dA,     [d_n u] = (grad u|_A - grad u|_B) n,
+//   delta_F(w) = delta0 h_F^2 / pa (w.n)^2 at each face point,    h_F = sqrt(sum_q JxW_face) (get_h_face, 182-209),  pa = 2^3.5.
+// The face rule is QGauss(3)^2, the mapping MappingQ1; entries of u and w on strongly constrained DoFs read as 0, constrained rows
+// and the pressure rows receive nothing.  The weight velocity w is an argument of its own (the reference reads it from the source of
+// the vmult, 1623; see stfem_stokes_set_cip).
+// Cell-centric: a cell computes, for each of its up to six interior faces, the jump at the nine face points - its own normal
+// derivative minus the neighbour's, each with its own cell's Jacobian - and adds ONLY its own side's test contribution
+//   + delta_F ([d_n u]_own - [d_n u]_other) d_n v_own JxW     (the interior side's + and the exterior side's - of 1628-1629)
+// to its own 27 nodes.  n, JxW, h_F and w at the face are those of the cell's own side: the face is one bilinear patch, so both
+// sides compute the same surface element |det J| |J^-T e_d| and the same normal up to its sign, which enters squared.  The cell
+// reads the neighbour's 81 source values: safe while other colours write, a source is never a destination.  (A face-pair kernel
+// would scatter to 45 nodes of two cells and need 12 colours per direction.)
+// The launches follow those of the linear operator and of the convection term of the same set: every destination has been written,
+// so they read, add and write - eight colour launches (cells of one colour share no DoF), ascending, faces 0..5 and points 0..8 in
+// order, no atomics: bitwise reproducible.
+#include "stfem_stokes_internal.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace {
+
+// J^-1 and det J of the trilinear mapping of cell (cx, cy, cz) at the reference point xi
+__device__ __forceinline__ void cip_jacobian(const CipParams &prm, int cx, int cy, int cz, const double xi[3], double Ji[3][3], double &det)
+{
+  const double fx[2] = {1 - xi[0], xi[0]}, fy[2] = {1 - xi[1], xi[1]}, fz[2] = {1 - xi[2], xi[2]}, dd[2] = {-1.0, 1.0};
+  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  const long long nvx = prm.ncx + 1, nvy = prm.ncy + 1;
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const double *V = prm.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+          const double Ve = V[e];
+          J[e][0] += Ve * dd[i] * fy[j] * fz[k];
+          J[e][1] += Ve * fx[i] * dd[j] * fz[k];
+          J[e][2] += Ve * fx[i] * fy[j] * dd[k];
+        }
+      }
+  det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
+        J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+  const double id = 1.0 / det;
+  Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
+  Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
+  Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
+  Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
+  Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
+  Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
+  Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
+  Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
+  Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+}
+
+// One half-wave per cell, 256 threads = 8 cells at a time, the cells of one colour dealt round-robin to the half-waves
+// (the layout of stokes_inflow_kernel).  The reference-space derivatives of the 27 shape functions at the nine points of the six
+// faces are tabulated in LDS once per workgroup (sT[e][f][q][n]; CART keeps d/d xi_d alone: 11.4 KB, otherwise all three: 34 KB).
+// Per source and interior face: 27 lanes gather the neighbour's values; the 27 lanes as (face point q, component) evaluate the
+// geometry of q (the three component lanes redundantly, rather than idle), the normal derivatives of their component on both sides as
+// sums over the table rows, w.n and the flux; the 27 node lanes integrate with the same table rows.
+// CART: constant diagonal Jacobian, n = e_d.  MULTI: several sources, each with its own weight velocity; the weighted results
+// are summed in registers per destination (up to MAXSRC), one scatter; otherwise one source, the weights applied at scatter time to
+// up to MAXOUT destinations.
+template <bool CART, bool MULTI>
+__global__ __launch_bounds__(256) void stokes_cip_kernel(const CipParams prm)
+{
+  constexpr int NT = CART ? 1 : 3;
+  __shared__ double tS[9], tD[9], tE[6], tED[6], tX[3], tW[3];
+  __shared__ double sT[NT][6][9][27];                // d phi_n / d xi_e at point q of face f (CART: e = the face's direction)
+  __shared__ double sU[8][81], sW[8][81], sN[8][81]; // own source, own weight velocity, the neighbour's source
+  __shared__ double sF[8][9][6], sA[8][9];           // per face point: flux[3] and J^-1 n [3]; JxW
+  if (threadIdx.x < 9) { tS[threadIdx.x] = prm.Su[threadIdx.x]; tD[threadIdx.x] = prm.Du[threadIdx.x]; }
+  if (threadIdx.x < 6) { tE[threadIdx.x] = prm.Eu[threadIdx.x]; tED[threadIdx.x] = prm.EDu[threadIdx.x]; }
+  if (threadIdx.x < 3) { tX[threadIdx.x] = prm.xq[threadIdx.x]; tW[threadIdx.x] = prm.wq[threadIdx.x]; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 6 * 9 * 27; i += 256) {
+    const int n = i % 27, q = (i / 27) % 9, f = i / 243;
+    const int d = f >> 1, s = f & 1, t1 = d == 0 ? 1 : 0;
+    const int ka = n % 3, kb = (n / 3) % 3, kc = n / 9, qa = q % 3, qb = q / 3;
+    // (selects, no arrays indexed at run time: those would live in scratch)
+    const int t2 = d == 2 ? 1 : 2;
+    const int kd = d == 0 ? ka : (d == 1 ? kb : kc), k1 = t1 == 0 ? ka : kb, k2 = t2 == 1 ? kb : kc;
+    const double vd = tE[s * 3 + kd], v1 = tS[qa * 3 + k1], v2 = tS[qb * 3 + k2];
+    const double gd = tED[s * 3 + kd] * v1 * v2, gt1 = vd * tD[qa * 3 + k1] * v2, gt2 = vd * v1 * tD[qb * 3 + k2];
+    const double g0 = d == 0 ? gd : gt1, g1 = d == 1 ? gd : (d == 0 ? gt1 : gt2), g2 = d == 2 ? gd : gt2;
+    if constexpr (CART) {
+      sT[0][f][q][n] = d == 0 ? g0 : (d == 1 ? g1 : g2);
+    } else {
+      sT[0][f][q][n] = g0; sT[NT - 1 > 0 ? 1 : 0][f][q][n] = g1; sT[NT - 1][f][q][n] = g2;
+    }
+  }
+  __syncthreads();
+  const int slot = threadIdx.x >> 5, t32 = threadIdx.x & 31;
+  const bool lane27 = t32 < 27;
+  const int t = lane27 ? t32 : 0;
+  const int a = t % 3, b = (t / 3) % 3, c = t / 9;
+  const int q = t % 9, comp_q = t / 9, q1 = q % 3, q2 = q / 3; // the point phase: this lane's face point and component
+  const int px = prm.colour & 1, py = (prm.colour >> 1) & 1, pz = prm.colour >> 2;
+  const int ncxc = (prm.ncx - px + 1) / 2, ncyc = (prm.ncy - py + 1) / 2, nczc = (prm.ncz - pz + 1) / 2;
+  const long long ncells = (long long)ncxc * ncyc * nczc;
+  double *U = sU[slot], *Wv = sW[slot], *N = sN[slot];
+  for (long long item = (long long)blockIdx.x * 8 + slot; item - slot < ncells; item += (long long)gridDim.x * 8) {
+    const bool ok = item < ncells;
+    const long long cc = ok ? item : 0;
+    const int cx = 2 * int(cc % ncxc) + px, cy = 2 * int((cc / ncxc) % ncyc) + py, cz = 2 * int(cc / ((long long)ncxc * ncyc)) + pz;
+    int faces = 0; // the interior faces of the cell, bit 2 d + s
+    if (ok) faces = (cx > 0 ? 1 : 0) | (cx < prm.ncx - 1 ? 2 : 0) | (cy > 0 ? 4 : 0) | (cy < prm.ncy - 1 ? 8 : 0) | (cz > 0 ? 16 : 0) |
+                    (cz < prm.ncz - 1 ? 32 : 0);
+    if (!__builtin_amdgcn_readfirstlane(__ballot(faces != 0) != 0)) continue; // (wave-uniform skip only: the two half-waves fence together)
+    const int ix = 2 * cx + a, iy = 2 * cy + b, iz = 2 * cz + c;
+    const bool con = constrained_u(prm, ix, iy, iz);
+    const long long gu = ix + (long long)prm.ndu[0] * (iy + (long long)prm.ndu[1] * iz);
+    double accU[MULTI ? MAXSRC : 1][3];
+#pragma unroll
+    for (int o = 0; o < (MULTI ? MAXSRC : 1); ++o) accU[o][0] = accU[o][1] = accU[o][2] = 0.0;
+    const int nsrc = MULTI ? prm.nsrc : 1;
+    for (int src = 0; src < nsrc; ++src) {
+      const double *us = prm.us[src], *ws = prm.ws[src];
+      if (lane27) { // gather (read_dof_values: constrained entries read as 0)
+#pragma unroll
+        for (int comp = 0; comp < 3; ++comp) {
+          U[comp * 27 + t] = (ok && !con) ? us[comp * prm.Nu + gu] : 0.0;
+          Wv[comp * 27 + t] = (ok && !con) ? ws[comp * prm.Nu + gu] : 0.0;
+        }
+      }
+      // the source values of the neighbour behind face f (read_dof_values: constrained entries read as 0)
+      auto neighbour = [&](int f, double v[3]) {
+        const int d = f >> 1, s = f & 1;
+        const int jx = 2 * (cx + (d == 0 ? (s ? 1 : -1) : 0)) + a, jy = 2 * (cy + (d == 1 ? (s ? 1 : -1) : 0)) + b,
+                  jz = 2 * (cz + (d == 2 ? (s ? 1 : -1) : 0)) + c;
+        const bool take = (faces >> f & 1) && lane27 && !constrained_u(prm, jx, jy, jz);
+        const long long gn = jx + (long long)prm.ndu[0] * (jy + (long long)prm.ndu[1] * jz);
+#pragma unroll
+        for (int comp = 0; comp < 3; ++comp) v[comp] = take ? us[comp * prm.Nu + gn] : 0.0;
+      };
+      // CART: all six fetched before the first face is worked on (one memory latency, not six: 1.22 -> 1.16 ms on 64^3 cells); the
+      // general kernel has no registers to hold them (with them it ran at one wave per SIMD: 2.9 -> 4.1 ms) and fetches face by face
+      double nb[CART ? 6 : 1][3];
+      if constexpr (CART) {
+#pragma unroll
+        for (int f = 0; f < 6; ++f) neighbour(f, nb[f]);
+      }
+      wave_fence();
+      double rU[3] = {0, 0, 0};
+#pragma unroll
+      for (int f = 0; f < 6; ++f) {
+        const bool on = faces >> f & 1; // per half-wave
+        if (!__builtin_amdgcn_readfirstlane(__ballot(on) != 0)) continue;
+        const int d = f >> 1, s = f & 1, t1 = d == 0 ? 1 : 0;
+        const int ncx_ = cx + (d == 0 ? (s ? 1 : -1) : 0), ncy_ = cy + (d == 1 ? (s ? 1 : -1) : 0), ncz_ = cz + (d == 2 ? (s ? 1 : -1) : 0);
+        if constexpr (!CART) neighbour(f, nb[0]);
+        if (lane27) {
+#pragma unroll
+          for (int comp = 0; comp < 3; ++comp) N[comp * 27 + t] = nb[CART ? f : 0][comp];
+        }
+        wave_fence();
+        double go[3] = {0, 0, 0}, wn = 0.0, JxW = 0.0, jump = 0.0;
+        if (on && lane27) { // this lane's face point and component: geometry, normal derivatives of both sides, w.n
+          double gnb[3] = {0, 0, 0}, nrm[3] = {0, 0, 0};
+          if constexpr (CART) {
+            nrm[d] = 1.0;
+            go[d] = gnb[d] = prm.hinv[d];
+            JxW = prm.detJ * prm.hinv[d] * tW[q1] * tW[q2];
+          } else {
+            double xi[3], Ji[3][3], det;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) xi[k] = k == d ? double(s) : tX[k == t1 ? q1 : q2];
+            cip_jacobian(prm, cx, cy, cz, xi, Ji, det);
+            double len = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { nrm[k] = Ji[d][k]; len += nrm[k] * nrm[k]; } // J^-T e_d
+            len = sqrt(len);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) nrm[k] /= len;
+            JxW = fabs(det) * len * tW[q1] * tW[q2];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) go[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
+            xi[d] = double(1 - s);
+            cip_jacobian(prm, ncx_, ncy_, ncz_, xi, Ji, det);
+#pragma unroll
+            for (int e = 0; e < 3; ++e) gnb[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
+          }
+          // reference-space derivatives of this lane's component at the point: this side (face f) and the neighbour's (face f ^ 1)
+          const double *Uc = U + comp_q * 27, *Nc = N + comp_q * 27;
+#pragma unroll
+          for (int e = 0; e < NT; ++e) {
+            const double *To = sT[e][f][q], *Tn = sT[e][f ^ 1][q];
+            double so = 0.0, sn = 0.0;
+#pragma unroll 3
+            for (int n = 0; n < 27; ++n) { so = fma(To[n], Uc[n], so); sn = fma(Tn[n], Nc[n], sn); }
+            jump += go[CART ? d : e] * so - gnb[CART ? d : e] * sn;
+          }
+          // w at the point: the nine nodes of the face
+          double wval[3] = {0, 0, 0};
+#pragma unroll
+          for (int j2 = 0; j2 < 3; ++j2)
+#pragma unroll
+            for (int j1 = 0; j1 < 3; ++j1) {
+              const int k0 = d == 0 ? 2 * s : (t1 == 0 ? j1 : j2), k1 = d == 1 ? 2 * s : (t1 == 1 ? j1 : j2), k2 = d == 2 ? 2 * s : j2;
+              const double phi = tS[q1 * 3 + j1] * tS[q2 * 3 + j2];
+#pragma unroll
+              for (int c3 = 0; c3 < 3; ++c3) wval[c3] = fma(phi, Wv[c3 * 27 + k0 + 3 * k1 + 9 * k2], wval[c3]);
+            }
+          wn = wval[0] * nrm[0] + wval[1] * nrm[1] + wval[2] * nrm[2];
+          if (comp_q == 0) sA[slot][q] = JxW;
+        }
+        wave_fence();
+        if (on && lane27) { // h_F^2 = the face's area: the nine JxW in point order
+          double area = 0.0;
+#pragma unroll
+          for (int p = 0; p < 9; ++p) area += sA[slot][p];
+          const double delta = prm.scale * area * wn * wn;
+          sF[slot][q][comp_q] = delta * jump * JxW;
+          if (comp_q == 0) {
+#pragma unroll
+            for (int e = 0; e < 3; ++e) sF[slot][q][3 + e] = go[e];
+          }
+        }
+        wave_fence();
+        if (on && lane27) { // integrate: the normal derivative of the test function of node (a, b, c), this cell's side
+#pragma unroll
+          for (int p = 0; p < 9; ++p) {
+            const double *F = sF[slot][p];
+            double dv;
+            if constexpr (CART) dv = F[3 + d] * sT[0][f][p][t];
+            else dv = F[3] * sT[0][f][p][t] + F[4] * sT[NT - 1 > 0 ? 1 : 0][f][p][t] + F[5] * sT[NT - 1][f][p][t];
+#pragma unroll
+            for (int comp = 0; comp < 3; ++comp) rU[comp] = fma(dv, F[comp], rU[comp]);
+          }
+        }
+        wave_fence(); // the next face reuses the neighbour and point buffers
+      }
+      if constexpr (MULTI) {
+#pragma unroll
+        for (int o = 0; o < MAXSRC; ++o)
+          if (o < prm.nout) {
+#pragma unroll
+            for (int comp = 0; comp < 3; ++comp) accU[o][comp] = fma(prm.wKu[src][o], rU[comp], accU[o][comp]);
+          }
+      } else {
+#pragma unroll
+        for (int comp = 0; comp < 3; ++comp) accU[0][comp] = rU[comp];
+      }
+      wave_fence(); // the next source overwrites U, Wv
+    }
+    // distribute_local_to_global (add): constrained velocity rows are not written
+    if (ok && lane27 && !con) {
+      if constexpr (MULTI) {
+#pragma unroll
+        for (int o = 0; o < MAXSRC; ++o)
+          if (o < prm.nout) {
+            double *dptr = prm.out_u[o] + gu;
+#pragma unroll
+            for (int comp = 0; comp < 3; ++comp) dptr[comp * prm.Nu] += accU[o][comp];
+          }
+      } else {
+        for (int o = 0; o < prm.nout; ++o) {
+          double *dptr = prm.out_u[o] + gu;
+#pragma unroll
+          for (int comp = 0; comp < 3; ++comp) dptr[comp * prm.Nu] += prm.wKu[0][o] * accU[0][comp];
+        }
+      }
+    }
+  }
+}
+
+} // namespace
+
+int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, hipStream_t st)
+{
+  if (delta0 == 0.0) return STFEM_OK;
+  if (c->nc[0] < 2 && c->nc[1] < 2 && c->nc[2] < 2) return STFEM_OK; // no interior face
+  if (prm.nsrc < 1 || prm.nsrc > MAXSRC || prm.nout > (prm.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiations' bounds)
+  CipParams k;
+  k.vertices = prm.vertices;
+  k.ncx = prm.ncx; k.ncy = prm.ncy; k.ncz = prm.ncz;
+  for (int d = 0; d < 3; ++d) { k.ndu[d] = prm.ndu[d]; k.xq[d] = prm.xq[d]; k.wq[d] = prm.wq[d]; k.hinv[d] = prm.hinv[d]; }
+  k.Nu = prm.Nu;
+  k.dmask = prm.dmask;
+  for (int i = 0; i < 9; ++i) { k.Su[i] = prm.Su[i]; k.Du[i] = prm.Du[i]; }
+  { // FE_Q(2) values / derivatives at the end points 0 and 1, [s * 3 + a]
+    static const std::vector<double> ends_tables = [] {
+      const stfem::ShapeTables tu = stfem::make_shape_tables(2);
+      const std::vector<double> ends = {0.0, 1.0};
+      stfem::Mat E, ED;
+      stfem::lagrange_tables(tu.nodes, ends, E, ED);
+      std::vector<double> r(12);
+      for (int i = 0; i < 6; ++i) { r[i] = E[i]; r[6 + i] = ED[i]; }
+      return r;
+    }();
+    for (int i = 0; i < 6; ++i) { k.Eu[i] = ends_tables[i]; k.EDu[i] = ends_tables[6 + i]; }
+  }
+  k.colour = 0; k.cart = prm.cart;
+  k.detJ = prm.detJ;
+  k.scale = delta0 / (8.0 * std::sqrt(2.0)); // pa = degree^3.5, degree 2 (operators.h:1614-1615)
+  k.nsrc = prm.nsrc;
+  for (int s = 0; s < MAXSRC; ++s) {
+    k.us[s] = s < prm.nsrc ? prm.us[s] : nullptr;
+    k.ws[s] = s < prm.nsrc ? weight[s] : nullptr;
+    if (s < prm.nsrc && (!prm.us[s] || !weight[s])) return STFEM_ERR_INVALID_ARGUMENT;
+  }
+  // the destinations that receive the term: those with a non-zero weight of the K part
+  k.nout = 0;
+  for (int o = 0; o < MAXOUT; ++o) {
+    k.out_u[o] = nullptr;
+    for (int s = 0; s < MAXSRC; ++s) k.wKu[s][o] = 0.0;
+  }
+  for (int o = 0; o < prm.nout; ++o) {
+    bool use = false;
+    for (int s = 0; s < prm.nsrc; ++s) use = use || prm.wKu[s][o] != 0.0;
+    if (!use || !prm.out_u[o]) continue;
+    k.out_u[k.nout] = prm.out_u[o];
+    for (int s = 0; s < prm.nsrc; ++s) k.wKu[s][k.nout] = prm.wKu[s][o];
+    ++k.nout;
+  }
+  if (k.nout == 0) return STFEM_OK;
+
+  const bool multi = prm.nsrc > 1;
+  const int which = (multi ? 2 : 0) + (k.cart ? 1 : 0);
+  const void *kerns[4] = {(const void *)stokes_cip_kernel<false, false>, (const void *)stokes_cip_kernel<true, false>,
+                          (const void *)stokes_cip_kernel<false, true>, (const void *)stokes_cip_kernel<true, true>};
+  const void *kern = kerns[which];
+  (void)hipGetLastError();
+  for (int colour = 0; colour < 8; ++colour) { // ascending, like every colour sequence of the operator
+    const long long n = (long long)((c->nc[0] - (colour & 1) + 1) / 2) * ((c->nc[1] - ((colour >> 1) & 1) + 1) / 2) *
+                        ((c->nc[2] - (colour >> 2) + 1) / 2);
+    if (n == 0) continue; // a colour without cells
+    k.colour = colour;
+    const unsigned grid = (unsigned)std::min<long long>((n + 7) / 8, 8ll * c->n_cu);
+    void *args[] = {(void *)&k};
+    (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    snprintf(g_stokes_err, sizeof(g_stokes_err), "stokes_cip_kernel: %s", hipGetErrorString(e));
+    return STFEM_ERR_HIP;
+  }
+  return STFEM_OK;
+}
+
+extern "C" {
+
+int stfem_stokes_set_cip(stfem_stokes_ctx *c, double delta0, int weight)
+{
+  if (!c || !std::isfinite(delta0) || weight < STFEM_CIP_WEIGHT_SOURCE || weight > STFEM_CIP_WEIGHT_LINEARISATION)
+    return STFEM_ERR_INVALID_ARGUMENT;
+  c->cip_delta0 = delta0;
+  c->cip_weight = weight;
+  return STFEM_OK;
+}
+
+int stfem_stokes_cip_add(stfem_stokes_ctx *c, double *dst_u, const double *src_u, const double *weight_u, double delta0, void *stream)
+{
+  if (!c || !dst_u || !src_u || !weight_u || !std::isfinite(delta0)) return STFEM_ERR_INVALID_ARGUMENT;
+  if (dst_u == src_u || dst_u == weight_u) return STFEM_ERR_ALIAS;
+  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  StokesParams prm = c->base; // one source, one destination, weight 1: the term by itself
+  prm.nsrc = 1; prm.nout = 1;
+  prm.us[0] = src_u; prm.ps[0] = nullptr;
+  prm.out_u[0] = dst_u; prm.out_p[0] = nullptr;
+  prm.wKu[0][0] = 1.0;
+  return stokes_cip_launch(c, prm, &weight_u, delta0, static_cast<hipStream_t>(stream));
+}
+
+} // extern "C"

@@ -1,5 +1,5 @@
 // What the translation units of the Stokes two-field operator share (stfem_stokes.hip and stfem_stokes_{cell,coupling,boundary,
-// pressure,convection,divergence}.hip): the description of a launch, the context and the launchers.  Not part of the boundary.
+// pressure,convection,cip,divergence}.hip): the description of a launch, the context and the launchers.  Not part of the boundary.
 #pragma once
 #include "stfem_internal.h"
 
@@ -93,6 +93,27 @@ struct ConvectionParams {
   double Eu[6];
 };
 
+// The CIP interior-face launches (stfem_stokes_cip.hip), again a description of their own:
+//   out_u[o] += sum_s wKu[s][o] C(w_s; u_s),   C(w; u)(v) = sum_F int_F delta0 h_F^2 / pa (w.n)^2 [d_n u] . [d_n v] dA
+// Geometry, tables and the weights are copied from the StokesParams of the same set; only destinations with a non-zero wKu are listed.
+struct CipParams {
+  const double *vertices;
+  int ncx, ncy, ncz;
+  int ndu[3];
+  long long Nu;
+  int dmask;
+  int nsrc;
+  const double *us[MAXSRC], *ws[MAXSRC]; // source and weight velocity of every source
+  int nout;
+  double *out_u[MAXOUT];
+  double wKu[MAXSRC][MAXOUT];
+  double Su[9], Du[9], Eu[6], EDu[6]; // [q*3+a] at the Gauss points, [s*3+a] at the end points 0 and 1
+  double xq[3], wq[3];
+  int colour, cart;
+  double hinv[3], detJ;
+  double scale; // delta0 / pa
+};
+
 struct stfem_stokes_ctx {
   int device = 0;
   int nc[3] = {0, 0, 0};
@@ -126,6 +147,9 @@ struct stfem_stokes_ctx {
   double *d_g = nullptr; // Dirichlet data at the face quadrature points (stfem_stokes_nitsche_rhs)
   size_t g_points = 0;
   std::vector<double> h_vertices;
+  // CIP interior-face stabilisation (stfem_stokes_set_cip): 0.0 = no launches; whose velocity weighs it (STFEM_CIP_WEIGHT_*)
+  double cip_delta0 = 0.0;
+  int cip_weight = 0;
 };
 
 template <typename Params> // (StokesParams or ConvectionParams)
@@ -159,5 +183,8 @@ int stokes_boundary_launch(stfem_stokes_ctx *c, StokesParams &prm, const double 
 // faces, eight of the inflow-face kernel.  mode: STFEM_CONVECTION_FORM / _JACOBIAN; lin[s]: the linearisation velocity of source s.
 // Nothing is launched when all wKu of the set are zero.
 int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *lin, int mode, hipStream_t st);
+// The CIP launches after those (stfem_stokes_cip.hip): eight colour launches; weight[s]: the weight velocity of source s.  Nothing is
+// launched with delta0 == 0, on a mesh without interior faces, for a colour without cells or when all wKu of the set are zero.
+int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, hipStream_t st);
 #pragma GCC visibility pop
 

@@ -7,8 +7,10 @@
 // treatment=newton: the system applies the jacobian about the last iterate (NonlinearTreatment::Implicit); treatment=picard: the form
 // about it (Explicit).  Linear solves: FGMRES to lintol (relative), preconditioned by relaxation sweeps of the per-cell Vanka smoother
 // of the linearised operator, or with mg=<levels> by one V-cycle of GMGStokes with linearised levels.
+// delta0=<value>: the CIP interior-face stabilisation of the operator (default 0: none), weighted with the linearisation velocity in the
+// system matrix (TimeIntegratorNavierStokes); the preconditioners stay without it.
 // Usage: navier_convergence <type 0 = cG | 1 = dG> <k> <refinement> [treatment=newton|picard] [mg=<levels>] [dg=1] [nu=1] [nltol=1e-12]
-//                           [lintol=1e-3] [sweeps=3] [omega=0: estimated] [end_time=1] [warmup=<untimed slabs>]
+//                           [delta0=0] [lintol=1e-3] [sweeps=3] [omega=0: estimated] [end_time=1] [warmup=<untimed slabs>]
 // Prints: cells u-dofs p-dofs t-dofs  u:Linf-Linf  u:L2-L2  u:L2-H1semi  p:L2-L2  fgmres-iterations-per-solve
 //         nonlinear-steps-per-slab  fgmres-iterations-per-slab  |div u_h|(end time)  share:residuals  share:set_data  share:krylov
 //         most-nonlinear-steps-in-a-slab  all-slabs-converged
@@ -25,7 +27,7 @@ int main(int argc_all, char **argv_all)
 {
   unsigned mg_levels = 0, sweeps = 3, warmup = 0;
   bool dg_pressure = false, newton = true;
-  double nu = 1.0, nltol = 1e-12, lintol = 1e-3, omega_arg = 0.0, end_time = 1.0;
+  double nu = 1.0, nltol = 1e-12, lintol = 1e-3, omega_arg = 0.0, end_time = 1.0, delta0 = 0.0;
   std::vector<char *> pos;
   for (int i = 0; i < argc_all; ++i) {
     const char *a = argv_all[i];
@@ -36,6 +38,7 @@ int main(int argc_all, char **argv_all)
     else if (std::strcmp(a, "treatment=picard") == 0) newton = false;
     else if (std::strncmp(a, "nu=", 3) == 0) nu = std::atof(a + 3);
     else if (std::strncmp(a, "nltol=", 6) == 0) nltol = std::atof(a + 6);
+    else if (std::strncmp(a, "delta0=", 7) == 0) delta0 = std::atof(a + 7);
     else if (std::strncmp(a, "lintol=", 7) == 0) lintol = std::atof(a + 7);
     else if (std::strncmp(a, "sweeps=", 7) == 0) sweeps = unsigned(std::atoi(a + 7));
     else if (std::strncmp(a, "omega=", 6) == 0) omega_arg = std::atof(a + 6);
@@ -61,7 +64,7 @@ int main(int argc_all, char **argv_all)
   try {
     Mesh mesh;
     mesh.ncell[0] = mesh.ncell[1] = mesh.ncell[2] = n;
-    StokesMatrixFreeOperator<3, double> K(mesh, 2, nu, std::set<boundary_id>(), std::set<boundary_id>(), 20.0, 10.0, 0.0, 0.0, 0.0, dg_pressure, treatment);
+    StokesMatrixFreeOperator<3, double> K(mesh, 2, nu, std::set<boundary_id>(), std::set<boundary_id>(), 20.0, 10.0, 0.0, delta0, 0.0, dg_pressure, treatment);
     auto spaces = std::make_shared<StokesSpaces>(mesh, K.handle());
     const unsigned nt = type == TimeStepType::CGP ? k : k + 1;
     const BlockSlice slice(1, 2, nt), slice1(1, 2, 1);

@@ -365,6 +365,13 @@ public:
     pde_operator->set_data(data);
     if (static_cast<const void *>(pde_operator) != static_cast<const void *>(jac_operator)) jac_operator->set_data(data);
   }
+  // operators with a CIP term (SystemMatrixStokes, NavierStokesOperator): whose velocity weighs it - STFEM_CIP_WEIGHT_LINEARISATION makes
+  // vmult linear in its source; residual / form about the state itself are the same with both
+  void set_cip_weight(int weight) const
+  {
+    pde_operator->set_cip_weight(weight);
+    if (static_cast<const void *>(pde_operator) != static_cast<const void *>(jac_operator)) jac_operator->set_cip_weight(weight);
+  }
   void residual(BlockVectorType &dst, const BlockVectorType &src, const BlockVectorType &rhs_) const
   {
     rhs = &rhs_;

@@ -8,6 +8,7 @@
 #include "operators.h"
 
 #include <array>
+#include <cmath>
 #include <functional>
 #include <limits>
 #include <map>
@@ -136,8 +137,10 @@ inline void rhs_minus(std::vector<StokesVector> &dst, const std::vector<StokesVe
 }
 
 // operators.h:1193-1766: cell loop + boundary-face loop for the weak (Nitsche) ids.  Same constructor arguments after the mesh as
-// the reference (1199-1213), with dg_pressure before the nonlinear treatment; delta0 != 0 (CIP interior faces) throws, and so does a
-// nonlinear treatment together with outflow_penalty != 0 (the outflow faces' value term, 1705-1709, is not built).
+// the reference (1199-1213), with dg_pressure before the nonlinear treatment.  delta0 != 0 switches the CIP interior-face term on
+// (1605-1633, stfem_stokes_set_cip), weighted with the source of every vmult as in the reference; set_cip_weight chooses the
+// linearisation velocity instead.  delta1 is accepted and unused, as in the reference.  A nonlinear treatment together with
+// outflow_penalty != 0 throws (the outflow faces' value term, 1705-1709, is not built).
 template <int dim, typename Number> class StokesMatrixFreeOperator {
   static_assert(dim == 3 && std::is_same<Number, double>::value, "3D, fp64");
 
@@ -152,7 +155,7 @@ public:
   {
     // dg_pressure: FE_DGP(degree - 1) instead of FE_Q(degree - 1) for the pressure (the reference chooses the element of its
     // second DoFHandler, tests/tp_03stokes.cc:83-86: dGPressure)
-    if (delta0 != 0.0) throw Error(STFEM_ERR_UNSUPPORTED, "StokesMatrixFreeOperator: the CIP face term (delta0 != 0) is not built");
+    if (!std::isfinite(delta0)) throw Error(STFEM_ERR_INVALID_ARGUMENT, "StokesMatrixFreeOperator: delta0 is not finite");
     if (nonlinear && outflow_penalty != 0.0)
       throw Error(STFEM_ERR_UNSUPPORTED, "StokesMatrixFreeOperator: outflow_penalty != 0 with a nonlinear treatment is not built");
     create(mesh, velocity_degree, viscosity, dg_pressure);
@@ -160,7 +163,19 @@ public:
     for (boundary_id f : weak_boundary_ids) weak |= 1 << f;
     for (boundary_id f : outflow_boundary_ids) outflow |= 1 << f;
     if (weak || outflow) check(stfem_stokes_set_weak_boundaries(h_, weak, outflow, penalty1, penalty2), "stfem_stokes_set_weak_boundaries");
+    delta0_ = delta0;
+    if (delta0 != 0.0) check(stfem_stokes_set_cip(h_, delta0, STFEM_CIP_WEIGHT_SOURCE), "stfem_stokes_set_cip");
   }
+  // Whose velocity weighs the CIP term: STFEM_CIP_WEIGHT_SOURCE (the reference: the source of the vmult, cubic in it) or
+  // STFEM_CIP_WEIGHT_LINEARISATION (with a nonlinear treatment the linearisation velocity of set_data: linear in the source, what a
+  // Krylov method needs).  form(x) about x itself is the same with both.  The state of the device context, like set_data.
+  void set_cip_weight(int weight) const
+  {
+    check(stfem_stokes_set_cip(h_, delta0_, weight), "stfem_stokes_set_cip");
+    cip_weight_ = weight;
+  }
+  Number delta0() const { return delta0_; }
+  int cip_weight() const { return cip_weight_; }
 
 private:
   void create(const Mesh &mesh, unsigned velocity_degree, Number viscosity, bool dg_pressure)
@@ -254,6 +269,8 @@ private:
   NonlinearTreatment nonlinear_treatment;
   bool nonlinear;
   mutable const double *lin_ = nullptr; // data_lin[0]
+  Number delta0_ = 0.0;
+  mutable int cip_weight_ = STFEM_CIP_WEIGHT_SOURCE;
   size_t n_cells_ = 0;
   mutable StokesVector cells_; // device cell values of compute_divergence, made on demand
 };
@@ -315,6 +332,8 @@ public:
   // operators.h:385-388: the linearisation vector, in BlockSlice order (n x 1 systems: one {velocity, pressure} pair); referred to,
   // not copied.  Source time dof (it, id) is linearised about its block index(it, 0, id) (473-484, 843-846).
   void set_data(const BlockVectorType &solution_linearization_) const { solution_linearization = &solution_linearization_; }
+  // the weight velocity of the operator's CIP term (StokesMatrixFreeOperator::set_cip_weight)
+  void set_cip_weight(int weight) const { K.set_cip_weight(weight); }
   void vmult(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const // 696-700
   {
     tensorproduct_eval(dst, src, K.vmult_mode(), stream);

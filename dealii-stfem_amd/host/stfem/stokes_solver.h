@@ -173,6 +173,7 @@ public:
       for (unsigned b = 0; b < dst.n_blocks(); ++b) compress_add(*dst.view(b).context(), dst.view(b).handle(), stream);
   }
   void set_data(const StokesBlockVector &lin) const { A.set_data(lin.blocks()); }
+  void set_cip_weight(int weight) const { A.set_cip_weight(weight); }
 
 private:
   const SystemMatrixStokes<dim, Number> &A;
@@ -738,6 +739,9 @@ private:
 //   preconditioner: set_data(x), vmult - GMGStokes with the same treatment or RelaxedVankaStokes.
 // Per slab: x = previous solution; r = rhs - form(x); until |r| <= max(abstol, reltol |r_0|) or max_nonlinear steps (reported by
 // converged(), not thrown): set_data(x) on both, FGMRES on J delta = r from zero, x += delta.
+// With the CIP term (delta0 != 0) the system matrix is switched to the linearisation weight: the residual rhs - form(x) is taken about
+// x itself, where both weights coincide, and the Krylov operator becomes linear in the increment (with the source weight of the
+// reference it is cubic).  The preconditioners (GMGStokes levels, Vanka blocks) stay without the term.
 template <int dim, typename System, typename Preconditioner> class TimeIntegratorNavierStokes {
 public:
   TimeIntegratorNavierStokes(TimeStepType type, unsigned time_degree, const FullMatrix<double> &Alpha_1, const FullMatrix<double> &Gamma_1,
@@ -750,6 +754,7 @@ public:
       max_nonlinear(max_nonlinear)
   {
     if (const char *e = std::getenv("STFEM_FGMRES_VERBOSE")) solver.verbose = unsigned(std::atoi(e));
+    matrix.set_cip_weight(STFEM_CIP_WEIGHT_LINEARISATION);
   }
 
   // x, rhs: the slab's blocks; prev: one (velocity, pressure) pair (BlockSlice(1, 2, 1))

@@ -389,8 +389,8 @@ int stfem_coefficient_per_cell(const int32_t ncell[3], const double *vertices, d
 /* ---- Stokes two-field operator (BASELINE configs[4]): the cell loop (LoopType::Cell, include/operators.h:1228-1229) and,
  * after stfem_stokes_set_weak_boundaries below, the weak (Nitsche) boundary faces of operators.h:1662-1751; the convection modes of the
  * Navier-Stokes operator (OperatorMode::form / jacobian) through the *_convection entry points below; the divergence functional
- * (compute_divergence) through stfem_stokes_divergence.  Not built: the CIP
- * interior-face term (delta0 != 0, 1603-1638) and the outflow penalty (beta, 1705-1709).  Velocity FE_Q(2)^3, pressure FE_Q(1) (stfem_stokes_create)
+ * (compute_divergence) through stfem_stokes_divergence; the CIP interior-face term (delta0 != 0, 1603-1638) after
+ * stfem_stokes_set_cip.  Not built: the outflow penalty (beta, 1705-1709).  Velocity FE_Q(2)^3, pressure FE_Q(1) (stfem_stokes_create)
  * or FE_DGP(1) (stfem_stokes_create_ex), QGauss(3), MappingQ1 on the mesh of `mesh`; mesh->dirichlet_mask constrains the velocity
  * (homogeneous), the pressure is unconstrained.  fp64.
  * Layout: a velocity vector is 3 * n_velocity_dofs doubles, component-major, every component in
@@ -491,8 +491,35 @@ int stfem_stokes_divergence(stfem_stokes_ctx *ctx, const double *u, double *cell
  *       [point][3] in that order) is ADDED to dst_u / dst_p (device).  Synchronises `stream` once (upload of g).
  * With a convection mode (the *_convection entry points) the weak faces also get the inflow term - min(b.n, 0) u (1738-1743); the
  * outflow faces still add nothing: their back-flow term carries a factor 0.0 and their value term the outflow penalty.
- * Not built: the CIP interior-face term (delta0 != 0, operators.h:1603-1638) and outflow_penalty (beta). */
+ * Not built: outflow_penalty (beta). */
 int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *ctx, int weak_mask, int outflow_mask, double penalty1, double penalty2);
+/* The CIP gradient-jump stabilisation on the interior faces, StokesMatrixFreeOperator::do_face_integral_local (operators.h:1605-1633,
+ * the constructor argument delta0; delta1 is stored by the reference and never read).  Over every interior face F between a cell A and
+ * its neighbour B in direction d, unit normal n (J^-T e_d normalised), face rule QGauss(3)^2, each side's normal derivative with its
+ * own cell's Jacobian:
+ *   C(w; u)(v) = sum_F int_F delta_F(w) [d_n u] . [d_n v] dA,   [d_n u] = (grad u|_A - grad u|_B) n,
+ *   delta_F(w) = delta0 h_F^2 / pa (w.n)^2 at each face point,  h_F = sqrt(sum_q JxW_face) (get_h_face, 182-209),  pa = 2^3.5.
+ * Entries of u and w on strongly constrained DoFs read as 0; constrained rows and the pressure rows receive nothing.
+ *   set_cip: every later stfem_stokes_vmult, _st_vmult, _st_vmult_slice_add and their _convection forms adds, after all their other
+ *       launches, sum_s wKu C(w_s; u_s) to the velocity destinations that receive nu K u - B^T p (same weights, same skip rule).
+ *       delta0 == 0 (the default): no launch, every entry point issues exactly the launches it issues without this call.
+ *       weight STFEM_CIP_WEIGHT_SOURCE (default): w is the source u of the vmult in every entry point - the reference's behaviour
+ *       (u_in.get_value, 1623), so vmult is CUBIC in its argument and not a linearisation of anything.
+ *       weight STFEM_CIP_WEIGHT_LINEARISATION: in the *_convection entry points with a mode other than 0, w is the linearisation
+ *       velocity of that source (lin_u, lin_blocks[index(it, 0, id)]): the operator is linear in its source; with mode 0 it falls back
+ *       to the source.  About the state itself (form(x) with lin = x) both choices coincide; only the Krylov operator differs.
+ *       A non-finite delta0 or a weight outside 0..1 is STFEM_ERR_INVALID_ARGUMENT, decided before anything touches the device.
+ *   cip_add: dst_u += C(weight_u; src_u) with the given delta0, independent of set_cip: the term by itself.  weight_u may be src_u;
+ *       dst_u equal to either is STFEM_ERR_ALIAS, a null pointer STFEM_ERR_INVALID_ARGUMENT.
+ * stfem_stokes_mass_vmult never gets the term.  The Vanka smoothers (stfem_stokes_vanka_create, _create_linearised, _update) build their
+ * blocks WITHOUT it, whatever set_cip says (the class blocks of a box are probed on a context of their own, the per-cell blocks
+ * assembled by their own kernel): the smoother is that of the operator without the stabilisation - a preconditioner of a flexible
+ * method.  Eight colour launches, no atomics, fixed summation order: two calls agree bit for bit.  Not built: the term on multigrid
+ * levels and in the Vanka blocks, fp32, slab partitioning of these launches, the derivative of delta_F with respect to w (the
+ * reference has none either). */
+enum { STFEM_CIP_WEIGHT_SOURCE = 0, STFEM_CIP_WEIGHT_LINEARISATION = 1 };
+int stfem_stokes_set_cip(stfem_stokes_ctx *ctx, double delta0, int weight);
+int stfem_stokes_cip_add(stfem_stokes_ctx *ctx, double *dst_u, const double *src_u, const double *weight_u, double delta0, void *stream);
 int64_t stfem_stokes_n_face_points(const stfem_stokes_ctx *ctx);
 int stfem_stokes_face_points(const stfem_stokes_ctx *ctx, double *out);
 int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *ctx, const double *g_at_face_points, double *dst_u, double *dst_p, void *stream);
@@ -546,7 +573,8 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
  * not fit beside the free device memory: STFEM_ERR_OUT_OF_MEMORY, the sizes in stfem_stokes_vanka_last_error.
  * update: stages the same set-up again into the existing block storage for new linearisation states (same mode);
  * STFEM_ERR_UNSUPPORTED for the class blocks of stfem_stokes_vanka_create on a box.  n_classes: the cell count.  Not built: fp32
- * blocks, the CIP term and outflow_penalty, slab partitioning of this layout. */
+ * blocks, the CIP term in the blocks (stfem_stokes_set_cip: the smoother is that of the operator without it) and outflow_penalty,
+ * slab partitioning of this layout. */
 int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha,
                                          const double *Beta, int mode, const double *const *lin_blocks, stfem_stokes_vanka **out);
 int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_blocks);

@@ -1,0 +1,50 @@
+#!/usr/bin/env python3
+"""What the CIP interior-face launches (stfem_stokes_set_cip, delta0 != 0) add to one Stokes vmult, Q2/Q1 x cG(1), on a box (Kronecker
+path + CART kernel) and on a perturbed mesh (cell kernel + general kernel) of N^3 cells (default 64): wall time per call of a
+back-to-back sequence that ends in a device synchronise, the same context with delta0 = 0 and delta0 = 1 in alternating rounds of one
+process, median and range over the rounds.  For scale beside it: the convection launches of the jacobian mode on the same meshes took
+0.25 ms (box) / 0.31 ms (perturbed) in profiles/navier_convection.txt.
+Usage: stokes_cip_bench.py [N] [rounds] [calls per round]"""
+import importlib
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+stfem = importlib.import_module("dealii-stfem_amd")
+N = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+CALLS = int(sys.argv[3]) if len(sys.argv) > 3 else 40
+Alpha, Beta, _, _ = stfem.get_fe_time_weights_stokes(stfem.CGP, 1, 1.0 / 64, 1)
+for mesh in ("box", "perturbed"):
+    verts = stfem.mesh_vertices((N, N, N), distort=0.1, seed=7) if mesh == "perturbed" else None
+    op = stfem.StokesMatrixFreeOperator((N, N, N), vertices=verts, viscosity=1.0)
+    rng = np.random.default_rng(0)
+    src = [op.initialize_dof_vector(v, rng.uniform(-1, 1, 3 * op.n_velocity if v == 0 else op.n_pressure)) for v in (0, 1)]
+    dst = [op.initialize_dof_vector(v) for v in (0, 1)]
+
+    def timed(delta0):
+        op.set_cip(delta0)
+        for _ in range(3):
+            op.st_vmult(Alpha, Beta, 1, 1, dst, src)
+        dst[1].download()
+        t0 = time.perf_counter()
+        for _ in range(CALLS):
+            op.st_vmult(Alpha, Beta, 1, 1, dst, src)
+        dst[1].download()  # (synchronises; the pressure vector is the small one)
+        return (time.perf_counter() - t0) / CALLS * 1e3
+
+    timed(1.0), timed(0.0)  # code objects, first launches
+    without, with_term = [], []
+    for _ in range(ROUNDS):
+        without.append(timed(0.0))
+        with_term.append(timed(1.0))
+    diff = [b - a for a, b in zip(without, with_term)]
+    fmt = lambda v: f"{np.median(v):7.3f} ms (range {min(v):.3f} .. {max(v):.3f})"  # noqa: E731
+    print(f"{mesh:9s} {N}^3 cells, {3 * op.n_velocity + op.n_pressure} DoFs, {ROUNDS} rounds x {CALLS} calls, measured:", flush=True)
+    print(f"    vmult, delta0 = 0 : {fmt(without)}")
+    print(f"    vmult, delta0 = 1 : {fmt(with_term)}")
+    print(f"    the CIP launches  : {fmt(diff)}", flush=True)
+    del op, src, dst

@@ -26,8 +26,8 @@ class StfemError(RuntimeError):
     def __init__(self, status, what=""):
         self.status = status
         msg = lib().stfem_strerror(status).decode()
-        hip = lib().stfem_last_hip_error().decode()
-        super().__init__(f"{what}: {msg} ({status})" + (f" [{hip}]" if hip else ""))
+        why = lib().stfem_last_error().decode()
+        super().__init__(f"{what}: {msg} ({status})" + (f" [{why}]" if why else ""))
 
 
 def build(force=False):
@@ -198,6 +198,7 @@ SIGNATURES = {
     "stfem_stokes_vanka_step": (C.c_int, [_vp, C.POINTER(_vp), C.c_double, C.c_int, C.POINTER(_vp), _vp]),
     "stfem_stokes_vanka_last_error": (C.c_char_p, []),
     "stfem_strerror": (C.c_char_p, [C.c_int]),
+    "stfem_last_error": (C.c_char_p, []),
     "stfem_last_hip_error": (C.c_char_p, []),
     "stfem_last_kernel_name": (C.c_char_p, [_vp]),
     "stfem_last_sweep_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
@@ -681,12 +682,6 @@ def vector_convert(dst, src, stream=None):
 
 # ------------------------------------------------------- around the operator: load vectors, error norms (8 f-3)
 
-def _check_driver(status, what):
-    """_check with the text the driver entry points keep of their failing HIP call"""
-    if status != 0:
-        raise StfemError(status, what + ": " + lib().stfem_driver_last_error().decode() if status == -3 else what)
-
-
 def support_points(ctx):
     """[n_dofs, 3]: the nodes in the order of the vectors (VectorTools::interpolate = evaluate + upload)"""
     out = np.zeros((ctx.n_dofs, 3))
@@ -713,12 +708,12 @@ def _points_array(ctx, nq, values, per_point, what):
 def integrate_rhs(ctx, nq, f, dst, block=0, stream=None):
     """block `block` of dst = (f, phi_i) with QGauss(nq), f [n_cells, nq^3] at quadrature_points; constrained rows 0"""
     a, ptr = _points_array(ctx, nq, f, 1, "f")
-    _check_driver(lib().stfem_integrate_rhs(ctx._h, nq, ptr, dst._h, block, stream), "stfem_integrate_rhs")
+    _check(lib().stfem_integrate_rhs(ctx._h, nq, ptr, dst._h, block, stream), "stfem_integrate_rhs")
 
 
 def integrate_rhs_product(ctx, nq, amplitude, frequency, dst, block=0, stream=None):
     """the same with f(x) = amplitude * prod_d sin(2 pi frequency x_d) evaluated on the device"""
-    _check_driver(lib().stfem_integrate_rhs_product(ctx._h, nq, amplitude, frequency, dst._h, block, stream), "stfem_integrate_rhs_product")
+    _check(lib().stfem_integrate_rhs_product(ctx._h, nq, amplitude, frequency, dst._h, block, stream), "stfem_integrate_rhs_product")
 
 
 def integrate_difference(ctx, nq, u, block, exact, exact_grad=None, stream=None):
@@ -727,24 +722,24 @@ def integrate_difference(ctx, nq, u, block, exact, exact_grad=None, stream=None)
     e, pe = _points_array(ctx, nq, exact, 1, "exact")
     g, pg = _points_array(ctx, nq, exact_grad, 3, "exact_grad")
     out = np.zeros(3)
-    _check_driver(lib().stfem_integrate_difference(ctx._h, nq, u._h, block, pe, pg, _p(out), stream), "stfem_integrate_difference")
+    _check(lib().stfem_integrate_difference(ctx._h, nq, u._h, block, pe, pg, _p(out), stream), "stfem_integrate_difference")
     return out
 
 
 def integrate_difference_product(ctx, nq, u, block, amplitude, frequency, stream=None):
     """the same against amplitude * prod_d sin(2 pi frequency x_d) and its gradient, evaluated on the device"""
     out = np.zeros(3)
-    _check_driver(lib().stfem_integrate_difference_product(ctx._h, nq, u._h, block, amplitude, frequency, _p(out), stream), "stfem_integrate_difference_product")
+    _check(lib().stfem_integrate_difference_product(ctx._h, nq, u._h, block, amplitude, frequency, _p(out), stream), "stfem_integrate_difference_product")
     return out
 
 
 def vector_axpby(ctx, a, x, b, y, stream=None):
     """y = a x + b y on every block; a zero factor means "not read"; x and y may be the same vector"""
-    _check_driver(lib().stfem_vector_axpby(ctx._h, a, x._h, b, y._h, stream), "stfem_vector_axpby")
+    _check(lib().stfem_vector_axpby(ctx._h, a, x._h, b, y._h, stream), "stfem_vector_axpby")
 
 
 def vector_set_zero(ctx, y, stream=None):
-    _check_driver(lib().stfem_vector_set_zero(ctx._h, y._h, stream), "stfem_vector_set_zero")
+    _check(lib().stfem_vector_set_zero(ctx._h, y._h, stream), "stfem_vector_set_zero")
 
 
 def gauss_rule(n):
@@ -1027,13 +1022,12 @@ class StokesPreconditionVanka:
         h = _vp()
         if per_cell or mode != 0:
             rc = lib().stfem_stokes_vanka_create_linearised(op._h, self.nb, bv, _p(A), _p(B), int(mode), self._lin(lin), C.byref(h))
-            what = "stfem_stokes_vanka_create_linearised: "
+            what = "stfem_stokes_vanka_create_linearised"
         else:
             rc = lib().stfem_stokes_vanka_create(op._h, self.nb, bv, _p(A), _p(B), C.byref(h))
-            what = "stfem_stokes_vanka_create: "
-        if rc != 0:
-            assert not h.value
-            raise StfemError(rc, what + lib().stfem_stokes_vanka_last_error().decode())
+            what = "stfem_stokes_vanka_create"
+        assert rc == 0 or not h.value
+        _check(rc, what)
         self._h = h
 
     def _lin(self, lin):
@@ -1044,9 +1038,7 @@ class StokesPreconditionVanka:
 
     def update(self, lin):
         """the blocks again, linearised about `lin` (same mode, same storage)"""
-        rc = lib().stfem_stokes_vanka_update(self._h, self._lin(lin))
-        if rc != 0:
-            raise StfemError(rc, "stfem_stokes_vanka_update: " + lib().stfem_stokes_vanka_last_error().decode())
+        _check(lib().stfem_stokes_vanka_update(self._h, self._lin(lin)), "stfem_stokes_vanka_update")
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -1065,9 +1057,7 @@ class StokesPreconditionVanka:
     def step(self, dst_blocks, omega, accumulate, src_blocks, stream=None):
         d = (_vp * self.nb)(*[getattr(v, "ptr", v) for v in dst_blocks])
         s_ = (_vp * self.nb)(*[getattr(v, "ptr", v) for v in src_blocks])
-        rc = lib().stfem_stokes_vanka_step(self._h, d, omega, int(bool(accumulate)), s_, stream)
-        if rc != 0:
-            raise StfemError(rc, "stfem_stokes_vanka_step: " + lib().stfem_stokes_vanka_last_error().decode())
+        _check(lib().stfem_stokes_vanka_step(self._h, d, omega, int(bool(accumulate)), s_, stream), "stfem_stokes_vanka_step")
 
     def vmult(self, dst_blocks, src_blocks, stream=None):
         self.step(dst_blocks, 1.0, False, src_blocks, stream)

@@ -28,14 +28,6 @@ using namespace stfem;
 // the precision traits of the context's Number type T (stfem_by_prec)
 template <class T> using PrecOf = std::conditional_t<std::is_same<T, float>::value, f32::Prec, f64::Prec>;
 
-thread_local char g_hip_error[256] = "";
-
-int hip_fail(hipError_t e, const char *what)
-{
-  snprintf(g_hip_error, sizeof(g_hip_error), "%s: %s", what, hipGetErrorString(e));
-  return STFEM_ERR_HIP;
-}
-
 // The geometry of a new context: a box given by its extents, or a vertex grid, in which an axis-aligned uniform box is
 // recognised (deal.II compresses such cells as "Cartesian").
 static int set_geometry(stfem_ctx *c, const stfem_mesh_desc *mesh)
@@ -107,8 +99,6 @@ const char *stfem_strerror(int s)
   }
 }
 
-const char *stfem_last_hip_error(void) { return g_hip_error; }
-
 int stfem_ctx_create(const stfem_mesh_desc *mesh, const stfem_space_desc *space, stfem_ctx **out)
 {
   if (!mesh || !space || !out) return STFEM_ERR_INVALID_ARGUMENT;
@@ -121,7 +111,7 @@ int stfem_ctx_create(const stfem_mesh_desc *mesh, const stfem_space_desc *space,
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return STFEM_ERR_NO_DEVICE;
   if (mesh->device < 0 || mesh->device >= ndev) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_hip_error, hipSetDevice(mesh->device));
+  STFEM_TRY(hipSetDevice(mesh->device));
   int n_cu = 0;
   if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, mesh->device) != hipSuccess) n_cu = 0;
 
@@ -201,9 +191,9 @@ int stfem_last_tile_plan(const stfem_ctx *c, int32_t out[4])
 int stfem_set_coefficient(stfem_ctx *c, int which, int layout, const double *host)
 {
   if (!c || which < 0 || which > 1 || layout < 0 || layout > 2) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   if (c->d_coef[which]) {
-    STFEM_TRY(g_hip_error, hipFree(c->d_coef[which]));
+    STFEM_TRY(hipFree(c->d_coef[which]));
     c->d_coef[which] = nullptr;
   }
   c->coef_layout[which] = 0;
@@ -215,9 +205,9 @@ int stfem_set_coefficient(stfem_ctx *c, int which, int layout, const double *hos
   if (hipMalloc(&c->d_coef[which], n * c->es) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
   if (c->prec) {
     std::vector<float> tmp(host, host + n);
-    STFEM_TRY(g_hip_error, hipMemcpy(c->d_coef[which], tmp.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    STFEM_TRY(hipMemcpy(c->d_coef[which], tmp.data(), n * sizeof(float), hipMemcpyHostToDevice));
   } else {
-    STFEM_TRY(g_hip_error, hipMemcpy(c->d_coef[which], host, n * sizeof(double), hipMemcpyHostToDevice));
+    STFEM_TRY(hipMemcpy(c->d_coef[which], host, n * sizeof(double), hipMemcpyHostToDevice));
   }
   c->coef_layout[which] = layout;
   return STFEM_OK;
@@ -370,11 +360,12 @@ template <class PR> static int ensure_metric(stfem_ctx *c, bool use_lap, bool us
       (void)hipFree(dv);
       return STFEM_ERR_OUT_OF_MEMORY;
     }
-    if (hipMemcpy(dv, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dr, rule.data(), rule.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    hipError_t e = hipMemcpy(dv, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dr, rule.data(), rule.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
       (void)hipFree(dv);
       (void)hipFree(dr);
-      return hip_fail(hipGetLastError(), "metric table upload");
+      return stfem_set_error(STFEM_ERR_HIP, "metric table upload: %s", hipGetErrorString(e));
     }
     c->d_vertices = dv;
     c->d_rule = dr;
@@ -385,7 +376,7 @@ template <class PR> static int ensure_metric(stfem_ctx *c, bool use_lap, bool us
                             use_lap ? static_cast<const real *>(c->d_coef[1]) : nullptr, use_lap ? c->coef_layout[1] : 0,
                             use_mass ? static_cast<const real *>(c->d_coef[0]) : nullptr, use_mass ? c->coef_layout[0] : 0,
                             static_cast<real *>(c->d_metric), st);
-  if (rc != 0) return hip_fail(hipGetLastError(), "build_metric");
+  if (rc != 0) return rc; // (launch_build_metric has recorded the reason)
   c->metric_valid = true;
   c->metric_flags = flags;
   return STFEM_OK;
@@ -419,8 +410,8 @@ static int block_slots(int nbm) { return nbm <= 4 ? nbm : (nbm <= 6 ? 6 : 8); }
 static int grow_halo(stfem_ctx *c, size_t elements, hipStream_t st)
 {
   if (elements <= c->halo_doubles) return STFEM_OK;
-  STFEM_TRY(g_hip_error, hipStreamSynchronize(st));
-  if (c->d_halo) STFEM_TRY(g_hip_error, hipFree(c->d_halo));
+  STFEM_TRY(hipStreamSynchronize(st));
+  if (c->d_halo) STFEM_TRY(hipFree(c->d_halo));
   c->d_halo = nullptr;
   c->halo_doubles = 0;
   if (hipMalloc(&c->d_halo, elements * c->es) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
@@ -435,21 +426,21 @@ static int timeline_arm(stfem_ctx *c, size_t n, long long **plan_timeline, hipSt
 {
   if (!c->env_timeline) return STFEM_OK;
   if (c->tl_n < n) {
-    if (c->d_timeline) STFEM_TRY(g_hip_error, hipFree(c->d_timeline));
+    if (c->d_timeline) STFEM_TRY(hipFree(c->d_timeline));
     c->d_timeline = nullptr;
     if (hipMalloc(&c->d_timeline, n * sizeof(long long)) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
     c->tl_n = n;
   }
-  STFEM_TRY(g_hip_error, hipMemsetAsync(c->d_timeline, 0, n * sizeof(long long), st));
+  STFEM_TRY(hipMemsetAsync(c->d_timeline, 0, n * sizeof(long long), st));
   *plan_timeline = c->d_timeline;
   return STFEM_OK;
 }
 static int timeline_dump(stfem_ctx *c, size_t n, long long h0, long long h1, long long h2, long long h3, hipStream_t st)
 {
   if (!c->env_timeline) return STFEM_OK;
-  STFEM_TRY(g_hip_error, hipStreamSynchronize(st));
+  STFEM_TRY(hipStreamSynchronize(st));
   std::vector<long long> h(n);
-  STFEM_TRY(g_hip_error, hipMemcpy(h.data(), c->d_timeline, n * sizeof(long long), hipMemcpyDeviceToHost));
+  STFEM_TRY(hipMemcpy(h.data(), c->d_timeline, n * sizeof(long long), hipMemcpyDeviceToHost));
   if (FILE *f = fopen(c->env_timeline, "wb")) {
     const long long hdr[4] = {h0, h1, h2, h3};
     fwrite(hdr, sizeof(long long), 4, f);
@@ -459,12 +450,9 @@ static int timeline_dump(stfem_ctx *c, size_t n, long long h0, long long h1, lon
   return STFEM_OK;
 }
 
-// what a launch_*_panel returns for the status of its kernel launcher (stfem_kernels_decl.h)
-static int launch_status(int rc)
-{
-  if (rc == -3) return hip_fail(hipGetLastError(), "kernel launch");
-  return rc != 0 ? STFEM_ERR_UNSUPPORTED : STFEM_OK;
-}
+// what a launch_*_panel returns for the status of its kernel launcher (stfem_kernels_decl.h), which has recorded the reason
+// of a failed launch itself
+static int launch_status(int rc) { return rc == STFEM_OK || rc == STFEM_ERR_HIP ? rc : STFEM_ERR_UNSUPPORTED; }
 
 // Systems with more blocks than one launch takes are cut into panels (dst += for the later column panels).  On the
 // pencil path a launch needs two cells per wave - Q4 with seven or eight blocks has one - so those systems
@@ -527,7 +515,7 @@ static int launch_pencil_panel(stfem_ctx *c, typename PR::Sweep &prm, typename P
   }
   if (!c->d_work) {
     if (hipMalloc(&c->d_work, 8 * 32 * sizeof(int)) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
-    STFEM_TRY(g_hip_error, hipMemsetAsync(c->d_work, 0, 8 * 32 * sizeof(int), st));
+    STFEM_TRY(hipMemsetAsync(c->d_work, 0, 8 * 32 * sizeof(int), st));
   }
   pp.work = c->d_work;
   pp.grid = 2 * (c->n_cu > 0 ? c->n_cu : 256); // two 4-wave workgroups per CU (registers, LDS)
@@ -605,7 +593,7 @@ static int apply_tiled_t(stfem_ctx *c, int nbo, int nbi, const std::vector<doubl
                          const stfem_vec *src, int add, bool use_lap_coef, bool use_mass_coef, hipStream_t st)
 {
   using real = typename PR::real;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   for (int j = 0; j < nbo; ++j)
     for (int i = 0; i < nbi; ++i)
       if (dst->blk[j] == src->blk[i]) return STFEM_ERR_ALIAS;
@@ -617,7 +605,7 @@ static int apply_tiled_t(stfem_ctx *c, int nbo, int nbi, const std::vector<doubl
   const bool atomic = c->variant == 1 && !general;
   if (!add && atomic)
     for (int j = 0; j < nbo; ++j)
-      STFEM_TRY(g_hip_error, hipMemsetAsync(dst->blk[j], 0, size_t(c->ndofs) * sizeof(real), st));
+      STFEM_TRY(hipMemsetAsync(dst->blk[j], 0, size_t(c->ndofs) * sizeof(real), st));
   typename PR::Sweep prm;
   fill_common<PR>(c, prm);
   prm.coef_lap = (use_lap_coef && !general) ? static_cast<const real *>(c->d_coef[1]) : nullptr;
@@ -681,7 +669,7 @@ template <typename T> static int invert_diagonal(stfem_ctx *c, void *d, hipStrea
   const unsigned grid = (unsigned)std::min<int64_t>((c->ndofs + 255) / 256, 4096);
   hipLaunchKernelGGL(invert_diagonal_kernel<T>, dim3(grid), dim3(256), 0, st, c->ndofs, static_cast<T *>(d),
                      std::sqrt(std::numeric_limits<T>::epsilon()));
-  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
+  return stfem_launch_end("invert_diagonal_kernel");
 }
 
 template <class PR> static int diagonal_t(stfem_ctx *c, double ms, double ls, stfem_vec *diag, hipStream_t st)
@@ -689,14 +677,14 @@ template <class PR> static int diagonal_t(stfem_ctx *c, double ms, double ls, st
   using real = typename PR::real;
   if (!c || !diag || diag->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   if (diag->nb != 1) return STFEM_ERR_SHAPE_MISMATCH;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   const Scaling lap = effective_scaling(c, 1, ls), mass = effective_scaling(c, 0, ms);
   const bool general = is_general(c);
   if (general) {
     const int rc = ensure_metric<PR>(c, lap.coef, mass.coef, st);
     if (rc != STFEM_OK) return rc;
   }
-  STFEM_TRY(g_hip_error, hipMemsetAsync(diag->blk[0], 0, size_t(c->ndofs) * sizeof(real), st));
+  STFEM_TRY(hipMemsetAsync(diag->blk[0], 0, size_t(c->ndofs) * sizeof(real), st));
   typename PR::Diag prm;
   std::memset(&prm, 0, sizeof(prm));
   prm.diag = static_cast<real *>(diag->blk[0]);
@@ -727,8 +715,7 @@ template <class PR> static int diagonal_t(stfem_ctx *c, double ms, double ls, st
     prm.S[i] = real(c->tab.S[i]);
     prm.D[i] = real(c->tab.D[i]);
   }
-  if (PR::diagonal(prm, st) != 0) return hip_fail(hipGetLastError(), "diagonal launch");
-  return STFEM_OK;
+  return PR::diagonal(prm, st);
 }
 
 int stfem_st_vmult(stfem_ctx *c, int nrows, int ncols, const double *alpha, const double *beta,
@@ -777,7 +764,7 @@ int stfem_st_diagonal(stfem_ctx *c, int n, const double *alpha, const double *be
 {
   if (!c || !alpha || !beta || !diag || n < 1 || diag->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   if (diag->nb != n) return STFEM_ERR_SHAPE_MISMATCH;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // diag K and diag M (or their guarded inverses) once, then one linear combination per block
   stfem_vec *dk = nullptr, *dm = nullptr;
@@ -794,9 +781,10 @@ int stfem_st_diagonal(stfem_ctx *c, int n, const double *alpha, const double *be
       hipLaunchKernelGGL(lincomb_kernel<T>, dim3(grid), dim3(256), 0, st, c->ndofs, T(a), static_cast<const T *>(dk->blk[0]), T(b),
                          static_cast<const T *>(dm->blk[0]), static_cast<T *>(diag->blk[i]));
     });
-    if (hipGetLastError() != hipSuccess) rc = STFEM_ERR_HIP;
+    rc = stfem_launch_end("lincomb_kernel");
   }
-  if (hipStreamSynchronize(st) != hipSuccess && rc == STFEM_OK) rc = STFEM_ERR_HIP; // the temporaries go away below
+  const hipError_t sync = hipStreamSynchronize(st); // the temporaries go away below
+  if (sync != hipSuccess && rc == STFEM_OK) rc = stfem_set_error(STFEM_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(sync));
   stfem_vector_destroy(dk);
   stfem_vector_destroy(dm);
   return rc;

@@ -41,8 +41,6 @@ struct Rccl {
   bool ok = false;
 };
 
-thread_local char g_comm_err[256] = "";
-
 template <class F> bool bind(void *h, const char *name, F &f)
 {
   f = reinterpret_cast<F>(dlsym(h, name));
@@ -92,30 +90,25 @@ struct stfem_comm {
   size_t plane_bytes = 0; // of all blocks
 };
 
-#define COMM_NCCL(call)                                                                   \
-  do {                                                                                    \
-    ncclResult_t r_ = (call);                                                             \
-    if (r_ != ncclSuccess) {                                                              \
-      snprintf(g_comm_err, sizeof(g_comm_err), "%s: %s", #call, rccl().GetErrorString(r_)); \
-      return STFEM_ERR_COMM;                                                              \
-    }                                                                                     \
+#define COMM_NCCL(call)                                                                                               \
+  do {                                                                                                                \
+    ncclResult_t r_ = (call);                                                                                         \
+    if (r_ != ncclSuccess) return stfem_set_error(STFEM_ERR_COMM, "%s: %s", #call, rccl().GetErrorString(r_));        \
   } while (0)
 
 // inside ncclGroupStart / GroupEnd: a failed call still closes the group (an open group would swallow every later
 // RCCL call of this thread) before the error is returned
-#define COMM_NCCL_IN_GROUP(call)                                                          \
-  do {                                                                                    \
-    ncclResult_t r_ = (call);                                                             \
-    if (r_ != ncclSuccess) {                                                              \
-      snprintf(g_comm_err, sizeof(g_comm_err), "%s: %s", #call, rccl().GetErrorString(r_)); \
-      (void)rccl().GroupEnd();                                                            \
-      return STFEM_ERR_COMM;                                                              \
-    }                                                                                     \
+#define COMM_NCCL_IN_GROUP(call)                                                                                      \
+  do {                                                                                                                \
+    ncclResult_t r_ = (call);                                                                                         \
+    if (r_ != ncclSuccess) {                                                                                          \
+      (void)rccl().GroupEnd();                                                                                        \
+      return stfem_set_error(STFEM_ERR_COMM, "%s: %s", #call, rccl().GetErrorString(r_));                             \
+    }                                                                                                                 \
   } while (0)
 
 extern "C" {
 
-const char *stfem_comm_last_error(void) { return g_comm_err; }
 
 int stfem_comm_get_unique_id(void *id)
 {
@@ -123,8 +116,7 @@ int stfem_comm_get_unique_id(void *id)
   static_assert(STFEM_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
   if (!rccl().ok) {
     const char *why = dlerror(); // (a second call returns NULL)
-    snprintf(g_comm_err, sizeof(g_comm_err), "librccl.so not found: %s", why ? why : "");
-    return STFEM_ERR_UNSUPPORTED;
+    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "librccl.so not found: %s", why ? why : "");
   }
   ncclUniqueId u;
   COMM_NCCL(rccl().GetUniqueId(&u));
@@ -136,14 +128,11 @@ int stfem_comm_create(const void *id, int rank, int world, int device, stfem_com
 {
   if (!id || !out || world < 1 || rank < 0 || rank >= world) return STFEM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (!rccl().ok) {
-    snprintf(g_comm_err, sizeof(g_comm_err), "librccl.so not found");
-    return STFEM_ERR_UNSUPPORTED;
-  }
+  if (!rccl().ok) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "librccl.so not found");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return STFEM_ERR_NO_DEVICE;
   if (device < 0 || device >= ndev) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_comm_err, hipSetDevice(device));
+  STFEM_TRY(hipSetDevice(device));
   stfem_comm *c = new (std::nothrow) stfem_comm;
   if (!c) return STFEM_ERR_OUT_OF_MEMORY;
   c->rank = rank; c->world = world; c->device = device;
@@ -151,16 +140,16 @@ int stfem_comm_create(const void *id, int rank, int world, int device, stfem_com
   std::memcpy(u.internal, id, NCCL_UNIQUE_ID_BYTES);
   ncclResult_t r = rccl().CommInitRank(&c->comm, world, u, rank);
   if (r != ncclSuccess) {
-    snprintf(g_comm_err, sizeof(g_comm_err), "ncclCommInitRank: %s", rccl().GetErrorString(r));
     delete c;
-    return STFEM_ERR_COMM;
+    return stfem_set_error(STFEM_ERR_COMM, "ncclCommInitRank: %s", rccl().GetErrorString(r));
   }
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->packed, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->arrived, hipEventDisableTiming) != hipSuccess ||
-      hipMalloc(&c->d_red, sizeof(double)) != hipSuccess) {
+  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->packed, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->arrived, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipMalloc(&c->d_red, sizeof(double));
+  if (e != hipSuccess) {
     stfem_comm_destroy(c);
-    return STFEM_ERR_HIP;
+    return stfem_set_error(STFEM_ERR_HIP, "communicator stream, events and buffer: %s", hipGetErrorString(e));
   }
   *out = c;
   return STFEM_OK;
@@ -203,8 +192,8 @@ static int plane_geometry(stfem_ctx *ctx, const stfem_vec *v, size_t &plane_byte
 static int ensure_buffers(stfem_comm *c, size_t plane_bytes)
 {
   if (c->buf_bytes >= 4 * plane_bytes) return STFEM_OK;
-  STFEM_TRY(g_comm_err, hipStreamSynchronize(c->stream));
-  if (c->buf) STFEM_TRY(g_comm_err, hipFree(c->buf));
+  STFEM_TRY(hipStreamSynchronize(c->stream));
+  if (c->buf) STFEM_TRY(hipFree(c->buf));
   c->buf = nullptr;
   c->buf_bytes = 0;
   if (hipMalloc(&c->buf, 4 * plane_bytes) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
@@ -242,15 +231,15 @@ int stfem_halo_begin_split(stfem_comm *c, stfem_ctx *ctx_lo, stfem_vec *v_lo, st
     c->pending = true;
     return STFEM_OK;
   }
-  STFEM_TRY(g_comm_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   if ((rc = ensure_buffers(c, pb)) != STFEM_OK) return rc;
   char *ts = static_cast<char *>(c->buf), *bs = ts + pb, *tr = bs + pb, *br = tr + pb;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // this rank's partial sums of its two interface planes
   if (upper >= 0 && (rc = stfem_plane_pack(ctx_hi, v_hi, nz - 1, ts, st)) != STFEM_OK) return rc;
   if (lower >= 0 && (rc = stfem_plane_pack(ctx_lo, v_lo, 0, bs, st)) != STFEM_OK) return rc;
-  STFEM_TRY(g_comm_err, hipEventRecord(c->packed, st));
-  STFEM_TRY(g_comm_err, hipStreamWaitEvent(c->stream, c->packed, 0));
+  STFEM_TRY(hipEventRecord(c->packed, st));
+  STFEM_TRY(hipStreamWaitEvent(c->stream, c->packed, 0));
   const ncclDataType_t dt = stfem_ctx_precision(ctx) ? ncclFloat : ncclDouble;
   const size_t count = pb / (stfem_ctx_precision(ctx) ? sizeof(float) : sizeof(double));
   COMM_NCCL(rccl().GroupStart());
@@ -263,7 +252,7 @@ int stfem_halo_begin_split(stfem_comm *c, stfem_ctx *ctx_lo, stfem_vec *v_lo, st
     COMM_NCCL_IN_GROUP(rccl().Recv(br, count, dt, lower, c->comm, c->stream));
   }
   COMM_NCCL(rccl().GroupEnd());
-  STFEM_TRY(g_comm_err, hipEventRecord(c->arrived, c->stream));
+  STFEM_TRY(hipEventRecord(c->arrived, c->stream));
   c->lower = lower; c->upper = upper; c->plane_bytes = pb; // (only a successful begin leaves an exchange pending)
   c->pending = true;
   return STFEM_OK;
@@ -278,15 +267,15 @@ int stfem_halo_end(stfem_ctx *ctx, stfem_comm *c, stfem_vec *v, void *stream)
   int nz;
   int rc = plane_geometry(ctx, v, pb, nz);
   if (rc != STFEM_OK || pb != c->plane_bytes) return STFEM_ERR_SHAPE_MISMATCH;
-  STFEM_TRY(g_comm_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  STFEM_TRY(g_comm_err, hipStreamWaitEvent(st, c->arrived, 0));
+  STFEM_TRY(hipStreamWaitEvent(st, c->arrived, 0));
   char *tr = static_cast<char *>(c->buf) + 2 * pb, *br = tr + pb;
   if (c->upper >= 0 && (rc = stfem_plane_unpack(ctx, v, nz - 1, tr, 1, st)) != STFEM_OK) return rc;
   if (c->lower >= 0 && (rc = stfem_plane_unpack(ctx, v, 0, br, 1, st)) != STFEM_OK) return rc;
   // the buffers are reused by the next exchange: it must not start before these adds have read them
-  STFEM_TRY(g_comm_err, hipEventRecord(c->packed, st));
-  STFEM_TRY(g_comm_err, hipStreamWaitEvent(c->stream, c->packed, 0));
+  STFEM_TRY(hipEventRecord(c->packed, st));
+  STFEM_TRY(hipStreamWaitEvent(c->stream, c->packed, 0));
   return STFEM_OK;
 }
 
@@ -299,25 +288,25 @@ int stfem_ghost_update(stfem_ctx *ctx, stfem_comm *c, stfem_vec *v, int lower, i
   int nz;
   int rc = plane_geometry(ctx, v, pb, nz);
   if (rc != STFEM_OK) return rc;
-  STFEM_TRY(g_comm_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   if ((rc = ensure_buffers(c, pb)) != STFEM_OK) return rc;
   char *bs = static_cast<char *>(c->buf) + pb, *tr = bs + pb;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // the owner of an interface plane is the upper rank (its bottom plane); the lower rank's top plane is the ghost
   if (lower >= 0 && (rc = stfem_plane_pack(ctx, v, 0, bs, st)) != STFEM_OK) return rc;
-  STFEM_TRY(g_comm_err, hipEventRecord(c->packed, st));
-  STFEM_TRY(g_comm_err, hipStreamWaitEvent(c->stream, c->packed, 0));
+  STFEM_TRY(hipEventRecord(c->packed, st));
+  STFEM_TRY(hipStreamWaitEvent(c->stream, c->packed, 0));
   const ncclDataType_t dt = stfem_ctx_precision(ctx) ? ncclFloat : ncclDouble;
   const size_t count = pb / (stfem_ctx_precision(ctx) ? sizeof(float) : sizeof(double));
   COMM_NCCL(rccl().GroupStart());
   if (lower >= 0) COMM_NCCL_IN_GROUP(rccl().Send(bs, count, dt, lower, c->comm, c->stream));
   if (upper >= 0) COMM_NCCL_IN_GROUP(rccl().Recv(tr, count, dt, upper, c->comm, c->stream));
   COMM_NCCL(rccl().GroupEnd());
-  STFEM_TRY(g_comm_err, hipEventRecord(c->arrived, c->stream));
-  STFEM_TRY(g_comm_err, hipStreamWaitEvent(st, c->arrived, 0));
+  STFEM_TRY(hipEventRecord(c->arrived, c->stream));
+  STFEM_TRY(hipStreamWaitEvent(st, c->arrived, 0));
   if (upper >= 0 && (rc = stfem_plane_unpack(ctx, v, nz - 1, tr, 0, st)) != STFEM_OK) return rc;
-  STFEM_TRY(g_comm_err, hipEventRecord(c->packed, st));
-  STFEM_TRY(g_comm_err, hipStreamWaitEvent(c->stream, c->packed, 0));
+  STFEM_TRY(hipEventRecord(c->packed, st));
+  STFEM_TRY(hipStreamWaitEvent(c->stream, c->packed, 0));
   return STFEM_OK;
 }
 
@@ -332,11 +321,11 @@ int stfem_dot_global(stfem_ctx *ctx, stfem_comm *c, const stfem_vec *a, const st
     *out = local;
     return STFEM_OK;
   }
-  STFEM_TRY(g_comm_err, hipSetDevice(c->device));
-  STFEM_TRY(g_comm_err, hipMemcpyAsync(c->d_red, &local, sizeof(double), hipMemcpyHostToDevice, c->stream));
+  STFEM_TRY(hipSetDevice(c->device));
+  STFEM_TRY(hipMemcpyAsync(c->d_red, &local, sizeof(double), hipMemcpyHostToDevice, c->stream));
   COMM_NCCL(rccl().AllReduce(c->d_red, c->d_red, 1, ncclDouble, ncclSum, c->comm, c->stream));
-  STFEM_TRY(g_comm_err, hipMemcpyAsync(out, c->d_red, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  STFEM_TRY(g_comm_err, hipStreamSynchronize(c->stream));
+  STFEM_TRY(hipMemcpyAsync(out, c->d_red, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  STFEM_TRY(hipStreamSynchronize(c->stream));
   return STFEM_OK;
 }
 

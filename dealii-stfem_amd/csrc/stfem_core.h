@@ -11,6 +11,7 @@
 // cells: 13, see cell_core_general; the reference needs 2 x 12 per input block).
 #pragma once
 #include "stfem_device.h"
+#include "stfem_hip_check.h"
 #include "stfem_kernels.h"
 
 #include <hip/hip_runtime.h>

@@ -20,8 +20,6 @@
 #include <cstring>
 #include <vector>
 
-thread_local char g_driver_err[256] = "";
-
 namespace {
 
 // vertices of the structured block on the host (the context keeps them for general meshes only)
@@ -260,7 +258,7 @@ struct GeomUpload {
     const size_t ow = all.size();
     all.insert(all.end(), wq.begin(), wq.end());
     if (hipMalloc(&d, all.size() * sizeof(double)) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
-    if (hipMemcpy(d, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return STFEM_ERR_HIP;
+    STFEM_TRY(hipMemcpy(d, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice));
     g.vertices = d; g.S = d + oS; g.D = d + oD; g.xq = d + ox; g.wq = d + ow;
     g.ncx = c->nc[0]; g.ncy = c->nc[1]; g.ncz = c->nc[2]; g.nx = c->nd[0]; g.ny = c->nd[1];
     g.p = c->p; g.nq = nq; g.dmask = c->dmask;
@@ -276,8 +274,6 @@ struct GeomUpload {
 } // namespace
 
 extern "C" {
-
-const char *stfem_driver_last_error(void) { return g_driver_err; }
 
 int stfem_support_points(const stfem_ctx *c, double *out)
 {
@@ -316,7 +312,7 @@ int stfem_quadrature_points(const stfem_ctx *c, int nq, double *out)
 static int integrate_rhs_impl(stfem_ctx *c, int nq, const double *f_at_points, const ProductFn pf, stfem_vec *dst, int block, void *stream)
 {
   if (!c || (!f_at_points && !pf.on) || !dst || dst->ctx != c || block < 0 || block >= dst->nb || nq < 1 || nq > 8) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_driver_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   GeomUpload geo;
   int rc = geo.build(c, nq);
@@ -330,23 +326,20 @@ static int integrate_rhs_impl(stfem_ctx *c, int nq, const double *f_at_points, c
   }
   if (e == hipSuccess) e = hipMemsetAsync(dst->blk[block], 0, size_t(c->ndofs) * c->es, st);
   const size_t lds = size_t(nq) * nq * nq * sizeof(double);
-  (void)hipGetLastError(); // an error some earlier, unrelated call left behind is not this call's
-  for (int par = 0; par < 8 && e == hipSuccess; ++par) { // fixed sequence on one stream: see the kernel
+  stfem_launch_begin();
+  for (int par = 0; par < 8 && e == hipSuccess && rc == STFEM_OK; ++par) { // fixed sequence on one stream: see the kernel
     const long long nblk = (long long)((c->nc[0] - (par & 1) + 1) / 2) * ((c->nc[1] - ((par >> 1) & 1) + 1) / 2) * ((c->nc[2] - (par >> 2) + 1) / 2);
     if (nblk == 0) continue;
     stfem_by_prec(c, [&](auto t) {
       using T = decltype(t);
       hipLaunchKernelGGL(integrate_rhs_kernel<T>, dim3((unsigned)nblk), dim3(256), lds, st, geo.g, d_f, static_cast<T *>(dst->blk[block]), pf, par);
     });
-    e = hipGetLastError();
+    rc = stfem_launch_end("integrate_rhs_kernel");
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && rc == STFEM_OK) e = hipStreamSynchronize(st);
   if (d_f) (void)hipFree(d_f);
-  if (e != hipSuccess) {
-    snprintf(g_driver_err, sizeof(g_driver_err), "stfem_integrate_rhs: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  return STFEM_OK;
+  if (e != hipSuccess) return stfem_set_error(STFEM_ERR_HIP, "stfem_integrate_rhs: %s", hipGetErrorString(e));
+  return rc;
 }
 
 int stfem_integrate_rhs(stfem_ctx *c, int nq, const double *f_at_points, stfem_vec *dst, int block, void *stream)
@@ -363,7 +356,7 @@ static int integrate_difference_impl(stfem_ctx *c, int nq, const stfem_vec *u, i
 {
   if (!c || !u || u->ctx != c || block < 0 || block >= u->nb || (!exact_at_points && !pf.on) || !out || nq < 1 || nq > 8)
     return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_driver_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   GeomUpload geo;
   int rc = geo.build(c, nq);
@@ -387,21 +380,19 @@ static int integrate_difference_impl(stfem_ctx *c, int nq, const stfem_vec *u, i
   if (e == hipSuccess) {
     const int n = c->p + 1;
     const size_t lds = (size_t(n) * n * n + 3 * 256) * sizeof(double);
-    (void)hipGetLastError();
+    stfem_launch_begin();
     stfem_by_prec(c, [&](auto t) {
       using T = decltype(t);
       hipLaunchKernelGGL(integrate_difference_kernel<T>, dim3((unsigned)c->ncells), dim3(256), lds, st, geo.g,
                          static_cast<const T *>(u->blk[block]), d_e, d_g, d_out, pf);
     });
-    e = hipGetLastError();
+    rc = stfem_launch_end("integrate_difference_kernel");
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_out, part.size() * sizeof(double), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && rc == STFEM_OK) e = hipMemcpyAsync(part.data(), d_out, part.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == STFEM_OK) e = hipStreamSynchronize(st);
   cleanup();
-  if (e != hipSuccess) {
-    snprintf(g_driver_err, sizeof(g_driver_err), "stfem_integrate_difference: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
+  if (e != hipSuccess) return stfem_set_error(STFEM_ERR_HIP, "stfem_integrate_difference: %s", hipGetErrorString(e));
+  if (rc != STFEM_OK) return rc;
   out[0] = out[1] = out[2] = 0.0;
   for (int64_t cell = 0; cell < c->ncells; ++cell) {
     out[0] += part[cell * 3];

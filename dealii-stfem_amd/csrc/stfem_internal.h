@@ -6,23 +6,13 @@
 #include "../../include/stfem.h"
 
 #include "host_tables.h"
+#include "stfem_hip_check.h" // STFEM_TRY, stfem_launch_begin / _end, stfem_set_error
 
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <vector>
-
-// Returns STFEM_ERR_HIP from the calling function if a HIP runtime call fails, leaving "<call>: <reason>" in `err`, the
-// thread-local char array behind the calling unit's exported *_last_error accessor.
-#define STFEM_TRY(err, call)                                                \
-  do {                                                                      \
-    hipError_t e_ = (call);                                                 \
-    if (e_ != hipSuccess) {                                                 \
-      snprintf(err, sizeof(err), "%s: %s", #call, hipGetErrorString(e_));   \
-      return STFEM_ERR_HIP;                                                 \
-    }                                                                       \
-  } while (0)
 
 namespace stfem {
 // stfem_ctx::d_scratch (always double): the results of the reductions, then the stage-1 partial sums of up to DOT_VECS inner
@@ -103,12 +93,6 @@ struct stfem_stokes_desc {
 int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *out);
 
 #pragma GCC visibility push(hidden)
-// the text behind stfem_last_hip_error (stfem_capi.hip; written by stfem_vector.hip too) and behind stfem_driver_last_error
-// (stfem_driver.hip; written by the vector arithmetic that came from there) and behind stfem_transfer_last_error
-// (stfem_transfer.hip; written by stfem_vector_convert and by the stream and graph calls of stfem_stream.hip too)
-extern thread_local char g_hip_error[256], g_driver_err[256], g_transfer_err[256];
-int hip_fail(hipError_t e, const char *what); // "<what>: <reason>" to g_hip_error, returns STFEM_ERR_HIP
-
 // stfem_vanka.hip: vanka_invert_kernel<double> on `count` m x m matrices at B (row-major, destroyed), the inverses in the apply's
 // layout [kpad][mpad] from block cell0 of out; *singular (device) is set to 1 by a matrix without a pivot.  `stream`: a hipStream_t.
 int stfem_vanka_invert_launch(double *B, double *out, int m, int mpad, int kpad, long long cell0, unsigned count, int *singular, void *stream);
@@ -122,10 +106,10 @@ struct stokes_cell_vanka_desc {
 struct stokes_cell_vanka;
 // row table: nblk-block rows -> (vector | variable << 8, element offset from the cell's first DoF of the variable), m entries of two ints
 int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &d, const int *rowtab_xy, const double *const *lin,
-                             stokes_cell_vanka **out, char (&err)[256]);
-int stokes_cell_vanka_update(stokes_cell_vanka *v, const double *const *lin, char (&err)[256]);
+                             stokes_cell_vanka **out);
+int stokes_cell_vanka_update(stokes_cell_vanka *v, const double *const *lin);
 int stokes_cell_vanka_setup_batches(const stokes_cell_vanka *v);
 // rows of y = B_c^-1 gather(src) of every cell to the scratch array [cell][mpad], returned in *rows
-int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_blocks, const double **rows, void *stream, char (&err)[256]);
+int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_blocks, const double **rows, void *stream);
 void stokes_cell_vanka_destroy(stokes_cell_vanka *v);
 #pragma GCC visibility pop

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void st_sweep_cart_atomic(const SweepParams pr
 
 template <int P, int NBM> int launch_atomic_t(const SweepParams &prm, hipStream_t st)
 {
-  (void)hipGetLastError(); // drop a stale sticky error of an unrelated earlier call
+  stfem_launch_begin();
   using G = Geometry<P, NBM>;
   const int64_t cells_per_block = int64_t(G::CELLS_PER_WAVE) * G::WAVES;
   const int64_t blocks = (prm.ncells + cells_per_block - 1) / cells_per_block;
@@ -91,7 +91,7 @@ template <int P, int NBM> int launch_atomic_t(const SweepParams &prm, hipStream_
     hipLaunchKernelGGL((st_sweep_cart_atomic<P, NBM, true>), dim3((unsigned)blocks), dim3(256), 0, st, prm);
   else
     hipLaunchKernelGGL((st_sweep_cart_atomic<P, NBM, false>), dim3((unsigned)blocks), dim3(256), 0, st, prm);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return stfem_launch_end("st_sweep_cart_atomic");
 }
 
 } // namespace
@@ -140,10 +140,10 @@ __global__ __launch_bounds__(128) void diagonal_kernel(const DiagParams prm)
 
 int launch_diagonal(const DiagParams &prm, void *stream)
 {
-  (void)hipGetLastError(); // drop a stale sticky error of an unrelated earlier call
+  stfem_launch_begin();
   const int64_t ncells = int64_t(prm.ncx) * prm.ncy * prm.ncz;
   hipLaunchKernelGGL(diagonal_kernel, dim3((unsigned)ncells), dim3(128), 0, static_cast<hipStream_t>(stream), prm);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return stfem_launch_end("diagonal_kernel");
 }
 
 int launch_cart_atomic(int p, const SweepParams &prm, void *stream)

@@ -722,7 +722,7 @@ __global__ __launch_bounds__(256) void st_pencil_fixup(const SweepParams prm, co
 template <int P, int NBM, int TY> int launch_pencil_ty(const SweepParams &prm, const PencilPlan &pp, hipStream_t st)
 {
   using PG = PencilGeom<P, NBM, TY>;
-  (void)hipGetLastError();
+  stfem_launch_begin();
   const bool coef = prm.coef_lap || prm.coef_mass;
   const int nblocks = pp.ntx * pp.ntyw * pp.ntc;
   const int grid = nblocks < pp.grid ? nblocks : pp.grid;
@@ -730,9 +730,8 @@ template <int P, int NBM, int TY> int launch_pencil_ty(const SweepParams &prm, c
   do {                                                                                                            \
     static bool lds_set = false;                                                                                  \
     if (!lds_set) {                                                                                               \
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(&st_sweep_pencil<P, NBM, TY, AA, CC>),               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, int(PG::LDS_BYTES)) != hipSuccess)      \
-        return -3;                                                                                                \
+      STFEM_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&st_sweep_pencil<P, NBM, TY, AA, CC>),         \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, int(PG::LDS_BYTES)));             \
       lds_set = true;                                                                                             \
     }                                                                                                             \
     hipLaunchKernelGGL((st_sweep_pencil<P, NBM, TY, AA, CC>), dim3(grid), dim3(PG::NT), PG::LDS_BYTES, st, prm, pp); \
@@ -742,9 +741,8 @@ template <int P, int NBM, int TY> int launch_pencil_ty(const SweepParams &prm, c
       if (pp.add || coef) return -2;
       static bool lds_set = false;
       if (!lds_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&st_sweep_pencil<P, NBM, TY, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                int(PG::LDS_BYTES)) != hipSuccess)
-          return -3;
+        STFEM_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&st_sweep_pencil<P, NBM, TY, false, false, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(PG::LDS_BYTES)));
         lds_set = true;
       }
       hipLaunchKernelGGL((st_sweep_pencil<P, NBM, TY, false, false, true>), dim3(grid), dim3(PG::NT), PG::LDS_BYTES, st, prm, pp);
@@ -759,15 +757,16 @@ template <int P, int NBM, int TY> int launch_pencil_ty(const SweepParams &prm, c
   // The tile counters are zero on entry: zeroed at allocation and again after every sweep - by the fix-up kernel, or
   // by a memset where there is no fix-up or a launch has failed (counters left at their end values would make every
   // later sweep on this context pull no tile and return with dst unwritten).
-  const bool sweep_ok = hipGetLastError() == hipSuccess;
-  bool fixed_up = false;
-  if (sweep_ok && (pp.ntyw > 1 || pp.ntc > 1)) {
+  const int swept = stfem_launch_end("st_sweep_pencil");
+  if (swept == STFEM_OK && (pp.ntyw > 1 || pp.ntc > 1)) {
     hipLaunchKernelGGL((st_pencil_fixup<P>), dim3(nblocks, prm.nbo, 2), dim3(256), 0, st, prm, pp, NBM, PG::CPW, TY);
-    fixed_up = hipGetLastError() == hipSuccess;
-    if (!fixed_up) (void)hipMemsetAsync(pp.work, 0, 8 * 32 * sizeof(int), st);
-    return fixed_up ? 0 : -3;
+    const int fixed_up = stfem_launch_end("st_pencil_fixup");
+    if (fixed_up != STFEM_OK) (void)hipMemsetAsync(pp.work, 0, 8 * 32 * sizeof(int), st);
+    return fixed_up;
   }
-  if (hipMemsetAsync(pp.work, 0, 8 * 32 * sizeof(int), st) != hipSuccess || !sweep_ok) return -3;
+  const hipError_t reset = hipMemsetAsync(pp.work, 0, 8 * 32 * sizeof(int), st);
+  if (swept != STFEM_OK) return swept; // (its reason stays the recorded one)
+  if (reset != hipSuccess) return stfem_set_error(STFEM_ERR_HIP, "hipMemsetAsync(tile counters): %s", hipGetErrorString(reset));
   return 0;
 }
 

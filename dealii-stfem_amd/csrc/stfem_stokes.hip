@@ -18,7 +18,6 @@
 #include <limits>
 #include <new>
 
-thread_local char g_stokes_err[256] = "";
 static int stokes_lowest_priority()
 {
   int lo = 0, hi = 0; // (numerically highest value = lowest priority)
@@ -42,8 +41,6 @@ static hipStream_t stokes_side_stream(int device)
 
 extern "C" {
 
-const char *stfem_stokes_last_hip_error(void) { return g_stokes_err; }
-
 int stfem_stokes_last_sweep_plan(const stfem_stokes_ctx *c, int32_t out[3])
 {
   if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
@@ -66,13 +63,10 @@ int stfem_stokes_create_ex(const stfem_mesh_desc *mesh, int velocity_degree, int
   int ndev = 0;
   {
     const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0) {
-      snprintf(g_stokes_err, sizeof(g_stokes_err), "hipGetDeviceCount: %s (%d devices)", hipGetErrorString(e), ndev);
-      return STFEM_ERR_NO_DEVICE;
-    }
+    if (e != hipSuccess || ndev == 0) return stfem_set_error(STFEM_ERR_NO_DEVICE, "hipGetDeviceCount: %s (%d devices)", hipGetErrorString(e), ndev);
   }
   if (mesh->device < 0 || mesh->device >= ndev) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_stokes_err, hipSetDevice(mesh->device));
+  STFEM_TRY(hipSetDevice(mesh->device));
   stfem_stokes_ctx *c = new (std::nothrow) stfem_stokes_ctx;
   if (!c) return STFEM_ERR_OUT_OF_MEMORY;
   c->device = mesh->device;
@@ -109,10 +103,11 @@ int stfem_stokes_create_ex(const stfem_mesh_desc *mesh, int velocity_degree, int
     delete c;
     return STFEM_ERR_OUT_OF_MEMORY;
   }
-  if (hipMemcpy(c->d_vertices, v.data(), nv * 3 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+  const hipError_t up = hipMemcpy(c->d_vertices, v.data(), nv * 3 * sizeof(double), hipMemcpyHostToDevice);
+  if (up != hipSuccess) {
     (void)hipFree(c->d_vertices);
     delete c;
-    return STFEM_ERR_HIP;
+    return stfem_set_error(STFEM_ERR_HIP, "vertex upload: %s", hipGetErrorString(up));
   }
   c->h_vertices = v;
   std::memset(&c->bnd, 0, sizeof(c->bnd));
@@ -224,12 +219,13 @@ int stfem_stokes_vector_create(stfem_stokes_ctx *c, int variable, double **devic
 {
   if (!c || !device_out || variable < 0 || variable > 1) return STFEM_ERR_INVALID_ARGUMENT;
   *device_out = nullptr;
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   double *d = nullptr;
   if (hipMalloc(&d, stokes_len(c, variable) * sizeof(double)) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
-  if (hipMemset(d, 0, stokes_len(c, variable) * sizeof(double)) != hipSuccess) {
+  const hipError_t e = hipMemset(d, 0, stokes_len(c, variable) * sizeof(double));
+  if (e != hipSuccess) {
     (void)hipFree(d);
-    return STFEM_ERR_HIP;
+    return stfem_set_error(STFEM_ERR_HIP, "hipMemset(new vector): %s", hipGetErrorString(e));
   }
   *device_out = d;
   return STFEM_OK;
@@ -245,16 +241,16 @@ void stfem_stokes_vector_destroy(stfem_stokes_ctx *c, double *device_vec)
 int stfem_stokes_vector_upload(stfem_stokes_ctx *c, int variable, double *device_vec, const double *host)
 {
   if (!c || !device_vec || !host || variable < 0 || variable > 1) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
-  STFEM_TRY(g_stokes_err, hipMemcpy(device_vec, host, stokes_len(c, variable) * sizeof(double), hipMemcpyHostToDevice));
+  STFEM_TRY(hipSetDevice(c->device));
+  STFEM_TRY(hipMemcpy(device_vec, host, stokes_len(c, variable) * sizeof(double), hipMemcpyHostToDevice));
   return STFEM_OK;
 }
 
 int stfem_stokes_vector_download(stfem_stokes_ctx *c, int variable, const double *device_vec, double *host)
 {
   if (!c || !device_vec || !host || variable < 0 || variable > 1) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
-  STFEM_TRY(g_stokes_err, hipMemcpy(host, device_vec, stokes_len(c, variable) * sizeof(double), hipMemcpyDeviceToHost));
+  STFEM_TRY(hipSetDevice(c->device));
+  STFEM_TRY(hipMemcpy(host, device_vec, stokes_len(c, variable) * sizeof(double), hipMemcpyDeviceToHost));
   return STFEM_OK;
 }
 
@@ -337,7 +333,7 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
       k_u = k_u || (prm.out_u[o] && k.wKu[o][q] != 0.0);
     }
   }
-  (void)hipGetLastError();
+  stfem_launch_begin();
   // ---- 2. out_p (=, +=) sum_q wKp B u_q, beside the velocity sweep (STFEM_STOKES_SERIAL=1: on the caller's stream, after it)
   static const bool serial = [] { const char *e = getenv("STFEM_STOKES_SERIAL"); return e && atoi(e) != 0; }();
   // The fork onto the side stream - ONE per device, shared by every Stokes context: with a stream per context (a multigrid has one
@@ -357,7 +353,7 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
   const bool forked = any_p && !serial && c->side && !grad_in_sweep && (long long)k.ncx * k.ncy * k.ncz >= fork_min_cells;
   // (the fork point is here, before the sweep; the side stream's commands are enqueued after the sweep's so that the sweep's
   // persistent workgroups - exactly the resident number - are placed first and the divergence kernel fills what is left)
-  if (forked) STFEM_TRY(g_stokes_err, hipEventRecord(c->ev_fork, st));
+  if (forked) STFEM_TRY(hipEventRecord(c->ev_fork, st));
   bool grad_done = false; // (a sweep that has no gradient hook leaves the term to step 3)
   // ---- 1. velocity blocks: out_u[o] (=, +=) sum_q (nu wKu K + wM M) u_q, component by component as scalar FE_Q(2) systems
   // (one launch with the three components as blocks when there is a single source and destination)
@@ -400,28 +396,20 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
       }
       if (vd) stfem_vector_destroy(vd);
       if (vs) stfem_vector_destroy(vs);
-      if (rc != STFEM_OK) {
-        snprintf(g_stokes_err, sizeof(g_stokes_err), "velocity sweep: status %d (%s)", rc, stfem_last_hip_error());
-        return rc;
-      }
+      if (rc != STFEM_OK) return stfem_set_error(rc, "velocity sweep: status %d (%s)", rc, stfem_last_error());
     }
   }
   if (forked) {
-    STFEM_TRY(g_stokes_err, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    STFEM_TRY(hipStreamWaitEvent(c->side, c->ev_fork, 0));
     stokes_div_launch(k, c->Np, c->side);
-    STFEM_TRY(g_stokes_err, hipEventRecord(c->ev_join, c->side));
+    STFEM_TRY(hipEventRecord(c->ev_join, c->side));
   }
   // ---- 3. out_u -= sum_q wKu B^T p_q
   c->last_grad_in_sweep = grad_done;
   if (k_u && !grad_done) stokes_grad_launch(k, st);
-  if (forked) STFEM_TRY(g_stokes_err, hipStreamWaitEvent(st, c->ev_join, 0));
+  if (forked) STFEM_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
   else if (any_p) stokes_div_launch(k, c->Np, st);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_stokes_err, sizeof(g_stokes_err), "stokes coupling kernels: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  return STFEM_OK;
+  return stfem_launch_end("stokes coupling kernels");
 }
 
 // In this fixed order: the linear part (Kronecker path or cell kernel), its boundary launches, then - with a convection mode - the
@@ -474,7 +462,7 @@ int stfem_stokes_vmult_convection(stfem_stokes_ctx *c, int mode, double *dst_u, 
     return STFEM_ERR_INVALID_ARGUMENT;
   if (dst_u == src_u || dst_p == src_p) return STFEM_ERR_ALIAS;
   if (mode != STFEM_CONVECTION_NONE && (lin_u == dst_u || lin_u == dst_p)) return STFEM_ERR_ALIAS;
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
   launch.add_source(src_u, src_p, lin_u);
   const double one = 1.0, zero = 0.0;
@@ -487,7 +475,7 @@ int stfem_stokes_mass_vmult(stfem_stokes_ctx *c, double *dst_u, const double *sr
 {
   if (!c || !dst_u || !src_u) return STFEM_ERR_INVALID_ARGUMENT;
   if (dst_u == src_u) return STFEM_ERR_ALIAS;
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   StokesLaunch launch(c, static_cast<hipStream_t>(stream));
   launch.add_source(src_u, nullptr);
   const double one = 1.0, zero = 0.0;
@@ -529,7 +517,7 @@ int stfem_stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timest
       for (int it = 0; it < ns; ++it)
         for (int d = 0; d < nt; ++d)
           if (dst_blocks[j] == lin_blocks[index(it, 0, d)]) return STFEM_ERR_ALIAS;
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // dst = 0.0 (operators.h:833): the first launch that reaches a block overwrites it; blocks no launch
   // reaches are zeroed at the end
@@ -562,8 +550,8 @@ int stfem_stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timest
   }
   for (int it = 0; it < ns; ++it)
     for (int d = 0; d < nt; ++d) {
-      if (!written[index(it, 0, d)]) STFEM_TRY(g_stokes_err, hipMemsetAsync(dst_blocks[index(it, 0, d)], 0, sizeof(double) * 3 * c->Nu, st));
-      if (!written[index(it, 1, d)]) STFEM_TRY(g_stokes_err, hipMemsetAsync(dst_blocks[index(it, 1, d)], 0, sizeof(double) * c->Np, st));
+      if (!written[index(it, 0, d)]) STFEM_TRY(hipMemsetAsync(dst_blocks[index(it, 0, d)], 0, sizeof(double) * 3 * c->Nu, st));
+      if (!written[index(it, 1, d)]) STFEM_TRY(hipMemsetAsync(dst_blocks[index(it, 1, d)], 0, sizeof(double) * c->Np, st));
     }
   return STFEM_OK;
 }
@@ -594,7 +582,7 @@ int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, in
     if (dst_blocks[j] == src_u || dst_blocks[j] == src_p) return STFEM_ERR_ALIAS;
     if (mode != STFEM_CONVECTION_NONE && dst_blocks[j] == lin_u) return STFEM_ERR_ALIAS;
   }
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
   launch.add_source(src_u, src_p, lin_u);
   for (int it = 0; it < ns; ++it)

@@ -244,18 +244,13 @@ int stokes_boundary_launch(stfem_stokes_ctx *c, StokesParams &prm, const double 
   const long long items = bp.foff[6];
   if (items == 0) return STFEM_OK;
   const unsigned grid = (unsigned)std::min<long long>((items + 7) / 8, 4ll * c->n_cu);
-  (void)hipGetLastError();
+  stfem_launch_begin();
   for (int colour = 0; colour < 8; ++colour) {
     prm.colour = colour;
     if (prm.nsrc > 1) hipLaunchKernelGGL(stokes_boundary_kernel<true>, dim3(grid), dim3(256), 0, st, prm, bp);
     else hipLaunchKernelGGL(stokes_boundary_kernel<false>, dim3(grid), dim3(256), 0, st, prm, bp);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_stokes_err, sizeof(g_stokes_err), "stokes_boundary_kernel: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  return STFEM_OK;
+  return stfem_launch_end("stokes_boundary_kernel");
 }
 
 extern "C" {
@@ -331,17 +326,17 @@ int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *c, const double *g_at_face_points
   if (!c || !g_at_face_points || !dst_u || !dst_p) return STFEM_ERR_INVALID_ARGUMENT;
   const size_t npts = size_t(stfem_stokes_n_face_points(c));
   if (npts == 0) return STFEM_OK; // no Dirichlet functions: vmult does nothing (operators.h:1836)
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (c->g_points < npts) {
-    if (c->d_g) STFEM_TRY(g_stokes_err, hipFree(c->d_g));
+    if (c->d_g) STFEM_TRY(hipFree(c->d_g));
     c->d_g = nullptr;
     c->g_points = 0;
     if (hipMalloc(&c->d_g, npts * 3 * sizeof(double)) != hipSuccess) return STFEM_ERR_OUT_OF_MEMORY;
     c->g_points = npts;
   }
-  STFEM_TRY(g_stokes_err, hipMemcpyAsync(c->d_g, g_at_face_points, npts * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  STFEM_TRY(g_stokes_err, hipStreamSynchronize(st)); // (the caller's host array may go away)
+  STFEM_TRY(hipMemcpyAsync(c->d_g, g_at_face_points, npts * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  STFEM_TRY(hipStreamSynchronize(st)); // (the caller's host array may go away)
   StokesParams prm = c->base; // no source: the data takes its place
   prm.nsrc = 1;
   prm.nout = 1;

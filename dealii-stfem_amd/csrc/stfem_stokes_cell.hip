@@ -359,7 +359,7 @@ int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st)
 {
   const int which = (prm.pdg ? 4 : 0) + (prm.nsrc > 1 ? 2 : 0) + (prm.cart ? 1 : 0);
   if (prm.nsrc < 1 || prm.nsrc > MAXSRC || prm.nout > (prm.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiation's bounds)
-  (void)hipGetLastError();
+  stfem_launch_begin();
   for (int colour = 0; colour < 8; ++colour) { // ascending: see store_u / store_p
     const long long n = (long long)((c->nc[0] - (colour & 1) + 1) / 2) * ((c->nc[1] - ((colour >> 1) & 1) + 1) / 2) *
                         ((c->nc[2] - (colour >> 2) + 1) / 2);
@@ -384,10 +384,5 @@ int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st)
     void *args[] = {(void *)&prm};
     (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_stokes_err, sizeof(g_stokes_err), "stokes_cell_kernel: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  return STFEM_OK;
+  return stfem_launch_end("stokes_cell_kernel");
 }

@@ -325,7 +325,7 @@ int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double
   const void *kerns[4] = {(const void *)stokes_cip_kernel<false, false>, (const void *)stokes_cip_kernel<true, false>,
                           (const void *)stokes_cip_kernel<false, true>, (const void *)stokes_cip_kernel<true, true>};
   const void *kern = kerns[which];
-  (void)hipGetLastError();
+  stfem_launch_begin();
   for (int colour = 0; colour < 8; ++colour) { // ascending, like every colour sequence of the operator
     const long long n = (long long)((c->nc[0] - (colour & 1) + 1) / 2) * ((c->nc[1] - ((colour >> 1) & 1) + 1) / 2) *
                         ((c->nc[2] - (colour >> 2) + 1) / 2);
@@ -335,12 +335,7 @@ int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double
     void *args[] = {(void *)&k};
     (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_stokes_err, sizeof(g_stokes_err), "stokes_cip_kernel: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  return STFEM_OK;
+  return stfem_launch_end("stokes_cip_kernel");
 }
 
 extern "C" {
@@ -358,7 +353,7 @@ int stfem_stokes_cip_add(stfem_stokes_ctx *c, double *dst_u, const double *src_u
 {
   if (!c || !dst_u || !src_u || !weight_u || !std::isfinite(delta0)) return STFEM_ERR_INVALID_ARGUMENT;
   if (dst_u == src_u || dst_u == weight_u) return STFEM_ERR_ALIAS;
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   StokesParams prm = c->base; // one source, one destination, weight 1: the term by itself
   prm.nsrc = 1; prm.nout = 1;
   prm.us[0] = src_u; prm.ps[0] = nullptr;

@@ -455,7 +455,7 @@ int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const
   static int resident_of[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int &resident = resident_of[which];
   if (resident < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, 256, 0) != hipSuccess || resident < 1)) resident = 2;
-  (void)hipGetLastError();
+  stfem_launch_begin();
   for (int colour = 0; colour < 8; ++colour) { // ascending, like every colour sequence of the operator
     const long long n = (long long)((c->nc[0] - (colour & 1) + 1) / 2) * ((c->nc[1] - ((colour >> 1) & 1) + 1) / 2) *
                         ((c->nc[2] - (colour >> 2) + 1) / 2);
@@ -474,10 +474,5 @@ int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const
       else hipLaunchKernelGGL(stokes_inflow_kernel<false>, dim3(grid), dim3(256), 0, st, k);
     }
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_stokes_err, sizeof(g_stokes_err), "stokes_convection_kernel: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  return STFEM_OK;
+  return stfem_launch_end("stokes_convection_kernel");
 }

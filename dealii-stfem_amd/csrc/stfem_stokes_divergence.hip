@@ -162,7 +162,7 @@ extern "C" {
 int stfem_stokes_divergence(stfem_stokes_ctx *c, const double *u, double *cell_out, double *total, void *stream)
 {
   if (!c || !u || !total) return STFEM_ERR_INVALID_ARGUMENT; // (before anything touches the device)
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long ncells = (long long)c->nc[0] * c->nc[1] * c->nc[2];
   if (!c->d_div) {
@@ -181,18 +181,14 @@ int stfem_stokes_divergence(stfem_stokes_ctx *c, const double *u, double *cell_o
   k.Nu = c->Nu;
   for (int i = 0; i < 9; ++i) { k.Su[i] = c->base.Su[i]; k.Du[i] = c->base.Du[i]; }
   for (int i = 0; i < 3; ++i) { k.xq[i] = c->base.xq[i]; k.wq[i] = c->base.wq[i]; }
-  (void)hipGetLastError();
+  stfem_launch_begin();
   const unsigned grid = (unsigned)std::min<long long>((ncells + 7) / 8, 4ll * c->n_cu);
   hipLaunchKernelGGL(stokes_divergence_kernel, dim3(grid), dim3(256), 0, st, k);
   hipLaunchKernelGGL(stokes_divergence_finish, dim3(1), dim3(256), 0, st, ncells, (const double *)k.cell_out, c->d_div + ncells);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_stokes_err, sizeof(g_stokes_err), "stokes_divergence_kernel: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
+  if (const int rc = stfem_launch_end("stokes_divergence_kernel")) return rc;
   double sum = 0.0;
-  STFEM_TRY(g_stokes_err, hipMemcpyAsync(&sum, c->d_div + ncells, sizeof(double), hipMemcpyDeviceToHost, st));
-  STFEM_TRY(g_stokes_err, hipStreamSynchronize(st));
+  STFEM_TRY(hipMemcpyAsync(&sum, c->d_div + ncells, sizeof(double), hipMemcpyDeviceToHost, st));
+  STFEM_TRY(hipStreamSynchronize(st));
   *total = std::sqrt(sum);
   return STFEM_OK;
 }

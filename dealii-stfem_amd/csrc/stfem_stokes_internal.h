@@ -169,12 +169,11 @@ __device__ __forceinline__ void wave_fence()
 }
 
 #pragma GCC visibility push(hidden) // (the library exports what include/stfem.h declares)
-extern thread_local char g_stokes_err[256]; // stfem_stokes_last_hip_error
 
 // The eight colour launches of the cell kernel (general meshes; stfem_stokes_cell.hip)
 int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st);
-// The coupling kernels (stfem_stokes_coupling.hip): out_u -= sum_s wKu B^T p_s; out_p (=, +=) sum_s wKp B u_s.  They report through
-// hipGetLastError.
+// The coupling kernels (stfem_stokes_coupling.hip): out_u -= sum_s wKu B^T p_s; out_p (=, +=) sum_s wKp B u_s.  A failed launch is
+// left to the caller's stfem_launch_end (stokes_cart_launch).
 void stokes_grad_launch(const CouplingParams &k, hipStream_t st);
 void stokes_div_launch(const CouplingParams &k, long long Np, hipStream_t st);
 // The eight colour launches of the boundary kernel (stfem_stokes_boundary.hip); d_g: the Dirichlet data of the rhs mode, or nullptr

@@ -188,13 +188,13 @@ int stfem_stokes_pressure_difference(stfem_stokes_ctx *c, int nq, const double *
 {
   if (!c || !p || !exact_at_points || !out || nq < 1 || nq > 8) return STFEM_ERR_INVALID_ARGUMENT;
   if (!c->base.cart) return STFEM_ERR_UNSUPPORTED;
-  STFEM_TRY(g_stokes_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long ncells = (long long)c->nc[0] * c->nc[1] * c->nc[2];
   const size_t npts = size_t(ncells) * nq * nq * nq;
   if (c->pq_points < npts) {
-    if (c->d_pq) STFEM_TRY(g_stokes_err, hipFree(c->d_pq));
-    if (c->d_pred) STFEM_TRY(g_stokes_err, hipFree(c->d_pred));
+    if (c->d_pq) STFEM_TRY(hipFree(c->d_pq));
+    if (c->d_pred) STFEM_TRY(hipFree(c->d_pred));
     c->d_pq = c->d_pred = nullptr;
     c->pq_points = 0;
     if (hipMalloc(&c->d_pq, (npts + 16) * sizeof(double)) != hipSuccess || hipMalloc(&c->d_pred, (2 * size_t(ncells) + 2) * sizeof(double)) != hipSuccess)
@@ -205,9 +205,9 @@ int stfem_stokes_pressure_difference(stfem_stokes_ctx *c, int nq, const double *
   stfem::gauss_rule(nq, xq, wq);
   std::vector<double> rule(xq);
   rule.insert(rule.end(), wq.begin(), wq.end());
-  STFEM_TRY(g_stokes_err, hipMemcpyAsync(c->d_pq, exact_at_points, npts * sizeof(double), hipMemcpyHostToDevice, st));
-  STFEM_TRY(g_stokes_err, hipMemcpyAsync(c->d_pq + npts, rule.data(), rule.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  (void)hipGetLastError();
+  STFEM_TRY(hipMemcpyAsync(c->d_pq, exact_at_points, npts * sizeof(double), hipMemcpyHostToDevice, st));
+  STFEM_TRY(hipMemcpyAsync(c->d_pq + npts, rule.data(), rule.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  stfem_launch_begin();
   if (c->pspace)
     hipLaunchKernelGGL(pressure_difference_kernel<true>, dim3((unsigned)ncells), dim3(64), 0, st, c->nc[0], c->nc[1], c->nc[2], nq, c->base.detJ,
                        c->d_pq + npts, c->d_pq + npts + nq, p, c->d_pq, c->d_pred);
@@ -215,9 +215,9 @@ int stfem_stokes_pressure_difference(stfem_stokes_ctx *c, int nq, const double *
     hipLaunchKernelGGL(pressure_difference_kernel<false>, dim3((unsigned)ncells), dim3(64), 0, st, c->nc[0], c->nc[1], c->nc[2], nq, c->base.detJ,
                        c->d_pq + npts, c->d_pq + npts + nq, p, c->d_pq, c->d_pred);
   hipLaunchKernelGGL(pressure_difference_finish, dim3(1), dim3(256), 0, st, ncells, c->d_pred, c->d_pred + 2 * ncells);
-  if (hipGetLastError() != hipSuccess) return STFEM_ERR_HIP;
-  STFEM_TRY(g_stokes_err, hipMemcpyAsync(out, c->d_pred + 2 * ncells, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-  STFEM_TRY(g_stokes_err, hipStreamSynchronize(st));
+  if (const int rc = stfem_launch_end("pressure_difference_kernel")) return rc;
+  STFEM_TRY(hipMemcpyAsync(out, c->d_pred + 2 * ncells, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  STFEM_TRY(hipStreamSynchronize(st));
   return STFEM_OK;
 }
 
@@ -230,11 +230,11 @@ int stfem_stokes_dgp_prolongate(stfem_stokes_ctx *fine, stfem_stokes_ctx *coarse
   if (!fine->pspace || !coarse->pspace) return STFEM_ERR_UNSUPPORTED;
   for (int d = 0; d < 3; ++d)
     if (fine->nc[d] != 2 * coarse->nc[d]) return STFEM_ERR_SHAPE_MISMATCH;
-  STFEM_TRY(g_stokes_err, hipSetDevice(fine->device));
+  STFEM_TRY(hipSetDevice(fine->device));
   const long long nc = (long long)coarse->nc[0] * coarse->nc[1] * coarse->nc[2];
   hipLaunchKernelGGL(dgp_transfer_kernel<false>, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), coarse->nc[0],
                      coarse->nc[1], coarse->nc[2], dst_fine, src_coarse, add);
-  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
+  return stfem_launch_end("dgp_transfer_kernel<false>");
 }
 int stfem_stokes_dgp_restrict(stfem_stokes_ctx *fine, stfem_stokes_ctx *coarse, double *dst_coarse, const double *src_fine, int add, void *stream)
 {
@@ -242,11 +242,11 @@ int stfem_stokes_dgp_restrict(stfem_stokes_ctx *fine, stfem_stokes_ctx *coarse, 
   if (!fine->pspace || !coarse->pspace) return STFEM_ERR_UNSUPPORTED;
   for (int d = 0; d < 3; ++d)
     if (fine->nc[d] != 2 * coarse->nc[d]) return STFEM_ERR_SHAPE_MISMATCH;
-  STFEM_TRY(g_stokes_err, hipSetDevice(fine->device));
+  STFEM_TRY(hipSetDevice(fine->device));
   const long long nc = (long long)coarse->nc[0] * coarse->nc[1] * coarse->nc[2];
   hipLaunchKernelGGL(dgp_transfer_kernel<true>, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), coarse->nc[0],
                      coarse->nc[1], coarse->nc[2], dst_coarse, src_fine, add);
-  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
+  return stfem_launch_end("dgp_transfer_kernel<true>");
 }
 
 } // extern "C"

@@ -38,8 +38,6 @@ namespace vanka = stfem::vanka;
 
 namespace {
 
-thread_local char g_sv_err[256] = "";
-
 struct StokesCollectParams {
   double *dst[VK_MAX_BLOCKS];
   const double *y;   // [slot][mpad]
@@ -204,10 +202,7 @@ int build_class_blocks(stfem_stokes_vanka *v, const vanka::ClassTable &t, int np
   for (size_t ci = 0; ci < t.key.size(); ++ci) {
     const int key = t.key[ci];
     const int rc = probe_class(d, key, npl, A, Mu);
-    if (rc != STFEM_OK) {
-      snprintf(g_sv_err, sizeof(g_sv_err), "probing the block of class %d: status %d (%s)", key, rc, stfem_stokes_last_hip_error());
-      return rc;
-    }
+    if (rc != STFEM_OK) return stfem_set_error(rc, "probing the block of class %d: status %d (%s)", key, rc, stfem_last_error());
     // valence and strong constraints of the cell's DoFs
     std::vector<double> val(nl, 1.0);
     std::vector<char> con(nl, 0);
@@ -230,11 +225,10 @@ int build_class_blocks(stfem_stokes_vanka *v, const vanka::ClassTable &t, int np
       }
     vanka::combine_two_variable(v->nblk, v->var, v->rowbase, m, 81, nl, Alpha, Beta, A, Mu, B);
     if (!vanka::finish_block(m, B, dof, con, val, all.data() + bsz * ci, v->mpad, v->kpad)) {
-      snprintf(g_sv_err, sizeof(g_sv_err), "singular cell block (class %d)", key);
-      return STFEM_ERR_INVALID_ARGUMENT;
+      return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "singular cell block (class %d)", key);
     }
   }
-  return vk_upload(&v->d_blocks, all, g_sv_err);
+  return vk_upload(&v->d_blocks, all);
 }
 
 // The row table: row -> (vector, variable, element offset from the cell's first DoF of the variable)
@@ -279,20 +273,18 @@ int build_tables(stfem_stokes_vanka *v, const vanka::ClassTable &t, int npl)
       }
   const vanka::CellList list = vanka::cell_list(t, -1);
   v->nquad = int(list.cls.size());
-  rc = vk_upload(&v->d_rowtab, rowtab, g_sv_err);
-  if (rc == STFEM_OK) rc = vk_upload(&v->d_cellu, vanka::gather_cells(list.order, firstu, -1), g_sv_err);
-  if (rc == STFEM_OK) rc = vk_upload(&v->d_cellp, vanka::gather_cells(list.order, firstp, 0), g_sv_err);
-  if (rc == STFEM_OK) rc = vk_upload(&v->d_cls, list.cls, g_sv_err);
-  if (rc == STFEM_OK) rc = vk_upload(&v->d_slot, list.slot, g_sv_err);
-  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&v->d_flat), list.order.size() * v->mpad * sizeof(double), g_sv_err);
+  rc = vk_upload(&v->d_rowtab, rowtab);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_cellu, vanka::gather_cells(list.order, firstu, -1));
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_cellp, vanka::gather_cells(list.order, firstp, 0));
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_cls, list.cls);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_slot, list.slot);
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&v->d_flat), list.order.size() * v->mpad * sizeof(double));
   return rc;
 }
 
 } // namespace
 
 extern "C" {
-
-const char *stfem_stokes_vanka_last_error(void) { return g_sv_err; }
 
 void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v)
 {
@@ -347,7 +339,7 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
   v->mtw = plan.mtw; v->parts = plan.parts; v->mt = plan.parts * plan.mtw;
   v->mpad = 16 * v->mt;
   v->kpad = ((v->m + KS - 1) / KS) * KS;
-  STFEM_TRY(g_sv_err, hipSetDevice(d.device));
+  STFEM_TRY(hipSetDevice(d.device));
   const vanka::ClassTable t = vanka::class_table(d.nc, 0);
   v->nclasses = int(t.key.size());
   rc = build_class_blocks(v.get(), t, npl, Alpha, Beta);
@@ -393,8 +385,8 @@ int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, co
   cd.nblk = n_blocks; cd.m = v->m; cd.mpad = v->mpad; cd.kpad = v->kpad; cd.mode = mode;
   for (int i = 0; i < n_blocks; ++i) cd.var[i] = v->var[i];
   for (int i = 0; i < n_blocks * n_blocks; ++i) { cd.Alpha[i] = Alpha[i]; cd.Beta[i] = Beta[i]; }
-  STFEM_TRY(g_sv_err, hipSetDevice(d.device));
-  rc = stokes_cell_vanka_create(ctx, cd, &rowtab[0].x, lin_blocks, &v->cell, g_sv_err);
+  STFEM_TRY(hipSetDevice(d.device));
+  rc = stokes_cell_vanka_create(ctx, cd, &rowtab[0].x, lin_blocks, &v->cell);
   if (rc == STFEM_OK) *out = v.release();
   return rc;
 }
@@ -409,8 +401,8 @@ int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_bl
     for (int i = 0; i < v->nblk; ++i)
       if (v->var[i] == 0 && !lin_blocks[i]) return STFEM_ERR_INVALID_ARGUMENT;
   }
-  STFEM_TRY(g_sv_err, hipSetDevice(v->d.device));
-  return stokes_cell_vanka_update(v->cell, lin_blocks, g_sv_err);
+  STFEM_TRY(hipSetDevice(v->d.device));
+  return stokes_cell_vanka_update(v->cell, lin_blocks);
 }
 
 // dst = (accumulate ? dst : 0) + omega * (sum over cells of scatter(B_c^-1 gather(src))); blocks in the order of the BlockSlice
@@ -425,12 +417,12 @@ int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, do
       if (dst_blocks[i] == src_blocks[j]) return STFEM_ERR_ALIAS;
   }
   TraceScope scope("vanka"); // the reference's TimerOutput scope "vanka" (stmg.h:835)
-  STFEM_TRY(g_sv_err, hipSetDevice(v->d.device));
+  STFEM_TRY(hipSetDevice(v->d.device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const double *rows = v->d_flat;
-  (void)hipGetLastError();
+  stfem_launch_begin();
   if (v->cell) { // one block per cell: every block streamed once, rows to the scratch array
-    const int rc = stokes_cell_vanka_apply(v->cell, src_blocks, &rows, st, g_sv_err);
+    const int rc = stokes_cell_vanka_apply(v->cell, src_blocks, &rows, st);
     if (rc != STFEM_OK) return rc;
   } else {
     VankaParams prm;
@@ -445,7 +437,7 @@ int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, do
     prm.flat = v->d_flat; prm.omega = 1.0;
     const void *k = sv_kernel(v->mtw);
     if (!k) return STFEM_ERR_UNSUPPORTED;
-    const int rc = vk_launch(k, dim3(v->nquad, v->parts), &prm, st, "vanka_apply_kernel", g_sv_err);
+    const int rc = vk_launch(k, dim3(v->nquad, v->parts), &prm, st, "vanka_apply_kernel");
     if (rc != STFEM_OK) return rc;
   }
   StokesCollectParams cp;
@@ -456,7 +448,7 @@ int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, do
   cp.Nu = v->d.Nu; cp.Np = v->d.Np; cp.omega = omega; cp.accumulate = accumulate;
   const long long big = std::max(3 * v->d.Nu, v->d.Np);
   return vk_launch(reinterpret_cast<const void *>(&stokes_vanka_collect_kernel), dim3((unsigned)((big + 255) / 256), v->nblk), &cp, st,
-                   "stokes_vanka_collect_kernel", g_sv_err);
+                   "stokes_vanka_collect_kernel");
 }
 
 int stfem_stokes_vanka_vmult(stfem_stokes_vanka *v, double *const *dst_blocks, const double *const *src_blocks, void *stream)

@@ -369,7 +369,7 @@ namespace {
 
 // Stages 1 - 3 into v->d_blocks, a few cell layers at a time with a window of cell matrices (the batch's layers and one on either
 // side), as vanka_create_per_cell_device does it.  fresh: the blocks are not allocated yet - they must fit beside the scratch.
-int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh, char (&err)[256])
+int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
 {
   stfem_stokes_ctx *c = v->ctx;
   const stokes_cell_vanka_desc &d = v->d;
@@ -381,7 +381,7 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh, cha
   const int nstates = vanka::distinct_states(d.nblk, d.var, d.mode ? lin : nullptr, sel, state);
   const size_t nl2 = size_t(nl) * nl;
   const size_t km_layer = (size_t(nstates) * nl2 + 729) * cpl * sizeof(double), b_layer = cpl * size_t(m) * m * sizeof(double);
-  if (hipSetDevice(c->device) != hipSuccess) return STFEM_ERR_HIP;
+  STFEM_TRY(hipSetDevice(c->device));
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
   const double need = double(ncells) * double(bsz) * sizeof(double);
@@ -389,16 +389,15 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh, cha
   // what is left beside the blocks themselves
   const double budget = std::min(6e9, 0.9 * double(free_b) - (fresh ? need : 0.0));
   if (budget < 3.0 * double(km_layer) + double(b_layer)) {
-    snprintf(err, sizeof(err), "per-cell Stokes blocks of %zu cells need %.2f GB and %.2f GB of set-up scratch (%.2f GB free)", ncells, need * 1e-9,
-             (3.0 * double(km_layer) + double(b_layer)) * 1e-9, double(free_b) * 1e-9);
-    return STFEM_ERR_OUT_OF_MEMORY;
+    return stfem_set_error(STFEM_ERR_OUT_OF_MEMORY, "per-cell Stokes blocks of %zu cells need %.2f GB and %.2f GB of set-up scratch (%.2f GB free)",
+                           ncells, need * 1e-9, (3.0 * double(km_layer) + double(b_layer)) * 1e-9, double(free_b) * 1e-9);
   }
   int L = int((budget - 2.0 * double(km_layer)) / double(km_layer + b_layer));
   L = std::max(1, std::min(L, ncz));
   if (const char *e = getenv("STFEM_VANKA_SETUP_LAYERS")) // at most this many cell layers per batch (tests: the batch loop on small meshes)
     if (atoi(e) > 0) L = std::min(L, atoi(e));
   if (fresh) {
-    const int rc = vk_alloc(reinterpret_cast<void **>(&v->d_blocks), ncells * bsz * sizeof(double), err);
+    const int rc = vk_alloc(reinterpret_cast<void **>(&v->d_blocks), ncells * bsz * sizeof(double));
     if (rc != STFEM_OK) return rc;
   }
   const size_t win_cells = cpl * size_t(std::min(ncz, L + 2));
@@ -410,10 +409,10 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh, cha
     (void)hipFree(d_B);
     (void)hipFree(d_flag);
   };
-  int rc = vk_alloc(reinterpret_cast<void **>(&d_A), size_t(nstates) * win_cells * nl2 * sizeof(double), err);
-  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_M), win_cells * 729 * sizeof(double), err);
-  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_B), cpl * L * size_t(m) * m * sizeof(double), err);
-  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_flag), sizeof(int), err);
+  int rc = vk_alloc(reinterpret_cast<void **>(&d_A), size_t(nstates) * win_cells * nl2 * sizeof(double));
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_M), win_cells * 729 * sizeof(double));
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_B), cpl * L * size_t(m) * m * sizeof(double));
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_flag), sizeof(int));
   if (rc != STFEM_OK) {
     cleanup();
     return rc;
@@ -434,7 +433,7 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh, cha
   for (int i = 0; i < d.nblk; ++i) { ap.var[i] = d.var[i]; ap.sel[i] = sel[i]; }
   for (int i = 0; i < d.nblk * d.nblk; ++i) { ap.Alpha[i] = d.Alpha[i]; ap.Beta[i] = d.Beta[i]; }
   const void *cellk = c->pspace ? reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<false>);
-  (void)hipGetLastError();
+  stfem_launch_begin();
   v->setup_batches = 0;
   for (int z0 = 0; z0 < ncz && e == hipSuccess && rc == STFEM_OK; z0 += L) {
     ++v->setup_batches;
@@ -445,28 +444,19 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh, cha
       mp.b = state[s];
       mp.Ac = d_A + size_t(s) * ap.state_stride;
       mp.Mc = s == 0 ? d_M : nullptr;
-      rc = vk_launch(cellk, dim3((unsigned)wcells), &mp, nullptr, "stokes_cell_matrices_kernel", err);
+      rc = vk_launch(cellk, dim3((unsigned)wcells), &mp, nullptr, "stokes_cell_matrices_kernel");
     }
     ap.zw0 = zw0; ap.z0 = z0;
-    if (rc == STFEM_OK) rc = vk_launch(reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel), dim3((unsigned)bcells), &ap, nullptr, "stokes_vanka_assemble_kernel", err);
-    if (rc == STFEM_OK) {
-      rc = stfem_vanka_invert_launch(d_B, v->d_blocks, m, d.mpad, d.kpad, (long long)cpl * z0, (unsigned)bcells, d_flag, nullptr);
-      if (rc != STFEM_OK) snprintf(err, sizeof(err), "vanka_invert_kernel: launch failed");
-    }
+    if (rc == STFEM_OK) rc = vk_launch(reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel), dim3((unsigned)bcells), &ap, nullptr, "stokes_vanka_assemble_kernel");
+    if (rc == STFEM_OK) rc = stfem_vanka_invert_launch(d_B, v->d_blocks, m, d.mpad, d.kpad, (long long)cpl * z0, (unsigned)bcells, d_flag, nullptr);
     if (rc == STFEM_OK) e = hipDeviceSynchronize(); // (the next batch reuses the scratch)
   }
   int flag = 0;
   if (rc == STFEM_OK && e == hipSuccess) e = hipMemcpy(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost);
   cleanup();
   if (rc != STFEM_OK) return rc;
-  if (e != hipSuccess) {
-    snprintf(err, sizeof(err), "per-cell Stokes block set-up: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  if (flag) {
-    snprintf(err, sizeof(err), "singular cell block");
-    return STFEM_ERR_INVALID_ARGUMENT;
-  }
+  if (e != hipSuccess) return stfem_set_error(STFEM_ERR_HIP, "per-cell Stokes block set-up: %s", hipGetErrorString(e));
+  if (flag) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "singular cell block");
   return STFEM_OK;
 }
 
@@ -486,7 +476,7 @@ void stokes_cell_vanka_destroy(stokes_cell_vanka *v)
 }
 
 int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &d, const int *rowtab_xy, const double *const *lin,
-                             stokes_cell_vanka **out, char (&err)[256])
+                             stokes_cell_vanka **out)
 {
   *out = nullptr;
   stokes_cell_vanka *v = new (std::nothrow) stokes_cell_vanka;
@@ -501,13 +491,13 @@ int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &
   std::vector<int2> rowtab(d.m);
   for (int r = 0; r < d.m; ++r) rowtab[r] = make_int2(rowtab_xy[2 * r], rowtab_xy[2 * r + 1]);
   const size_t ncells = size_t(c->nc[0]) * c->nc[1] * c->nc[2];
-  int rc = vk_upload(&v->d_nbr, t.nbr, err);
-  if (rc == STFEM_OK) rc = vk_upload(&v->d_face, t.face, err);
-  if (rc == STFEM_OK) rc = vk_upload(&v->d_rowblk, rowblk, err);
-  if (rc == STFEM_OK) rc = vk_upload(&v->d_rowdof, rowdof, err);
-  if (rc == STFEM_OK) rc = vk_upload(&v->d_rowtab, rowtab, err);
-  if (rc == STFEM_OK) rc = build_blocks(v, lin, true, err);
-  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&v->d_flat), ncells * d.mpad * sizeof(double), err);
+  int rc = vk_upload(&v->d_nbr, t.nbr);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_face, t.face);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_rowblk, rowblk);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_rowdof, rowdof);
+  if (rc == STFEM_OK) rc = vk_upload(&v->d_rowtab, rowtab);
+  if (rc == STFEM_OK) rc = build_blocks(v, lin, true);
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&v->d_flat), ncells * d.mpad * sizeof(double));
   if (rc != STFEM_OK) {
     stokes_cell_vanka_destroy(v);
     return rc;
@@ -516,10 +506,10 @@ int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &
   return STFEM_OK;
 }
 
-int stokes_cell_vanka_update(stokes_cell_vanka *v, const double *const *lin, char (&err)[256]) { return build_blocks(v, lin, false, err); }
+int stokes_cell_vanka_update(stokes_cell_vanka *v, const double *const *lin) { return build_blocks(v, lin, false); }
 int stokes_cell_vanka_setup_batches(const stokes_cell_vanka *v) { return v ? v->setup_batches : 0; }
 
-int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_blocks, const double **rows, void *stream, char (&err)[256])
+int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_blocks, const double **rows, void *stream)
 {
   const stfem_stokes_ctx *c = v->ctx;
   StokesCellApplyParams p;
@@ -531,5 +521,5 @@ int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_block
   *rows = v->d_flat;
   const size_t ncells = size_t(c->nc[0]) * c->nc[1] * c->nc[2];
   return vk_launch(reinterpret_cast<const void *>(&stokes_vanka_apply_percell_kernel), dim3((unsigned)ncells), &p, static_cast<hipStream_t>(stream),
-                   "stokes_vanka_apply_percell_kernel", err);
+                   "stokes_vanka_apply_percell_kernel");
 }

@@ -1,6 +1,5 @@
 // Streams and stream capture (include/stfem.h): a fixed sequence of launches (one V-cycle: ~1300 kernels, most of them on
 // coarse levels where the launch costs more than the kernel) recorded once into a hipGraph and replayed.
-// Errors: stfem_transfer_last_error, as the header documents.
 #include "stfem_internal.h"
 
 #include <hip/hip_runtime.h>
@@ -15,7 +14,7 @@ int stfem_stream_create(void **stream_out)
 {
   if (!stream_out) return STFEM_ERR_INVALID_ARGUMENT;
   hipStream_t s = nullptr;
-  STFEM_TRY(g_transfer_err, hipStreamCreate(&s)); // a blocking stream: ordered against the legacy default stream the other calls use
+  STFEM_TRY(hipStreamCreate(&s)); // a blocking stream: ordered against the legacy default stream the other calls use
   *stream_out = s;
   return STFEM_OK;
 }
@@ -25,13 +24,13 @@ void stfem_stream_destroy(void *stream)
 }
 int stfem_stream_synchronize(void *stream)
 {
-  STFEM_TRY(g_transfer_err, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+  STFEM_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
   return STFEM_OK;
 }
 int stfem_graph_begin(void *stream)
 {
   if (!stream) return STFEM_ERR_INVALID_ARGUMENT; // the legacy default stream cannot be captured
-  STFEM_TRY(g_transfer_err, hipStreamBeginCapture(static_cast<hipStream_t>(stream), hipStreamCaptureModeThreadLocal));
+  STFEM_TRY(hipStreamBeginCapture(static_cast<hipStream_t>(stream), hipStreamCaptureModeThreadLocal));
   return STFEM_OK;
 }
 int stfem_graph_end(void *stream, stfem_graph **out)
@@ -39,14 +38,13 @@ int stfem_graph_end(void *stream, stfem_graph **out)
   if (!stream || !out) return STFEM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
   hipGraph_t g = nullptr;
-  STFEM_TRY(g_transfer_err, hipStreamEndCapture(static_cast<hipStream_t>(stream), &g));
+  STFEM_TRY(hipStreamEndCapture(static_cast<hipStream_t>(stream), &g));
   stfem_graph *r = new stfem_graph;
   const hipError_t e = hipGraphInstantiate(&r->exec, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
   if (e != hipSuccess) {
-    snprintf(g_transfer_err, sizeof(g_transfer_err), "hipGraphInstantiate: %s", hipGetErrorString(e));
     delete r;
-    return STFEM_ERR_HIP;
+    return stfem_set_error(STFEM_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
   }
   *out = r;
   return STFEM_OK;
@@ -54,7 +52,7 @@ int stfem_graph_end(void *stream, stfem_graph **out)
 int stfem_graph_launch(stfem_graph *g, void *stream)
 {
   if (!g || !g->exec) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_transfer_err, hipGraphLaunch(g->exec, static_cast<hipStream_t>(stream)));
+  STFEM_TRY(hipGraphLaunch(g->exec, static_cast<hipStream_t>(stream)));
   return STFEM_OK;
 }
 void stfem_graph_destroy(stfem_graph *g)

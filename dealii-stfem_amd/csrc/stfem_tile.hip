@@ -730,7 +730,7 @@ __global__ __launch_bounds__(256) void st_tile_fixup(const SweepParams prm, cons
 template <int P, int NBM, int WV> int launch_tile_w(const SweepParams &prm, const TilePlan &tp0, hipStream_t st)
 {
   TilePlan tp = tp0;
-  (void)hipGetLastError(); // drop a stale sticky error of an unrelated earlier call
+  stfem_launch_begin();
   for (int colour = 1; colour >= 0; --colour) { // odd tiles first: they feed the even ones
     tp.xcolor = colour;
     const int ntxh = (tp.ntx - colour + 1) / 2;
@@ -752,11 +752,11 @@ template <int P, int NBM, int WV> int launch_tile_w(const SweepParams &prm, cons
     else if (coef) STFEM_LAUNCH(WV, false, true, false);
     else STFEM_LAUNCH(WV, false, false, false);
 #undef STFEM_LAUNCH
-    if (hipGetLastError() != hipSuccess) return -3;
+    if (const int rc = stfem_launch_end("st_sweep_cart_tile")) return rc;
   }
   if (tp.nty > 1 || tp.ntc > 1) {
     hipLaunchKernelGGL((st_tile_fixup<P>), dim3(tp.ntx * tp.nty * tp.ntc, prm.nbo, 2), dim3(256), 0, st, prm, tp, NBM);
-    if (hipGetLastError() != hipSuccess) return -3;
+    return stfem_launch_end("st_tile_fixup");
   }
   return 0;
 }
@@ -879,11 +879,11 @@ int launch_build_metric(int p, const int nc[3], const double *d_vertices, const 
 {
   const int n = p + 1;
   const int64_t ncells = int64_t(nc[0]) * nc[1] * nc[2], total = ncells * n * n * n;
-  (void)hipGetLastError();
+  stfem_launch_begin();
   hipLaunchKernelGGL(build_metric_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), n, nc[0], nc[1], ncells, d_vertices, d_xq, d_wq,
                      coef_lap, lap_layout, coef_mass, mass_layout, d_metric);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return stfem_launch_end("build_metric_kernel");
 }
 
 int tile_geometry(int p, int nbm, int general, TilePlan &plan)

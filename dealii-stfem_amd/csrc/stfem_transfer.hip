@@ -22,8 +22,6 @@
 #include <cstdio>
 #include <vector>
 
-thread_local char g_transfer_err[256] = "";
-
 namespace {
 
 // one banded 1D matrix in row-compressed form: row o = sum_k w[off[o] + k] * in[first[o] + k], k < off[o+1] - off[o]
@@ -289,12 +287,12 @@ namespace {
 
 int upload(Band &b)
 {
-  STFEM_TRY(g_transfer_err, hipMalloc(&b.d_first, b.first.size() * sizeof(int)));
-  STFEM_TRY(g_transfer_err, hipMalloc(&b.d_off, b.off.size() * sizeof(int)));
-  STFEM_TRY(g_transfer_err, hipMalloc(&b.d_w, b.w.size() * sizeof(double)));
-  STFEM_TRY(g_transfer_err, hipMemcpy(b.d_first, b.first.data(), b.first.size() * sizeof(int), hipMemcpyHostToDevice));
-  STFEM_TRY(g_transfer_err, hipMemcpy(b.d_off, b.off.data(), b.off.size() * sizeof(int), hipMemcpyHostToDevice));
-  STFEM_TRY(g_transfer_err, hipMemcpy(b.d_w, b.w.data(), b.w.size() * sizeof(double), hipMemcpyHostToDevice));
+  STFEM_TRY(hipMalloc(&b.d_first, b.first.size() * sizeof(int)));
+  STFEM_TRY(hipMalloc(&b.d_off, b.off.size() * sizeof(int)));
+  STFEM_TRY(hipMalloc(&b.d_w, b.w.size() * sizeof(double)));
+  STFEM_TRY(hipMemcpy(b.d_first, b.first.data(), b.first.size() * sizeof(int), hipMemcpyHostToDevice));
+  STFEM_TRY(hipMemcpy(b.d_off, b.off.data(), b.off.size() * sizeof(int), hipMemcpyHostToDevice));
+  STFEM_TRY(hipMemcpy(b.d_w, b.w.data(), b.w.size() * sizeof(double), hipMemcpyHostToDevice));
   return STFEM_OK;
 }
 void release(Band &b)
@@ -337,8 +335,7 @@ int launch_axis(T *out, const T *in, const int dims[3], int axis, const Band &b,
   const long long total = (long long)dims[0] * dims[1] * dims[2];
   const int blocks = int(std::min<long long>((total + 255) / 256, 1 << 20));
   axis_apply_kernel<T><<<blocks, 256, 0, s>>>(out, in, dims[0], dims[1], dims[2], axis, b.n_in, b.d_first, b.d_off, b.d_w, add);
-  STFEM_TRY(g_transfer_err, hipGetLastError());
-  return STFEM_OK;
+  return stfem_launch_end("axis_apply_kernel");
 }
 
 template <typename T> CellMat<T> cell_mat(const double *L)
@@ -360,8 +357,7 @@ int launch_cell(int pc, int R, int nseg, T *out, const T *in, long long S, int n
   if (pc == PC_ && R == R_) {                                                                                                 \
     if (nseg) cell_restrict_march_kernel<T, PC_, R_><<<blocks, 256, 0, s>>>(out, in, S, ncell, nseg, total, m, flags, add);   \
     else cell_prolongate_kernel<T, PC_, R_><<<blocks, 256, 0, s>>>(out, in, S, ncell, total, m, flags, add);                  \
-    STFEM_TRY(g_transfer_err, hipGetLastError());                                                                             \
-    return STFEM_OK;                                                                                                          \
+    return stfem_launch_end(nseg ? "cell_restrict_march_kernel" : "cell_prolongate_kernel");                                  \
   }
   STFEM_CELL_SHAPES(STFEM_CELL_CASE)
 #undef STFEM_CELL_CASE
@@ -377,8 +373,7 @@ int launch_cell_yz(int pc, int R, T *out, const T *in, int nx, int ncy, int ncz,
 #define STFEM_CELL_CASE(PC_, R_)                                                                                              \
   if (pc == PC_ && R == R_) {                                                                                                 \
     cell_prolongate_yz_kernel<T, PC_, R_><<<blocks, 256, 0, s>>>(out, in, nx, ncy, ncz, total, m, flags_y, flags_z, add);     \
-    STFEM_TRY(g_transfer_err, hipGetLastError());                                                                             \
-    return STFEM_OK;                                                                                                          \
+    return stfem_launch_end("cell_prolongate_yz_kernel");                                                                     \
   }
   STFEM_CELL_YZ_SHAPES(STFEM_CELL_CASE)
 #undef STFEM_CELL_CASE
@@ -431,8 +426,6 @@ int run(stfem_transfer *t, const Band B[3], const TransferPlan &plan, stfem_ctx 
 
 extern "C" {
 
-const char *stfem_transfer_last_error(void) { return g_transfer_err; }
-
 int stfem_transfer_create(stfem_ctx *fine, stfem_ctx *coarse, stfem_transfer **out)
 {
   return stfem_transfer_create_partitioned(fine, coarse, 0, out);
@@ -447,7 +440,7 @@ int stfem_transfer_create_partitioned(stfem_ctx *fine, stfem_ctx *coarse, int ne
     if (!same && !twice) return STFEM_ERR_SHAPE_MISMATCH;
   }
   if (coarse->p > fine->p) return STFEM_ERR_SHAPE_MISMATCH;
-  STFEM_TRY(g_transfer_err, hipSetDevice(fine->device));
+  STFEM_TRY(hipSetDevice(fine->device));
   stfem_transfer *t = new stfem_transfer;
   t->fine = fine;
   t->coarse = coarse;

@@ -336,8 +336,6 @@ __global__ __launch_bounds__(256) void vanka_invert_kernel(double *__restrict__ 
   }
 }
 
-thread_local char g_vanka_err[256] = "";
-
 } // namespace
 
 // vanka_invert_kernel<double> for the other translation units (the per-cell Stokes blocks, stfem_stokes_vanka_cell.hip)
@@ -345,7 +343,7 @@ int stfem_vanka_invert_launch(double *B, double *out, int m, int mpad, int kpad,
 {
   if (m < 1 || m > VK_MAX_ROWS || count == 0) return STFEM_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(vanka_invert_kernel<double>, dim3(count), dim3(256), 0, static_cast<hipStream_t>(stream), B, out, m, mpad, kpad, cell0, singular);
-  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
+  return stfem_launch_end("vanka_invert_kernel");
 }
 
 constexpr int VK_FLAT = 8; // the launch after the eight colours: all cells at once (two-phase apply)
@@ -413,7 +411,7 @@ static int vanka_collect(const stfem_vanka *v, stfem_vec *dst, double omega, int
   cp.nb = v->nb; cp.nloc = v->nloc; cp.p = c->p; cp.mpad = v->mpad;
   cp.ncx = c->nc[0]; cp.ncy = c->nc[1]; cp.ncz = c->nc[2]; cp.nx = c->nd[0]; cp.ny = c->nd[1]; cp.nz = c->nd[2];
   cp.omega = omega; cp.accumulate = accumulate;
-  return vk_launch(VK_TYPED(c, vanka_collect_kernel), dim3((unsigned)((c->ndofs + 255) / 256)), &cp, st, "vanka_collect_kernel", g_vanka_err);
+  return vk_launch(VK_TYPED(c, vanka_collect_kernel), dim3((unsigned)((c->ndofs + 255) / 256)), &cp, st, "vanka_collect_kernel");
 }
 
 // a new smoother on context c, nothing built yet
@@ -436,7 +434,7 @@ static int vanka_offset_table(stfem_vanka *v)
   for (int kz = 0; kz < n; ++kz)
     for (int jy = 0; jy < n; ++jy)
       for (int ix = 0; ix < n; ++ix) off[ix + n * (jy + n * kz)] = ix + c->nd[0] * (jy + c->nd[1] * kz);
-  return vk_upload(&v->d_off, off, g_vanka_err);
+  return vk_upload(&v->d_off, off);
 }
 
 // per-cell variant: one block of mt row tiles per cell
@@ -470,7 +468,7 @@ struct VankaHostBlocks {
     return v->ctx->prec ? vanka::finish_block(v->m, B, dof, con, val, f32.data() + at, v->mpad, v->kpad)
                         : vanka::finish_block(v->m, B, dof, con, val, f64.data() + at, v->mpad, v->kpad);
   }
-  int upload(stfem_vanka *to) const { return v->ctx->prec ? vk_upload(&to->d_blocks, f32, g_vanka_err) : vk_upload(&to->d_blocks, f64, g_vanka_err); }
+  int upload(stfem_vanka *to) const { return v->ctx->prec ? vk_upload(&to->d_blocks, f32) : vk_upload(&to->d_blocks, f64); }
 };
 } // namespace
 
@@ -486,12 +484,12 @@ static int vanka_per_cell_tables(stfem_vanka *v)
       for (int cy = (colour >> 1) & 1; cy < ncy; cy += 2)
         for (int cx = colour & 1; cx < ncx; cx += 2) cells.push_back(cx + ncx * (cy + ncy * cz));
     v->ngrid[colour] = int(cells.size());
-    if (!cells.empty()) rc = vk_upload(&v->d_cell[colour], cells, g_vanka_err);
+    if (!cells.empty()) rc = vk_upload(&v->d_cell[colour], cells);
   }
   if (rc != STFEM_OK || !vanka_wants_flat(c)) return rc;
   v->ngrid[VK_FLAT] = int(c->ncells);
   v->flat = true;
-  return vk_alloc(&v->d_flat, size_t(c->ncells) * v->mpad * c->es, g_vanka_err);
+  return vk_alloc(&v->d_flat, size_t(c->ncells) * v->mpad * c->es);
 }
 
 // Set-up of the per-cell blocks (general meshes, coefficient tables): cell matrices on the device from the stored
@@ -506,9 +504,8 @@ static int vanka_create_per_cell_host(stfem_vanka *v, const double *Alpha, const
   vanka_per_cell_shape(v);
   const size_t bsz = size_t(v->kpad) * v->mpad;
   if (double(c->ncells) * double(bsz) * double(c->es) > 64e9) {
-    snprintf(g_vanka_err, sizeof(g_vanka_err), "per-cell blocks of %lld cells need %.1f GB", (long long)c->ncells,
-             double(c->ncells) * double(bsz) * double(c->es) * 1e-9);
-    return STFEM_ERR_OUT_OF_MEMORY;
+    return stfem_set_error(STFEM_ERR_OUT_OF_MEMORY, "per-cell blocks of %lld cells need %.1f GB", (long long)c->ncells,
+                           double(c->ncells) * double(bsz) * double(c->es) * 1e-9);
   }
   // ---- cell matrices
   const void *metric = nullptr;
@@ -532,21 +529,20 @@ static int vanka_create_per_cell_host(stfem_vanka *v, const double *Alpha, const
   {
     hipError_t e = hipMemcpy(d_tab, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice);
     const size_t lds = (size_t(nloc) * 7 + 2 * n * n) * sizeof(double);
+    int launched = STFEM_OK;
     if (e == hipSuccess) {
       stfem_by_prec(c, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL(vanka_cell_matrices_kernel<T>, dim3((unsigned)c->ncells), dim3(256), lds, 0, n, static_cast<const T *>(metric), d_tab,
                            d_tab + n * n, d_K, d_M);
       });
-      e = hipGetLastError();
+      launched = stfem_launch_end("vanka_cell_matrices_kernel");
     }
-    if (e == hipSuccess) e = hipMemcpy(Kc.data(), d_K, nmat * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(Mc.data(), d_M, nmat * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && launched == STFEM_OK) e = hipMemcpy(Kc.data(), d_K, nmat * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && launched == STFEM_OK) e = hipMemcpy(Mc.data(), d_M, nmat * sizeof(double), hipMemcpyDeviceToHost);
     cleanup();
-    if (e != hipSuccess) {
-      snprintf(g_vanka_err, sizeof(g_vanka_err), "cell matrices: %s", hipGetErrorString(e));
-      return STFEM_ERR_HIP;
-    }
+    if (e != hipSuccess) return stfem_set_error(STFEM_ERR_HIP, "cell matrices: %s", hipGetErrorString(e));
+    if (launched != STFEM_OK) return launched;
   }
   // ---- blocks
   const int ncx = c->nc[0], ncy = c->nc[1], ncz = c->nc[2];
@@ -598,10 +594,7 @@ static int vanka_create_per_cell_host(stfem_vanka *v, const double *Alpha, const
           }
         }
         // from here on as for the class blocks: constraints, valence, Kronecker with Alpha / Beta, Gauss-Jordan
-        if (!blocks.add(cell, Kr, Mr, cn, val)) {
-          snprintf(g_vanka_err, sizeof(g_vanka_err), "singular cell block (cell %zu)", cell);
-          return STFEM_ERR_INVALID_ARGUMENT;
-        }
+        if (!blocks.add(cell, Kr, Mr, cn, val)) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "singular cell block (cell %zu)", cell);
       }
   rc = blocks.upload(v);
   if (rc != STFEM_OK) return rc;
@@ -628,8 +621,7 @@ static int vanka_create_per_cell_device(stfem_vanka *v, const double *Alpha, con
   // and never more than what is left beside the blocks themselves
   const double budget = std::min(6e9, 0.9 * double(free_b) - need);
   if (budget < 3.0 * double(km_layer) + double(b_layer)) {
-    snprintf(g_vanka_err, sizeof(g_vanka_err), "per-cell blocks of %lld cells need %.1f GB (%.1f GB free)", (long long)c->ncells, need * 1e-9, double(free_b) * 1e-9);
-    return STFEM_ERR_OUT_OF_MEMORY;
+    return stfem_set_error(STFEM_ERR_OUT_OF_MEMORY, "per-cell blocks of %lld cells need %.1f GB (%.1f GB free)", (long long)c->ncells, need * 1e-9, double(free_b) * 1e-9);
   }
   int L = int((budget - 2.0 * double(km_layer)) / double(km_layer + b_layer));
   L = std::max(1, std::min(L, ncz));
@@ -650,7 +642,7 @@ static int vanka_create_per_cell_device(stfem_vanka *v, const double *Alpha, con
   std::vector<double> tabs(2 * n * n);
   for (int i = 0; i < n * n; ++i) { tabs[i] = c->tab.S[i]; tabs[n * n + i] = c->tab.D[i]; }
   const size_t win_cells = cpl * size_t(std::min(ncz, L + 2));
-  rc = vk_alloc(&v->d_blocks, size_t(c->ncells) * bsz * c->es, g_vanka_err);
+  rc = vk_alloc(&v->d_blocks, size_t(c->ncells) * bsz * c->es);
   if (rc != STFEM_OK) return rc;
   if (hipMalloc(&d_tab, tabs.size() * sizeof(double)) != hipSuccess || hipMalloc(&d_K, win_cells * nloc * nloc * sizeof(double)) != hipSuccess ||
       hipMalloc(&d_M, win_cells * nloc * nloc * sizeof(double)) != hipSuccess || hipMalloc(&d_B, cpl * L * size_t(m) * m * sizeof(double)) != hipSuccess ||
@@ -666,7 +658,8 @@ static int vanka_create_per_cell_device(stfem_vanka *v, const double *Alpha, con
   for (int i = 0; i < nb * nb; ++i) { ap.Alpha[i] = Alpha[i]; ap.Beta[i] = Beta[i]; }
   const size_t lds = (size_t(nloc) * 7 + 2 * n * n) * sizeof(double);
   v->setup_batches = 0;
-  for (int z0 = 0; z0 < ncz && e == hipSuccess; z0 += L) {
+  int launched = STFEM_OK;
+  for (int z0 = 0; z0 < ncz && e == hipSuccess && launched == STFEM_OK; z0 += L) {
     ++v->setup_batches;
     const int z1 = std::min(ncz, z0 + L), zw0 = std::max(0, z0 - 1), zw1 = std::min(ncz, z1 + 1);
     const size_t wcells = cpl * size_t(zw1 - zw0), bcells = cpl * size_t(z1 - z0);
@@ -683,20 +676,15 @@ static int vanka_create_per_cell_device(stfem_vanka *v, const double *Alpha, con
       using T = decltype(t);
       hipLaunchKernelGGL(vanka_invert_kernel<T>, dim3((unsigned)bcells), dim3(256), 0, 0, d_B, static_cast<T *>(v->d_blocks), m, v->mpad, v->kpad, cell0, d_flag);
     });
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize(); // (the next batch reuses the scratch)
+    launched = stfem_launch_end("per-cell block set-up kernels");
+    if (launched == STFEM_OK) e = hipDeviceSynchronize(); // (the next batch reuses the scratch)
   }
   int flag = 0;
-  if (e == hipSuccess) e = hipMemcpy(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && launched == STFEM_OK) e = hipMemcpy(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost);
   cleanup();
-  if (e != hipSuccess) {
-    snprintf(g_vanka_err, sizeof(g_vanka_err), "per-cell block set-up: %s", hipGetErrorString(e));
-    return STFEM_ERR_HIP;
-  }
-  if (flag) {
-    snprintf(g_vanka_err, sizeof(g_vanka_err), "singular cell block");
-    return STFEM_ERR_INVALID_ARGUMENT;
-  }
+  if (e != hipSuccess) return stfem_set_error(STFEM_ERR_HIP, "per-cell block set-up: %s", hipGetErrorString(e));
+  if (launched != STFEM_OK) return launched;
+  if (flag) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "singular cell block");
   v->nclasses = int(c->ncells);
   return vanka_per_cell_tables(v);
 }
@@ -767,10 +755,7 @@ static int build_class_blocks(stfem_vanka *v, const vanka::ClassTable &t, const 
                 Kr[size_t(r) * nloc + s] = mz * my * kx + mz * ky * mx + kz1 * my * mx;
               }
         }
-    if (!blocks.add(ci, Kr, Mr, cn, val)) {
-      snprintf(g_vanka_err, sizeof(g_vanka_err), "singular cell block (class %d)", key);
-      return STFEM_ERR_INVALID_ARGUMENT;
-    }
+    if (!blocks.add(ci, Kr, Mr, cn, val)) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "singular cell block (class %d)", key);
   }
   return blocks.upload(v);
 }
@@ -790,18 +775,16 @@ static int build_cell_lists(stfem_vanka *v, const vanka::ClassTable &t)
     const vanka::CellList list = vanka::cell_list(t, l == VK_FLAT ? -1 : l);
     v->ngrid[l] = int(list.cls.size());
     if (list.cls.empty()) continue;
-    rc = vk_upload(&v->d_cell[l], vanka::gather_cells(list.order, first, -1), g_vanka_err);
-    if (rc == STFEM_OK) rc = vk_upload(&v->d_cls[l], list.cls, g_vanka_err);
+    rc = vk_upload(&v->d_cell[l], vanka::gather_cells(list.order, first, -1));
+    if (rc == STFEM_OK) rc = vk_upload(&v->d_cls[l], list.cls);
     if (l != VK_FLAT) continue; // cell -> slot for the second phase, and the rows between the two
-    if (rc == STFEM_OK) rc = vk_upload(&v->d_slot, list.slot, g_vanka_err);
-    if (rc == STFEM_OK) rc = vk_alloc(&v->d_flat, list.order.size() * v->mpad * c->es, g_vanka_err);
+    if (rc == STFEM_OK) rc = vk_upload(&v->d_slot, list.slot);
+    if (rc == STFEM_OK) rc = vk_alloc(&v->d_flat, list.order.size() * v->mpad * c->es);
   }
   return rc;
 }
 
 extern "C" {
-
-const char *stfem_vanka_last_error(void) { return g_vanka_err; }
 
 int stfem_vanka_create(stfem_ctx *c, int nb, const double *Alpha, const double *Beta, stfem_vanka **out)
 {
@@ -815,7 +798,7 @@ int stfem_vanka_create_partitioned(stfem_ctx *c, int nb, const double *Alpha, co
   *out = nullptr;
   const int n = c->p + 1;
   if (nb * n * n * n > VK_MAX_ROWS) return STFEM_ERR_UNSUPPORTED; // Q4 with more than 4 temporal blocks, Q5 with more than 2
-  STFEM_TRY(g_vanka_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   VankaPtr v = vanka_new(c, nb);
   if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   int rc;
@@ -871,7 +854,7 @@ int stfem_vanka_create_partitioned_general(stfem_ctx *slab, stfem_ctx *extended,
   const size_t bsz = size_t(v->kpad) * v->mpad;
   v->d_blocks = static_cast<char *>(v->d_blocks_base) + size_t(glo) * size_t(slab->nc[0]) * slab->nc[1] * bsz * slab->es;
   ve.reset();
-  STFEM_TRY(g_vanka_err, hipSetDevice(slab->device));
+  STFEM_TRY(hipSetDevice(slab->device));
   rc = vanka_per_cell_tables(v.get());
   if (rc == STFEM_OK) *out = v.release();
   return rc;
@@ -915,7 +898,7 @@ int stfem_vanka_step(stfem_vanka *v, stfem_vec *dst, double omega, int accumulat
     for (int j = 0; j < v->nb; ++j)
       if (dst->blk[i] == src->blk[j]) return STFEM_ERR_ALIAS;
   stfem_ctx *c = v->ctx;
-  STFEM_TRY(g_vanka_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // the parameters of both kernels; a launch changes the cell list and the colour only
   VankaParams prm;
@@ -934,7 +917,7 @@ int stfem_vanka_step(stfem_vanka *v, stfem_vec *dst, double omega, int accumulat
   prm.omega = cp.omega = omega; prm.accumulate = cp.accumulate = accumulate;
   const void *kernel = v->per_cell ? VK_TYPED(c, vanka_apply_percell_kernel) : vanka_kernel(c, v->mtw);
   if (!kernel) return STFEM_ERR_UNSUPPORTED;
-  (void)hipGetLastError();
+  stfem_launch_begin();
   // dst = 0 (stmg.h:836) is not a pass of its own: the first cell to touch a DoF stores (every DoF has one)
   for (int l = v->flat ? VK_FLAT : 0; l <= (v->flat ? VK_FLAT : 7); ++l) {
     if (v->ngrid[l] == 0) continue;
@@ -942,8 +925,8 @@ int stfem_vanka_step(stfem_vanka *v, stfem_vec *dst, double omega, int accumulat
     prm.cls = v->d_cls[l];
     prm.nquad = v->ngrid[l];
     prm.colour = cp.colour = l & 7;
-    const int rc = v->per_cell ? vk_launch(kernel, dim3(v->ngrid[l]), &cp, st, "vanka_apply_percell_kernel", g_vanka_err)
-                               : vk_launch(kernel, dim3(v->ngrid[l], v->parts), &prm, st, "vanka_apply_kernel", g_vanka_err);
+    const int rc = v->per_cell ? vk_launch(kernel, dim3(v->ngrid[l]), &cp, st, "vanka_apply_percell_kernel")
+                               : vk_launch(kernel, dim3(v->ngrid[l], v->parts), &prm, st, "vanka_apply_kernel");
     if (rc != STFEM_OK) return rc;
   }
   return v->flat ? vanka_collect(v, dst, omega, accumulate, st) : STFEM_OK;

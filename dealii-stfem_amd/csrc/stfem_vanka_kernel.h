@@ -3,6 +3,7 @@
 // node -> cells rule of the collecting kernels.  Not part of the boundary.
 #pragma once
 #include "../../include/stfem.h"
+#include "stfem_error.h"
 
 #include <hip/hip_runtime.h>
 
@@ -35,34 +36,31 @@ struct VankaParams {
   const int *cell2;
 };
 
-// ---- host helpers: a failure leaves its reason in the caller's last-error string `err` ----
-inline int vk_alloc(void **dev, size_t bytes, char (&err)[256])
+// ---- host helpers: a failure leaves its reason in the error record ----
+inline int vk_alloc(void **dev, size_t bytes)
 {
   if (hipMalloc(dev, bytes) == hipSuccess) return STFEM_OK;
   (void)hipGetLastError();
-  snprintf(err, sizeof(err), "device allocation of %zu bytes failed", bytes);
-  return STFEM_ERR_OUT_OF_MEMORY;
+  return stfem_set_error(STFEM_ERR_OUT_OF_MEMORY, "device allocation of %zu bytes failed", bytes);
 }
 // a new device allocation holding a copy of host
-template <typename D, typename T> int vk_upload(D **dev, const std::vector<T> &host, char (&err)[256])
+template <typename D, typename T> int vk_upload(D **dev, const std::vector<T> &host)
 {
   const size_t bytes = host.size() * sizeof(T);
-  const int rc = vk_alloc(reinterpret_cast<void **>(dev), bytes, err);
+  const int rc = vk_alloc(reinterpret_cast<void **>(dev), bytes);
   if (rc != STFEM_OK) return rc;
   const hipError_t e = hipMemcpy(*dev, host.data(), bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess) return STFEM_OK;
-  snprintf(err, sizeof(err), "upload of %zu bytes: %s", bytes, hipGetErrorString(e));
-  return STFEM_ERR_HIP;
+  return stfem_set_error(STFEM_ERR_HIP, "upload of %zu bytes: %s", bytes, hipGetErrorString(e));
 }
 // one launch of 256-thread workgroups with the parameter struct prm
-inline int vk_launch(const void *kernel, dim3 grid, void *prm, hipStream_t st, const char *name, char (&err)[256])
+inline int vk_launch(const void *kernel, dim3 grid, void *prm, hipStream_t st, const char *name)
 {
   void *args[] = {prm};
   const hipError_t e = hipLaunchKernel(kernel, grid, dim3(256), args, 0, st); // (returns what a launch statement leaves to hipGetLastError)
   if (e == hipSuccess) return STFEM_OK;
-  snprintf(err, sizeof(err), "%s: %s", name, hipGetErrorString(e));
-  (void)hipGetLastError();
-  return STFEM_ERR_HIP;
+  (void)hipGetLastError(); // (the same error again: dropped)
+  return stfem_set_error(STFEM_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
 }
 
 // The cells holding node idx of a Q_p mesh of nc cells and its local index there, per direction (a vertex node: the cell below

@@ -17,7 +17,7 @@ using namespace stfem;
 int stfem_vector_create(stfem_ctx *c, int nb, stfem_vec **out)
 {
   if (!c || !out || nb < 1) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   stfem_vec *v = new (std::nothrow) stfem_vec;
   if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   v->ctx = c;
@@ -30,9 +30,10 @@ int stfem_vector_create(stfem_ctx *c, int nb, stfem_vec **out)
       stfem_vector_destroy(v);
       return STFEM_ERR_OUT_OF_MEMORY;
     }
-    if (hipMemset(v->blk[b], 0, size_t(c->ndofs) * c->es) != hipSuccess) {
+    const hipError_t e = hipMemset(v->blk[b], 0, size_t(c->ndofs) * c->es);
+    if (e != hipSuccess) {
       stfem_vector_destroy(v);
-      return STFEM_ERR_HIP;
+      return stfem_set_error(STFEM_ERR_HIP, "hipMemset(new vector): %s", hipGetErrorString(e));
     }
   }
   *out = v;
@@ -93,15 +94,15 @@ void *stfem_vector_block(const stfem_vec *v, int b)
 int stfem_vector_upload(stfem_vec *v, const double *const *host)
 {
   if (!v || !host) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_hip_error, hipSetDevice(v->ctx->device));
+  STFEM_TRY(hipSetDevice(v->ctx->device));
   const size_t n = size_t(v->ctx->ndofs);
   std::vector<float> tmp(v->ctx->prec ? n : 0);
   for (int b = 0; b < v->nb; ++b) {
     if (v->ctx->prec) { // host side is always double; fp32 contexts convert here
       for (size_t i = 0; i < n; ++i) tmp[i] = float(host[b][i]);
-      STFEM_TRY(g_hip_error, hipMemcpy(v->blk[b], tmp.data(), n * sizeof(float), hipMemcpyHostToDevice));
+      STFEM_TRY(hipMemcpy(v->blk[b], tmp.data(), n * sizeof(float), hipMemcpyHostToDevice));
     } else {
-      STFEM_TRY(g_hip_error, hipMemcpy(v->blk[b], host[b], n * sizeof(double), hipMemcpyHostToDevice));
+      STFEM_TRY(hipMemcpy(v->blk[b], host[b], n * sizeof(double), hipMemcpyHostToDevice));
     }
   }
   return STFEM_OK;
@@ -110,16 +111,16 @@ int stfem_vector_upload(stfem_vec *v, const double *const *host)
 int stfem_vector_download(const stfem_vec *v, double *const *host)
 {
   if (!v || !host) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_hip_error, hipSetDevice(v->ctx->device));
-  STFEM_TRY(g_hip_error, hipDeviceSynchronize());
+  STFEM_TRY(hipSetDevice(v->ctx->device));
+  STFEM_TRY(hipDeviceSynchronize());
   const size_t n = size_t(v->ctx->ndofs);
   std::vector<float> tmp(v->ctx->prec ? n : 0);
   for (int b = 0; b < v->nb; ++b) {
     if (v->ctx->prec) {
-      STFEM_TRY(g_hip_error, hipMemcpy(tmp.data(), v->blk[b], n * sizeof(float), hipMemcpyDeviceToHost));
+      STFEM_TRY(hipMemcpy(tmp.data(), v->blk[b], n * sizeof(float), hipMemcpyDeviceToHost));
       for (size_t i = 0; i < n; ++i) host[b][i] = tmp[i];
     } else {
-      STFEM_TRY(g_hip_error, hipMemcpy(host[b], v->blk[b], n * sizeof(double), hipMemcpyDeviceToHost));
+      STFEM_TRY(hipMemcpy(host[b], v->blk[b], n * sizeof(double), hipMemcpyDeviceToHost));
     }
   }
   return STFEM_OK;
@@ -169,7 +170,7 @@ int stfem_tensorproduct_add(stfem_ctx *c, int nrows, int ncols, const double *A,
 {
   if (!c || !A || !cv || !b || cv->ctx != c || b->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   if (cv->nb != nrows || b->nb != ncols) return STFEM_ERR_SHAPE_MISMATCH;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   return stfem_by_prec(c, [&](auto t) { return tensorproduct_add_t<decltype(t)>(c, nrows, ncols, A, cv, b, st); });
 }
@@ -261,7 +262,7 @@ static int multi_dot_device(stfem_ctx *c, int k, const stfem_vec *const *as, con
     if (!as[i] || as[i]->nb != b->nb || as[i]->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   const int grid = (int)std::min<int64_t>((n_own + 255) / 256, DOT_GRID);
   double *partial = c->d_scratch + DOT_RESULTS; // [DOT_VECS][DOT_GRID]
-  (void)hipGetLastError();
+  stfem_launch_begin();
   for (int k0 = 0; k0 < k; k0 += DOT_VECS) {
     DotArgs args;
     std::memset(&args, 0, sizeof(args));
@@ -273,14 +274,14 @@ static int multi_dot_device(stfem_ctx *c, int k, const stfem_vec *const *as, con
     stfem_by_prec(c, [&](auto t) { hipLaunchKernelGGL(multi_dot_kernel<decltype(t)>, dim3(grid), dim3(256), 0, st, n_own, args, partial); });
     hipLaunchKernelGGL(dot_finish_kernel, dim3(1), dim3(256), 0, st, args.nvec, grid, partial, d_out + k0);
   }
-  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
+  return stfem_launch_end("multi_dot_kernel");
 }
 
 int stfem_dot(stfem_ctx *c, const stfem_vec *a, const stfem_vec *b, int64_t n_own, double *out, void *stream)
 {
   if (!c || !a || !b || !out || a->nb != b->nb || a->ctx != c || b->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   if (n_own <= 0 || n_own > c->ndofs) n_own = c->ndofs;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a->nb > MAX_BLOCKS) { // (vectors of more than eight blocks: eight at a time)
     double sum = 0.0;
@@ -299,9 +300,9 @@ int stfem_dot(stfem_ctx *c, const stfem_vec *a, const stfem_vec *b, int64_t n_ow
   }
   const stfem_vec *as[1] = {a};
   const int rc = multi_dot_device(c, 1, as, b, n_own, c->d_scratch, st);
-  if (rc != STFEM_OK) return rc == STFEM_ERR_HIP ? hip_fail(hipGetLastError(), "dot") : rc;
-  STFEM_TRY(g_hip_error, hipMemcpyAsync(out, c->d_scratch, sizeof(double), hipMemcpyDeviceToHost, st));
-  STFEM_TRY(g_hip_error, hipStreamSynchronize(st));
+  if (rc != STFEM_OK) return rc;
+  STFEM_TRY(hipMemcpyAsync(out, c->d_scratch, sizeof(double), hipMemcpyDeviceToHost, st));
+  STFEM_TRY(hipStreamSynchronize(st));
   return STFEM_OK;
 }
 
@@ -309,12 +310,12 @@ int stfem_multi_dot(stfem_ctx *c, int k, const stfem_vec *const *as, const stfem
 {
   if (!c || !as || !b || !out || k < 1 || k > DOT_RESULTS - 8 || b->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
   if (n_own <= 0 || n_own > c->ndofs) n_own = c->ndofs;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int rc = multi_dot_device(c, k, as, b, n_own, c->d_scratch, st);
-  if (rc != STFEM_OK) return rc == STFEM_ERR_HIP ? hip_fail(hipGetLastError(), "multi_dot") : rc;
-  STFEM_TRY(g_hip_error, hipMemcpyAsync(out, c->d_scratch, sizeof(double) * k, hipMemcpyDeviceToHost, st));
-  STFEM_TRY(g_hip_error, hipStreamSynchronize(st));
+  if (rc != STFEM_OK) return rc;
+  STFEM_TRY(hipMemcpyAsync(out, c->d_scratch, sizeof(double) * k, hipMemcpyDeviceToHost, st));
+  STFEM_TRY(hipStreamSynchronize(st));
   return STFEM_OK;
 }
 
@@ -324,10 +325,10 @@ int stfem_multi_axpy(stfem_ctx *c, int k, const double *coef, const stfem_vec *c
   if (y->nb > MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
   for (int i = 0; i < k; ++i) // a refused call modifies nothing: every vector is checked before the first launch
     if (!xs[i] || xs[i]->nb != y->nb || xs[i]->ctx != c || xs[i] == y) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = (unsigned)std::min<int64_t>((c->ndofs + 255) / 256, 2048);
-  (void)hipGetLastError();
+  stfem_launch_begin();
   for (int k0 = 0; k0 < k; k0 += DOT_VECS) {
     MultiAxpyArgs args;
     std::memset(&args, 0, sizeof(args));
@@ -340,7 +341,7 @@ int stfem_multi_axpy(stfem_ctx *c, int k, const double *coef, const stfem_vec *c
     }
     stfem_by_prec(c, [&](auto t) { hipLaunchKernelGGL(multi_axpy_kernel<decltype(t)>, dim3(grid, y->nb), dim3(256), 0, st, c->ndofs, args); });
   }
-  return hipGetLastError() == hipSuccess ? STFEM_OK : hip_fail(hipGetLastError(), "multi_axpy");
+  return stfem_launch_end("multi_axpy_kernel");
 }
 
 // One classical Gram-Schmidt pass of w against v_0 .. v_{k-1} entirely on the device: h = V^T w (two-stage reduction),
@@ -355,13 +356,13 @@ int stfem_orthogonalize(stfem_ctx *c, int k, const stfem_vec *const *vs, stfem_v
     if (vs[i] == w) return STFEM_ERR_ALIAS;
   }
   if (n_own <= 0 || n_own > c->ndofs) n_own = c->ndofs;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // slots of the scratch array: [0, k) coefficients, k: <w, w> before (rides in the same launch as the coefficients), k + 1: after
   std::vector<const stfem_vec *> all(vs, vs + k);
   if (norm2_before) all.push_back(w);
   int rc = multi_dot_device(c, int(all.size()), all.data(), w, n_own, c->d_scratch, st);
-  if (rc != STFEM_OK) return rc == STFEM_ERR_HIP ? hip_fail(hipGetLastError(), "orthogonalize") : rc;
+  if (rc != STFEM_OK) return rc;
   const unsigned grid = (unsigned)std::min<int64_t>((c->ndofs + 255) / 256, 2048);
   for (int k0 = 0; k0 < k; k0 += DOT_VECS) {
     MultiAxpyArgs args;
@@ -374,15 +375,15 @@ int stfem_orthogonalize(stfem_ctx *c, int k, const stfem_vec *const *vs, stfem_v
       for (int j = 0; j < w->nb; ++j) args.x[v][j] = vs[k0 + v]->blk[j];
     stfem_by_prec(c, [&](auto t) { hipLaunchKernelGGL(multi_axpy_kernel<decltype(t)>, dim3(grid, w->nb), dim3(256), 0, st, c->ndofs, args); });
   }
+  if ((rc = stfem_launch_end("multi_axpy_kernel")) != STFEM_OK) return rc; // (before multi_dot_device begins a sequence of its own)
   if (norm2_out) { // <w, w> after the projection, in the slot behind the coefficients
     const stfem_vec *ws[1] = {w};
     rc = multi_dot_device(c, 1, ws, w, n_own, c->d_scratch + k + 1, st);
-    if (rc != STFEM_OK) return rc == STFEM_ERR_HIP ? hip_fail(hipGetLastError(), "orthogonalize") : rc;
+    if (rc != STFEM_OK) return rc;
   }
-  if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "orthogonalize");
   std::vector<double> host(size_t(k) + 2);
-  STFEM_TRY(g_hip_error, hipMemcpyAsync(host.data(), c->d_scratch, sizeof(double) * (k + 2), hipMemcpyDeviceToHost, st));
-  STFEM_TRY(g_hip_error, hipStreamSynchronize(st));
+  STFEM_TRY(hipMemcpyAsync(host.data(), c->d_scratch, sizeof(double) * (k + 2), hipMemcpyDeviceToHost, st));
+  STFEM_TRY(hipStreamSynchronize(st));
   for (int i = 0; i < k; ++i) h_out[i] = host[i];
   if (norm2_before) *norm2_before = host[k];
   if (norm2_out) *norm2_out = host[k + 1];
@@ -438,10 +439,10 @@ __global__ __launch_bounds__(256) void axpby_many_kernel(T a, T b, const AxpbyMa
 int stfem_vector_axpby(stfem_ctx *c, double a, const stfem_vec *x, double b, stfem_vec *y, void *stream)
 {
   if (!c || !x || !y || x->ctx != c || y->ctx != c || x->nb != y->nb) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_driver_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = (unsigned)std::min<int64_t>((c->ndofs + 255) / 256, 4096);
-  (void)hipGetLastError();
+  stfem_launch_begin();
   for (int b0 = 0; b0 < x->nb; b0 += 8) {
     const int nb = std::min(8, x->nb - b0);
     AxpbyBlocks bl{};
@@ -454,7 +455,7 @@ int stfem_vector_axpby(stfem_ctx *c, double a, const stfem_vec *x, double b, stf
       hipLaunchKernelGGL(axpby_kernel<T>, dim3(grid, nb), dim3(256), 0, st, c->ndofs, T(a), T(b), bl);
     });
   }
-  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
+  return stfem_launch_end("axpby_kernel");
 }
 
 int stfem_axpby_many(stfem_ctx *c, int n_arrays, const int64_t *len, double a, const void *const *x, double b, void *const *y, void *stream)
@@ -462,9 +463,9 @@ int stfem_axpby_many(stfem_ctx *c, int n_arrays, const int64_t *len, double a, c
   if (!c || n_arrays < 0 || (n_arrays > 0 && (!len || !y || (a != 0.0 && !x)))) return STFEM_ERR_INVALID_ARGUMENT;
   for (int j = 0; j < n_arrays; ++j)
     if (len[j] < 0 || !y[j] || (a != 0.0 && !x[j])) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_driver_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  (void)hipGetLastError();
+  stfem_launch_begin();
   for (int b0 = 0; b0 < n_arrays; b0 += 8) {
     const int nb = std::min(8, n_arrays - b0);
     AxpbyMany v{};
@@ -482,20 +483,19 @@ int stfem_axpby_many(stfem_ctx *c, int n_arrays, const int64_t *len, double a, c
       hipLaunchKernelGGL(axpby_many_kernel<T>, dim3(grid, nb), dim3(256), 0, st, T(a), T(b), v);
     });
   }
-  return hipGetLastError() == hipSuccess ? STFEM_OK : STFEM_ERR_HIP;
+  return stfem_launch_end("axpby_many_kernel");
 }
 
 int stfem_vector_set_zero(stfem_ctx *c, stfem_vec *y, void *stream)
 {
   if (!c || !y || y->ctx != c) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_driver_err, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   const size_t bytes = size_t(c->ndofs) * c->es;
-  for (int j = 0; j < y->nb; ++j) STFEM_TRY(g_driver_err, hipMemsetAsync(y->blk[j], 0, bytes, static_cast<hipStream_t>(stream)));
+  for (int j = 0; j < y->nb; ++j) STFEM_TRY(hipMemsetAsync(y->blk[j], 0, bytes, static_cast<hipStream_t>(stream)));
   return STFEM_OK;
 }
 
-// the precision change between the solver's vectors and the multigrid's (GMG::vmult, stmg.h:1330-1343: copy_locally_owned_data_from);
-// errors: stfem_transfer_last_error
+// the precision change between the solver's vectors and the multigrid's (GMG::vmult, stmg.h:1330-1343: copy_locally_owned_data_from)
 namespace {
 template <typename TD, typename TS> __global__ void convert_kernel(TD *__restrict__ d, const TS *__restrict__ s, long long n)
 {
@@ -512,12 +512,11 @@ int stfem_vector_convert(stfem_vec *dst, const stfem_vec *src, void *stream)
   const int blocks = int(std::min<long long>((n + 255) / 256, 1 << 16));
   for (int b = 0; b < dst->nb; ++b) {
     const int pd = dst->ctx->prec, ps = src->ctx->prec;
-    if (pd == ps) STFEM_TRY(g_transfer_err, hipMemcpyAsync(dst->blk[b], src->blk[b], size_t(n) * dst->ctx->es, hipMemcpyDeviceToDevice, s));
+    if (pd == ps) STFEM_TRY(hipMemcpyAsync(dst->blk[b], src->blk[b], size_t(n) * dst->ctx->es, hipMemcpyDeviceToDevice, s));
     else if (pd == 1) convert_kernel<float, double><<<blocks, 256, 0, s>>>(static_cast<float *>(dst->blk[b]), static_cast<const double *>(src->blk[b]), n);
     else convert_kernel<double, float><<<blocks, 256, 0, s>>>(static_cast<double *>(dst->blk[b]), static_cast<const float *>(src->blk[b]), n);
   }
-  STFEM_TRY(g_transfer_err, hipGetLastError());
-  return STFEM_OK;
+  return stfem_launch_end("convert_kernel");
 }
 
 // ------------------------------------------------------------------------------------ plane exchange
@@ -532,10 +531,10 @@ __global__ __launch_bounds__(256) void plane_copy_kernel(int64_t n, const T *src
 int stfem_plane_pack(stfem_ctx *c, const stfem_vec *v, int iz, void *buf, void *stream)
 {
   if (!c || !v || !buf || iz < 0 || iz >= c->nd[2]) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   const int64_t plane = int64_t(c->nd[0]) * c->nd[1];
   for (int b = 0; b < v->nb; ++b)
-    STFEM_TRY(g_hip_error, hipMemcpyAsync(static_cast<char *>(buf) + size_t(b) * plane * c->es,
+    STFEM_TRY(hipMemcpyAsync(static_cast<char *>(buf) + size_t(b) * plane * c->es,
                            static_cast<const char *>(v->blk[b]) + size_t(plane) * iz * c->es, plane * c->es,
                            hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
   return STFEM_OK;
@@ -544,7 +543,7 @@ int stfem_plane_pack(stfem_ctx *c, const stfem_vec *v, int iz, void *buf, void *
 int stfem_plane_unpack(stfem_ctx *c, stfem_vec *v, int iz, const void *buf, int add, void *stream)
 {
   if (!c || !v || !buf || iz < 0 || iz >= c->nd[2]) return STFEM_ERR_INVALID_ARGUMENT;
-  STFEM_TRY(g_hip_error, hipSetDevice(c->device));
+  STFEM_TRY(hipSetDevice(c->device));
   const int64_t plane = int64_t(c->nd[0]) * c->nd[1];
   const unsigned grid = (unsigned)std::min<int64_t>((plane + 255) / 256, 4096);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -584,7 +583,7 @@ int stfem_planes_move(stfem_ctx *cs, const stfem_vec *src, int iz_src, stfem_ctx
   if (cs->nd[0] != cd->nd[0] || cs->nd[1] != cd->nd[1] || cs->prec != cd->prec || cs->device != cd->device || src->nb != dst->nb)
     return STFEM_ERR_SHAPE_MISMATCH;
   if (src->nb > MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
-  STFEM_TRY(g_hip_error, hipSetDevice(cd->device));
+  STFEM_TRY(hipSetDevice(cd->device));
   const int64_t plane = int64_t(cd->nd[0]) * cd->nd[1];
   PlanesMoveArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -595,6 +594,5 @@ int stfem_planes_move(stfem_ctx *cs, const stfem_vec *src, int iz_src, stfem_ctx
   const dim3 grid((unsigned)std::min<int64_t>((plane + 255) / 256, 1024), nplanes, src->nb);
   hipStream_t st = static_cast<hipStream_t>(stream);
   stfem_by_prec(cd, [&](auto t) { hipLaunchKernelGGL(planes_move_kernel<decltype(t)>, grid, dim3(256), 0, st, plane, nplanes, add_mask, a); });
-  if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "planes_move_kernel");
-  return STFEM_OK;
+  return stfem_launch_end("planes_move_kernel");
 }

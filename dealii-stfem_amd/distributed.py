@@ -132,7 +132,7 @@ class Communicator:
         h = C.c_void_p()
         rc = self._L.stfem_comm_create(C.create_string_buffer(raw, 128), rank, world, device, C.byref(h))
         if rc != 0:
-            raise RuntimeError(f"stfem_comm_create: status {rc}: {self._L.stfem_comm_last_error().decode()}")
+            raise RuntimeError(f"stfem_comm_create: status {rc}: {self._L.stfem_last_error().decode()}")
         self._h, self.rank, self.world = h, rank, world
 
     def close(self):
@@ -144,7 +144,7 @@ class Communicator:
 
     def _chk(self, rc, what):
         if rc != 0:
-            raise RuntimeError(f"{what}: status {rc}: {self._L.stfem_comm_last_error().decode()}")
+            raise RuntimeError(f"{what}: status {rc}: {self._L.stfem_last_error().decode()}")
 
     def ghost_update(self, ctx, vec, lower, upper, stream=None):
         self._chk(self._L.stfem_ghost_update(ctx._h, self._h, vec._h, lower, upper, stream), "stfem_ghost_update")

@@ -16,14 +16,13 @@ namespace stfem {
 inline void ghost_update(const Context &c, stfem_vec *v, void *stream)
 {
   if (c.partitioned())
-    Communicator::check_comm(stfem_ghost_update(c.h, c.comm->handle(), v, c.lower_rank, c.upper_rank, stream),
-                             "stfem_ghost_update");
+    check(stfem_ghost_update(c.h, c.comm->handle(), v, c.lower_rank, c.upper_rank, stream), "stfem_ghost_update");
 }
 inline void compress_add(const Context &c, stfem_vec *v, void *stream)
 {
   if (!c.partitioned()) return;
-  Communicator::check_comm(stfem_halo_begin(c.h, c.comm->handle(), v, c.lower_rank, c.upper_rank, stream), "stfem_halo_begin");
-  Communicator::check_comm(stfem_halo_end(c.h, c.comm->handle(), v, stream), "stfem_halo_end");
+  check(stfem_halo_begin(c.h, c.comm->handle(), v, c.lower_rank, c.upper_rank, stream), "stfem_halo_begin");
+  check(stfem_halo_end(c.h, c.comm->handle(), v, stream), "stfem_halo_end");
 }
 // BlockVector::operator* (an MPI_Allreduce in the reference): owned entries only, summed over the ranks
 template <typename Number> double dot(const BlockVectorT<Number> &a, const BlockVectorT<Number> &b, void *stream = nullptr)
@@ -31,8 +30,7 @@ template <typename Number> double dot(const BlockVectorT<Number> &a, const Block
   const Context &c = *a.context();
   double out = 0.0;
   if (c.comm)
-    Communicator::check_comm(stfem_dot_global(c.h, c.comm->handle(), a.handle(), b.handle(), c.n_owned(), &out, stream),
-                             "stfem_dot_global");
+    check(stfem_dot_global(c.h, c.comm->handle(), a.handle(), b.handle(), c.n_owned(), &out, stream), "stfem_dot_global");
   else
     check(stfem_dot(c.h, a.handle(), b.handle(), 0, &out, stream), "stfem_dot");
   return out;
@@ -295,13 +293,13 @@ public:
     const int rc = (neighbours && ctx_->extended)
                      ? stfem_vanka_create_partitioned_general(ctx_->h, ctx_->extended->h, int(Alpha.m()), a.data(), b.data(), neighbours, &v)
                      : stfem_vanka_create_partitioned(ctx_->h, int(Alpha.m()), a.data(), b.data(), neighbours, &v);
-    if (rc != STFEM_OK) throw Error(rc, std::string("stfem_vanka_create: ") + stfem_vanka_last_error());
+    if (rc != STFEM_OK) throw Error(rc, "stfem_vanka_create");
     v_.reset(v, stfem_vanka_destroy);
   }
   void vmult(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const
   {
     const int rc = stfem_vanka_vmult(v_.get(), dst.handle(), src.handle(), stream);
-    if (rc != STFEM_OK) throw Error(rc, std::string("PreconditionVanka::vmult: ") + stfem_vanka_last_error());
+    if (rc != STFEM_OK) throw Error(rc, "PreconditionVanka::vmult");
     compress_add(*ctx_, dst.handle(), stream); // partitioned: the interface planes hold partial sums (dst.compress(add) in the reference)
   }
   // dst = (accumulate ? dst : 0) + omega * vmult(src): the step of PreconditionRelaxation (stmg.h:1199-1238), fused into the
@@ -317,7 +315,7 @@ public:
       return;
     }
     const int rc = stfem_vanka_step(v_.get(), dst.handle(), omega, accumulate ? 1 : 0, src.handle(), stream);
-    if (rc != STFEM_OK) throw Error(rc, std::string("PreconditionVanka::step: ") + stfem_vanka_last_error());
+    if (rc != STFEM_OK) throw Error(rc, "PreconditionVanka::step");
     compress_add(*ctx_, dst.handle(), stream);
   }
   void smooth(BlockVectorType &u, const BlockVectorType &rhs) const { vmult(u, rhs); }

@@ -141,7 +141,7 @@ public:
     // z-slab partition (the same ranks below / above on both levels): the restriction leaves partial sums in the coarse interface planes
     const int neighbours = (fine->lower_rank >= 0 ? 16 : 0) | (fine->upper_rank >= 0 ? 32 : 0);
     const int rc = stfem_transfer_create_partitioned(fine->h, coarse->h, neighbours, &t);
-    if (rc != STFEM_OK) throw Error(rc, std::string("stfem_transfer_create: ") + stfem_transfer_last_error());
+    if (rc != STFEM_OK) throw Error(rc, "stfem_transfer_create");
     t_.reset(t, stfem_transfer_destroy);
   }
   stfem_transfer *handle() const { return t_.get(); }
@@ -632,7 +632,7 @@ private:
         throw;
       }
       const int rc = stfem_graph_end(stream_, &g);
-      if (rc != STFEM_OK) throw Error(rc, std::string("stfem_graph_end: ") + stfem_transfer_last_error());
+      if (rc != STFEM_OK) throw Error(rc, "stfem_graph_end");
       graph_.reset(g, stfem_graph_destroy);
       check(stfem_graph_launch(graph_.get(), stream_), "stfem_graph_launch");
     } else {

@@ -470,7 +470,7 @@ public:
     for (unsigned i = 0; i < nb_; ++i) var[i] = int32_t(blk_slice.decompose(i)[1]);
     stfem_stokes_vanka *v = nullptr;
     const int rc = stfem_stokes_vanka_create(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), &v);
-    if (rc != STFEM_OK) throw Error(rc, std::string("stfem_stokes_vanka_create: ") + stfem_stokes_vanka_last_error());
+    if (rc != STFEM_OK) throw Error(rc, "stfem_stokes_vanka_create");
     v_.reset(v, stfem_stokes_vanka_destroy);
   }
   // The smoother of the LINEARISED operator, one block per cell (reinit_asm, stmg.h:929-965: set_data(mg_data[l]), the assembled
@@ -490,7 +490,7 @@ public:
     const std::vector<const double *> l = linearization(solution_linearization);
     stfem_stokes_vanka *v = nullptr;
     const int rc = stfem_stokes_vanka_create_linearised(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), mode, l.data(), &v);
-    if (rc != STFEM_OK) throw Error(rc, std::string("stfem_stokes_vanka_create_linearised: ") + stfem_stokes_vanka_last_error());
+    if (rc != STFEM_OK) throw Error(rc, "stfem_stokes_vanka_create_linearised");
     v_.reset(v, stfem_stokes_vanka_destroy);
   }
   // the blocks again for a new linearisation vector (same treatment, same storage): the next Newton / Picard step
@@ -498,7 +498,7 @@ public:
   {
     const std::vector<const double *> l = linearization(solution_linearization);
     const int rc = stfem_stokes_vanka_update(v_.get(), l.data());
-    if (rc != STFEM_OK) throw Error(rc, std::string("stfem_stokes_vanka_update: ") + stfem_stokes_vanka_last_error());
+    if (rc != STFEM_OK) throw Error(rc, "stfem_stokes_vanka_update");
   }
   void vmult(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const { step(dst, 1.0, false, src, stream); }
   void smooth(BlockVectorType &u, const BlockVectorType &rhs) const { vmult(u, rhs); }
@@ -510,7 +510,7 @@ public:
     std::vector<const double *> s(nb_);
     for (unsigned i = 0; i < nb_; ++i) { d[i] = dst[i].data(); s[i] = src[i].data(); }
     const int rc = stfem_stokes_vanka_step(v_.get(), d.data(), omega, accumulate ? 1 : 0, s.data(), stream);
-    if (rc != STFEM_OK) throw Error(rc, std::string("PreconditionVankaStokes::vmult: ") + stfem_stokes_vanka_last_error());
+    if (rc != STFEM_OK) throw Error(rc, "PreconditionVankaStokes::vmult");
   }
   // the same on a vector that holds its blocks (StokesBlockVector): the smoother interface PreconditionRelaxation and the power iteration consume
   template <typename V> void vmult(V &dst, const V &src, void *stream = nullptr) const { step(dst.blocks(), 1.0, false, src.blocks(), stream); }

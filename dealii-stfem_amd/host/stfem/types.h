@@ -27,7 +27,7 @@ struct TraceRange {
 struct Error : std::runtime_error {
   int status;
   Error(int s, const std::string &what)
-    : std::runtime_error(what + ": " + stfem_strerror(s) + " [" + stfem_last_hip_error() + "]"), status(s) {}
+    : std::runtime_error(what + ": " + stfem_strerror(s) + " [" + stfem_last_error() + "]"), status(s) {}
 };
 inline void check(int status, const char *what)
 {
@@ -121,12 +121,12 @@ public:
   static UniqueId unique_id()
   {
     UniqueId id;
-    check_comm(stfem_comm_get_unique_id(id.data()), "stfem_comm_get_unique_id");
+    check(stfem_comm_get_unique_id(id.data()), "stfem_comm_get_unique_id");
     return id;
   }
   Communicator(const UniqueId &id, int rank, int world, int device)
   {
-    check_comm(stfem_comm_create(id.data(), rank, world, device, &h_), "stfem_comm_create");
+    check(stfem_comm_create(id.data(), rank, world, device, &h_), "stfem_comm_create");
   }
   ~Communicator() { stfem_comm_destroy(h_); }
   Communicator(const Communicator &) = delete;
@@ -134,12 +134,6 @@ public:
   int rank() const { return stfem_comm_rank(h_); }
   int size() const { return stfem_comm_size(h_); }
   stfem_comm *handle() const { return h_; }
-  static void check_comm(int status, const char *what)
-  {
-    if (status == STFEM_ERR_COMM || status == STFEM_ERR_UNSUPPORTED)
-      throw Error(status, std::string(what) + ": " + stfem_comm_last_error());
-    check(status, what);
-  }
 
 private:
   stfem_comm *h_ = nullptr;

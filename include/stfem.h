@@ -37,12 +37,12 @@ typedef enum {
   STFEM_OK = 0,
   STFEM_ERR_INVALID_ARGUMENT = -1,
   STFEM_ERR_UNSUPPORTED = -2, /* degree / block count / mode not built */
-  STFEM_ERR_HIP = -3,         /* a HIP runtime call failed: see stfem_last_hip_error */
+  STFEM_ERR_HIP = -3,         /* a HIP runtime call failed: see stfem_last_error */
   STFEM_ERR_NO_DEVICE = -4,
   STFEM_ERR_SHAPE_MISMATCH = -5,
   STFEM_ERR_ALIAS = -6, /* vmult(dst, src) with dst == src (reference forbids it too) */
   STFEM_ERR_OUT_OF_MEMORY = -7,
-  STFEM_ERR_COMM = -8 /* an RCCL call failed: see stfem_comm_last_error */
+  STFEM_ERR_COMM = -8 /* an RCCL call failed: see stfem_last_error */
 } stfem_status;
 
 typedef struct stfem_ctx stfem_ctx; /* replaces MatrixFree + MatrixFreeOperator state */
@@ -194,7 +194,6 @@ int stfem_comm_available(void);
 int stfem_comm_rccl_count(const stfem_comm *comm);
 int stfem_comm_rank(const stfem_comm *comm);
 int stfem_comm_size(const stfem_comm *comm);
-const char *stfem_comm_last_error(void);
 /* src.update_ghost_values(): the top plane of every block <- the upper neighbour's bottom plane.
  * Enqueued on `stream` (the transfer itself runs on the communicator's own stream in between). */
 int stfem_ghost_update(stfem_ctx *ctx, stfem_comm *comm, stfem_vec *v, int lower_rank, int upper_rank,
@@ -266,7 +265,6 @@ void stfem_transfer_destroy(stfem_transfer *t);
 int stfem_transfer_prolongate(stfem_transfer *t, stfem_vec *dst_fine, const stfem_vec *src_coarse, int add, void *stream);
 int stfem_transfer_restrict(stfem_transfer *t, stfem_vec *dst_coarse, const stfem_vec *src_fine, int add, void *stream);
 int stfem_transfer_interpolate(stfem_transfer *t, stfem_vec *dst_coarse, const stfem_vec *src_fine, void *stream);
-const char *stfem_transfer_last_error(void);
 /* diagnostics: {the last prolongation ran its y and z passes as one fused kernel (0 / 1), most coarse cells one thread marched
  * through in the last restriction along y, the same along z (0: table-driven pass)} */
 int stfem_transfer_last_path(const stfem_transfer *t, int32_t out[3]);
@@ -283,7 +281,7 @@ int stfem_vector_convert(stfem_vec *dst, const stfem_vec *src, void *stream);
  * is recorded, not run (calls that allocate or synchronise - vector_create, dot, upload, the first use of an operator on a
  * context - are not allowed in between: run the sequence once before recording it); graph_end returns the instantiated
  * graph; graph_launch replays it on `stream` with the vectors (device pointers) it was recorded with.  Errors:
- * stfem_transfer_last_error. */
+ * stfem_last_error. */
 typedef struct stfem_graph stfem_graph;
 int stfem_stream_create(void **stream_out);
 void stfem_stream_destroy(void *stream);
@@ -326,7 +324,6 @@ int stfem_vanka_vmult(stfem_vanka *v, stfem_vec *dst, const stfem_vec *src, void
 /* dst = (accumulate ? dst : 0) + omega * V src: the step x <- x + omega P^-1 r of PreconditionRelaxation around the smoother
  * (include/stmg.h:1199-1238) fused into the smoother's scatter - no temporary vector, no separate update pass. */
 int stfem_vanka_step(stfem_vanka *v, stfem_vec *dst, double omega, int accumulate, const stfem_vec *src, void *stream);
-const char *stfem_vanka_last_error(void);
 
 /* Around the operator, for the slab driver (include/time_integrators.h, tests/tp_01.cc:382-400, 646-725,
  * include/exact_solution.h:503-649).  The caller evaluates its functions at the points and hands the values in
@@ -359,7 +356,6 @@ int stfem_vector_set_zero(stfem_ctx *ctx, stfem_vec *y, void *stream);
  * zero-factor rules of stfem_vector_axpby (x may be NULL when a = 0).  For vectors whose blocks differ in length - the velocity and
  * pressure blocks of the Stokes system (BlockVectorT::sadd / equ / = 0 over all blocks of a two-variable vector) */
 int stfem_axpby_many(stfem_ctx *ctx, int n_arrays, const int64_t *len, double a, const void *const *x, double b, void *const *y, void *stream);
-const char *stfem_driver_last_error(void);
 /* QGauss(n) on [0, 1]; the support points of the temporal basis, get_time_quad (fe_time.cc:152-161): QGaussLobatto(r + 1)
  * for cG(r) (type 0), QGaussRadau(r + 1, right) for dG(r) (type 1); r + 1 values */
 int stfem_gauss_rule(int n, double *points, double *weights);
@@ -523,7 +519,6 @@ int stfem_stokes_cip_add(stfem_stokes_ctx *ctx, double *dst_u, const double *src
 int64_t stfem_stokes_n_face_points(const stfem_stokes_ctx *ctx);
 int stfem_stokes_face_points(const stfem_stokes_ctx *ctx, double *out);
 int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *ctx, const double *g_at_face_points, double *dst_u, double *dst_p, void *stream);
-const char *stfem_stokes_last_hip_error(void);
 /* diagnostics: {tiles, workgroups} as stfem_last_sweep_plan of the last velocity sweep (pencil sweep of the scalar FE_Q(2) context:
  * box meshes), and whether that sweep of the last vmult added the pressure gradient itself (1) or the gradient kernel ran (0) */
 int stfem_stokes_last_sweep_plan(const stfem_stokes_ctx *ctx, int32_t out[3]);
@@ -570,7 +565,7 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
  * the device; the apply streams every block from HBM once (kpad * mpad * 8 bytes per cell: 70 kB at 89 rows).
  * Refusals, decided before anything touches the device, *out = NULL: a mode outside 0..2 or a null lin_blocks (entry of a velocity
  * block) with a mode other than 0: STFEM_ERR_INVALID_ARGUMENT; more than 8 blocks or 512 rows: STFEM_ERR_UNSUPPORTED.  Blocks that do
- * not fit beside the free device memory: STFEM_ERR_OUT_OF_MEMORY, the sizes in stfem_stokes_vanka_last_error.
+ * not fit beside the free device memory: STFEM_ERR_OUT_OF_MEMORY, the sizes in stfem_last_error.
  * update: stages the same set-up again into the existing block storage for new linearisation states (same mode);
  * STFEM_ERR_UNSUPPORTED for the class blocks of stfem_stokes_vanka_create on a box.  n_classes: the cell count.  Not built: fp32
  * blocks, the CIP term in the blocks (stfem_stokes_set_cip: the smoother is that of the operator without it) and outflow_penalty,
@@ -585,11 +580,18 @@ int stfem_stokes_vanka_setup_batches(const stfem_stokes_vanka *v);
 int stfem_stokes_vanka_vmult(stfem_stokes_vanka *v, double *const *dst_blocks, const double *const *src_blocks, void *stream);
 int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, double omega, int accumulate, const double *const *src_blocks,
                             void *stream);
-const char *stfem_stokes_vanka_last_error(void);
 
 const char *stfem_strerror(int status);
-/* text of the last failing HIP call on this thread ("" if none) */
+/* the reason of the most recent failing call on this thread that had one; not cleared by a success ("" if none yet) */
+const char *stfem_last_error(void);
+/* synonyms of stfem_last_error, kept for existing callers: the same record */
 const char *stfem_last_hip_error(void);
+const char *stfem_comm_last_error(void);
+const char *stfem_transfer_last_error(void);
+const char *stfem_vanka_last_error(void);
+const char *stfem_driver_last_error(void);
+const char *stfem_stokes_last_hip_error(void);
+const char *stfem_stokes_vanka_last_error(void);
 /* Named trace ranges (roctx, bound at run time: no-ops without the profiler's library or with STFEM_TRACE=0).  The library
  * opens "vmult" / "Tvmult" around stfem_st_vmult and "vanka" around stfem_vanka_vmult - the names of the reference's
  * TimerOutput scopes (operators.h:539, 564, 590; stmg.h:835); callers add their own ("gmg", stmg.h:1335; "step"). */

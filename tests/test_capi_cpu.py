@@ -116,3 +116,27 @@ def test_no_silent_cpu_fallback(stfem):
         pytest.skip("GPU present")
     with pytest.raises(stfem.StfemError):
         stfem.MatrixFreeOperator(2, (2, 2, 2))
+
+
+ACCESSORS = ("stfem_last_error", "stfem_last_hip_error", "stfem_comm_last_error", "stfem_transfer_last_error", "stfem_vanka_last_error",
+             "stfem_driver_last_error", "stfem_stokes_last_hip_error", "stfem_stokes_vanka_last_error")
+
+
+def test_failure_reason_behind_every_accessor(stfem):
+    """Without a GPU a stream cannot be created: the reason of that failure is what all eight accessors return and what
+    StfemError prints (one record for the library, whichever unit the failing call lives in)."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    L = stfem.lib()
+    s = C.c_void_p()
+    assert L.stfem_stream_create(C.byref(s)) == -3
+    texts = {getattr(L, name)() for name in ACCESSORS}
+    assert len(texts) == 1
+    text = texts.pop().decode()
+    assert text.startswith("hipStreamCreate") and len(text) > len("hipStreamCreate(&s): ")
+    raw = C.CDLL(stfem.LIB_PATH)
+    for name in ACCESSORS:
+        getattr(raw, name).restype = C.c_void_p
+    assert len({getattr(raw, name)() for name in ACCESSORS}) == 1  # the same pointer
+    assert text in str(stfem.StfemError(-3, "x"))

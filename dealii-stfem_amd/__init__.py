@@ -115,6 +115,7 @@ SIGNATURES = {
     "stfem_time_prolongation_matrix": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int32)]),
     "stfem_time_restriction_matrix": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int32)]),
     "stfem_time_projection_matrix": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int32)]),
+    "stfem_time_evaluation_matrix": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int32)]),
     "stfem_poly_mg_sequence": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "stfem_mg_sequence": (C.c_int, [C.c_int] * 5 + [C.c_char] + [C.c_int] * 4 + [C.c_char_p, C.POINTER(C.c_int32)]),
     "stfem_precondition_stmg_types": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
@@ -186,6 +187,8 @@ SIGNATURES = {
     "stfem_stokes_pressure_quadrature_points": (C.c_int, [_vp, C.c_int, _dp]),
     "stfem_stokes_pressure_difference": (C.c_int, [_vp, C.c_int, _vp, _dp, _dp, _vp]),
     "stfem_stokes_divergence": (C.c_int, [_vp, _vp, _vp, _dp, _vp]),
+    "stfem_stokes_drag_lift_n_items": (C.c_int64, [_vp, C.c_int]),
+    "stfem_stokes_drag_lift": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _vp, _dp, _vp]),
     "stfem_stokes_dgp_prolongate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "stfem_stokes_dgp_restrict": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "stfem_stokes_vanka_create": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.POINTER(_vp)]),
@@ -255,6 +258,12 @@ def get_time_restriction_matrix(ttype, r, n_timesteps_at_once=2):
 def get_time_projection_matrix(ttype, r_src, r_dst, n_timesteps_at_once=1):
     """fe_time.h:749-803"""
     return _time_transfer(lib().stfem_time_projection_matrix, ttype, r_src, r_dst, n_timesteps_at_once)
+
+
+def get_time_evaluation_matrix(ttype, r, samples_per_interval):
+    """fe_time.h:308-326 for the basis of get_time_basis(ttype, r): [samples_per_interval, r + 1], the temporal basis at
+    s / (samples_per_interval - 1).  For cG the first column belongs to the step's initial value."""
+    return _time_transfer(lib().stfem_time_evaluation_matrix, ttype, r, samples_per_interval)
 
 
 def get_fe_time_weights(ttype, r, time_step_size=1.0, n_timesteps_at_once=1):
@@ -791,6 +800,13 @@ def get_fe_time_weights_stokes(type_, r, time_step_size, n_timesteps_at_once=1):
     return Alpha, Beta, Gamma, Zeta
 
 
+def _face_mask(faces):
+    """bit mask of a set of boundary ids 0..5 (face 2 d + s); an int is taken as the mask itself"""
+    if isinstance(faces, (int, np.integer)):
+        return int(faces)
+    return sum(1 << int(f) for f in set(faces))
+
+
 # The Navier-Stokes modes of StokesMatrixFreeOperator (OperatorMode::form / jacobian, operators.h:1288-1297): the `mode` of vmult,
 # st_vmult and st_vmult_slice_add; 0 is the linear operator
 CONVECTION_NONE, CONVECTION_FORM, CONVECTION_JACOBIAN = 0, 1, 2
@@ -984,6 +1000,50 @@ class StokesMatrixFreeOperator:
             dptr = None if cells is False or cells is None else getattr(cells, "ptr", cells)
         _check(lib().stfem_stokes_divergence(self._h, getattr(u, "ptr", u), dptr, C.byref(total), stream), "stfem_stokes_divergence")
         return (total.value, scratch.download()[:self.n_cells].copy()) if scratch is not None else total.value
+
+    def drag_lift_n_items(self, faces):
+        """work items of drag_lift: the pairs (face of `faces`, boundary cell of that face)"""
+        n = lib().stfem_stokes_drag_lift_n_items(self._h, _face_mask(faces))
+        if n < 0:
+            raise StfemError(int(n), "stfem_stokes_drag_lift_n_items")
+        return int(n)
+
+    def drag_lift(self, u, p, faces, scale=1.0, plain=False, items=False, stream=None):
+        """StokesMatrixFreeOperator::compute_drag_lift (operators.h:1344-1389): scale * sum over the boundary faces `faces` (ids
+        0..5, face 2 d + s: the reference's obstacle_id; or the bit mask) of int (p n - nu (grad u + grad u^T) n) dA at the 3 x 3 face
+        Gauss points -> [3].  u, p: one device velocity and pressure vector, or two lists of the same length -> [n, 3] from one call.
+        plain=False reads velocity entries on strongly constrained DoFs as 0 (the reference), plain=True as stored.
+        items=True: (force, item values [n_items, 3] or [n, n_items, 3]): the unscaled force of every (face, boundary cell) pair,
+        faces ascending, the cells of a face with the lower tangential axis fastest."""
+        single = not isinstance(u, (list, tuple))
+        if isinstance(p, (list, tuple)) == single or (not single and len(u) != len(p)):
+            raise ValueError("drag_lift: u and p are one pair or two lists of the same length")
+        us, ps = ([u], [p]) if single else (list(u), list(p))
+        n, mask = len(us), _face_mask(faces)
+        U = [getattr(v, "ptr", v) for v in us]
+        P = [getattr(v, "ptr", v) for v in ps]
+        out = np.zeros((max(n, 1), 3))
+
+        def call(first, count, d_items):
+            o = np.zeros((max(count, 1), 3))
+            _check(lib().stfem_stokes_drag_lift(self._h, mask, float(scale), int(bool(plain)), count, (_vp * max(count, 1))(*U[first:first + count]),
+                                                (_vp * max(count, 1))(*P[first:first + count]), d_items, _p(o), stream), "stfem_stokes_drag_lift")
+            out[first:first + max(count, 1)] = o
+
+        if not items:
+            call(0, n, None)
+            return out[0] if single else out
+        # a velocity vector holds the item values (n_items < n_velocity on every mesh): as many pairs per call as fit into it;
+        # how the pairs are grouped changes no bit of a result
+        nitems = self.drag_lift_n_items(mask)
+        scratch = StokesVector(self, 0)
+        per_call = max(self.n_velocity // nitems, 1)
+        it = np.zeros((max(n, 1), nitems, 3))
+        for first in range(0, max(n, 1), per_call):
+            count = min(per_call, n - first)
+            call(first, count, scratch.ptr)
+            it[first:first + count] = scratch.download()[:count * nitems * 3].reshape(count, nitems, 3)
+        return (out[0], it[0]) if single else (out, it)
 
     def pressure_mean_vectors(self):
         """(ones, weights, volume): coefficients of p = 1, (1, psi_j), and the volume: mean(p) = weights . p / volume"""

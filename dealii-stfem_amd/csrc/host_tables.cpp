@@ -536,6 +536,17 @@ Mat mass_like(const std::vector<double> &rows, const std::vector<double> &cols, 
 }
 } // namespace
 
+int time_evaluation(int type, int r, int samples, Mat &out, int &m, int &n)
+{
+  if ((type != 0 && type != 1) || r < (type == 0 ? 1 : 0) || r > 8 || samples < 2) return -1;
+  const double sample_step = 1.0 / (samples - 1);
+  std::vector<double> x(samples);
+  for (int s = 0; s < samples; ++s) x[s] = s * sample_step;
+  out = lagrange_at(time_nodes(type, r), x);
+  m = samples; n = r + 1;
+  return 0;
+}
+
 int time_prolongation(int type, int r, int nsteps, Mat &out, int &m, int &n)
 {
   if ((type != 0 && type != 1) || r < (type == 0 ? 1 : 0) || r > 8 || nsteps < 2 || (nsteps & (nsteps - 1))) return -1;

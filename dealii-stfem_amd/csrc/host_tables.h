@@ -57,6 +57,8 @@ int fe_time_weights_wave(int type, int r, double tau, int nsteps, Mat &A_lhs, Ma
 int time_prolongation(int type, int r, int nsteps, Mat &out, int &m, int &n);
 int time_restriction(int type, int r, int nsteps, Mat &out, int &m, int &n);
 int time_projection(int type, int r_src, int r_dst, int nsteps, Mat &out, int &m, int &n);
+// get_time_evaluation_matrix (fe_time.h:308-326) of the basis of get_time_basis(type, r): samples x (r + 1), the basis at s / (samples - 1)
+int time_evaluation(int type, int r, int samples, Mat &out, int &m, int &n);
 
 // ---- level schedule of the space-time multigrid (fe_time.cc:17-150); levels are 't' (tau), 'k', 'h', 'p' like MGType ----
 // get_poly_mg_sequence: sequence_type 0 = bisect, 1 = decrease_by_one, 2 = go_to_one; coarsest first

@@ -82,6 +82,13 @@ int stfem_time_projection_matrix(int type, int r_src, int r_dst, int n_timesteps
   const int rc = time_projection(type, r_src, r_dst, n_timesteps_at_once, M, m, n);
   return time_transfer_out(rc, M, m, n, out, dims);
 }
+int stfem_time_evaluation_matrix(int type, int r, int samples_per_interval, double *out, int32_t dims[2])
+{
+  Mat M;
+  int m = 0, n = 0;
+  const int rc = time_evaluation(type, r, samples_per_interval, M, m, n);
+  return time_transfer_out(rc, M, m, n, out, dims);
+}
 
 int stfem_fe_time_weights(int type, int r, double tau, int ns, double *Alpha, double *Beta,
                           double *Gamma, double *Zeta)

@@ -189,6 +189,7 @@ void stfem_stokes_destroy(stfem_stokes_ctx *c)
   if (c->d_pq) (void)hipFree(c->d_pq);
   if (c->d_pred) (void)hipFree(c->d_pred);
   if (c->d_div) (void)hipFree(c->d_div);
+  if (c->d_trac) (void)hipFree(c->d_trac);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   delete c;

@@ -1,5 +1,5 @@
 // What the translation units of the Stokes two-field operator share (stfem_stokes.hip and stfem_stokes_{cell,coupling,boundary,
-// pressure,convection,cip,divergence}.hip): the description of a launch, the context and the launchers.  Not part of the boundary.
+// pressure,convection,cip,divergence,traction}.hip): the description of a launch, the context and the launchers.  Not part of the boundary.
 #pragma once
 #include "stfem_internal.h"
 
@@ -140,6 +140,8 @@ struct stfem_stokes_ctx {
   size_t pq_points = 0;
   double *d_pred = nullptr;            // its reduction results
   double *d_div = nullptr;             // cell values and their sum of stfem_stokes_divergence (n_cells + 1), made on demand
+  double *d_trac = nullptr;            // item values and their sums of stfem_stokes_drag_lift (trac_cap doubles), made on demand
+  size_t trac_cap = 0;
   // weak (Nitsche) / outflow boundary faces (operators.h:1206-1211): bit f = 2 d + s
   int weak_mask = 0, outflow_mask = 0;
   double penalty1 = 20.0, penalty2 = 10.0;

@@ -64,5 +64,11 @@ FullMatrix<Number> get_time_projection_matrix(TimeStepType type, unsigned r_src,
   return time_transfer_matrix<Number>(stfem_time_projection_matrix, "get_time_projection_matrix", int(type), int(r_src), int(r_dst),
                                       int(n_timesteps_at_once));
 }
+// fe_time.h:308-326 for the basis of get_time_basis(type, r): samples_per_interval x (r + 1), the basis at s / (samples - 1).  For cG
+// the first column belongs to the step's initial value (tests/tp_03stokes.cc:927-935 prepends the previous end value).
+template <typename Number = double> FullMatrix<Number> get_time_evaluation_matrix(TimeStepType type, unsigned r, unsigned samples_per_interval)
+{
+  return time_transfer_matrix<Number>(stfem_time_evaluation_matrix, "get_time_evaluation_matrix", int(type), int(r), int(samples_per_interval));
+}
 
 } // namespace stfem

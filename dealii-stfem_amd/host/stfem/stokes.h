@@ -255,6 +255,41 @@ public:
     check(stfem_stokes_divergence(h_, velocity.data(), nullptr, &total, stream), "stfem_stokes_divergence");
     return total;
   }
+  // operators.h:1344-1389: scale * sum over the boundary faces of obstacle_id of int (p n - nu (grad u + grad u^T) n) dA for the pair
+  // src = {velocity, pressure}, the reference's argument order.  Velocity entries on strongly constrained DoFs read as 0 as in the
+  // reference (read_dof_values, 1366); plain = true reads them as stored (inhomogeneous strong data).  Slabs: every rank leaves its
+  // interface faces out of obstacle_id and the ranks' results add (the reference's MPI sum, 1387).
+  std::array<Number, 3> compute_drag_lift(const BlockVectorType &src, const std::set<boundary_id> &obstacle_id, Number scale,
+                                          bool plain = false, void *stream = nullptr) const
+  {
+    return compute_drag_lift(std::vector<const StokesVector *>{&src.at(0)}, std::vector<const StokesVector *>{&src.at(1)}, obstacle_id, scale,
+                             plain, stream)[0];
+  }
+  // several (velocity, pressure) pairs in one call - the time DoFs of a slab, tests/tp_03stokes.cc:936-966: bit for bit what the calls
+  // with one pair give, the face geometry evaluated once for (up to four of) them
+  std::vector<std::array<Number, 3>> compute_drag_lift(const std::vector<const StokesVector *> &velocities,
+                                                       const std::vector<const StokesVector *> &pressures,
+                                                       const std::set<boundary_id> &obstacle_id, Number scale, bool plain = false,
+                                                       void *stream = nullptr) const
+  {
+    if (velocities.size() != pressures.size()) throw Error(STFEM_ERR_SHAPE_MISMATCH, "compute_drag_lift: velocities and pressures");
+    int faces = 0;
+    for (boundary_id f : obstacle_id) {
+      if (f > 5) throw Error(STFEM_ERR_INVALID_ARGUMENT, "compute_drag_lift: boundary id above 5");
+      faces |= 1 << f;
+    }
+    const size_t n = velocities.size();
+    std::vector<const double *> u(n), p(n);
+    for (size_t i = 0; i < n; ++i) {
+      u[i] = velocities[i] ? velocities[i]->data() : nullptr;
+      p[i] = pressures[i] ? pressures[i]->data() : nullptr;
+    }
+    std::vector<std::array<Number, 3>> f(n);
+    static_assert(sizeof(std::array<Number, 3>) == 3 * sizeof(double), "out is [n][3]");
+    check(stfem_stokes_drag_lift(h_, faces, scale, plain ? 1 : 0, int(n), u.data(), p.data(), nullptr, n ? f[0].data() : nullptr, stream),
+          "stfem_stokes_drag_lift");
+    return f;
+  }
   unsigned long long m() const { return 3ull * stfem_stokes_n_velocity_dofs(h_) + stfem_stokes_n_pressure_dofs(h_); }
   stfem_stokes_ctx *handle() const { return h_; }
 

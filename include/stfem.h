@@ -228,6 +228,13 @@ int stfem_dot_global(stfem_ctx *ctx, stfem_comm *comm, const stfem_vec *a, const
 int stfem_time_prolongation_matrix(int type, int r, int n_timesteps_at_once, double *out, int32_t dims[2]);
 int stfem_time_restriction_matrix(int type, int r, int n_timesteps_at_once, double *out, int32_t dims[2]);
 int stfem_time_projection_matrix(int type, int r_src, int r_dst, int n_timesteps_at_once, double *out, int32_t dims[2]);
+/* get_time_evaluation_matrix (include/fe_time.h:308-326) for the basis of get_time_basis(type, r) (fe_time.cc:164-169: the Lagrange
+ * polynomials on the Gauss-Lobatto (cG) / right Gauss-Radau (dG) points of stfem_fe_time_points): row-major dims[0] x dims[1] =
+ * samples_per_interval x (r + 1), entry (s, j) = basis function j at s / (samples_per_interval - 1).  Applied to the per-DoF values of
+ * a functional it gives the time series over one step (tests/tp_03stokes.cc:908-913, 968-970).  For cG the first basis function
+ * belongs to the step's initial value: the caller prepends the previous end value (tp_03stokes.cc:927-935).  `out` may be NULL to ask
+ * for the dimensions only.  cG: r >= 1, dG: r >= 0, r <= 8, samples_per_interval >= 2. */
+int stfem_time_evaluation_matrix(int type, int r, int samples_per_interval, double *out, int32_t dims[2]);
 
 /* Level schedule of the space-time multigrid (include/fe_time.cc:17-150).  Transfer kinds are the characters of the
  * reference's MGType: 't' (tau: half the time steps per slab), 'k' (temporal degree), 'h' (mesh), 'p' (spatial degree);
@@ -385,7 +392,7 @@ int stfem_coefficient_per_cell(const int32_t ncell[3], const double *vertices, d
 /* ---- Stokes two-field operator (BASELINE configs[4]): the cell loop (LoopType::Cell, include/operators.h:1228-1229) and,
  * after stfem_stokes_set_weak_boundaries below, the weak (Nitsche) boundary faces of operators.h:1662-1751; the convection modes of the
  * Navier-Stokes operator (OperatorMode::form / jacobian) through the *_convection entry points below; the divergence functional
- * (compute_divergence) through stfem_stokes_divergence; the CIP interior-face term (delta0 != 0, 1603-1638) after
+ * (compute_divergence) through stfem_stokes_divergence, the boundary force (compute_drag_lift) through stfem_stokes_drag_lift; the CIP interior-face term (delta0 != 0, 1603-1638) after
  * stfem_stokes_set_cip.  Not built: the outflow penalty (beta, 1705-1709).  Velocity FE_Q(2)^3, pressure FE_Q(1) (stfem_stokes_create)
  * or FE_DGP(1) (stfem_stokes_create_ex), QGauss(3), MappingQ1 on the mesh of `mesh`; mesh->dirichlet_mask constrains the velocity
  * (homogeneous), the pressure is unconstrained.  fp64.
@@ -472,6 +479,33 @@ int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *ctx, int mode, 
  * kernel for boxes and general meshes; the sums have a fixed order (no atomics): two calls agree bit for bit.  Synchronises `stream`.
  * A null u or total is STFEM_ERR_INVALID_ARGUMENT, decided before anything touches the device. */
 int stfem_stokes_divergence(stfem_stokes_ctx *ctx, const double *u, double *cell_out, double *total, void *stream);
+/* StokesMatrixFreeOperator::compute_drag_lift (operators.h:1344-1389): the force on boundary faces.  For every pair (u[i], p[i]) of
+ * device vectors, i < n, one velocity and one pressure of this context:
+ *   out[3 i + k] = scale sum_{f in face_mask} sum_{boundary cells of f} sum_{q < 9} ( p n - nu (grad u + grad u^T) n )_k JxW_face
+ * - the reference's tau (1372-1377) integrated by integrate_value (1379), nu the context's viscosity, at the operator's 3 x 3 face
+ * Gauss points; n the outward unit normal (J^-T e_d normalised, signed by the side) and JxW_face the face area element times the
+ * weights, both as on the weak faces; grad u the full physical gradient at the face point with the cell's own Jacobian.
+ *   face_mask: bit f = 2 d + s like dirichlet_mask and weak_mask, 1..63 - the reference's obstacle_id set on the colorized box.  Which
+ *       boundary condition a face carries plays no part (the reference tests the boundary id only, 1363).
+ *   read_plain: 0 = velocity entries on strongly constrained DoFs read as 0 (read_dof_values, 1366 - the reference, and what every
+ *       vmult here does); 1 = as stored (read_dof_values_plain, like stfem_stokes_divergence): for inhomogeneous strong data.  The
+ *       pressure is read as stored, FE_Q(1) or FE_DGP(1).
+ *   work items: the pairs (face in face_mask, boundary cell of that face) in the order of stfem_stokes_face_points: faces ascending, the
+ *       cells of a face lexicographic with the lower tangential axis fastest; a cell on two selected faces is two items.  n_items
+ *       counts them.  item_out (device, n * n_items * 3 doubles, or NULL) receives [i][item][3], the UNSCALED force of every item:
+ *       the wall force cell by cell, the counterpart of cell_out of the divergence.
+ *   out: host, [n][3].
+ * One kernel for boxes and general meshes, then one workgroup summing the items; up to four pairs share one launch of each (an item's
+ * geometry is computed once for them), more run in groups of four.  Fixed summation order, no atomics: two calls agree bit for bit,
+ * and a call with n pairs gives bit for bit what n calls with one pair give.  Synchronises `stream` once, to read the 3 n sums.
+ * Slabs need nothing new: a z-slab is a mesh of its own, the caller leaves its interface faces out of face_mask and adds the slabs'
+ * results (the reference's Utilities::MPI::sum, 1387).
+ * STFEM_ERR_INVALID_ARGUMENT with its reason in stfem_last_error, decided before anything touches the device and with `out` untouched:
+ * a null ctx, u, p, out, u[i] or p[i]; n < 1; face_mask outside 1..63; a non-finite scale.  n_items returns that status too for a
+ * null ctx or such a mask. */
+int64_t stfem_stokes_drag_lift_n_items(const stfem_stokes_ctx *ctx, int face_mask);
+int stfem_stokes_drag_lift(stfem_stokes_ctx *ctx, int face_mask, double scale, int read_plain, int n, const double *const *u,
+                           const double *const *p, double *item_out, double *out, void *stream);
 /* Weak boundary conditions of StokesMatrixFreeOperator (reference include/operators.h:1206-1211, 1220-1221, 1640-1741) and
  * StokesNitscheMatrixFreeOperator (1768-1951), linear operator (NonlinearTreatment::None).
  * Faces are numbered f = 2 d + s (direction d, side s: 0 = lower, 1 = upper; bit f of the masks) - the boundary ids of deal.II's

@@ -27,19 +27,26 @@ struct StokesSpaces {
     check(stfem_stokes_pressure_ctx(stokes, &pc), "stfem_stokes_pressure_ctx");
     q1 = std::make_shared<Context>(pc, false);
     q1->degree = 1;
+    int32_t nd[3];
+    check(stfem_n_dofs_1d(pc, nd), "stfem_n_dofs_1d");
+    carrier = nd[0] != mesh.ncell[0] + 1 || nd[1] != mesh.ncell[1] + 1 || nd[2] != mesh.ncell[2] + 1; // (FE_DGP(1): 2 x 2 x n_cells)
   }
   // z-slab partition (the mesh is this rank's slab, interface faces taken out of its Dirichlet mask): the operator leaves partial
   // sums in the interface planes of every velocity component and of the pressure (tests/test_gpu_stokes.py::
   // test_stokes_on_z_slabs_equals_whole_mesh); StokesSystem::vmult completes them with the scalar spaces' add-exchange
-  // (stfem_halo_begin / end), inner products count owned planes only (stfem_dot_global) - as for the scalar operators
+  // (stfem_halo_begin / end), inner products count owned planes only (stfem_dot_global) - as for the scalar operators.  FE_DGP(1)
+  // pressure DoFs are cell-local: nothing to exchange and every entry owned, and the "planes" of the carrier context are the DoFs of
+  // the slab's first and last cell - it gets the communicator (its inner products are summed over the ranks) and no neighbours
   void set_partition(const std::shared_ptr<Communicator> &comm, int lower_rank, int upper_rank)
   {
     for (auto &c : {q2, q1}) {
+      const bool exchanges = c == q2 || !carrier;
       c->comm = comm;
-      c->lower_rank = lower_rank;
-      c->upper_rank = upper_rank;
+      c->lower_rank = exchanges ? lower_rank : -1;
+      c->upper_rank = exchanges ? upper_rank : -1;
     }
   }
+  bool carrier = false; // q1 is the FE_DGP(1) carrier context
 };
 
 // BlockVectorT over a two-variable BlockSlice (LinearAlgebra::distributed::BlockVector with velocity and pressure blocks)

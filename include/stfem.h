@@ -545,8 +545,15 @@ int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *ctx, int weak_mask, int o
  * blocks WITHOUT it, whatever set_cip says (the class blocks of a box are probed on a context of their own, the per-cell blocks
  * assembled by their own kernel): the smoother is that of the operator without the stabilisation - a preconditioner of a flexible
  * method.  Eight colour launches, no atomics, fixed summation order: two calls agree bit for bit.  Not built: the term on multigrid
- * levels and in the Vanka blocks, fp32, slab partitioning of these launches, the derivative of delta_F with respect to w (the
- * reference has none either). */
+ * levels and in the Vanka blocks, fp32, the derivative of delta_F with respect to w (the reference has none either).
+ * On a z-slab of a partitioned mesh (interface faces out of the Dirichlet mask, the weak set and the outflow set) every other launch
+ * of the operator - cell, coupling, boundary and convection launches, vector mass, nitsche_rhs, divergence, drag_lift - is cell-local
+ * and leaves partial sums in the interface planes, which the add-exchange of the scalar views completes (the velocity components on
+ * a FE_Q(2) context of the slab, the FE_Q(1) pressure on stfem_stokes_pressure_ctx; FE_DGP(1) pressure DoFs are cell-local and the
+ * carrier context must not be exchanged).  NOT partitioned: this term - a face in an interface plane needs the cells of the
+ * neighbour slab, which a slab context does not hold, so with delta0 != 0 the slabs' sums lack the interface faces - and the
+ * per-cell layout of the two-variable Vanka smoother (stfem_stokes_vanka_create_linearised), whose blocks next to an interface
+ * would need the neighbour's cells as the scalar smoother's ghost layers provide them. */
 enum { STFEM_CIP_WEIGHT_SOURCE = 0, STFEM_CIP_WEIGHT_LINEARISATION = 1 };
 int stfem_stokes_set_cip(stfem_stokes_ctx *ctx, double delta0, int weight);
 int stfem_stokes_cip_add(stfem_stokes_ctx *ctx, double *dst_u, const double *src_u, const double *weight_u, double delta0, void *stream);

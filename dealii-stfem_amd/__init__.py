@@ -193,6 +193,8 @@ SIGNATURES = {
     "stfem_stokes_dgp_restrict": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "stfem_stokes_vanka_create": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.POINTER(_vp)]),
     "stfem_stokes_vanka_create_linearised": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.c_int, C.POINTER(_vp), C.POINTER(_vp)]),
+    "stfem_stokes_vanka_create_linearised_cip": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.c_int, C.POINTER(_vp), C.c_double,
+                                                 C.POINTER(_vp)]),
     "stfem_stokes_vanka_update": (C.c_int, [_vp, C.POINTER(_vp)]),
     "stfem_stokes_vanka_destroy": (None, [_vp]),
     "stfem_stokes_vanka_n_classes": (C.c_int, [_vp]),
@@ -857,7 +859,7 @@ class StokesMatrixFreeOperator:
 
     def set_cip(self, delta0, weight=CIP_WEIGHT_SOURCE):
         """The CIP gradient-jump term sum_F int_F delta0 h_F^2 / 2^3.5 (w.n)^2 [d_n u].[d_n v] on the interior faces in every later
-        vmult / st_vmult / st_vmult_slice_add (not mass_vmult, not the Vanka blocks).  weight: CIP_WEIGHT_SOURCE (w = the source, as
+        vmult / st_vmult / st_vmult_slice_add (not mass_vmult; the Vanka blocks take a delta0 of their own, StokesPreconditionVanka).  weight: CIP_WEIGHT_SOURCE (w = the source, as
         the reference has it) or CIP_WEIGHT_LINEARISATION (w = `lin` where a convection mode is given).  delta0 = 0: no launch."""
         _check(lib().stfem_stokes_set_cip(self._h, float(delta0), int(weight)), "stfem_stokes_set_cip")
         self.delta0, self.cip_weight = float(delta0), int(weight)
@@ -1070,17 +1072,23 @@ class StokesPreconditionVanka:
     block_variable[i] = 0 (velocity) / 1 (pressure) for the blocks in BlockSlice order; Alpha, Beta: the matrices of
     get_fe_time_weights_stokes.  per_cell=True or a convection mode builds one block per cell from the operator linearised about
     `lin` (reinit_asm, stmg.h:929-965): device vectors in BlockSlice order like those of st_vmult, only the velocity entries are read
-    (pressure entries may be None); update(lin) rebuilds the blocks for new states.  The defaults are the class blocks of a box (one
-    block per cell on a general mesh)."""
+    (pressure entries may be None); update(lin) rebuilds the blocks for new states.  delta0 != 0 (implies one block per cell): the
+    blocks hold the CIP term C(lin_j; .) too, weighted by the linearisation state of the column block in every mode
+    (stfem_stokes_vanka_create_linearised_cip); update keeps that delta0.  The defaults are the class blocks of a box (one block per
+    cell on a general mesh)."""
 
-    def __init__(self, op, block_variable, Alpha, Beta, lin=None, mode=0, per_cell=False):
+    def __init__(self, op, block_variable, Alpha, Beta, lin=None, mode=0, per_cell=False, delta0=0.0):
         self.op = op
         self.nb = len(block_variable)
         bv = (C.c_int32 * self.nb)(*[int(v) for v in block_variable])
         A = np.ascontiguousarray(Alpha, dtype=np.float64); B = np.ascontiguousarray(Beta, dtype=np.float64)
         assert A.shape == (self.nb, self.nb) and B.shape == (self.nb, self.nb)
         h = _vp()
-        if per_cell or mode != 0:
+        if delta0 != 0.0:
+            rc = lib().stfem_stokes_vanka_create_linearised_cip(op._h, self.nb, bv, _p(A), _p(B), int(mode), self._lin(lin), float(delta0),
+                                                                C.byref(h))
+            what = "stfem_stokes_vanka_create_linearised_cip"
+        elif per_cell or mode != 0:
             rc = lib().stfem_stokes_vanka_create_linearised(op._h, self.nb, bv, _p(A), _p(B), int(mode), self._lin(lin), C.byref(h))
             what = "stfem_stokes_vanka_create_linearised"
         else:

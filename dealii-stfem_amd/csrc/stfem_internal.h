@@ -102,6 +102,7 @@ struct stokes_cell_vanka_desc {
   int nblk, m, mpad, kpad, mode;
   int var[8];                 // 0 velocity / 1 pressure, in BlockSlice order
   double Alpha[64], Beta[64]; // nblk x nblk, row-major
+  double delta0;              // CIP term C(b_j; .) in the velocity-velocity entries (0: none; otherwise `lin` is read in every mode)
 };
 struct stokes_cell_vanka;
 // row table: nblk-block rows -> (vector | variable << 8, element offset from the cell's first DoF of the variable), m entries of two ints

@@ -22,41 +22,6 @@
 
 namespace {
 
-// J^-1 and det J of the trilinear mapping of cell (cx, cy, cz) at the reference point xi
-__device__ __forceinline__ void cip_jacobian(const CipParams &prm, int cx, int cy, int cz, const double xi[3], double Ji[3][3], double &det)
-{
-  const double fx[2] = {1 - xi[0], xi[0]}, fy[2] = {1 - xi[1], xi[1]}, fz[2] = {1 - xi[2], xi[2]}, dd[2] = {-1.0, 1.0};
-  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  const long long nvx = prm.ncx + 1, nvy = prm.ncy + 1;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const double *V = prm.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-          const double Ve = V[e];
-          J[e][0] += Ve * dd[i] * fy[j] * fz[k];
-          J[e][1] += Ve * fx[i] * dd[j] * fz[k];
-          J[e][2] += Ve * fx[i] * fy[j] * dd[k];
-        }
-      }
-  det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-        J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-  const double id = 1.0 / det;
-  Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
-  Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-  Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-  Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
-  Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-  Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-  Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
-  Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-  Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-}
-
 // One half-wave per cell, 256 threads = 8 cells at a time, the cells of one colour dealt round-robin to the half-waves
 // (the layout of stokes_inflow_kernel).  The reference-space derivatives of the 27 shape functions at the nine points of the six
 // faces are tabulated in LDS once per workgroup (sT[e][f][q][n]; CART keeps d/d xi_d alone: 11.4 KB, otherwise all three: 34 KB).
@@ -80,14 +45,9 @@ __global__ __launch_bounds__(256) void stokes_cip_kernel(const CipParams prm)
   __syncthreads();
   for (int i = threadIdx.x; i < 6 * 9 * 27; i += 256) {
     const int n = i % 27, q = (i / 27) % 9, f = i / 243;
-    const int d = f >> 1, s = f & 1, t1 = d == 0 ? 1 : 0;
-    const int ka = n % 3, kb = (n / 3) % 3, kc = n / 9, qa = q % 3, qb = q / 3;
-    // (selects, no arrays indexed at run time: those would live in scratch)
-    const int t2 = d == 2 ? 1 : 2;
-    const int kd = d == 0 ? ka : (d == 1 ? kb : kc), k1 = t1 == 0 ? ka : kb, k2 = t2 == 1 ? kb : kc;
-    const double vd = tE[s * 3 + kd], v1 = tS[qa * 3 + k1], v2 = tS[qb * 3 + k2];
-    const double gd = tED[s * 3 + kd] * v1 * v2, gt1 = vd * tD[qa * 3 + k1] * v2, gt2 = vd * v1 * tD[qb * 3 + k2];
-    const double g0 = d == 0 ? gd : gt1, g1 = d == 1 ? gd : (d == 0 ? gt1 : gt2), g2 = d == 2 ? gd : gt2;
+    const int d = f >> 1;
+    double g0, g1, g2;
+    cip_face_gradient(tS, tD, tE, tED, f, q, n, g0, g1, g2);
     if constexpr (CART) {
       sT[0][f][q][n] = d == 0 ? g0 : (d == 1 ? g1 : g2);
     } else {
@@ -271,6 +231,20 @@ __global__ __launch_bounds__(256) void stokes_cip_kernel(const CipParams prm)
 
 } // namespace
 
+void stokes_cip_end_tables(double Eu[6], double EDu[6])
+{
+  static const std::vector<double> ends_tables = [] {
+    const stfem::ShapeTables tu = stfem::make_shape_tables(2);
+    const std::vector<double> ends = {0.0, 1.0};
+    stfem::Mat E, ED;
+    stfem::lagrange_tables(tu.nodes, ends, E, ED);
+    std::vector<double> r(12);
+    for (int i = 0; i < 6; ++i) { r[i] = E[i]; r[6 + i] = ED[i]; }
+    return r;
+  }();
+  for (int i = 0; i < 6; ++i) { Eu[i] = ends_tables[i]; EDu[i] = ends_tables[6 + i]; }
+}
+
 int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, hipStream_t st)
 {
   if (delta0 == 0.0) return STFEM_OK;
@@ -283,18 +257,7 @@ int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double
   k.Nu = prm.Nu;
   k.dmask = prm.dmask;
   for (int i = 0; i < 9; ++i) { k.Su[i] = prm.Su[i]; k.Du[i] = prm.Du[i]; }
-  { // FE_Q(2) values / derivatives at the end points 0 and 1, [s * 3 + a]
-    static const std::vector<double> ends_tables = [] {
-      const stfem::ShapeTables tu = stfem::make_shape_tables(2);
-      const std::vector<double> ends = {0.0, 1.0};
-      stfem::Mat E, ED;
-      stfem::lagrange_tables(tu.nodes, ends, E, ED);
-      std::vector<double> r(12);
-      for (int i = 0; i < 6; ++i) { r[i] = E[i]; r[6 + i] = ED[i]; }
-      return r;
-    }();
-    for (int i = 0; i < 6; ++i) { k.Eu[i] = ends_tables[i]; k.EDu[i] = ends_tables[6 + i]; }
-  }
+  stokes_cip_end_tables(k.Eu, k.EDu);
   k.colour = 0; k.cart = prm.cart;
   k.detJ = prm.detJ;
   k.scale = delta0 / (8.0 * std::sqrt(2.0)); // pa = degree^3.5, degree 2 (operators.h:1614-1615)

@@ -170,8 +170,65 @@ __device__ __forceinline__ void wave_fence()
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// What the CIP kernel of the operator (stfem_stokes_cip.hip) and the CIP cell matrices of the per-cell Vanka blocks
+// (stfem_stokes_vanka_cell.hip) share.
+// J^-1 and det J of the trilinear mapping of cell (cx, cy, cz) at the reference point xi (Params: vertices, ncx, ncy)
+template <typename Params>
+__device__ __forceinline__ void cip_jacobian(const Params &prm, int cx, int cy, int cz, const double xi[3], double Ji[3][3], double &det)
+{
+  const double fx[2] = {1 - xi[0], xi[0]}, fy[2] = {1 - xi[1], xi[1]}, fz[2] = {1 - xi[2], xi[2]}, dd[2] = {-1.0, 1.0};
+  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  const long long nvx = prm.ncx + 1, nvy = prm.ncy + 1;
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const double *V = prm.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+          const double Ve = V[e];
+          J[e][0] += Ve * dd[i] * fy[j] * fz[k];
+          J[e][1] += Ve * fx[i] * dd[j] * fz[k];
+          J[e][2] += Ve * fx[i] * fy[j] * dd[k];
+        }
+      }
+  det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
+        J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+  const double id = 1.0 / det;
+  Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
+  Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
+  Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
+  Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
+  Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
+  Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
+  Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
+  Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
+  Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+}
+
+// The face tables: (g0, g1, g2) = d phi_n / d xi_e of FE_Q(2) node n at point q = q1 + 3 q2 (lower tangential axis fastest) of face
+// f = 2 d + s, from the 1D tables tS / tD [q * 3 + a] at the Gauss points and tE / tED [s * 3 + a] at the end points 0 and 1
+__device__ __forceinline__ void cip_face_gradient(const double *tS, const double *tD, const double *tE, const double *tED, int f, int q, int n,
+                                                  double &g0, double &g1, double &g2)
+{
+  const int d = f >> 1, s = f & 1, t1 = d == 0 ? 1 : 0;
+  const int ka = n % 3, kb = (n / 3) % 3, kc = n / 9, qa = q % 3, qb = q / 3;
+  // (selects, no arrays indexed at run time: those would live in scratch)
+  const int t2 = d == 2 ? 1 : 2;
+  const int kd = d == 0 ? ka : (d == 1 ? kb : kc), k1 = t1 == 0 ? ka : kb, k2 = t2 == 1 ? kb : kc;
+  const double vd = tE[s * 3 + kd], v1 = tS[qa * 3 + k1], v2 = tS[qb * 3 + k2];
+  const double gd = tED[s * 3 + kd] * v1 * v2, gt1 = vd * tD[qa * 3 + k1] * v2, gt2 = vd * v1 * tD[qb * 3 + k2];
+  g0 = d == 0 ? gd : gt1;
+  g1 = d == 1 ? gd : (d == 0 ? gt1 : gt2);
+  g2 = d == 2 ? gd : gt2;
+}
+
 #pragma GCC visibility push(hidden) // (the library exports what include/stfem.h declares)
 
+// FE_Q(2) values / derivatives at the end points 0 and 1, [s * 3 + a] (stfem_stokes_cip.hip)
+void stokes_cip_end_tables(double Eu[6], double EDu[6]);
 // The eight colour launches of the cell kernel (general meshes; stfem_stokes_cell.hip)
 int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st);
 // The coupling kernels (stfem_stokes_coupling.hip): out_u -= sum_s wKu B^T p_s; out_p (=, +=) sum_s wKp B u_s.  A failed launch is

@@ -109,6 +109,7 @@ struct stfem_stokes_vanka {
   int2 *d_rowtab = nullptr;
   int *d_cellu = nullptr, *d_cellp = nullptr, *d_cls = nullptr, *d_slot = nullptr;
   int mode = 0;                      // convection mode of the per-cell blocks
+  double delta0 = 0.0;               // their CIP term (stfem_stokes_vanka_create_linearised_cip)
   stokes_cell_vanka *cell = nullptr; // one block per cell (stfem_stokes_vanka_cell.hip): none of the class arrays above
 };
 
@@ -351,8 +352,9 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
 // One block per cell, on every mesh, of the operator linearised about lin_blocks (reinit_asm, stmg.h:929-965: set_data, then the
 // assembled matrix of compute_matrix_helper<OperatorMode::jacobian>, operators.h:1310-1318, and one inverted block per cell from it,
 // stmg.h:704-742, compute_block_matrix.h:50-139).  Every refusal is decided before anything touches the device.
-int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta,
-                                         int mode, const double *const *lin_blocks, stfem_stokes_vanka **out)
+// delta0 != 0: with the CIP term C(b_j; .) in the velocity-velocity entries (stfem_stokes_vanka_create_linearised_cip)
+static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta, int mode,
+                           const double *const *lin_blocks, double delta0, stfem_stokes_vanka **out)
 {
   if (!out) return STFEM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
@@ -382,6 +384,8 @@ int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, co
   stokes_cell_vanka_desc cd;
   std::memset(&cd, 0, sizeof(cd));
   v->mode = mode;
+  v->delta0 = delta0;
+  cd.delta0 = delta0;
   cd.nblk = n_blocks; cd.m = v->m; cd.mpad = v->mpad; cd.kpad = v->kpad; cd.mode = mode;
   for (int i = 0; i < n_blocks; ++i) cd.var[i] = v->var[i];
   for (int i = 0; i < n_blocks * n_blocks; ++i) { cd.Alpha[i] = Alpha[i]; cd.Beta[i] = Beta[i]; }
@@ -391,12 +395,37 @@ int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, co
   return rc;
 }
 
+int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta,
+                                         int mode, const double *const *lin_blocks, stfem_stokes_vanka **out)
+{
+  return create_per_cell(ctx, n_blocks, block_variable, Alpha, Beta, mode, lin_blocks, 0.0, out);
+}
+
+// The same blocks of the operator WITH the CIP term (stfem_stokes_set_cip, weight STFEM_CIP_WEIGHT_LINEARISATION): K = the assembled
+// A(b_j) + C(b_j; .), the weight velocity of C the linearisation state of the column block - in every mode, so lin_blocks is needed even
+// with mode 0.  delta0 == 0 is stfem_stokes_vanka_create_linearised.
+int stfem_stokes_vanka_create_linearised_cip(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha,
+                                             const double *Beta, int mode, const double *const *lin_blocks, double delta0, stfem_stokes_vanka **out)
+{
+  if (!out) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_vanka_create_linearised_cip: out is null");
+  *out = nullptr;
+  if (!std::isfinite(delta0)) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_vanka_create_linearised_cip: delta0 is not finite");
+  if (delta0 == 0.0) return stfem_stokes_vanka_create_linearised(ctx, n_blocks, block_variable, Alpha, Beta, mode, lin_blocks, out);
+  if (!lin_blocks)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_vanka_create_linearised_cip: delta0 = %g needs lin_blocks, the weight velocity of the term", delta0);
+  if (block_variable && n_blocks >= 1 && n_blocks <= VK_MAX_BLOCKS)
+    for (int i = 0; i < n_blocks; ++i)
+      if (block_variable[i] == 0 && !lin_blocks[i])
+        return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_vanka_create_linearised_cip: delta0 = %g and lin_blocks[%d] of a velocity block is null", delta0, i);
+  return create_per_cell(ctx, n_blocks, block_variable, Alpha, Beta, mode, lin_blocks, delta0, out);
+}
+
 // The blocks of a smoother of stfem_stokes_vanka_create_linearised again, for new linearisation states: same mode, same storage
 int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_blocks)
 {
   if (!v) return STFEM_ERR_INVALID_ARGUMENT;
   if (!v->cell) return STFEM_ERR_UNSUPPORTED; // (class blocks hold the linear operator only)
-  if (v->mode != STFEM_CONVECTION_NONE) {
+  if (v->mode != STFEM_CONVECTION_NONE || v->delta0 != 0.0) { // (the CIP term keeps the delta0 of creation and reads its weight from lin_blocks)
     if (!lin_blocks) return STFEM_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < v->nblk; ++i)
       if (v->var[i] == 0 && !lin_blocks[i]) return STFEM_ERR_INVALID_ARGUMENT;

@@ -219,8 +219,143 @@ __global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesC
   }
 }
 
+constexpr int CIP_CELL = 27 * 7 * 27; // doubles of a cell's CIP matrix
+
+struct StokesCipCellParams {
+  const double *vertices; // (nc + 1)^3 x 3
+  const double *w;        // weight velocity (3 Nu, component-major)
+  double *Cc;             // [cell of the window][27 rows][7 column groups][27]
+  int ncx, ncy, ncz, ndu[3];
+  long long Nu, cell0;    // first cell of the window
+  int dmask;
+  double Su[9], Du[9], Eu[6], EDu[6]; // the 1D tables of CipParams
+  double xq[3], wq[3];
+  double hinv[3], detJ;   // CART
+  double scale;           // delta0 / pa
+};
+
+// The CIP term C(w; .) of stfem_stokes_cip.hip in plain matrix form, scalar (the term is component-diagonal), cell-centric like
+// stokes_cip_kernel: one workgroup per cell; the rows are the cell's own 27 test functions ("adds only its own side's test
+// contribution"), column group 0 the cell's own 27 nodes, summed over its interior faces in the order 0..5, column group 1 + f the 27
+// nodes of the neighbour behind face f, with the minus sign of the jump (zeros behind a boundary face).  Geometry, normal, JxW, h_F
+// and w are those of the cell's own side, exactly as stokes_cip_kernel takes them; entries of w on strongly constrained DoFs read as 0,
+// u carries no constraint (the assembly applies them).  Per face: nine threads take the geometry of the nine points, 243 the normal
+// derivatives of the 27 nodes of both sides, then every thread up to three of the 729 entries.  Set-up code: not tuned.
+template <bool CART>
+__global__ __launch_bounds__(256) void stokes_cip_cell_matrices_kernel(const StokesCipCellParams P)
+{
+  __shared__ double tS[9], tD[9], tE[6], tED[6];
+  __shared__ double sW[81];
+  __shared__ double sGO[9][3], sGN[9][3], sJxW[9], sWN[9]; // J^-1 n of this side and of the neighbour's, JxW, w.n
+  __shared__ double sDO[9][27], sDN[9][27];                // d_n phi_n at the points: this side, the neighbour's
+  const int tid = threadIdx.x;
+  const long long cell = P.cell0 + blockIdx.x;
+  const int cx = int(cell % P.ncx), cy = int((cell / P.ncx) % P.ncy), cz = int(cell / ((long long)P.ncx * P.ncy));
+  double *Cc = P.Cc + (size_t)blockIdx.x * CIP_CELL;
+  if (tid < 9) { tS[tid] = P.Su[tid]; tD[tid] = P.Du[tid]; }
+  if (tid < 6) { tE[tid] = P.Eu[tid]; tED[tid] = P.EDu[tid]; }
+  if (tid < 81) { // read_dof_values: entries on strongly constrained DoFs read as 0
+    const int comp = tid / 27, n = tid % 27;
+    const int ix = 2 * cx + n % 3, iy = 2 * cy + (n / 3) % 3, iz = 2 * cz + n / 9;
+    sW[tid] = constrained_u(P, ix, iy, iz) ? 0.0 : P.w[comp * P.Nu + ix + (long long)P.ndu[0] * (iy + (long long)P.ndu[1] * iz)];
+  }
+  __syncthreads();
+  double own0 = 0.0, own1 = 0.0, own2 = 0.0; // entries tid, tid + 256, tid + 512 of column group 0
+#pragma unroll
+  for (int f = 0; f < 6; ++f) {
+    const int d = f >> 1, s = f & 1, t1 = d == 0 ? 1 : 0;
+    const int cd = d == 0 ? cx : (d == 1 ? cy : cz), ncd = d == 0 ? P.ncx : (d == 1 ? P.ncy : P.ncz);
+    if (!(s ? cd < ncd - 1 : cd > 0)) { // a boundary face (uniform)
+      for (int e = tid; e < 729; e += 256) Cc[(e / 27) * 189 + (1 + f) * 27 + e % 27] = 0.0;
+      continue;
+    }
+    if (tid < 9) { // the geometry of face point tid, both sides, and w.n
+      const int q1 = tid % 3, q2 = tid / 3;
+      double go[3] = {0, 0, 0}, gnb[3] = {0, 0, 0}, nrm[3] = {0, 0, 0}, JxW;
+      if constexpr (CART) {
+        nrm[d] = 1.0;
+        go[d] = gnb[d] = P.hinv[d];
+        JxW = P.detJ * P.hinv[d] * P.wq[q1] * P.wq[q2];
+      } else {
+        double xi[3], Ji[3][3], det;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xi[k] = k == d ? double(s) : P.xq[k == t1 ? q1 : q2];
+        cip_jacobian(P, cx, cy, cz, xi, Ji, det);
+        double len = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { nrm[k] = Ji[d][k]; len += nrm[k] * nrm[k]; } // J^-T e_d
+        len = sqrt(len);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) nrm[k] /= len;
+        JxW = fabs(det) * len * P.wq[q1] * P.wq[q2];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) go[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
+        xi[d] = double(1 - s);
+        cip_jacobian(P, cx + (d == 0 ? (s ? 1 : -1) : 0), cy + (d == 1 ? (s ? 1 : -1) : 0), cz + (d == 2 ? (s ? 1 : -1) : 0), xi, Ji, det);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) gnb[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
+      }
+      double wval[3] = {0, 0, 0}; // w at the point: the nine nodes of the face
+#pragma unroll
+      for (int j2 = 0; j2 < 3; ++j2)
+#pragma unroll
+        for (int j1 = 0; j1 < 3; ++j1) {
+          const int k0 = d == 0 ? 2 * s : (t1 == 0 ? j1 : j2), k1 = d == 1 ? 2 * s : (t1 == 1 ? j1 : j2), k2 = d == 2 ? 2 * s : j2;
+          const double phi = tS[q1 * 3 + j1] * tS[q2 * 3 + j2];
+#pragma unroll
+          for (int c3 = 0; c3 < 3; ++c3) wval[c3] = fma(phi, sW[c3 * 27 + k0 + 3 * k1 + 9 * k2], wval[c3]);
+        }
+#pragma unroll
+      for (int e = 0; e < 3; ++e) { sGO[tid][e] = go[e]; sGN[tid][e] = gnb[e]; }
+      sJxW[tid] = JxW;
+      sWN[tid] = wval[0] * nrm[0] + wval[1] * nrm[1] + wval[2] * nrm[2];
+    }
+    __syncthreads();
+    if (tid < 243) { // the normal derivative of node n at point q: this side (face f) and the neighbour's (face f ^ 1)
+      const int q = tid / 27, n = tid % 27;
+      double g0, g1, g2;
+      cip_face_gradient(tS, tD, tE, tED, f, q, n, g0, g1, g2);
+      sDO[q][n] = sGO[q][0] * g0 + sGO[q][1] * g1 + sGO[q][2] * g2;
+      cip_face_gradient(tS, tD, tE, tED, f ^ 1, q, n, g0, g1, g2);
+      sDN[q][n] = sGN[q][0] * g0 + sGN[q][1] * g1 + sGN[q][2] * g2;
+    }
+    __syncthreads();
+    double area = 0.0; // h_F^2 = the face's area: the nine JxW in point order
+#pragma unroll
+    for (int q = 0; q < 9; ++q) area += sJxW[q];
+    double cq[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) cq[q] = P.scale * area * sWN[q] * sWN[q] * sJxW[q];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int e = tid + 256 * k;
+      if (e < 729) {
+        const int a = e / 27, b = e % 27;
+        double so = 0.0, sn = 0.0;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+          const double t = cq[q] * sDO[q][a];
+          so = fma(t, sDO[q][b], so);
+          sn = fma(t, sDN[q][b], sn);
+        }
+        if (k == 0) own0 += so;
+        else if (k == 1) own1 += so;
+        else own2 += so;
+        Cc[a * 189 + (1 + f) * 27 + b] = -sn;
+      }
+    }
+    __syncthreads(); // the next face rewrites the tables
+  }
+  Cc[(tid / 27) * 189 + tid % 27] = own0;
+  Cc[((tid + 256) / 27) * 189 + (tid + 256) % 27] = own1;
+  if (tid + 512 < 729) Cc[((tid + 512) / 27) * 189 + (tid + 512) % 27] = own2;
+}
+
 struct StokesAssembleParams {
   const double *Ac, *Mc;    // cell matrices of the cell layers [zw0, ...): Ac[state][cell of the window][nl][nl], Mc[cell][27][27]
+  const double *Cc;         // CIP matrices Cc[state][cell of the window][27][7][27]; nullptr: no CIP term
+  size_t cip_stride;        // doubles between the states of Cc
+  int selc[VK_MAX_BLOCKS];  // the state of Cc of every column block
   size_t state_stride;      // doubles between the states of Ac
   double *B;                // [cell of the batch][m][m]
   const int *nbr, *face;    // vanka::CellDofTables
@@ -274,6 +409,32 @@ __global__ __launch_bounds__(256) void stokes_vanka_assemble_kernel(const Stokes
         const size_t c2 = size_t(cx + sh % 3 - 1) + size_t(P.nc[0]) * (size_t(cy + (sh / 3) % 3 - 1) + size_t(P.nc[1]) * size_t(cz + sh / 9 - 1 - P.zw0));
         ks += A[c2 * nl2 + size_t(a2) * P.nl + b2];
         if (mass) ms += P.Mc[c2 * 729 + (a2 % 27) * 27 + b2 % 27];
+      }
+      if (P.Cc && mass) {
+        // the assembled CIP matrix: every patch cell K' = K + sh holding a adds its own-side rows - its column group 0 when it holds b
+        // too, and for each of its interior faces f the group 1 + f when the neighbour behind that face is a patch cell holding b
+        // (only patch cells hold b).  Shifts ascending, group 0 first, faces 0..5: a fixed order.
+        const double *Cs = P.Cc + size_t(P.selc[j]) * P.cip_stride;
+        double cs = 0.0;
+        for (int sh = 0; sh < 27; ++sh) {
+          const int a2 = P.nbr[a * 27 + sh];
+          if (a2 < 0 || !has_cell(sh)) continue;
+          const int sx = sh % 3 - 1, sy = (sh / 3) % 3 - 1, sz = sh / 9 - 1;
+          const size_t c2 = size_t(cx + sx) + size_t(P.nc[0]) * (size_t(cy + sy) + size_t(P.nc[1]) * size_t(cz + sz - P.zw0));
+          const double *row = Cs + c2 * CIP_CELL + size_t(a2 % 27) * 189;
+          const int b2 = P.nbr[b * 27 + sh];
+          if (b2 >= 0) cs += row[b2 % 27];
+          for (int f = 0; f < 6; ++f) {
+            const int fd = f >> 1, e = (f & 1) ? 1 : -1;
+            const int tx = sx + (fd == 0 ? e : 0), ty = sy + (fd == 1 ? e : 0), tz = sz + (fd == 2 ? e : 0);
+            if (tx < -1 || tx > 1 || ty < -1 || ty > 1 || tz < -1 || tz > 1) continue;
+            const int sh2 = (tx + 1) + 3 * (ty + 1) + 9 * (tz + 1);
+            if (!has_cell(sh2)) continue;
+            const int b3 = P.nbr[b * 27 + sh2];
+            if (b3 >= 0) cs += row[(1 + f) * 27 + b3 % 27];
+          }
+        }
+        ks += cs;
       }
       const double al = P.Alpha[i * P.nblk + j], be = P.Beta[i * P.nblk + j];
       if (be != 0.0 && P.var[i] == 0 && P.var[j] == 0) out += be * ms; // M_mask(0, 0) only
@@ -379,8 +540,13 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
   int sel[VK_MAX_BLOCKS];
   const double *state[VK_MAX_BLOCKS];
   const int nstates = vanka::distinct_states(d.nblk, d.var, d.mode ? lin : nullptr, sel, state);
+  // the CIP term: a weight velocity per distinct state of `lin`, whatever the mode; a mesh without interior faces has none
+  const bool cip = d.delta0 != 0.0 && (ncx > 1 || ncy > 1 || ncz > 1);
+  int selc[VK_MAX_BLOCKS];
+  const double *weight[VK_MAX_BLOCKS];
+  const int ncip = cip ? vanka::distinct_states(d.nblk, d.var, lin, selc, weight) : 0;
   const size_t nl2 = size_t(nl) * nl;
-  const size_t km_layer = (size_t(nstates) * nl2 + 729) * cpl * sizeof(double), b_layer = cpl * size_t(m) * m * sizeof(double);
+  const size_t km_layer = (size_t(nstates) * nl2 + 729 + size_t(ncip) * CIP_CELL) * cpl * sizeof(double), b_layer = cpl * size_t(m) * m * sizeof(double);
   STFEM_TRY(hipSetDevice(c->device));
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
@@ -401,17 +567,19 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
     if (rc != STFEM_OK) return rc;
   }
   const size_t win_cells = cpl * size_t(std::min(ncz, L + 2));
-  double *d_A = nullptr, *d_M = nullptr, *d_B = nullptr;
+  double *d_A = nullptr, *d_M = nullptr, *d_B = nullptr, *d_C = nullptr;
   int *d_flag = nullptr;
   auto cleanup = [&]() {
     (void)hipFree(d_A);
     (void)hipFree(d_M);
     (void)hipFree(d_B);
+    (void)hipFree(d_C);
     (void)hipFree(d_flag);
   };
   int rc = vk_alloc(reinterpret_cast<void **>(&d_A), size_t(nstates) * win_cells * nl2 * sizeof(double));
   if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_M), win_cells * 729 * sizeof(double));
   if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_B), cpl * L * size_t(m) * m * sizeof(double));
+  if (rc == STFEM_OK && cip) rc = vk_alloc(reinterpret_cast<void **>(&d_C), size_t(ncip) * win_cells * CIP_CELL * sizeof(double));
   if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_flag), sizeof(int));
   if (rc != STFEM_OK) {
     cleanup();
@@ -432,6 +600,21 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
   ap.dmask = c->dmask; ap.nl = nl; ap.m = m; ap.nblk = d.nblk;
   for (int i = 0; i < d.nblk; ++i) { ap.var[i] = d.var[i]; ap.sel[i] = sel[i]; }
   for (int i = 0; i < d.nblk * d.nblk; ++i) { ap.Alpha[i] = d.Alpha[i]; ap.Beta[i] = d.Beta[i]; }
+  StokesCipCellParams cp;
+  std::memset(&cp, 0, sizeof(cp));
+  if (cip) {
+    const StokesParams &b = c->base;
+    cp.vertices = c->d_vertices;
+    cp.ncx = ncx; cp.ncy = ncy; cp.ncz = ncz;
+    for (int k = 0; k < 3; ++k) { cp.ndu[k] = c->ndu[k]; cp.xq[k] = b.xq[k]; cp.wq[k] = b.wq[k]; cp.hinv[k] = b.hinv[k]; }
+    for (int i = 0; i < 9; ++i) { cp.Su[i] = b.Su[i]; cp.Du[i] = b.Du[i]; }
+    stokes_cip_end_tables(cp.Eu, cp.EDu);
+    cp.Nu = c->Nu; cp.dmask = c->dmask; cp.detJ = b.detJ;
+    cp.scale = d.delta0 / (8.0 * std::sqrt(2.0)); // pa = degree^3.5, degree 2 (operators.h:1614-1615)
+    ap.Cc = d_C; ap.cip_stride = win_cells * CIP_CELL;
+    for (int i = 0; i < d.nblk; ++i) ap.selc[i] = selc[i];
+  }
+  const void *cipk = c->base.cart ? reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<false>);
   const void *cellk = c->pspace ? reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<false>);
   stfem_launch_begin();
   v->setup_batches = 0;
@@ -445,6 +628,12 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
       mp.Ac = d_A + size_t(s) * ap.state_stride;
       mp.Mc = s == 0 ? d_M : nullptr;
       rc = vk_launch(cellk, dim3((unsigned)wcells), &mp, nullptr, "stokes_cell_matrices_kernel");
+    }
+    for (int s = 0; s < ncip && rc == STFEM_OK; ++s) {
+      cp.w = weight[s];
+      cp.Cc = d_C + size_t(s) * ap.cip_stride;
+      cp.cell0 = (long long)cpl * zw0;
+      rc = vk_launch(cipk, dim3((unsigned)wcells), &cp, nullptr, "stokes_cip_cell_matrices_kernel");
     }
     ap.zw0 = zw0; ap.z0 = z0;
     if (rc == STFEM_OK) rc = vk_launch(reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel), dim3((unsigned)bcells), &ap, nullptr, "stokes_vanka_assemble_kernel");

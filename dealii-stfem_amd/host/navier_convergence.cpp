@@ -8,9 +8,11 @@
 // about it (Explicit).  Linear solves: FGMRES to lintol (relative), preconditioned by relaxation sweeps of the per-cell Vanka smoother
 // of the linearised operator, or with mg=<levels> by one V-cycle of GMGStokes with linearised levels.
 // delta0=<value>: the CIP interior-face stabilisation of the operator (default 0: none), weighted with the linearisation velocity in the
-// system matrix (TimeIntegratorNavierStokes); the preconditioners stay without it.
+// system matrix (TimeIntegratorNavierStokes).  cipprec=1 (default 0) hands that delta0 to the preconditioner too: the term in the
+// blocks of the per-cell Vanka smoother, or with mg= on every level (level operators and level smoothers); without it the
+// preconditioners are those of the operator without the stabilisation.
 // Usage: navier_convergence <type 0 = cG | 1 = dG> <k> <refinement> [treatment=newton|picard] [mg=<levels>] [dg=1] [nu=1] [nltol=1e-12]
-//                           [delta0=0] [lintol=1e-3] [sweeps=3] [omega=0: estimated] [end_time=1] [warmup=<untimed slabs>]
+//                           [delta0=0] [cipprec=0] [lintol=1e-3] [sweeps=3] [omega=0: estimated] [end_time=1] [warmup=<untimed slabs>]
 // Prints: cells u-dofs p-dofs t-dofs  u:Linf-Linf  u:L2-L2  u:L2-H1semi  p:L2-L2  fgmres-iterations-per-solve
 //         nonlinear-steps-per-slab  fgmres-iterations-per-slab  |div u_h|(end time)  share:residuals  share:set_data  share:krylov
 //         most-nonlinear-steps-in-a-slab  all-slabs-converged
@@ -26,7 +28,7 @@ using namespace stfem;
 int main(int argc_all, char **argv_all)
 {
   unsigned mg_levels = 0, sweeps = 3, warmup = 0;
-  bool dg_pressure = false, newton = true;
+  bool dg_pressure = false, newton = true, cipprec = false;
   double nu = 1.0, nltol = 1e-12, lintol = 1e-3, omega_arg = 0.0, end_time = 1.0, delta0 = 0.0;
   std::vector<char *> pos;
   for (int i = 0; i < argc_all; ++i) {
@@ -39,6 +41,7 @@ int main(int argc_all, char **argv_all)
     else if (std::strncmp(a, "nu=", 3) == 0) nu = std::atof(a + 3);
     else if (std::strncmp(a, "nltol=", 6) == 0) nltol = std::atof(a + 6);
     else if (std::strncmp(a, "delta0=", 7) == 0) delta0 = std::atof(a + 7);
+    else if (std::strncmp(a, "cipprec=", 8) == 0) cipprec = std::atoi(a + 8) != 0;
     else if (std::strncmp(a, "lintol=", 7) == 0) lintol = std::atof(a + 7);
     else if (std::strncmp(a, "sweeps=", 7) == 0) sweeps = unsigned(std::atoi(a + 7));
     else if (std::strncmp(a, "omega=", 6) == 0) omega_arg = std::atof(a + 6);
@@ -61,6 +64,7 @@ int main(int argc_all, char **argv_all)
   const double tau = std::ldexp(1.0, -int(refinement + 1));
   const NonlinearTreatment treatment = newton ? NonlinearTreatment::Implicit : NonlinearTreatment::Explicit;
   const unsigned max_nonlinear = 40;
+  const double prec_delta0 = cipprec ? delta0 : 0.0;
   try {
     Mesh mesh;
     mesh.ncell[0] = mesh.ncell[1] = mesh.ncell[2] = n;
@@ -77,7 +81,7 @@ int main(int argc_all, char **argv_all)
     const bool cgp = type == TimeStepType::CGP;
     SystemMatrixStokes<3, double> rhs_matrix(K, cgp ? w[2] : zero, cgp ? w[3] : w[2], slice, treatment);
     StokesSystem<3, double> system(matrix, spaces, K.handle(), slice);
-    RelaxedVankaStokes<3> preconditioner(K, system, w[0], w[1], slice, treatment, sweeps, omega_arg);
+    RelaxedVankaStokes<3> preconditioner(K, system, w[0], w[1], slice, treatment, sweeps, omega_arg, true, prec_delta0);
 
     const VectorPointFunction force = stokes_problem::force(nu, true);
 
@@ -87,6 +91,7 @@ int main(int argc_all, char **argv_all)
       GMGStokes<3>::AdditionalData ad;
       ad.smoothing_degree = sweeps;
       ad.relaxation = omega_arg;
+      ad.delta0 = prec_delta0;
       gmg = std::make_unique<GMGStokes<3>>(mesh, mg_levels, nu, w[0], w[1], slice, ad, std::set<boundary_id>(), dg_pressure, treatment);
     }
     struct Prec {

@@ -512,9 +512,12 @@ public:
   // matrix of compute_matrix_helper<OperatorMode::jacobian>, operators.h:1310-1318, and the blocks from it, stmg.h:704-742): the
   // column blocks of time dof (it, id) are linearised about block index(it, 0, id) of solution_linearization (operators.h:835-866).
   // NonlinearTreatment::None gives the plain Stokes blocks, Explicit the form, Implicit the jacobian (as the operator's vmult).
+  // delta0 != 0: the blocks hold the CIP term C(b_j; .) weighted by the linearisation state too (the reference's blocks are cut out of
+  // the matrix of an operator that holds delta0, tests/tp_03stokes.cc:610-623, 655-726); update keeps it.
   template <int dim>
   PreconditionVankaStokes(const StokesMatrixFreeOperator<dim, Number> &K, const FullMatrix<Number> &Alpha, const FullMatrix<Number> &Beta,
-                          const BlockSlice &blk_slice, NonlinearTreatment nonlinear_treatment, const BlockVectorType &solution_linearization)
+                          const BlockSlice &blk_slice, NonlinearTreatment nonlinear_treatment, const BlockVectorType &solution_linearization,
+                          Number delta0 = 0)
     : nb_(blk_slice.n_blocks()), slice_(blk_slice)
   {
     if (Alpha.m() != nb_ || Alpha.n() != nb_ || Beta.m() != nb_ || Beta.n() != nb_) throw std::invalid_argument("Alpha/Beta do not match the block slice");
@@ -524,8 +527,9 @@ public:
                      : nonlinear_treatment == NonlinearTreatment::Explicit ? STFEM_CONVECTION_FORM : STFEM_CONVECTION_JACOBIAN;
     const std::vector<const double *> l = linearization(solution_linearization);
     stfem_stokes_vanka *v = nullptr;
-    const int rc = stfem_stokes_vanka_create_linearised(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), mode, l.data(), &v);
-    if (rc != STFEM_OK) throw Error(rc, "stfem_stokes_vanka_create_linearised");
+    const int rc = delta0 != 0 ? stfem_stokes_vanka_create_linearised_cip(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), mode, l.data(), delta0, &v)
+                               : stfem_stokes_vanka_create_linearised(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), mode, l.data(), &v);
+    if (rc != STFEM_OK) throw Error(rc, delta0 != 0 ? "stfem_stokes_vanka_create_linearised_cip" : "stfem_stokes_vanka_create_linearised");
     v_.reset(v, stfem_stokes_vanka_destroy);
   }
   // the blocks again for a new linearisation vector (same treatment, same storage): the next Newton / Picard step

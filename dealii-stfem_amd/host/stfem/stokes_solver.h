@@ -222,14 +222,18 @@ struct SynchronisedTimer {
 // every later one updates its blocks (PreconditionVankaStokes::update), and the damping follows the operator.  relaxation == 0:
 // omega is estimated as the reference's default does (20 power iterations on P^-1 A), at the first set_data and - unless
 // reestimate_relaxation is false - at every later one.  The preconditioner interface of TimeIntegratorNavierStokes beside GMGStokes.
+// delta0 != 0 (a nonlinear treatment only): the blocks hold the CIP term weighted by the linearisation
+// (PreconditionVankaStokes, stfem_stokes_vanka_create_linearised_cip); the estimate sees whatever `system` applies.
 template <int dim> class RelaxedVankaStokes {
 public:
   RelaxedVankaStokes(const StokesMatrixFreeOperator<dim, double> &K, const StokesSystem<dim, double> &system, const FullMatrix<double> &Alpha,
                      const FullMatrix<double> &Beta, const BlockSlice &slice, NonlinearTreatment treatment, unsigned n_iterations, double relaxation = 0.0,
-                     bool reestimate_relaxation = true)
+                     bool reestimate_relaxation = true, double delta0 = 0.0)
     : K(K), system(system), Alpha(Alpha), Beta(Beta), slice(slice), treatment(treatment), n_iterations(n_iterations), relaxation_(relaxation),
-      reestimate(reestimate_relaxation)
+      reestimate(reestimate_relaxation), delta0(delta0)
   {
+    if (delta0 != 0.0 && treatment == NonlinearTreatment::None)
+      throw std::invalid_argument("RelaxedVankaStokes: the CIP term in the blocks (delta0 != 0) needs a nonlinear treatment");
     if (treatment != NonlinearTreatment::None) return;
     vanka = std::make_unique<PreconditionVankaStokes<double>>(K, Alpha, Beta, slice);
     relax_with_new_omega();
@@ -238,7 +242,7 @@ public:
   {
     if (treatment == NonlinearTreatment::None) throw std::invalid_argument("RelaxedVankaStokes::set_data: a smoother without a nonlinear treatment");
     if (vanka) vanka->update(lin.blocks());
-    else vanka = std::make_unique<PreconditionVankaStokes<double>>(K, Alpha, Beta, slice, treatment, lin.blocks());
+    else vanka = std::make_unique<PreconditionVankaStokes<double>>(K, Alpha, Beta, slice, treatment, lin.blocks(), delta0);
     relax_with_new_omega();
   }
   void vmult(StokesBlockVector &dst, const StokesBlockVector &src, void *stream = nullptr) const
@@ -266,6 +270,7 @@ private:
   unsigned n_iterations;
   double relaxation_, omega = 1.0;
   bool reestimate;
+  double delta0;
   std::unique_ptr<PreconditionVankaStokes<double>> vanka;
   std::unique_ptr<Relaxation> relax;
 };
@@ -289,6 +294,10 @@ public:
     unsigned smoothing_degree = 1;     // sweeps of PreconditionRelaxation per step
     double relaxation = 0.0;           // its omega; 0: estimated per level (20 power iterations on P^-1 A), as the reference's default
     bool reestimate_relaxation = true; // linearised levels, relaxation == 0: a fresh estimate at every set_data (false: the first one is kept)
+    // the CIP term on every level (tests/tp_03stokes.cc:610-623: stokes_parameters.delta0 to the operator of every level, h_F of the
+    // level's own mesh does the scaling): level operators with set_cip(delta0, STFEM_CIP_WEIGHT_LINEARISATION), level smoothers with
+    // the term in their blocks; needs a nonlinear treatment.  0: levels and smoothers of the operator without it
+    double delta0 = 0.0;
   };
   // the finest mesh has mesh.ncell cells; level l < n_levels - 1 has them halved n_levels - 1 - l times
   GMGStokes(const Mesh &mesh, unsigned n_levels, double viscosity, const FullMatrix<double> &Alpha, const FullMatrix<double> &Beta,
@@ -297,6 +306,8 @@ public:
     : data_(data)
   {
     if (n_levels < 1) throw std::invalid_argument("GMGStokes: at least one level");
+    if (data.delta0 != 0.0 && treatment == NonlinearTreatment::None)
+      throw std::invalid_argument("GMGStokes: the CIP term on the levels (delta0 != 0) needs a nonlinear treatment");
     dg_ = dg_pressure;
     treatment_ = treatment;
     levels_.resize(n_levels);
@@ -318,6 +329,7 @@ public:
     : data_(data)
   {
     if (treatment != NonlinearTreatment::None) throw std::invalid_argument("GMGStokes: the linearisation on k / tau levels is not built");
+    if (data.delta0 != 0.0) throw std::invalid_argument("GMGStokes: the CIP term on the levels (delta0 != 0) needs a nonlinear treatment");
     dg_ = dg_pressure;
     const unsigned n_levels = unsigned(mg_type_level.size()) + 1;
     levels_.resize(n_levels);
@@ -437,13 +449,14 @@ private:
         if (mesh.ncell[d] % f) throw std::invalid_argument("GMGStokes: the cell counts must be divisible by 2^(space levels - 1)");
         L.mesh.ncell[d] = mesh.ncell[d] / f;
       }
-      L.K = std::make_unique<StokesMatrixFreeOperator<dim, double>>(L.mesh, 2, viscosity, weak_boundary_ids, std::set<boundary_id>(), 20.0, 10.0, 0.0, 0.0, 0.0,
+      L.K = std::make_unique<StokesMatrixFreeOperator<dim, double>>(L.mesh, 2, viscosity, weak_boundary_ids, std::set<boundary_id>(), 20.0, 10.0, 0.0, data_.delta0, 0.0,
                                                                    dg_, treatment_);
+      if (data_.delta0 != 0.0) L.K->set_cip_weight(STFEM_CIP_WEIGHT_LINEARISATION);
       L.spaces = std::make_shared<StokesSpaces>(L.mesh, L.K->handle());
       L.A = std::make_unique<SystemMatrixStokes<dim, double>>(*L.K, L.Alpha, L.Beta, L.slice, treatment_);
       L.system = std::make_unique<StokesSystem<dim, double>>(*L.A, L.spaces, L.K->handle(), L.slice);
       L.smoother = std::make_unique<RelaxedVankaStokes<dim>>(*L.K, *L.system, L.Alpha, L.Beta, L.slice, treatment_, data_.smoothing_degree, data_.relaxation,
-                                                           data_.reestimate_relaxation);
+                                                           data_.reestimate_relaxation, data_.delta0);
       L.system->initialize_dof_vector(L.defect);
       L.system->initialize_dof_vector(L.solution);
       L.system->initialize_dof_vector(L.t);
@@ -748,7 +761,8 @@ private:
 // converged(), not thrown): set_data(x) on both, FGMRES on J delta = r from zero, x += delta.
 // With the CIP term (delta0 != 0) the system matrix is switched to the linearisation weight: the residual rhs - form(x) is taken about
 // x itself, where both weights coincide, and the Krylov operator becomes linear in the increment (with the source weight of the
-// reference it is cubic).  The preconditioners (GMGStokes levels, Vanka blocks) stay without the term.
+// reference it is cubic).  The preconditioners hold the term when they are given its delta0 themselves (GMGStokes::AdditionalData::delta0,
+// the last argument of RelaxedVankaStokes); without it they are those of the operator without the stabilisation.
 template <int dim, typename System, typename Preconditioner> class TimeIntegratorNavierStokes {
 public:
   TimeIntegratorNavierStokes(TimeStepType type, unsigned time_degree, const FullMatrix<double> &Alpha_1, const FullMatrix<double> &Gamma_1,

@@ -541,11 +541,12 @@ int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *ctx, int weak_mask, int o
  *       A non-finite delta0 or a weight outside 0..1 is STFEM_ERR_INVALID_ARGUMENT, decided before anything touches the device.
  *   cip_add: dst_u += C(weight_u; src_u) with the given delta0, independent of set_cip: the term by itself.  weight_u may be src_u;
  *       dst_u equal to either is STFEM_ERR_ALIAS, a null pointer STFEM_ERR_INVALID_ARGUMENT.
- * stfem_stokes_mass_vmult never gets the term.  The Vanka smoothers (stfem_stokes_vanka_create, _create_linearised, _update) build their
- * blocks WITHOUT it, whatever set_cip says (the class blocks of a box are probed on a context of their own, the per-cell blocks
- * assembled by their own kernel): the smoother is that of the operator without the stabilisation - a preconditioner of a flexible
- * method.  Eight colour launches, no atomics, fixed summation order: two calls agree bit for bit.  Not built: the term on multigrid
- * levels and in the Vanka blocks, fp32, the derivative of delta_F with respect to w (the reference has none either).
+ * stfem_stokes_mass_vmult never gets the term.  The Vanka smoothers do not read set_cip: stfem_stokes_vanka_create and
+ * _create_linearised build their blocks WITHOUT the term (the class blocks of a box are probed on a context of their own, the per-cell
+ * blocks assembled by their own kernel) - the smoother of the operator without the stabilisation, a preconditioner of a flexible
+ * method; stfem_stokes_vanka_create_linearised_cip builds the per-cell blocks WITH it, from a delta0 of its own.
+ * Eight colour launches, no atomics, fixed summation order: two calls agree bit for bit.  Not built: the term in the class blocks of a
+ * box, fp32, the derivative of delta_F with respect to w (the reference has none either).
  * On a z-slab of a partitioned mesh (interface faces out of the Dirichlet mask, the weak set and the outflow set) every other launch
  * of the operator - cell, coupling, boundary and convection launches, vector mass, nitsche_rhs, divergence, drag_lift - is cell-local
  * and leaves partial sums in the interface planes, which the add-exchange of the scalar views completes (the velocity components on
@@ -608,11 +609,26 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
  * block) with a mode other than 0: STFEM_ERR_INVALID_ARGUMENT; more than 8 blocks or 512 rows: STFEM_ERR_UNSUPPORTED.  Blocks that do
  * not fit beside the free device memory: STFEM_ERR_OUT_OF_MEMORY, the sizes in stfem_last_error.
  * update: stages the same set-up again into the existing block storage for new linearisation states (same mode);
- * STFEM_ERR_UNSUPPORTED for the class blocks of stfem_stokes_vanka_create on a box.  n_classes: the cell count.  Not built: fp32
- * blocks, the CIP term in the blocks (stfem_stokes_set_cip: the smoother is that of the operator without it) and outflow_penalty,
- * slab partitioning of this layout. */
+ * STFEM_ERR_UNSUPPORTED for the class blocks of stfem_stokes_vanka_create on a box.  n_classes: the cell count.
+ * create_linearised_cip: the same blocks of the operator WITH the CIP term (tests/tp_03stokes.cc:610-623, 655-726: the reference cuts
+ * its blocks out of compute_system_matrix of an operator that holds delta0): K = the assembled A(b_j) + C(b_j; .), C the bilinear form
+ * of stfem_stokes_set_cip with the weight velocity w = the linearisation state b_j of the column block (STFEM_CIP_WEIGHT_LINEARISATION)
+ * and no derivative of delta_F.  C is component-diagonal, enters the velocity-velocity entries only and is scaled by Alpha(i, j) like
+ * the rest of K; entry (k, l) of the assembled C gets a share of every interior face F(C1 | C2) with k and l in C1 u C2, so a cell's
+ * block holds shares of all interior faces of its 27-cell patch and of the faces between a patch cell and a cell outside it.  Assembled
+ * on the unconstrained mesh with the entries of b_j on strongly constrained DoFs read as 0, then constrained rows and columns dropped,
+ * the diagonal - the CIP diagonal included - kept.  All modes; with mode 0 lin_blocks is read as the weight only.  Block layout, size,
+ * inversion and apply are unchanged; update keeps the delta0 of creation (and then needs lin_blocks with mode 0 too).  delta0 == 0:
+ * create_linearised itself, the same launches and bits.  Further refusals, decided before anything touches the device, each with its
+ * reason in stfem_last_error: a non-finite delta0, or delta0 != 0 with a null lin_blocks (entry of a velocity block) in any mode:
+ * STFEM_ERR_INVALID_ARGUMENT.  The set-up adds one launch per batch and state and 40.8 kB of scratch per cell and state.
+ * Not built: fp32 blocks, the CIP term in the class blocks of a box (stfem_stokes_vanka_create), outflow_penalty, slab partitioning
+ * of the term and of this layout. */
 int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha,
                                          const double *Beta, int mode, const double *const *lin_blocks, stfem_stokes_vanka **out);
+int stfem_stokes_vanka_create_linearised_cip(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha,
+                                             const double *Beta, int mode, const double *const *lin_blocks, double delta0,
+                                             stfem_stokes_vanka **out);
 int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_blocks);
 void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v);
 int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v);

@@ -4,7 +4,12 @@ path + CART kernel) and on a perturbed mesh (cell kernel + general kernel) of N^
 back-to-back sequence that ends in a device synchronise, the same context with delta0 = 0 and delta0 = 1 in alternating rounds of one
 process, median and range over the rounds.  For scale beside it: the convection launches of the jacobian mode on the same meshes took
 0.25 ms (box) / 0.31 ms (perturbed) in profiles/navier_convection.txt.
-Usage: stokes_cip_bench.py [N] [rounds] [calls per round]"""
+Set-up mode: what the CIP term in the per-cell Vanka blocks (StokesPreconditionVanka(..., delta0=1)) adds to one update() of the blocks,
+jacobian mode, cG(1), on N^3 cells (default 32): two smoothers of the same context, delta0 = 0 and delta0 = 1, updated in alternating
+rounds, each update ended by a device synchronise.  --root DIR loads the package of another checkout (one without the term times
+delta0 = 0 alone), to run the two checkouts in alternating processes.
+Usage: stokes_cip_bench.py [N] [rounds] [calls per round]
+       stokes_cip_bench.py setup [N] [rounds] [--root DIR]"""
 import importlib
 import os
 import sys
@@ -12,8 +17,53 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT, WHICH = os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "this checkout"
+if "--root" in sys.argv:
+    at = sys.argv.index("--root")
+    ROOT = os.path.abspath(sys.argv[at + 1])
+    WHICH = "the --root checkout"
+    del sys.argv[at:at + 2]
+sys.path.insert(0, ROOT)
 stfem = importlib.import_module("dealii-stfem_amd")
+fmt = lambda v: f"{np.median(v):8.3f} ms (range {min(v):.3f} .. {max(v):.3f})"  # noqa: E731
+
+
+def setup_mode(n, rounds):
+    Alpha, Beta, _, _ = stfem.get_fe_time_weights_stokes(stfem.CGP, 1, 1.0 / 64, 1)
+    deltas = (0.0, 1.0) if "stfem_stokes_vanka_create_linearised_cip" in stfem.SIGNATURES else (0.0,)
+    for mesh in ("box", "perturbed"):
+        verts = stfem.mesh_vertices((n, n, n), distort=0.1, seed=7) if mesh == "perturbed" else None
+        op = stfem.StokesMatrixFreeOperator((n, n, n), vertices=verts, viscosity=1.0)
+        rng = np.random.default_rng(0)
+        lin = [op.initialize_dof_vector(0, rng.uniform(-1, 1, 3 * op.n_velocity)), None]
+        probe = op.initialize_dof_vector(1)
+        smoothers = {d: stfem.StokesPreconditionVanka(op, [0, 1], Alpha, Beta, lin=lin, mode=2, per_cell=True, **({"delta0": d} if d else {}))
+                     for d in deltas}
+
+        def timed(v):
+            probe.download()
+            t0 = time.perf_counter()
+            v.update(lin)
+            probe.download()  # (synchronises)
+            return (time.perf_counter() - t0) * 1e3
+
+        times = {d: [] for d in deltas}
+        for v in smoothers.values():
+            timed(v)
+        for _ in range(rounds):
+            for d in deltas:
+                times[d].append(timed(smoothers[d]))
+        print(f"{mesh:9s} {n}^3 cells, jacobian, cG(1), {rounds} rounds, {smoothers[0.0].setup_batches} batch(es), measured ({WHICH}):", flush=True)
+        for d in deltas:
+            print(f"    update, delta0 = {d:g} : {fmt(times[d])}")
+        if len(deltas) > 1:
+            print(f"    the CIP term       : {fmt([b - a for a, b in zip(times[0.0], times[1.0])])}", flush=True)
+        del smoothers, op, lin, probe
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "setup":
+    setup_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 32, int(sys.argv[3]) if len(sys.argv) > 3 else 7)
+    sys.exit(0)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 9
 CALLS = int(sys.argv[3]) if len(sys.argv) > 3 else 40
@@ -42,7 +92,6 @@ for mesh in ("box", "perturbed"):
         without.append(timed(0.0))
         with_term.append(timed(1.0))
     diff = [b - a for a, b in zip(without, with_term)]
-    fmt = lambda v: f"{np.median(v):7.3f} ms (range {min(v):.3f} .. {max(v):.3f})"  # noqa: E731
     print(f"{mesh:9s} {N}^3 cells, {3 * op.n_velocity + op.n_pressure} DoFs, {ROUNDS} rounds x {CALLS} calls, measured:", flush=True)
     print(f"    vmult, delta0 = 0 : {fmt(without)}")
     print(f"    vmult, delta0 = 1 : {fmt(with_term)}")

@@ -96,6 +96,7 @@ SIGNATURES = {
     "stfem_comm_last_error": (C.c_char_p, []),
     "stfem_ghost_update": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "stfem_halo_begin": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "stfem_neighbour_exchange": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "stfem_halo_end": (C.c_int, [_vp, _vp, _vp, _vp]),
     "stfem_halo_begin_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "stfem_planes_move": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
@@ -182,6 +183,13 @@ SIGNATURES = {
     "stfem_stokes_nitsche_rhs": (C.c_int, [_vp, _dp, _vp, _vp, _vp]),
     "stfem_stokes_set_cip": (C.c_int, [_vp, C.c_double, C.c_int]),
     "stfem_stokes_cip_add": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, _vp]),
+    "stfem_stokes_set_cip_neighbours": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "stfem_stokes_cip_ghost_size": (C.c_int64, [_vp]),
+    "stfem_stokes_cip_ghost_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "stfem_stokes_cip_ghost_destroy": (None, [_vp, _vp]),
+    "stfem_stokes_cip_pack": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    "stfem_stokes_cip_add_slab": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
+    "stfem_stokes_cip_bind_ghosts": (C.c_int, [_vp, _vp, _vp, _vp]),
     "stfem_stokes_pressure_ctx": (C.c_int, [_vp, C.POINTER(_vp)]),
     "stfem_stokes_pressure_mean_vectors": (C.c_int, [_vp, _dp, _dp, _dp]),
     "stfem_stokes_pressure_quadrature_points": (C.c_int, [_vp, C.c_int, _dp]),
@@ -193,6 +201,8 @@ SIGNATURES = {
     "stfem_stokes_dgp_restrict": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "stfem_stokes_vanka_create": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.POINTER(_vp)]),
     "stfem_stokes_vanka_create_linearised": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.c_int, C.POINTER(_vp), C.POINTER(_vp)]),
+    "stfem_stokes_vanka_create_linearised_partitioned": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.c_int, C.POINTER(_vp),
+                                                         C.c_double, C.c_int, C.c_int, C.POINTER(_vp)]),
     "stfem_stokes_vanka_create_linearised_cip": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), _dp, _dp, C.c_int, C.POINTER(_vp), C.c_double,
                                                  C.POINTER(_vp)]),
     "stfem_stokes_vanka_update": (C.c_int, [_vp, C.POINTER(_vp)]),
@@ -869,6 +879,45 @@ class StokesMatrixFreeOperator:
         dst_u, src_u, weight_u = (getattr(v, "ptr", v) for v in (dst_u, src_u, weight_u))
         _check(lib().stfem_stokes_cip_add(self._h, dst_u, src_u, weight_u, float(delta0), stream), "stfem_stokes_cip_add")
 
+    def set_cip_neighbours(self, neighbour_mask, lower_vertices=None, upper_vertices=None):
+        """This operator is a z-slab with a slab below (bit 4) and / or above (bit 5): the CIP term treats the interface faces as
+        interior.  lower / upper_vertices: [(ncx + 1)(ncy + 1)][3], the vertex plane one cell layer beyond the interface (general
+        meshes; None on a box).  Mask 0: the state of an operator that never had neighbours."""
+        lo, up = (None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in (lower_vertices, upper_vertices))
+        plane = (self.ncell[0] + 1) * (self.ncell[1] + 1) * 3
+        assert all(v is None or v.size == plane for v in (lo, up))
+        _check(lib().stfem_stokes_set_cip_neighbours(self._h, int(neighbour_mask), None if lo is None else _p(lo),
+                                                     None if up is None else _p(up)), "stfem_stokes_set_cip_neighbours")
+        self.cip_neighbours = int(neighbour_mask)
+
+    @property
+    def cip_ghost_size(self):
+        """doubles of one side's ghost planes: 3 components, 2 planes"""
+        return int(lib().stfem_stokes_cip_ghost_size(self._h))
+
+    def cip_ghost_vector(self):
+        """a zeroed device array of cip_ghost_size doubles (object with .ptr, .size, free()); freeing it drops its bindings"""
+        return StokesCipGhost(self)
+
+    def cip_pack(self, src_u, side, out, stream=None):
+        """out <- what the neighbour on `side` (0 lower, 1 upper) needs of src_u: this slab's two DoF planes next to that interface
+        plane, 0 on the DoFs this operator constrains strongly; out: cip_ghost_size doubles on the device"""
+        _check(lib().stfem_stokes_cip_pack(self._h, getattr(src_u, "ptr", src_u), int(side), getattr(out, "ptr", out), stream),
+               "stfem_stokes_cip_pack")
+
+    def cip_add_slab(self, dst_u, src_u, weight_u, delta0, lower_ghost=None, upper_ghost=None, stream=None):
+        """cip_add with the interface faces of set_cip_neighbours: lower / upper_ghost are the neighbours' cip_pack results (None for
+        a side without neighbour); the interface planes of dst_u receive partial sums"""
+        dst_u, src_u, weight_u, lower_ghost, upper_ghost = (getattr(v, "ptr", v) for v in (dst_u, src_u, weight_u, lower_ghost, upper_ghost))
+        _check(lib().stfem_stokes_cip_add_slab(self._h, dst_u, src_u, weight_u, float(delta0), lower_ghost, upper_ghost, stream),
+               "stfem_stokes_cip_add_slab")
+
+    def cip_bind_ghosts(self, src_u, lower_ghost=None, upper_ghost=None):
+        """The ghost planes that vmult / st_vmult / st_vmult_slice_add read for the velocity source src_u (looked up by its pointer)
+        once set_cip and set_cip_neighbours are in force; None, None unbinds"""
+        src_u, lower_ghost, upper_ghost = (getattr(v, "ptr", v) for v in (src_u, lower_ghost, upper_ghost))
+        _check(lib().stfem_stokes_cip_bind_ghosts(self._h, src_u, lower_ghost, upper_ghost), "stfem_stokes_cip_bind_ghosts")
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.stfem_stokes_destroy(self._h)
@@ -1077,14 +1126,25 @@ class StokesPreconditionVanka:
     (stfem_stokes_vanka_create_linearised_cip); update keeps that delta0.  The defaults are the class blocks of a box (one block per
     cell on a general mesh)."""
 
-    def __init__(self, op, block_variable, Alpha, Beta, lin=None, mode=0, per_cell=False, delta0=0.0):
+    def __init__(self, op, block_variable, Alpha, Beta, lin=None, mode=0, per_cell=False, delta0=0.0, partition=None):
+        """partition=(extended_op, neighbour_mask, beyond_mask): `op` is a z-slab; the per-cell blocks are set up on extended_op (the
+        slab plus one ghost cell layer per z neighbour of neighbour_mask, bit 4 below / 5 above; `lin`, also of update, lives there),
+        built for the slab's own cells and applied on `op`, partial sums in the interface planes.  beyond_mask: cells beyond a ghost
+        layer (read with delta0 != 0).  stfem_stokes_vanka_create_linearised_partitioned."""
         self.op = op
+        self.partition = partition
         self.nb = len(block_variable)
         bv = (C.c_int32 * self.nb)(*[int(v) for v in block_variable])
         A = np.ascontiguousarray(Alpha, dtype=np.float64); B = np.ascontiguousarray(Beta, dtype=np.float64)
         assert A.shape == (self.nb, self.nb) and B.shape == (self.nb, self.nb)
         h = _vp()
-        if delta0 != 0.0:
+        if partition is not None:
+            ext, nmask, bmask = partition
+            rc = lib().stfem_stokes_vanka_create_linearised_partitioned(getattr(op, "_h", None), getattr(ext, "_h", None), self.nb, bv, _p(A),
+                                                                        _p(B), int(mode), self._lin(lin), float(delta0), int(nmask),
+                                                                        int(bmask), C.byref(h))
+            what = "stfem_stokes_vanka_create_linearised_partitioned"
+        elif delta0 != 0.0:
             rc = lib().stfem_stokes_vanka_create_linearised_cip(op._h, self.nb, bv, _p(A), _p(B), int(mode), self._lin(lin), float(delta0),
                                                                 C.byref(h))
             what = "stfem_stokes_vanka_create_linearised_cip"
@@ -1160,6 +1220,26 @@ class StokesVector:
     def __del__(self):
         if getattr(self, "ptr", None) and _lib is not None and getattr(self.op, "_h", None):
             _lib.stfem_stokes_vector_destroy(self.op._h, self.ptr)
+            self.ptr = None
+
+
+class StokesCipGhost:
+    """The two velocity DoF planes beyond one interface of a slab, all three components (StokesMatrixFreeOperator.cip_pack fills one,
+    cip_add_slab / cip_bind_ghosts read one)."""
+
+    def __init__(self, op):
+        self.op, self.size = op, op.cip_ghost_size
+        h = _vp()
+        _check(lib().stfem_stokes_cip_ghost_create(op._h, C.byref(h)), "stfem_stokes_cip_ghost_create")
+        self.ptr = h.value
+
+    def free(self):
+        """frees the array now; the operator forgets every binding that names it"""
+        self.__del__()
+
+    def __del__(self):
+        if getattr(self, "ptr", None) and _lib is not None and getattr(self.op, "_h", None):
+            _lib.stfem_stokes_cip_ghost_destroy(self.op._h, self.ptr)
             self.ptr = None
 
 

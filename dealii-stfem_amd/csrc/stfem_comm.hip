@@ -310,6 +310,29 @@ int stfem_ghost_update(stfem_ctx *ctx, stfem_comm *c, stfem_vec *v, int lower, i
   return STFEM_OK;
 }
 
+// Caller's buffers, no packing.  Each send is followed by the receive it meets on the self-loop communicator, where the pairs match in
+// the order they are issued: up -> below, down -> above.
+int stfem_neighbour_exchange(stfem_comm *c, int lower, int upper, int64_t count, const double *send_down, const double *send_up,
+                             double *recv_below, double *recv_above, void *stream)
+{
+  if (!c || count < 0 || check_neighbours(c, lower, upper) != STFEM_OK || c->pending) return STFEM_ERR_INVALID_ARGUMENT;
+  if ((lower >= 0 && (!send_down || !recv_below)) || (upper >= 0 && (!send_up || !recv_above))) return STFEM_ERR_INVALID_ARGUMENT;
+  if ((lower < 0 && upper < 0) || count == 0) return STFEM_OK;
+  STFEM_TRY(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  STFEM_TRY(hipEventRecord(c->packed, st));
+  STFEM_TRY(hipStreamWaitEvent(c->stream, c->packed, 0));
+  COMM_NCCL(rccl().GroupStart());
+  if (upper >= 0) COMM_NCCL_IN_GROUP(rccl().Send(send_up, size_t(count), ncclDouble, upper, c->comm, c->stream));
+  if (lower >= 0) COMM_NCCL_IN_GROUP(rccl().Recv(recv_below, size_t(count), ncclDouble, lower, c->comm, c->stream));
+  if (lower >= 0) COMM_NCCL_IN_GROUP(rccl().Send(send_down, size_t(count), ncclDouble, lower, c->comm, c->stream));
+  if (upper >= 0) COMM_NCCL_IN_GROUP(rccl().Recv(recv_above, size_t(count), ncclDouble, upper, c->comm, c->stream));
+  COMM_NCCL(rccl().GroupEnd());
+  STFEM_TRY(hipEventRecord(c->arrived, c->stream));
+  STFEM_TRY(hipStreamWaitEvent(st, c->arrived, 0));
+  return STFEM_OK;
+}
+
 int stfem_dot_global(stfem_ctx *ctx, stfem_comm *c, const stfem_vec *a, const stfem_vec *b, int64_t n_own,
                      double *out, void *stream)
 {

@@ -103,6 +103,11 @@ struct stokes_cell_vanka_desc {
   int var[8];                 // 0 velocity / 1 pressure, in BlockSlice order
   double Alpha[64], Beta[64]; // nblk x nblk, row-major
   double delta0;              // CIP term C(b_j; .) in the velocity-velocity entries (0: none; otherwise `lin` is read in every mode)
+  // a z-slab (stfem_stokes_vanka_create_linearised_partitioned): the context the blocks are SET UP on - the slab plus one ghost cell
+  // layer per z neighbour, `lin` lives there -, the first of its cell layers that is the slab's own, and whether there are cells beyond
+  // a ghost layer (bit 4 / 5: its outer z face is interior for the CIP term).  nullptr: the context of the apply, all layers own.
+  stfem_stokes_ctx *setup;
+  int own0, beyond;
 };
 struct stokes_cell_vanka;
 // row table: nblk-block rows -> (vector | variable << 8, element offset from the cell's first DoF of the variable), m entries of two ints

@@ -190,6 +190,8 @@ void stfem_stokes_destroy(stfem_stokes_ctx *c)
   if (c->d_pred) (void)hipFree(c->d_pred);
   if (c->d_div) (void)hipFree(c->d_div);
   if (c->d_trac) (void)hipFree(c->d_trac);
+  for (double *v : c->d_cip_vertices)
+    if (v) (void)hipFree(v);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   delete c;
@@ -463,6 +465,7 @@ int stfem_stokes_vmult_convection(stfem_stokes_ctx *c, int mode, double *dst_u, 
     return STFEM_ERR_INVALID_ARGUMENT;
   if (dst_u == src_u || dst_p == src_p) return STFEM_ERR_ALIAS;
   if (mode != STFEM_CONVECTION_NONE && (lin_u == dst_u || lin_u == dst_p)) return STFEM_ERR_ALIAS;
+  if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
   STFEM_TRY(hipSetDevice(c->device));
   StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
   launch.add_source(src_u, src_p, lin_u);
@@ -518,6 +521,9 @@ int stfem_stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timest
       for (int it = 0; it < ns; ++it)
         for (int d = 0; d < nt; ++d)
           if (dst_blocks[j] == lin_blocks[index(it, 0, d)]) return STFEM_ERR_ALIAS;
+  for (int it = 0; it < ns; ++it)
+    for (int d = 0; d < nt; ++d)
+      if (const int rg = stokes_cip_source_ready(c, src_blocks[index(it, 0, d)])) return rg;
   STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // dst = 0.0 (operators.h:833): the first launch that reaches a block overwrites it; blocks no launch
@@ -583,6 +589,7 @@ int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, in
     if (dst_blocks[j] == src_u || dst_blocks[j] == src_p) return STFEM_ERR_ALIAS;
     if (mode != STFEM_CONVECTION_NONE && dst_blocks[j] == lin_u) return STFEM_ERR_ALIAS;
   }
+  if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
   STFEM_TRY(hipSetDevice(c->device));
   StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
   launch.add_source(src_u, src_p, lin_u);

@@ -15,10 +15,14 @@
 // The launches follow those of the linear operator and of the convection term of the same set: every destination has been written,
 // so they read, add and write - eight colour launches (cells of one colour share no DoF), ascending, faces 0..5 and points 0..8 in
 // order, no atomics: bitwise reproducible.
+// On a z-slab of a partitioned mesh (stfem_stokes_set_cip_neighbours) the same design partitions: the cells next to an interface plane
+// treat that face as interior, read the neighbour slab's cell from two ghost DoF planes per source (stfem_stokes_cip_pack on the
+// sender) and one ghost vertex plane, and write inside the slab - partial sums in the interface planes, like every other launch.
 #include "stfem_stokes_internal.h"
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -31,8 +35,11 @@ namespace {
 // CART: constant diagonal Jacobian, n = e_d.  MULTI: several sources, each with its own weight velocity; the weighted results
 // are summed in registers per destination (up to MAXSRC), one scatter; otherwise one source, the weights applied at scatter time to
 // up to MAXOUT destinations.
-template <bool CART, bool MULTI>
-__global__ __launch_bounds__(256) void stokes_cip_kernel(const CipParams prm)
+// SLAB: a z-slab with neighbours (CipSlabParams).  Face 4 of the bottom cell layer / face 5 of the top one is interior where
+// `neighbours` names that side; the neighbour cell's 18 nodes beyond the interface plane come from the ghost planes of the source, its
+// Jacobian from the two-plane vertex arrays.  The destination writes stay what they are: inside the slab.
+template <bool CART, bool MULTI, bool SLAB = false>
+__global__ __launch_bounds__(256) void stokes_cip_kernel(const std::conditional_t<SLAB, CipSlabParams, CipParams> prm)
 {
   constexpr int NT = CART ? 1 : 3;
   __shared__ double tS[9], tD[9], tE[6], tED[6], tX[3], tW[3];
@@ -71,6 +78,9 @@ __global__ __launch_bounds__(256) void stokes_cip_kernel(const CipParams prm)
     int faces = 0; // the interior faces of the cell, bit 2 d + s
     if (ok) faces = (cx > 0 ? 1 : 0) | (cx < prm.ncx - 1 ? 2 : 0) | (cy > 0 ? 4 : 0) | (cy < prm.ncy - 1 ? 8 : 0) | (cz > 0 ? 16 : 0) |
                     (cz < prm.ncz - 1 ? 32 : 0);
+    if constexpr (SLAB) {
+      if (ok) faces |= (cz == 0 ? prm.neighbours & 16 : 0) | (cz == prm.ncz - 1 ? prm.neighbours & 32 : 0);
+    }
     if (!__builtin_amdgcn_readfirstlane(__ballot(faces != 0) != 0)) continue; // (wave-uniform skip only: the two half-waves fence together)
     const int ix = 2 * cx + a, iy = 2 * cy + b, iz = 2 * cz + c;
     const bool con = constrained_u(prm, ix, iy, iz);
@@ -95,6 +105,23 @@ __global__ __launch_bounds__(256) void stokes_cip_kernel(const CipParams prm)
                   jz = 2 * (cz + (d == 2 ? (s ? 1 : -1) : 0)) + c;
         const bool take = (faces >> f & 1) && lane27 && !constrained_u(prm, jx, jy, jz);
         const long long gn = jx + (long long)prm.ndu[0] * (jy + (long long)prm.ndu[1] * jz);
+        if constexpr (SLAB) {
+          // Behind an interface face jz = 2 (cz -+ 1) + c leaves the slab.  Face 4 is on only with cz == 0 and bit 4 (see `faces`):
+          // jz = c - 2 in {-2, -1, 0}; 0 is the slab's own plane, -2 and -1 are ghost planes jz + 2 in {0, 1} of ghost_lo.  Face 5
+          // is on only with cz == ncz - 1 and bit 5: jz = ndu[2] - 1 + c; c == 0 is the slab's own top plane, c in {1, 2} gives
+          // ghost planes jz - ndu[2] in {0, 1} of ghost_hi.  With jx in [0, ndu[0]) and jy in [0, ndu[1]) (the x / y faces of the
+          // same `take` are on only inside the slab) the index (comp * 2 + plane) ndu[0] ndu[1] + jy ndu[0] + jx lies in
+          // [0, 3 * 2 * ndu[0] ndu[1]) = [0, stfem_stokes_cip_ghost_size).  No other face leaves [0, ndu[2]).  The sender has written
+          // 0 on the DoFs its z mask constrains; constrained_u below sees the x / y masks, which both slabs share.
+          if (d == 2 && (jz < 0 || jz >= prm.ndu[2])) {
+            const double *g = jz < 0 ? prm.ghost_lo[MULTI ? src : 0] : prm.ghost_hi[MULTI ? src : 0];
+            const long long plane = (long long)prm.ndu[0] * prm.ndu[1];
+            const long long gg = (jz < 0 ? jz + 2 : jz - prm.ndu[2]) * plane + jx + (long long)prm.ndu[0] * jy;
+#pragma unroll
+            for (int comp = 0; comp < 3; ++comp) v[comp] = take ? g[comp * 2 * plane + gg] : 0.0;
+            return;
+          }
+        }
 #pragma unroll
         for (int comp = 0; comp < 3; ++comp) v[comp] = take ? us[comp * prm.Nu + gn] : 0.0;
       };
@@ -141,7 +168,16 @@ __global__ __launch_bounds__(256) void stokes_cip_kernel(const CipParams prm)
 #pragma unroll
             for (int e = 0; e < 3; ++e) go[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
             xi[d] = double(1 - s);
-            cip_jacobian(prm, ncx_, ncy_, ncz_, xi, Ji, det);
+            if constexpr (SLAB) {
+              // the neighbour cell of an interface face (ncz_ == -1 or ncz, on only with its bit: the array is there) is cell layer
+              // 0 of the side's two vertex planes: reads 3 ((cx + i) + (ncx + 1) ((cy + j) + (ncy + 1) k)), k in {0, 1}, inside
+              // 2 (ncx + 1) (ncy + 1) * 3
+              const bool below = ncz_ < 0, beyond = below || ncz_ >= prm.ncz;
+              const CipGhostGeometry geo = {beyond ? prm.ghost_vertices[below ? 0 : 1] : prm.vertices, prm.ncx, prm.ncy};
+              cip_jacobian(geo, ncx_, ncy_, beyond ? 0 : ncz_, xi, Ji, det);
+            } else {
+              cip_jacobian(prm, ncx_, ncy_, ncz_, xi, Ji, det);
+            }
 #pragma unroll
             for (int e = 0; e < 3; ++e) gnb[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
           }
@@ -245,12 +281,79 @@ void stokes_cip_end_tables(double Eu[6], double EDu[6])
   for (int i = 0; i < 6; ++i) { Eu[i] = ends_tables[i]; EDu[i] = ends_tables[6 + i]; }
 }
 
+namespace {
+
+// One plane pair of a velocity source for the neighbour slab (stfem_stokes_cip_pack): out[comp][p][iy][ix] = src[comp][z0 + p][iy][ix],
+// 0 on the DoFs this context constrains.  i < 3 * 2 * plane; reads comp * Nu + (z0 + p) * plane + r with z0 + p <= ndu[2] - 2.
+__global__ __launch_bounds__(256) void stokes_cip_pack_kernel(const double *__restrict__ src, double *__restrict__ out, int ndx, int ndy,
+                                                              int ndz, int z0, long long Nu, int dmask)
+{
+  const long long plane = (long long)ndx * ndy, n = 6 * plane;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += 256ll * gridDim.x) {
+    const long long r = i % plane;
+    const int p = int((i / plane) % 2), comp = int(i / (2 * plane)), ix = int(r % ndx), iy = int(r / ndx), iz = z0 + p;
+    const bool con = ((dmask & 1) && ix == 0) || ((dmask & 2) && ix == ndx - 1) || ((dmask & 4) && iy == 0) || ((dmask & 8) && iy == ndy - 1) ||
+                     ((dmask & 16) && iz == 0) || ((dmask & 32) && iz == ndz - 1);
+    out[i] = con ? 0.0 : src[comp * Nu + iz * plane + r];
+  }
+}
+
+// the eight colour launches; ghost_lo / ghost_hi: per source the neighbours' planes (read for the sides of c->cip_neighbours only)
+int cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, const double *const *ghost_lo,
+               const double *const *ghost_hi, hipStream_t st);
+
+} // namespace
+
+int stokes_cip_source_ready(const stfem_stokes_ctx *c, const double *src_u)
+{
+  if (!c->cip_neighbours || c->cip_delta0 == 0.0) return STFEM_OK;
+  for (const auto &b : c->cip_bindings)
+    if (b.src == src_u) {
+      if ((c->cip_neighbours & 16) && !b.lower)
+        return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "CIP term on a slab: the source's binding has no lower ghost planes");
+      if ((c->cip_neighbours & 32) && !b.upper)
+        return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "CIP term on a slab: the source's binding has no upper ghost planes");
+      return STFEM_OK;
+    }
+  return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "CIP term on a slab with neighbours: no ghost planes bound to the velocity source "
+                                                     "(stfem_stokes_cip_bind_ghosts)");
+}
+
 int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, hipStream_t st)
 {
+  if (delta0 == 0.0 || !c->cip_neighbours) return cip_launch(c, prm, weight, delta0, nullptr, nullptr, st);
+  const double *lo[MAXSRC] = {}, *hi[MAXSRC] = {};
+  for (int s = 0; s < prm.nsrc && s < MAXSRC; ++s) {
+    const int rc = stokes_cip_source_ready(c, prm.us[s]);
+    if (rc != STFEM_OK) return rc;
+    for (const auto &b : c->cip_bindings)
+      if (b.src == prm.us[s]) { lo[s] = b.lower; hi[s] = b.upper; }
+  }
+  return cip_launch(c, prm, weight, delta0, lo, hi, st);
+}
+
+namespace {
+
+int cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, const double *const *ghost_lo,
+               const double *const *ghost_hi, hipStream_t st)
+{
   if (delta0 == 0.0) return STFEM_OK;
-  if (c->nc[0] < 2 && c->nc[1] < 2 && c->nc[2] < 2) return STFEM_OK; // no interior face
+  const int neighbours = ghost_lo && ghost_hi ? c->cip_neighbours : 0;
+  if (c->nc[0] < 2 && c->nc[1] < 2 && c->nc[2] < 2 && !neighbours) return STFEM_OK; // no interior face
   if (prm.nsrc < 1 || prm.nsrc > MAXSRC || prm.nout > (prm.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiations' bounds)
-  CipParams k;
+  CipSlabParams k; // (the instantiations without SLAB read its CipParams part alone)
+  k.neighbours = neighbours;
+  for (int side = 0; side < 2; ++side) k.ghost_vertices[side] = c->d_cip_vertices[side];
+  for (int s = 0; s < MAXSRC; ++s) {
+    k.ghost_lo[s] = neighbours && s < prm.nsrc ? ghost_lo[s] : nullptr;
+    k.ghost_hi[s] = neighbours && s < prm.nsrc ? ghost_hi[s] : nullptr;
+    if (s < prm.nsrc && (((neighbours & 16) && !k.ghost_lo[s]) || ((neighbours & 32) && !k.ghost_hi[s])))
+      return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "CIP term on a slab: ghost planes missing for a side with a neighbour");
+  }
+  if (neighbours && !prm.cart)
+    for (int side = 0; side < 2; ++side)
+      if ((neighbours >> (4 + side) & 1) && !k.ghost_vertices[side])
+        return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "CIP term on a slab: no ghost vertex plane on side %d", side);
   k.vertices = prm.vertices;
   k.ncx = prm.ncx; k.ncy = prm.ncy; k.ncz = prm.ncz;
   for (int d = 0; d < 3; ++d) { k.ndu[d] = prm.ndu[d]; k.xq[d] = prm.xq[d]; k.wq[d] = prm.wq[d]; k.hinv[d] = prm.hinv[d]; }
@@ -287,7 +390,10 @@ int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double
   const int which = (multi ? 2 : 0) + (k.cart ? 1 : 0);
   const void *kerns[4] = {(const void *)stokes_cip_kernel<false, false>, (const void *)stokes_cip_kernel<true, false>,
                           (const void *)stokes_cip_kernel<false, true>, (const void *)stokes_cip_kernel<true, true>};
-  const void *kern = kerns[which];
+  // a slab with neighbours: the SLAB instantiations; without, the four above on the CipParams part of k - today's launches
+  const void *slab_kerns[4] = {(const void *)stokes_cip_kernel<false, false, true>, (const void *)stokes_cip_kernel<true, false, true>,
+                               (const void *)stokes_cip_kernel<false, true, true>, (const void *)stokes_cip_kernel<true, true, true>};
+  const void *kern = neighbours ? slab_kerns[which] : kerns[which];
   stfem_launch_begin();
   for (int colour = 0; colour < 8; ++colour) { // ascending, like every colour sequence of the operator
     const long long n = (long long)((c->nc[0] - (colour & 1) + 1) / 2) * ((c->nc[1] - ((colour >> 1) & 1) + 1) / 2) *
@@ -295,11 +401,24 @@ int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double
     if (n == 0) continue; // a colour without cells
     k.colour = colour;
     const unsigned grid = (unsigned)std::min<long long>((n + 7) / 8, 8ll * c->n_cu);
-    void *args[] = {(void *)&k};
+    void *args[] = {neighbours ? (void *)&k : (void *)static_cast<CipParams *>(&k)};
     (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
   }
   return stfem_launch_end("stokes_cip_kernel");
 }
+
+// the term by itself: one source, one destination, weight 1
+StokesParams cip_single(const stfem_stokes_ctx *c, double *dst_u, const double *src_u)
+{
+  StokesParams prm = c->base;
+  prm.nsrc = 1; prm.nout = 1;
+  prm.us[0] = src_u; prm.ps[0] = nullptr;
+  prm.out_u[0] = dst_u; prm.out_p[0] = nullptr;
+  prm.wKu[0][0] = 1.0;
+  return prm;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -317,12 +436,117 @@ int stfem_stokes_cip_add(stfem_stokes_ctx *c, double *dst_u, const double *src_u
   if (!c || !dst_u || !src_u || !weight_u || !std::isfinite(delta0)) return STFEM_ERR_INVALID_ARGUMENT;
   if (dst_u == src_u || dst_u == weight_u) return STFEM_ERR_ALIAS;
   STFEM_TRY(hipSetDevice(c->device));
-  StokesParams prm = c->base; // one source, one destination, weight 1: the term by itself
-  prm.nsrc = 1; prm.nout = 1;
-  prm.us[0] = src_u; prm.ps[0] = nullptr;
-  prm.out_u[0] = dst_u; prm.out_p[0] = nullptr;
-  prm.wKu[0][0] = 1.0;
-  return stokes_cip_launch(c, prm, &weight_u, delta0, static_cast<hipStream_t>(stream));
+  const StokesParams prm = cip_single(c, dst_u, src_u);
+  return cip_launch(c, prm, &weight_u, delta0, nullptr, nullptr, static_cast<hipStream_t>(stream)); // (the faces inside the slab alone)
+}
+
+int stfem_stokes_set_cip_neighbours(stfem_stokes_ctx *c, int neighbour_mask, const double *lower_vertices, const double *upper_vertices)
+{
+  if (!c) return STFEM_ERR_INVALID_ARGUMENT;
+  if (neighbour_mask & ~48) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "neighbour_mask %d: only bits 4 and 5 name a z neighbour", neighbour_mask);
+  const double *given[2] = {lower_vertices, upper_vertices};
+  if (!c->base.cart)
+    for (int side = 0; side < 2; ++side)
+      if ((neighbour_mask >> (4 + side) & 1) && !given[side])
+        return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "general mesh: the %s neighbour needs its vertex plane", side ? "upper" : "lower");
+  STFEM_TRY(hipSetDevice(c->device));
+  // the new arrays first, then the swap: a failure leaves the context as it was
+  double *fresh[2] = {nullptr, nullptr};
+  if (!c->base.cart) {
+    const size_t plane = size_t(c->nc[0] + 1) * (c->nc[1] + 1) * 3;
+    std::vector<double> two(2 * plane);
+    for (int side = 0; side < 2; ++side) {
+      if (!(neighbour_mask >> (4 + side) & 1)) continue;
+      // [ghost | plane 0] below, [top plane | ghost] above: the neighbour cell layer as a mesh of one layer
+      const double *own = c->h_vertices.data() + (side ? size_t(c->nc[2]) * plane : 0);
+      std::copy(given[side], given[side] + plane, two.begin() + (side ? plane : 0));
+      std::copy(own, own + plane, two.begin() + (side ? 0 : plane));
+      hipError_t e = hipMalloc(&fresh[side], 2 * plane * sizeof(double));
+      const bool oom = e != hipSuccess;
+      if (oom) fresh[side] = nullptr;
+      else e = hipMemcpy(fresh[side], two.data(), 2 * plane * sizeof(double), hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (double *f : fresh)
+          if (f) (void)hipFree(f);
+        return oom ? STFEM_ERR_OUT_OF_MEMORY : stfem_set_error(STFEM_ERR_HIP, "ghost vertex planes: %s", hipGetErrorString(e));
+      }
+    }
+  }
+  for (int side = 0; side < 2; ++side) {
+    if (c->d_cip_vertices[side]) (void)hipFree(c->d_cip_vertices[side]); // (synchronises: no launch still reads it)
+    c->d_cip_vertices[side] = fresh[side];
+  }
+  c->cip_neighbours = neighbour_mask;
+  return STFEM_OK;
+}
+
+int64_t stfem_stokes_cip_ghost_size(const stfem_stokes_ctx *c) { return c ? 6ll * c->ndu[0] * c->ndu[1] : 0; }
+
+int stfem_stokes_cip_ghost_create(stfem_stokes_ctx *c, double **device_out)
+{
+  if (!c || !device_out) return STFEM_ERR_INVALID_ARGUMENT;
+  *device_out = nullptr;
+  STFEM_TRY(hipSetDevice(c->device));
+  const size_t bytes = size_t(stfem_stokes_cip_ghost_size(c)) * sizeof(double);
+  double *d = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return STFEM_ERR_OUT_OF_MEMORY;
+  }
+  const hipError_t e = hipMemset(d, 0, bytes);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return stfem_set_error(STFEM_ERR_HIP, "hipMemset(ghost planes): %s", hipGetErrorString(e));
+  }
+  *device_out = d;
+  return STFEM_OK;
+}
+
+void stfem_stokes_cip_ghost_destroy(stfem_stokes_ctx *c, double *ghost)
+{
+  if (!c || !ghost) return;
+  (void)hipSetDevice(c->device);
+  // bindings that name the array go with it: a later launch must not read freed memory
+  auto &b = c->cip_bindings;
+  b.erase(std::remove_if(b.begin(), b.end(), [&](const stfem_stokes_ctx::CipBinding &e) { return e.lower == ghost || e.upper == ghost; }), b.end());
+  (void)hipFree(ghost);
+}
+
+int stfem_stokes_cip_pack(stfem_stokes_ctx *c, const double *src_u, int side, double *out, void *stream)
+{
+  if (!c || !src_u || !out || side < 0 || side > 1) return STFEM_ERR_INVALID_ARGUMENT;
+  if (out == src_u) return STFEM_ERR_ALIAS;
+  STFEM_TRY(hipSetDevice(c->device));
+  const long long n = 6ll * c->ndu[0] * c->ndu[1];
+  const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 8ll * c->n_cu);
+  stfem_launch_begin();
+  stokes_cip_pack_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(src_u, out, c->ndu[0], c->ndu[1], c->ndu[2],
+                                                                             side ? c->ndu[2] - 3 : 1, c->Nu, c->dmask);
+  return stfem_launch_end("stokes_cip_pack_kernel");
+}
+
+int stfem_stokes_cip_add_slab(stfem_stokes_ctx *c, double *dst_u, const double *src_u, const double *weight_u, double delta0,
+                              const double *lower_ghost, const double *upper_ghost, void *stream)
+{
+  if (!c || !dst_u || !src_u || !weight_u || !std::isfinite(delta0)) return STFEM_ERR_INVALID_ARGUMENT;
+  if (((c->cip_neighbours & 16) && !lower_ghost) || ((c->cip_neighbours & 32) && !upper_ghost))
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "CIP term on a slab: ghost planes missing for a side with a neighbour (mask %d)",
+                           c->cip_neighbours);
+  if (dst_u == src_u || dst_u == weight_u || dst_u == lower_ghost || dst_u == upper_ghost) return STFEM_ERR_ALIAS;
+  STFEM_TRY(hipSetDevice(c->device));
+  const StokesParams prm = cip_single(c, dst_u, src_u);
+  return cip_launch(c, prm, &weight_u, delta0, &lower_ghost, &upper_ghost, static_cast<hipStream_t>(stream));
+}
+
+int stfem_stokes_cip_bind_ghosts(stfem_stokes_ctx *c, const double *src_u, const double *lower_ghost, const double *upper_ghost)
+{
+  if (!c || !src_u) return STFEM_ERR_INVALID_ARGUMENT;
+  if (src_u == lower_ghost || src_u == upper_ghost) return STFEM_ERR_ALIAS;
+  auto &b = c->cip_bindings;
+  b.erase(std::remove_if(b.begin(), b.end(), [&](const stfem_stokes_ctx::CipBinding &e) { return e.src == src_u; }), b.end());
+  if (lower_ghost || upper_ghost) b.push_back({src_u, lower_ghost, upper_ghost});
+  return STFEM_OK;
 }
 
 } // extern "C"

@@ -113,6 +113,21 @@ struct CipParams {
   double hinv[3], detJ;
   double scale; // delta0 / pa
 };
+// The same on a z-slab with neighbours (stfem_stokes_set_cip_neighbours): the kernel's SLAB instantiations take this description, the
+// others CipParams as before.
+struct CipSlabParams : CipParams {
+  int neighbours; // bit 4: a slab below (face 4 of the bottom cell layer is interior), bit 5: a slab above
+  // general meshes: two vertex planes per side, [ghost plane | the slab's plane 0] below and [the slab's top plane | ghost plane]
+  // above, (ncx + 1)(ncy + 1) * 3 doubles each - the neighbour cell of an interface face as cell layer 0 of a mesh of its own
+  const double *ghost_vertices[2];
+  // per source the two velocity DoF planes beyond each interface, [comp][plane, ascending z][ndy][ndx] (stfem_stokes_cip_pack)
+  const double *ghost_lo[MAXSRC], *ghost_hi[MAXSRC];
+};
+// (what cip_jacobian reads of its Params: the two-plane vertex arrays above)
+struct CipGhostGeometry {
+  const double *vertices;
+  int ncx, ncy;
+};
 
 struct stfem_stokes_ctx {
   int device = 0;
@@ -152,6 +167,12 @@ struct stfem_stokes_ctx {
   // CIP interior-face stabilisation (stfem_stokes_set_cip): 0.0 = no launches; whose velocity weighs it (STFEM_CIP_WEIGHT_*)
   double cip_delta0 = 0.0;
   int cip_weight = 0;
+  // the slab's z neighbours for that term (stfem_stokes_set_cip_neighbours): mask, the two-plane vertex arrays of
+  // CipSlabParams::ghost_vertices (general meshes), and the ghost planes bound to velocity sources (stfem_stokes_cip_bind_ghosts)
+  int cip_neighbours = 0;
+  double *d_cip_vertices[2] = {nullptr, nullptr};
+  struct CipBinding { const double *src, *lower, *upper; };
+  std::vector<CipBinding> cip_bindings;
 };
 
 template <typename Params> // (StokesParams or ConvectionParams)
@@ -244,5 +265,9 @@ int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const
 // The CIP launches after those (stfem_stokes_cip.hip): eight colour launches; weight[s]: the weight velocity of source s.  Nothing is
 // launched with delta0 == 0, on a mesh without interior faces, for a colour without cells or when all wKu of the set are zero.
 int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, hipStream_t st);
+// On a slab with neighbours (stfem_stokes_set_cip_neighbours) and delta0 != 0 that launch looks up the ghost planes bound to each
+// source; the entry points ask this before anything touches the device: STFEM_ERR_INVALID_ARGUMENT, with its reason, for a velocity
+// source without a binding or with a binding that lacks a side
+int stokes_cip_source_ready(const stfem_stokes_ctx *c, const double *src_u);
 #pragma GCC visibility pop
 

@@ -353,8 +353,11 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
 // assembled matrix of compute_matrix_helper<OperatorMode::jacobian>, operators.h:1310-1318, and one inverted block per cell from it,
 // stmg.h:704-742, compute_block_matrix.h:50-139).  Every refusal is decided before anything touches the device.
 // delta0 != 0: with the CIP term C(b_j; .) in the velocity-velocity entries (stfem_stokes_vanka_create_linearised_cip)
+// setup != nullptr: a z-slab - the blocks of ctx's cells are set up on `setup` (ctx plus one ghost cell layer per z neighbour, own
+// layers from own0; lin_blocks live there), see stfem_stokes_vanka_create_linearised_partitioned
 static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta, int mode,
-                           const double *const *lin_blocks, double delta0, stfem_stokes_vanka **out)
+                           const double *const *lin_blocks, double delta0, stfem_stokes_vanka **out, stfem_stokes_ctx *setup = nullptr,
+                           int own0 = 0, int beyond = 0)
 {
   if (!out) return STFEM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
@@ -386,6 +389,7 @@ static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *b
   v->mode = mode;
   v->delta0 = delta0;
   cd.delta0 = delta0;
+  cd.setup = setup; cd.own0 = own0; cd.beyond = beyond;
   cd.nblk = n_blocks; cd.m = v->m; cd.mpad = v->mpad; cd.kpad = v->kpad; cd.mode = mode;
   for (int i = 0; i < n_blocks; ++i) cd.var[i] = v->var[i];
   for (int i = 0; i < n_blocks * n_blocks; ++i) { cd.Alpha[i] = Alpha[i]; cd.Beta[i] = Beta[i]; }
@@ -418,6 +422,40 @@ int stfem_stokes_vanka_create_linearised_cip(stfem_stokes_ctx *ctx, int n_blocks
       if (block_variable[i] == 0 && !lin_blocks[i])
         return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_vanka_create_linearised_cip: delta0 = %g and lin_blocks[%d] of a velocity block is null", delta0, i);
   return create_per_cell(ctx, n_blocks, block_variable, Alpha, Beta, mode, lin_blocks, delta0, out);
+}
+
+// The per-cell blocks of a z-slab: set up on `extended`, stored and applied on `slab`.  Every refusal before the device is touched.
+int stfem_stokes_vanka_create_linearised_partitioned(stfem_stokes_ctx *slab, stfem_stokes_ctx *extended, int n_blocks, const int32_t *block_variable,
+                                                     const double *Alpha, const double *Beta, int mode, const double *const *lin_blocks_extended,
+                                                     double delta0, int neighbour_mask, int beyond_mask, stfem_stokes_vanka **out)
+{
+  const char *me = "stfem_stokes_vanka_create_linearised_partitioned";
+  if (!out) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: out is null", me);
+  *out = nullptr;
+  if (!slab || !extended) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: a context is null", me);
+  if (!std::isfinite(delta0)) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: delta0 is not finite", me);
+  if (neighbour_mask & ~48) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: neighbour_mask %d, only bits 4 and 5 name a z neighbour", me, neighbour_mask);
+  if (beyond_mask & ~neighbour_mask)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: beyond_mask %d names a side without a neighbour (neighbour_mask %d)", me, beyond_mask, neighbour_mask);
+  stfem_stokes_desc ds, de;
+  int rc = stfem_stokes_internal_desc(slab, &ds);
+  if (rc == STFEM_OK) rc = stfem_stokes_internal_desc(extended, &de);
+  if (rc != STFEM_OK) return rc;
+  const int ghosts = (neighbour_mask >> 4 & 1) + (neighbour_mask >> 5 & 1);
+  if (de.nc[0] != ds.nc[0] || de.nc[1] != ds.nc[1] || de.nc[2] != ds.nc[2] + ghosts || de.pspace != ds.pspace || de.device != ds.device ||
+      de.cart != ds.cart)
+    return stfem_set_error(STFEM_ERR_SHAPE_MISMATCH, "%s: the extended context (%d x %d x %d cells, pressure space %d) is not the slab (%d x %d x %d, %d) plus %d "
+                           "ghost layer(s)", me, de.nc[0], de.nc[1], de.nc[2], de.pspace, ds.nc[0], ds.nc[1], ds.nc[2], ds.pspace, ghosts);
+  if (delta0 != 0.0) { // (the refusals of create_linearised_cip)
+    if (!lin_blocks_extended) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: delta0 = %g needs lin_blocks, the weight velocity of the term", me, delta0);
+    if (block_variable && n_blocks >= 1 && n_blocks <= VK_MAX_BLOCKS)
+      for (int i = 0; i < n_blocks; ++i)
+        if (block_variable[i] == 0 && !lin_blocks_extended[i])
+          return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: delta0 = %g and lin_blocks[%d] of a velocity block is null", me, delta0, i);
+  }
+  // (without the CIP term nothing reaches beyond a ghost layer: beyond_mask is ignored)
+  return create_per_cell(slab, n_blocks, block_variable, Alpha, Beta, mode, lin_blocks_extended, delta0, out, extended, neighbour_mask >> 4 & 1,
+                         delta0 != 0.0 ? beyond_mask : 0);
 }
 
 // The blocks of a smoother of stfem_stokes_vanka_create_linearised again, for new linearisation states: same mode, same storage

@@ -232,6 +232,10 @@ struct StokesCipCellParams {
   double xq[3], wq[3];
   double hinv[3], detJ;   // CART
   double scale;           // delta0 / pa
+  // a mesh that ends in a ghost cell layer of a z-slab (stokes_cell_vanka_desc::beyond): bit 4 / 5 - there are cells beyond the bottom /
+  // top layer.  Its outer z face is then interior for column group 0 (the own-side term needs the cell's own geometry and the weight on
+  // that plane alone); the group of the cell beyond stays zero and that cell is never evaluated: the mesh does not hold it.
+  int beyond;
 };
 
 // The CIP term C(w; .) of stfem_stokes_cip.hip in plain matrix form, scalar (the term is component-diagonal), cell-centric like
@@ -265,7 +269,8 @@ __global__ __launch_bounds__(256) void stokes_cip_cell_matrices_kernel(const Sto
   for (int f = 0; f < 6; ++f) {
     const int d = f >> 1, s = f & 1, t1 = d == 0 ? 1 : 0;
     const int cd = d == 0 ? cx : (d == 1 ? cy : cz), ncd = d == 0 ? P.ncx : (d == 1 ? P.ncy : P.ncz);
-    if (!(s ? cd < ncd - 1 : cd > 0)) { // a boundary face (uniform)
+    const bool outer = d == 2 && !(s ? cd < ncd - 1 : cd > 0) && (P.beyond >> f & 1); // the face to the cells beyond a ghost layer
+    if (!(s ? cd < ncd - 1 : cd > 0) && !outer) { // a boundary face (uniform)
       for (int e = tid; e < 729; e += 256) Cc[(e / 27) * 189 + (1 + f) * 27 + e % 27] = 0.0;
       continue;
     }
@@ -274,7 +279,8 @@ __global__ __launch_bounds__(256) void stokes_cip_cell_matrices_kernel(const Sto
       double go[3] = {0, 0, 0}, gnb[3] = {0, 0, 0}, nrm[3] = {0, 0, 0}, JxW;
       if constexpr (CART) {
         nrm[d] = 1.0;
-        go[d] = gnb[d] = P.hinv[d];
+        go[d] = P.hinv[d];
+        gnb[d] = outer ? 0.0 : P.hinv[d];
         JxW = P.detJ * P.hinv[d] * P.wq[q1] * P.wq[q2];
       } else {
         double xi[3], Ji[3][3], det;
@@ -290,10 +296,12 @@ __global__ __launch_bounds__(256) void stokes_cip_cell_matrices_kernel(const Sto
         JxW = fabs(det) * len * P.wq[q1] * P.wq[q2];
 #pragma unroll
         for (int e = 0; e < 3; ++e) go[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
+        // behind an outer face there is no cell in this mesh (cz -+ 1 would read vertex plane -1 or ncz + 1): the cell itself is
+        // evaluated in its place, in bounds, and the result dropped (one call either way: a branch here cost 66 VGPRs)
         xi[d] = double(1 - s);
-        cip_jacobian(P, cx + (d == 0 ? (s ? 1 : -1) : 0), cy + (d == 1 ? (s ? 1 : -1) : 0), cz + (d == 2 ? (s ? 1 : -1) : 0), xi, Ji, det);
+        cip_jacobian(P, cx + (d == 0 ? (s ? 1 : -1) : 0), cy + (d == 1 ? (s ? 1 : -1) : 0), cz + (d == 2 && !outer ? (s ? 1 : -1) : 0), xi, Ji, det);
 #pragma unroll
-        for (int e = 0; e < 3; ++e) gnb[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
+        for (int e = 0; e < 3; ++e) gnb[e] = outer ? 0.0 : Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
       }
       double wval[3] = {0, 0, 0}; // w at the point: the nine nodes of the face
 #pragma unroll
@@ -341,7 +349,7 @@ __global__ __launch_bounds__(256) void stokes_cip_cell_matrices_kernel(const Sto
         if (k == 0) own0 += so;
         else if (k == 1) own1 += so;
         else own2 += so;
-        Cc[a * 189 + (1 + f) * 27 + b] = -sn;
+        Cc[a * 189 + (1 + f) * 27 + b] = outer ? 0.0 : -sn;
       }
     }
     __syncthreads(); // the next face rewrites the tables
@@ -517,7 +525,9 @@ __global__ __launch_bounds__(256) void stokes_vanka_apply_percell_kernel(const S
 } // namespace
 
 struct stokes_cell_vanka {
-  stfem_stokes_ctx *ctx = nullptr;
+  stfem_stokes_ctx *ctx = nullptr;   // the context of the apply: its cells index the blocks
+  stfem_stokes_ctx *setup = nullptr; // the context of the set-up (ctx, or a slab's extended context); own layers [own0, own0 + ctx->nc[2])
+  int own0 = 0;
   stokes_cell_vanka_desc d;
   int nl = 0, npl = 0;
   int setup_batches = 0; // batches of cell layers the last build_blocks took
@@ -532,11 +542,15 @@ namespace {
 // side), as vanka_create_per_cell_device does it.  fresh: the blocks are not allocated yet - they must fit beside the scratch.
 int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
 {
-  stfem_stokes_ctx *c = v->ctx;
+  // Geometry, masks and states are those of the set-up context c; on a slab that is the extended context, whose cell layers
+  // [own0, own1) are the slab's own: only they get blocks, stored from cell 0 of the slab, and the window of cell matrices reaches
+  // into the ghost layers.
+  stfem_stokes_ctx *c = v->setup;
   const stokes_cell_vanka_desc &d = v->d;
   const int nl = v->nl, m = d.m;
   const int ncx = c->nc[0], ncy = c->nc[1], ncz = c->nc[2];
-  const size_t cpl = size_t(ncx) * ncy, ncells = cpl * ncz, bsz = size_t(d.kpad) * d.mpad;
+  const int own0 = v->own0, nown = v->ctx->nc[2], own1 = own0 + nown;
+  const size_t cpl = size_t(ncx) * ncy, ncells = cpl * nown, bsz = size_t(d.kpad) * d.mpad;
   int sel[VK_MAX_BLOCKS];
   const double *state[VK_MAX_BLOCKS];
   const int nstates = vanka::distinct_states(d.nblk, d.var, d.mode ? lin : nullptr, sel, state);
@@ -559,7 +573,7 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
                            ncells, need * 1e-9, (3.0 * double(km_layer) + double(b_layer)) * 1e-9, double(free_b) * 1e-9);
   }
   int L = int((budget - 2.0 * double(km_layer)) / double(km_layer + b_layer));
-  L = std::max(1, std::min(L, ncz));
+  L = std::max(1, std::min(L, nown));
   if (const char *e = getenv("STFEM_VANKA_SETUP_LAYERS")) // at most this many cell layers per batch (tests: the batch loop on small meshes)
     if (atoi(e) > 0) L = std::min(L, atoi(e));
   if (fresh) {
@@ -611,6 +625,7 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
     stokes_cip_end_tables(cp.Eu, cp.EDu);
     cp.Nu = c->Nu; cp.dmask = c->dmask; cp.detJ = b.detJ;
     cp.scale = d.delta0 / (8.0 * std::sqrt(2.0)); // pa = degree^3.5, degree 2 (operators.h:1614-1615)
+    cp.beyond = d.beyond;
     ap.Cc = d_C; ap.cip_stride = win_cells * CIP_CELL;
     for (int i = 0; i < d.nblk; ++i) ap.selc[i] = selc[i];
   }
@@ -618,9 +633,9 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
   const void *cellk = c->pspace ? reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<false>);
   stfem_launch_begin();
   v->setup_batches = 0;
-  for (int z0 = 0; z0 < ncz && e == hipSuccess && rc == STFEM_OK; z0 += L) {
+  for (int z0 = own0; z0 < own1 && e == hipSuccess && rc == STFEM_OK; z0 += L) {
     ++v->setup_batches;
-    const int z1 = std::min(ncz, z0 + L), zw0 = std::max(0, z0 - 1), zw1 = std::min(ncz, z1 + 1);
+    const int z1 = std::min(own1, z0 + L), zw0 = std::max(0, z0 - 1), zw1 = std::min(ncz, z1 + 1);
     const size_t wcells = cpl * size_t(zw1 - zw0), bcells = cpl * size_t(z1 - z0);
     mp.cell0 = (long long)cpl * zw0;
     for (int s = 0; s < nstates && rc == STFEM_OK; ++s) {
@@ -637,7 +652,7 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
     }
     ap.zw0 = zw0; ap.z0 = z0;
     if (rc == STFEM_OK) rc = vk_launch(reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel), dim3((unsigned)bcells), &ap, nullptr, "stokes_vanka_assemble_kernel");
-    if (rc == STFEM_OK) rc = stfem_vanka_invert_launch(d_B, v->d_blocks, m, d.mpad, d.kpad, (long long)cpl * z0, (unsigned)bcells, d_flag, nullptr);
+    if (rc == STFEM_OK) rc = stfem_vanka_invert_launch(d_B, v->d_blocks, m, d.mpad, d.kpad, (long long)cpl * (z0 - own0), (unsigned)bcells, d_flag, nullptr);
     if (rc == STFEM_OK) e = hipDeviceSynchronize(); // (the next batch reuses the scratch)
   }
   int flag = 0;
@@ -671,6 +686,8 @@ int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &
   stokes_cell_vanka *v = new (std::nothrow) stokes_cell_vanka;
   if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   v->ctx = c;
+  v->setup = d.setup ? d.setup : c;
+  v->own0 = d.setup ? d.own0 : 0;
   v->d = d;
   v->npl = c->pspace ? 4 : 8;
   v->nl = 81 + v->npl;

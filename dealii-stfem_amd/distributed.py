@@ -158,6 +158,12 @@ class Communicator:
     def halo_end(self, ctx, vec, stream=None):
         self._chk(self._L.stfem_halo_end(ctx._h, self._h, vec._h, stream), "stfem_halo_end")
 
+    def neighbour_exchange(self, lower, upper, count, send_down, send_up, recv_below, recv_above, stream=None):
+        """count doubles each way between device buffers (pointers or objects with .ptr): send_down -> the lower rank's recv_above,
+        send_up -> the upper rank's recv_below; a side with rank -1 is skipped (its buffers may be None)"""
+        ptrs = [getattr(v, "ptr", v) for v in (send_down, send_up, recv_below, recv_above)]
+        self._chk(self._L.stfem_neighbour_exchange(self._h, lower, upper, int(count), *ptrs, stream), "stfem_neighbour_exchange")
+
     def dot(self, ctx, a, b, n_own):
         import ctypes as C
         out = C.c_double(0.0)

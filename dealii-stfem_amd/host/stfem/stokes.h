@@ -176,6 +176,27 @@ public:
   }
   Number delta0() const { return delta0_; }
   int cip_weight() const { return cip_weight_; }
+  // The CIP term on a z-slab (stfem_stokes_set_cip_neighbours and its companions): neighbour_mask bit 4 / 5 a slab below / above,
+  // the vertex plane one cell layer beyond each interface on a general mesh; the ghost planes of a velocity source are what the
+  // neighbour's cip_pack made (StokesSystem packs, exchanges and binds them on a partitioned StokesSpaces).
+  void set_cip_neighbours(int neighbour_mask, const double *lower_vertices = nullptr, const double *upper_vertices = nullptr) const
+  {
+    check(stfem_stokes_set_cip_neighbours(h_, neighbour_mask, lower_vertices, upper_vertices), "stfem_stokes_set_cip_neighbours");
+  }
+  size_t cip_ghost_size() const { return size_t(stfem_stokes_cip_ghost_size(h_)); }
+  void cip_pack(const double *src_u, int side, double *out, void *stream = nullptr) const
+  {
+    check(stfem_stokes_cip_pack(h_, src_u, side, out, stream), "stfem_stokes_cip_pack");
+  }
+  void cip_add_slab(double *dst_u, const double *src_u, const double *weight_u, Number delta0, const double *lower_ghost,
+                    const double *upper_ghost, void *stream = nullptr) const
+  {
+    check(stfem_stokes_cip_add_slab(h_, dst_u, src_u, weight_u, delta0, lower_ghost, upper_ghost, stream), "stfem_stokes_cip_add_slab");
+  }
+  void cip_bind_ghosts(const double *src_u, const double *lower_ghost, const double *upper_ghost) const
+  {
+    check(stfem_stokes_cip_bind_ghosts(h_, src_u, lower_ghost, upper_ghost), "stfem_stokes_cip_bind_ghosts");
+  }
 
 private:
   void create(const Mesh &mesh, unsigned velocity_degree, Number viscosity, bool dg_pressure)
@@ -345,6 +366,26 @@ private:
   mutable Function g_;
 };
 
+// The ghost planes of one side of a slab for the CIP term (stfem_stokes_cip_ghost_create): 3 * 2 * ndx * ndy doubles on the device
+class CipGhost {
+public:
+  CipGhost() = default;
+  explicit CipGhost(stfem_stokes_ctx *c) : c_(c) { check(stfem_stokes_cip_ghost_create(c, &d_), "stfem_stokes_cip_ghost_create"); }
+  CipGhost(CipGhost &&o) noexcept : c_(o.c_), d_(o.d_) { o.d_ = nullptr; }
+  CipGhost &operator=(CipGhost &&o) noexcept
+  {
+    std::swap(c_, o.c_); std::swap(d_, o.d_);
+    return *this;
+  }
+  CipGhost(const CipGhost &) = delete;
+  ~CipGhost() { if (d_) stfem_stokes_cip_ghost_destroy(c_, d_); } // (drops the bindings that name it)
+  double *data() const { return d_; }
+
+private:
+  stfem_stokes_ctx *c_ = nullptr;
+  double *d_ = nullptr;
+};
+
 // operators.h:666-868; blocks in BlockSlice order
 template <int dim, typename Number> class SystemMatrixStokes {
 public:
@@ -369,6 +410,7 @@ public:
   void set_data(const BlockVectorType &solution_linearization_) const { solution_linearization = &solution_linearization_; }
   // the weight velocity of the operator's CIP term (StokesMatrixFreeOperator::set_cip_weight)
   void set_cip_weight(int weight) const { K.set_cip_weight(weight); }
+  Number delta0() const { return K.delta0(); }
   void vmult(BlockVectorType &dst, const BlockVectorType &src, void *stream = nullptr) const // 696-700
   {
     tensorproduct_eval(dst, src, K.vmult_mode(), stream);
@@ -530,6 +572,30 @@ public:
     const int rc = delta0 != 0 ? stfem_stokes_vanka_create_linearised_cip(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), mode, l.data(), delta0, &v)
                                : stfem_stokes_vanka_create_linearised(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), mode, l.data(), &v);
     if (rc != STFEM_OK) throw Error(rc, delta0 != 0 ? "stfem_stokes_vanka_create_linearised_cip" : "stfem_stokes_vanka_create_linearised");
+    v_.reset(v, stfem_stokes_vanka_destroy);
+  }
+  // The same on a z-slab of a partitioned mesh (stfem_stokes_vanka_create_linearised_partitioned).  K_extended: the operator of the slab
+  // plus ONE ghost cell layer on every z side of neighbour_mask (bit 4 below, bit 5 above; a z face of a ghost layer constrained / weak
+  // exactly where it is the global boundary); solution_linearization, also that of update, lives on K_extended; beyond_mask: there are
+  // cells beyond that ghost layer (read with delta0 != 0).  Blocks for the slab's own cells, applied on K_slab: vmult / step leave
+  // partial sums in the interface planes, completed by the add-exchange of the scalar views.  K_extended must outlive the smoother.
+  template <int dim>
+  PreconditionVankaStokes(const StokesMatrixFreeOperator<dim, Number> &K_slab, const StokesMatrixFreeOperator<dim, Number> &K_extended,
+                          const FullMatrix<Number> &Alpha, const FullMatrix<Number> &Beta, const BlockSlice &blk_slice,
+                          NonlinearTreatment nonlinear_treatment, const BlockVectorType &solution_linearization, Number delta0,
+                          int neighbour_mask, int beyond_mask)
+    : nb_(blk_slice.n_blocks()), slice_(blk_slice)
+  {
+    if (Alpha.m() != nb_ || Alpha.n() != nb_ || Beta.m() != nb_ || Beta.n() != nb_) throw std::invalid_argument("Alpha/Beta do not match the block slice");
+    std::vector<int32_t> var(nb_);
+    for (unsigned i = 0; i < nb_; ++i) var[i] = int32_t(blk_slice.decompose(i)[1]);
+    const int mode = nonlinear_treatment == NonlinearTreatment::None ? STFEM_CONVECTION_NONE
+                     : nonlinear_treatment == NonlinearTreatment::Explicit ? STFEM_CONVECTION_FORM : STFEM_CONVECTION_JACOBIAN;
+    const std::vector<const double *> l = linearization(solution_linearization);
+    stfem_stokes_vanka *v = nullptr;
+    const int rc = stfem_stokes_vanka_create_linearised_partitioned(K_slab.handle(), K_extended.handle(), int(nb_), var.data(), Alpha.data(),
+                                                                    Beta.data(), mode, l.data(), delta0, neighbour_mask, beyond_mask, &v);
+    if (rc != STFEM_OK) throw Error(rc, "stfem_stokes_vanka_create_linearised_partitioned");
     v_.reset(v, stfem_stokes_vanka_destroy);
   }
   // the blocks again for a new linearisation vector (same treatment, same storage): the next Newton / Picard step

@@ -7,6 +7,7 @@
 #include "stokes.h"
 #include "time_integrators.h"
 
+#include <array>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +31,7 @@ struct StokesSpaces {
     int32_t nd[3];
     check(stfem_n_dofs_1d(pc, nd), "stfem_n_dofs_1d");
     carrier = nd[0] != mesh.ncell[0] + 1 || nd[1] != mesh.ncell[1] + 1 || nd[2] != mesh.ncell[2] + 1; // (FE_DGP(1): 2 x 2 x n_cells)
+    box = mesh.vertices.empty();
   }
   // z-slab partition (the mesh is this rank's slab, interface faces taken out of its Dirichlet mask): the operator leaves partial
   // sums in the interface planes of every velocity component and of the pressure (tests/test_gpu_stokes.py::
@@ -37,7 +39,13 @@ struct StokesSpaces {
   // (stfem_halo_begin / end), inner products count owned planes only (stfem_dot_global) - as for the scalar operators.  FE_DGP(1)
   // pressure DoFs are cell-local: nothing to exchange and every entry owned, and the "planes" of the carrier context are the DoFs of
   // the slab's first and last cell - it gets the communicator (its inner products are summed over the ranks) and no neighbours
-  void set_partition(const std::shared_ptr<Communicator> &comm, int lower_rank, int upper_rank)
+  // The CIP term (delta0 != 0) crosses the interfaces once the operator knows its neighbours (stfem_stokes_set_cip_neighbours): on a
+  // box from this call alone; on a general mesh when the vertex plane one cell layer beyond each interface is handed in
+  // ((ncx + 1)(ncy + 1) * 3 doubles) - without them the operator is not told, and StokesSystem::vmult / form refuse delta0 != 0 on
+  // such a slab (the term would lack the interface faces).  Told, they pack, exchange and bind the ghost planes of their velocity
+  // sources.  The slabs are cuts of one mesh: on a box all of them have this slab's cell size.
+  void set_partition(const std::shared_ptr<Communicator> &comm, int lower_rank, int upper_rank, const double *lower_vertices = nullptr,
+                     const double *upper_vertices = nullptr)
   {
     for (auto &c : {q2, q1}) {
       const bool exchanges = c == q2 || !carrier;
@@ -45,8 +53,13 @@ struct StokesSpaces {
       c->lower_rank = exchanges ? lower_rank : -1;
       c->upper_rank = exchanges ? upper_rank : -1;
     }
+    const bool planes = box || ((lower_rank < 0 || lower_vertices) && (upper_rank < 0 || upper_vertices));
+    cip_neighbours = comm && planes ? (lower_rank >= 0 ? 16 : 0) | (upper_rank >= 0 ? 32 : 0) : 0;
+    check(stfem_stokes_set_cip_neighbours(stokes, cip_neighbours, lower_vertices, upper_vertices), "stfem_stokes_set_cip_neighbours");
   }
   bool carrier = false; // q1 is the FE_DGP(1) carrier context
+  bool box = true;      // axis-aligned uniform mesh (no vertex array)
+  int cip_neighbours = 0;
 };
 
 // BlockVectorT over a two-variable BlockSlice (LinearAlgebra::distributed::BlockVector with velocity and pressure blocks)
@@ -168,6 +181,7 @@ public:
   void initialize_dof_vector(StokesBlockVector &v) const { v.reinit(spaces, stokes, slice); }
   void vmult(StokesBlockVector &dst, const StokesBlockVector &src, void *stream = nullptr) const
   {
+    bind_cip_ghosts(src, stream);
     A.vmult(dst.blocks(), src.blocks(), stream);
     if (spaces->q2->comm) // partitioned: dst.compress(add) on every block through its scalar view
       for (unsigned b = 0; b < dst.n_blocks(); ++b) compress_add(*dst.view(b).context(), dst.view(b).handle(), stream);
@@ -175,6 +189,7 @@ public:
   // the nonlinear weak form (SystemMatrixStokes::form) and the linearisation vector of both (referred to, not copied)
   void form(StokesBlockVector &dst, const StokesBlockVector &src, void *stream = nullptr) const
   {
+    bind_cip_ghosts(src, stream);
     A.form(dst.blocks(), src.blocks(), stream);
     if (spaces->q2->comm)
       for (unsigned b = 0; b < dst.n_blocks(); ++b) compress_add(*dst.view(b).context(), dst.view(b).handle(), stream);
@@ -183,10 +198,59 @@ public:
   void set_cip_weight(int weight) const { A.set_cip_weight(weight); }
 
 private:
+  // Partitioned with the CIP term: every velocity source's two DoF planes next to each interface go to that neighbour
+  // (stfem_stokes_cip_pack, stfem_neighbour_exchange: one more message per neighbour and source, before the operator call) and what
+  // arrives is bound to the source (stfem_stokes_cip_bind_ghosts).  A pool of one receive pair per velocity block of the slice, of
+  // ghost size (CipGhost): slot k serves the k-th velocity block of every apply, and the source it served before is unbound, so the
+  // context holds at most that many bindings and none of a vector that has since been freed.  The two send buffers are shared:
+  // `stream` has waited for the arrival before the next pack.  All applies of one system are taken to run on one stream.  A weight
+  // velocity needs no ghosts (a face reads it on its own plane).
+  // A partitioned slab with delta0 != 0 whose operator was NOT told of its neighbours (set_partition on a general mesh without the
+  // vertex planes) would silently lack the interface faces: refused here.  Only vmult and form bind; the slice-add entry points of
+  // SystemMatrixStokes on such a slab return STFEM_ERR_INVALID_ARGUMENT from the boundary (no binding), they are not served yet.
+  void bind_cip_ghosts(const StokesBlockVector &src, void *stream) const
+  {
+    const Context &c = *spaces->q2;
+    if (!c.comm || A.delta0() == 0) return;
+    const int expected = (c.lower_rank >= 0 ? 16 : 0) | (c.upper_rank >= 0 ? 32 : 0);
+    if (spaces->cip_neighbours != expected)
+      throw Error(STFEM_ERR_INVALID_ARGUMENT, "StokesSystem: delta0 != 0 on a partitioned general mesh needs the neighbours' vertex planes "
+                                              "(StokesSpaces::set_partition): the CIP term would lack the interface faces");
+    if (!expected) return;
+    const int64_t n = stfem_stokes_cip_ghost_size(stokes);
+    if (!send[0].data())
+      for (CipGhost &g : send) g = CipGhost(stokes);
+    for (Slot &s : pool) { // (all first: an address may have moved to another slot since the last apply)
+      if (s.bound) check(stfem_stokes_cip_bind_ghosts(stokes, s.bound, nullptr, nullptr), "stfem_stokes_cip_bind_ghosts");
+      s.bound = nullptr;
+    }
+    unsigned k = 0;
+    for (unsigned b = 0; b < src.n_blocks(); ++b) {
+      if (slice.decompose(b)[1] != 0) continue;
+      const double *u = src.blocks()[b].data();
+      if (k == pool.size()) pool.push_back({nullptr, {CipGhost(stokes), CipGhost(stokes)}});
+      Slot &s = pool[k++];
+      if (c.lower_rank >= 0) check(stfem_stokes_cip_pack(stokes, u, 0, send[0].data(), stream), "stfem_stokes_cip_pack");
+      if (c.upper_rank >= 0) check(stfem_stokes_cip_pack(stokes, u, 1, send[1].data(), stream), "stfem_stokes_cip_pack");
+      check(stfem_neighbour_exchange(c.comm->handle(), c.lower_rank, c.upper_rank, n, send[0].data(), send[1].data(), s.recv[0].data(),
+                                     s.recv[1].data(), stream),
+            "stfem_neighbour_exchange");
+      check(stfem_stokes_cip_bind_ghosts(stokes, u, c.lower_rank >= 0 ? s.recv[0].data() : nullptr,
+                                         c.upper_rank >= 0 ? s.recv[1].data() : nullptr),
+            "stfem_stokes_cip_bind_ghosts");
+      s.bound = u;
+    }
+  }
+  struct Slot {
+    const double *bound; // the source this slot's planes are bound to
+    std::array<CipGhost, 2> recv;
+  };
   const SystemMatrixStokes<dim, Number> &A;
   std::shared_ptr<StokesSpaces> spaces;
   stfem_stokes_ctx *stokes;
   BlockSlice slice;
+  mutable std::array<CipGhost, 2> send;
+  mutable std::vector<Slot> pool;
 };
 
 // the start vector of the power iteration (estimate_max_eigenvalue in stmg.h): (i mod 11) - mean on every block, each of its own size

@@ -216,6 +216,13 @@ int stfem_halo_begin_split(stfem_comm *comm, stfem_ctx *ctx_lo, stfem_vec *v_lo,
                            void *stream);
 int stfem_planes_move(stfem_ctx *ctx_src, const stfem_vec *src, int iz_src, stfem_ctx *ctx_dst, stfem_vec *dst, int iz_dst, int nplanes,
                       int add_mask, void *stream);
+/* One raw exchange with the z neighbours (the ghost planes of stfem_stokes_cip_pack): count doubles each way, send_down -> the lower
+ * rank's recv_above, send_up -> the upper rank's recv_below; device pointers, one ncclGroup on the communicator's stream after what
+ * `stream` has enqueued, `stream` waits for the arrival; a side with rank -1 is skipped and its buffers are not touched.  On the
+ * self-loop communicator (world 1, both ranks 0) what is sent up arrives in recv_below and what is sent down in recv_above.  Not
+ * while a halo exchange is in flight (between begin and end). */
+int stfem_neighbour_exchange(stfem_comm *comm, int lower_rank, int upper_rank, int64_t count, const double *send_down,
+                             const double *send_up, double *recv_below, double *recv_above, void *stream);
 /* stfem_dot followed by the sum over all ranks (synchronous) */
 int stfem_dot_global(stfem_ctx *ctx, stfem_comm *comm, const stfem_vec *a, const stfem_vec *b,
                      int64_t n_own, double *out, void *stream);
@@ -551,13 +558,45 @@ int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *ctx, int weak_mask, int o
  * of the operator - cell, coupling, boundary and convection launches, vector mass, nitsche_rhs, divergence, drag_lift - is cell-local
  * and leaves partial sums in the interface planes, which the add-exchange of the scalar views completes (the velocity components on
  * a FE_Q(2) context of the slab, the FE_Q(1) pressure on stfem_stokes_pressure_ctx; FE_DGP(1) pressure DoFs are cell-local and the
- * carrier context must not be exchanged).  NOT partitioned: this term - a face in an interface plane needs the cells of the
- * neighbour slab, which a slab context does not hold, so with delta0 != 0 the slabs' sums lack the interface faces - and the
- * per-cell layout of the two-variable Vanka smoother (stfem_stokes_vanka_create_linearised), whose blocks next to an interface
- * would need the neighbour's cells as the scalar smoother's ghost layers provide them. */
+ * carrier context must not be exchanged).  This term: a face in an interface plane needs the cells of the neighbour slab.  A cell
+ * adds only its own side's test contribution, so a slab told of its neighbours (set_cip_neighbours) treats face 4 of its bottom cell
+ * layer / face 5 of its top one as interior, reads the neighbour's source values from two ghost DoF planes per side (cip_pack on the
+ * sender, any transport, e.g. stfem_neighbour_exchange) and the neighbour's geometry from one ghost vertex plane, and again leaves
+ * partial sums in the interface planes.  Without set_cip_neighbours the slabs' sums lack the interface faces.  The per-cell layout
+ * of the two-variable Vanka smoother, whose blocks next to an interface need the neighbour's cells, is built on a slab from an
+ * extended context with one ghost cell layer per neighbour (stfem_stokes_vanka_create_linearised_partitioned), as the scalar
+ * smoother's ghost layers provide them.  NOT partitioned: the class blocks of a box (stfem_stokes_vanka_create), GMGStokes. */
 enum { STFEM_CIP_WEIGHT_SOURCE = 0, STFEM_CIP_WEIGHT_LINEARISATION = 1 };
 int stfem_stokes_set_cip(stfem_stokes_ctx *ctx, double delta0, int weight);
 int stfem_stokes_cip_add(stfem_stokes_ctx *ctx, double *dst_u, const double *src_u, const double *weight_u, double delta0, void *stream);
+/* a z-slab's neighbours for the CIP term: neighbour_mask bit 4 a slab below, bit 5 a slab above, any other bit
+ * STFEM_ERR_INVALID_ARGUMENT; lower/upper_vertices: host, (ncx+1)(ncy+1)*3 doubles, the vertex plane one cell layer beyond the
+ * interface (NULL on axis-aligned uniform meshes, where it is not read; required otherwise for each side named); mask 0 restores the
+ * state of a context that never had neighbours: every entry point issues the launches it issues without this call.  The slabs are
+ * cuts of ONE mesh with the same x-y cell counts; without vertex planes that is one uniform box, and the neighbour's cells are taken
+ * to have this slab's edge lengths in all three directions (nothing can check it: two boxes of different hz give wrong numbers).
+ * A failure (STFEM_ERR_OUT_OF_MEMORY included) leaves the context as it was.  The bindings of stfem_stokes_cip_bind_ghosts stay until
+ * the caller unbinds them (NULL, NULL) or destroys the array with stfem_stokes_cip_ghost_destroy: unbind a source before it is freed. */
+int stfem_stokes_set_cip_neighbours(stfem_stokes_ctx *ctx, int neighbour_mask, const double *lower_vertices, const double *upper_vertices);
+int64_t stfem_stokes_cip_ghost_size(const stfem_stokes_ctx *ctx);            /* 3 * 2 * ndx * ndy */
+/* a zeroed device array of that size, for callers without an allocator of their own (any device array of the size serves as well);
+ * destroy also drops every binding of stfem_stokes_cip_bind_ghosts that names the array */
+int stfem_stokes_cip_ghost_create(stfem_stokes_ctx *ctx, double **device_out);
+void stfem_stokes_cip_ghost_destroy(stfem_stokes_ctx *ctx, double *ghost);
+/* what the neighbour on `side` (0 lower, 1 upper) needs of src_u: this slab's planes 1, 2 (side 0) or ndz-3, ndz-2 (side 1), laid out
+ * [comp][plane, ascending z][ndy][ndx]; entries on DoFs that THIS context constrains strongly are written as 0 (only the sender knows
+ * a global z boundary behind a one-layer slab) */
+int stfem_stokes_cip_pack(stfem_stokes_ctx *ctx, const double *src_u, int side, double *out, void *stream);
+/* the term by itself on a slab: stfem_stokes_cip_add with the neighbours' planes (NULL for a side without neighbour; a missing array
+ * for a side with one is STFEM_ERR_INVALID_ARGUMENT, dst_u equal to any other argument STFEM_ERR_ALIAS).  stfem_stokes_cip_add itself
+ * keeps adding the faces inside the slab alone. */
+int stfem_stokes_cip_add_slab(stfem_stokes_ctx *ctx, double *dst_u, const double *src_u, const double *weight_u, double delta0,
+                              const double *lower_ghost, const double *upper_ghost, void *stream);
+/* for the integrated entry points (vmult, st_vmult, st_vmult_slice_add and their _convection forms after set_cip): the ghost planes
+ * of a velocity source, looked up by the source pointer at launch; NULL, NULL unbinds; any number of bindings.  With neighbours set
+ * and delta0 != 0 an entry point whose velocity source has no binding, or one without the planes of a side with a neighbour, returns
+ * STFEM_ERR_INVALID_ARGUMENT before anything touches the device. */
+int stfem_stokes_cip_bind_ghosts(stfem_stokes_ctx *ctx, const double *src_u, const double *lower_ghost, const double *upper_ghost);
 int64_t stfem_stokes_n_face_points(const stfem_stokes_ctx *ctx);
 int stfem_stokes_face_points(const stfem_stokes_ctx *ctx, double *out);
 int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *ctx, const double *g_at_face_points, double *dst_u, double *dst_p, void *stream);
@@ -626,6 +665,20 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
  * of the term and of this layout. */
 int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha,
                                          const double *Beta, int mode, const double *const *lin_blocks, stfem_stokes_vanka **out);
+/* The per-cell blocks on a z-slab of a partitioned mesh.  extended: a Stokes context of the slab plus ONE ghost cell layer on every z
+ * side named in neighbour_mask (bit 4 below, bit 5 above; same x-y cell counts, pressure space, viscosity, x-y masks and weak set; a z
+ * face of a ghost layer is constrained / weak exactly where it is the GLOBAL boundary); lin_blocks live on `extended`; beyond_mask bit
+ * 4 / 5: there are cells beyond that ghost layer - with the CIP term the face between the ghost cell and the cell beyond adds, through
+ * the ghost cell's own side, to entries of the slab's outer cell layer, from the ghost layer's geometry and the weight on its outer
+ * plane alone; without the term beyond_mask is ignored.  Blocks are built for the slab's own cells only, stored and applied on `slab`:
+ * vmult / step leave PARTIAL sums in the interface planes, completed by the add-exchange of the scalar views.  `extended` must outlive
+ * the smoother, and stfem_stokes_vanka_update takes states on `extended`.  delta0 == 0: the blocks of create_linearised.
+ * STFEM_ERR_SHAPE_MISMATCH: an `extended` whose x-y cell counts, pressure space or layer count (slab + one per neighbour) do not fit;
+ * STFEM_ERR_INVALID_ARGUMENT: the refusals of create_linearised_cip, a neighbour bit outside 4 / 5, a beyond_mask bit without its
+ * neighbour bit - all before the device is touched. */
+int stfem_stokes_vanka_create_linearised_partitioned(stfem_stokes_ctx *slab, stfem_stokes_ctx *extended, int n_blocks,
+        const int32_t *block_variable, const double *Alpha, const double *Beta, int mode, const double *const *lin_blocks_extended,
+        double delta0, int neighbour_mask, int beyond_mask, stfem_stokes_vanka **out);
 int stfem_stokes_vanka_create_linearised_cip(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha,
                                              const double *Beta, int mode, const double *const *lin_blocks, double delta0,
                                              stfem_stokes_vanka **out);

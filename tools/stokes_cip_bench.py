@@ -8,8 +8,11 @@ Set-up mode: what the CIP term in the per-cell Vanka blocks (StokesPreconditionV
 jacobian mode, cG(1), on N^3 cells (default 32): two smoothers of the same context, delta0 = 0 and delta0 = 1, updated in alternating
 rounds, each update ended by a device synchronise.  --root DIR loads the package of another checkout (one without the term times
 delta0 = 0 alone), to run the two checkouts in alternating processes.
+Slab mode: the term by itself (cip_add) on a z-slab of NXY x NXY x NZ cells (default 64 x 64 x 32) without neighbours and, with
+cip_add_slab, with a neighbour on both sides; --root as above (a checkout without the slab entry points times cip_add alone).
 Usage: stokes_cip_bench.py [N] [rounds] [calls per round]
-       stokes_cip_bench.py setup [N] [rounds] [--root DIR]"""
+       stokes_cip_bench.py setup [N] [rounds] [--root DIR]
+       stokes_cip_bench.py slab [NXY] [NZ] [rounds] [calls per round] [--root DIR]"""
 import importlib
 import os
 import sys
@@ -61,6 +64,64 @@ def setup_mode(n, rounds):
         del smoothers, op, lin, probe
 
 
+def slab_mode(nxy, nz, rounds, calls):
+    """the term by itself on a slab of nxy x nxy x nz cells: cip_add (the faces inside the slab, the instantiations without SLAB) and,
+    where this checkout has it, cip_add_slab with a neighbour on both sides (ghost planes packed from the slab's own source, the ghost
+    vertex planes the slab's outer planes shifted by one layer), in alternating rounds"""
+    nc = (nxy, nxy, nz)
+    slab = "stfem_stokes_cip_add_slab" in stfem.SIGNATURES
+    for mesh in ("box", "perturbed"):
+        upper = (1.0, 1.0, nz / nxy)
+        verts = stfem.mesh_vertices(nc, upper=upper, distort=0.1, seed=7) if mesh == "perturbed" else None
+        op = stfem.StokesMatrixFreeOperator(nc, vertices=verts, upper=upper, dirichlet_mask=63 & ~48, viscosity=1.0)
+        rng = np.random.default_rng(0)
+        u, w = (op.initialize_dof_vector(0, rng.uniform(-1, 1, 3 * op.n_velocity)) for _ in range(2))
+        dst = op.initialize_dof_vector(0)
+        probe = op.initialize_dof_vector(1)
+        kinds = {"cip_add, no neighbours": lambda: op.cip_add(dst, u, w, 1.0)}
+        if slab:
+            V = np.asarray(verts).reshape(nz + 1, -1, 3) if verts is not None else None
+            shift = np.array([0.0, 0.0, upper[2] / nz])
+            lo, up = op.initialize_dof_vector(0), op.initialize_dof_vector(0)
+            op.cip_pack(u, 1, lo)
+            op.cip_pack(u, 0, up)
+
+            def with_neighbours(mask):
+                op.set_cip_neighbours(mask, None if V is None else V[0] - shift, None if V is None else V[nz] + shift)
+
+            def two_neighbours():
+                op.cip_add_slab(dst, u, w, 1.0, lo, up)
+
+            kinds["cip_add_slab, two neighbours"] = two_neighbours
+
+        def timed(name):
+            if slab:
+                with_neighbours(48 if "slab" in name else 0)
+            for _ in range(3):
+                kinds[name]()
+            probe.download()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                kinds[name]()
+            probe.download()  # (synchronises)
+            return (time.perf_counter() - t0) / calls * 1e3
+
+        times = {k: [] for k in kinds}
+        for k in kinds:
+            timed(k)
+        for _ in range(rounds):
+            for k in kinds:
+                times[k].append(timed(k))
+        print(f"{mesh:9s} {nxy} x {nxy} x {nz} cells, {rounds} rounds x {calls} calls, measured ({WHICH}):", flush=True)
+        for k in kinds:
+            print(f"    {k:29s}: {fmt(times[k])}", flush=True)
+        del op, u, w, dst, probe
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "slab":
+    a = [int(v) for v in sys.argv[2:]]
+    slab_mode(a[0] if len(a) > 0 else 64, a[1] if len(a) > 1 else 32, a[2] if len(a) > 2 else 9, a[3] if len(a) > 3 else 40)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "setup":
     setup_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 32, int(sys.argv[3]) if len(sys.argv) > 3 else 7)
     sys.exit(0)

@@ -684,8 +684,7 @@ template <class PR> static int diagonal_t(stfem_ctx *c, double ms, double ls, st
     const int rc = ensure_metric<PR>(c, lap.coef, mass.coef, st);
     if (rc != STFEM_OK) return rc;
   }
-  STFEM_TRY(hipMemsetAsync(diag->blk[0], 0, size_t(c->ndofs) * sizeof(real), st));
-  typename PR::Diag prm;
+  typename PR::Diag prm; // (the kernel stores every entry of the block: nothing to clear)
   std::memset(&prm, 0, sizeof(prm));
   prm.diag = static_cast<real *>(diag->blk[0]);
   prm.ncx = c->nc[0]; prm.ncy = c->nc[1]; prm.ncz = c->nc[2];

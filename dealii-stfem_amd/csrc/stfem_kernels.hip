@@ -98,41 +98,58 @@ template <int P, int NBM> int launch_atomic_t(const SweepParams &prm, hipStream_
 
 namespace {
 
-__global__ __launch_bounds__(128) void diagonal_kernel(const DiagParams prm)
+// what cell `cell` adds to the diagonal entry of its local DoF (a, b, c)
+__device__ inline real_t diagonal_of_cell(const DiagParams &prm, int64_t cell, int a, int b, int c)
 {
   const int n = prm.p + 1, n3 = n * n * n;
-  const int64_t cell = blockIdx.x;
-  const int cx = int(cell % prm.ncx), cy = int((cell / prm.ncx) % prm.ncy), cz = int(cell / (int64_t(prm.ncx) * prm.ncy));
-  for (int l = threadIdx.x; l < n3; l += blockDim.x) {
-    const int a = l % n, b = (l / n) % n, c = l / (n * n);
-    const int ix = prm.p * cx + a, iy = prm.p * cy + b, iz = prm.p * cz + c;
+  if (prm.metric) {
+    real_t v = real_t(0);
+    const real_t *m = prm.metric + cell * 8 * n3; // [q][8] records
+    for (int qz = 0; qz < n; ++qz)
+      for (int qy = 0; qy < n; ++qy)
+        for (int qx = 0; qx < n; ++qx) {
+          const int q = qx + n * (qy + n * qz);
+          const real_t sa = prm.S[qx * n + a], sb = prm.S[qy * n + b], sc = prm.S[qz * n + c];
+          const real_t val = sa * sb * sc;
+          const real_t g0 = prm.D[qx * n + a] * sb * sc, g1 = sa * prm.D[qy * n + b] * sc, g2 = sa * sb * prm.D[qz * n + c];
+          const real_t *mq = m + q * 8;
+          v += prm.ms * mq[6] * val * val +
+               prm.ls * (mq[0] * g0 * g0 + mq[3] * g1 * g1 + mq[5] * g2 * g2 +
+                         real_t(2) * (mq[1] * g0 * g1 + mq[2] * g0 * g2 + mq[4] * g1 * g2));
+        }
+    return v;
+  }
+  const real_t fK = prm.vol * (prm.coef_lap ? prm.coef_lap[cell] : real_t(1));
+  const real_t fM = prm.vol * (prm.coef_mass ? prm.coef_mass[cell] : real_t(1));
+  return prm.ms * fM * prm.m1[a] * prm.m1[b] * prm.m1[c] +
+         prm.ls * fK * (prm.ihx2 * prm.l1[a] * prm.m1[b] * prm.m1[c] + prm.ihy2 * prm.m1[a] * prm.l1[b] * prm.m1[c] +
+                        prm.ihz2 * prm.m1[a] * prm.m1[b] * prm.l1[c]);
+}
+
+// One thread per DoF: it adds what the (up to eight) cells around the DoF contribute, in the fixed order z, y, x ascending, and stores
+// the sum, so the diagonal repeats bit for bit (one global atomic add per cell and local DoF made the order of the sum, and with it
+// the last bits, depend on timing).  Constrained DoFs get an exact zero.
+__global__ __launch_bounds__(128) void diagonal_kernel(const DiagParams prm)
+{
+  const int p = prm.p, nz = p * prm.ncz + 1;
+  const int64_t ndofs = int64_t(prm.nx) * prm.ny * nz;
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < ndofs; i += int64_t(gridDim.x) * blockDim.x) {
+    const int ix = int(i % prm.nx), iy = int((i / prm.nx) % prm.ny), iz = int(i / (int64_t(prm.nx) * prm.ny));
     const bool con = ((prm.dmask & 1) && ix == 0) || ((prm.dmask & 2) && ix == prm.nx - 1) ||
                      ((prm.dmask & 4) && iy == 0) || ((prm.dmask & 8) && iy == prm.ny - 1) ||
-                     ((prm.dmask & 16) && iz == 0) || ((prm.dmask & 32) && iz == prm.p * prm.ncz);
-    if (con) continue;
+                     ((prm.dmask & 16) && iz == 0) || ((prm.dmask & 32) && iz == nz - 1);
     real_t v = real_t(0);
-    if (prm.metric) {
-      const real_t *m = prm.metric + cell * 8 * n3; // [q][8] records
-      for (int qz = 0; qz < n; ++qz)
-        for (int qy = 0; qy < n; ++qy)
-          for (int qx = 0; qx < n; ++qx) {
-            const int q = qx + n * (qy + n * qz);
-            const real_t sa = prm.S[qx * n + a], sb = prm.S[qy * n + b], sc = prm.S[qz * n + c];
-            const real_t val = sa * sb * sc;
-            const real_t g0 = prm.D[qx * n + a] * sb * sc, g1 = sa * prm.D[qy * n + b] * sc, g2 = sa * sb * prm.D[qz * n + c];
-            const real_t *mq = m + q * 8;
-            v += prm.ms * mq[6] * val * val +
-                 prm.ls * (mq[0] * g0 * g0 + mq[3] * g1 * g1 + mq[5] * g2 * g2 +
-                           real_t(2) * (mq[1] * g0 * g1 + mq[2] * g0 * g2 + mq[4] * g1 * g2));
-          }
-    } else {
-      const real_t fK = prm.vol * (prm.coef_lap ? prm.coef_lap[cell] : real_t(1));
-      const real_t fM = prm.vol * (prm.coef_mass ? prm.coef_mass[cell] : real_t(1));
-      v = prm.ms * fM * prm.m1[a] * prm.m1[b] * prm.m1[c] +
-          prm.ls * fK * (prm.ihx2 * prm.l1[a] * prm.m1[b] * prm.m1[c] + prm.ihy2 * prm.m1[a] * prm.l1[b] * prm.m1[c] +
-                         prm.ihz2 * prm.m1[a] * prm.m1[b] * prm.l1[c]);
+    if (!con) {
+      // the cells [x0, x1] that hold node ix: two where it lies on an inner cell boundary
+      const int x0 = (ix % p == 0 && ix > 0) ? ix / p - 1 : ix / p, x1 = ix == p * prm.ncx ? prm.ncx - 1 : ix / p;
+      const int y0 = (iy % p == 0 && iy > 0) ? iy / p - 1 : iy / p, y1 = iy == p * prm.ncy ? prm.ncy - 1 : iy / p;
+      const int z0 = (iz % p == 0 && iz > 0) ? iz / p - 1 : iz / p, z1 = iz == p * prm.ncz ? prm.ncz - 1 : iz / p;
+      for (int cz = z0; cz <= z1; ++cz)
+        for (int cy = y0; cy <= y1; ++cy)
+          for (int cx = x0; cx <= x1; ++cx)
+            v += diagonal_of_cell(prm, cx + int64_t(prm.ncx) * (cy + int64_t(prm.ncy) * cz), ix - p * cx, iy - p * cy, iz - p * cz);
     }
-    unsafeAtomicAdd(prm.diag + ix + int64_t(prm.nx) * (iy + int64_t(prm.ny) * iz), v);
+    prm.diag[i] = v;
   }
 }
 
@@ -141,8 +158,10 @@ __global__ __launch_bounds__(128) void diagonal_kernel(const DiagParams prm)
 int launch_diagonal(const DiagParams &prm, void *stream)
 {
   stfem_launch_begin();
-  const int64_t ncells = int64_t(prm.ncx) * prm.ncy * prm.ncz;
-  hipLaunchKernelGGL(diagonal_kernel, dim3((unsigned)ncells), dim3(128), 0, static_cast<hipStream_t>(stream), prm);
+  const int64_t ndofs = int64_t(prm.nx) * prm.ny * (int64_t(prm.p) * prm.ncz + 1);
+  const int64_t groups = (ndofs + 127) / 128;
+  const unsigned grid = (unsigned)(groups < (int64_t(1) << 20) ? groups : (int64_t(1) << 20));
+  hipLaunchKernelGGL(diagonal_kernel, dim3(grid), dim3(128), 0, static_cast<hipStream_t>(stream), prm);
   return stfem_launch_end("diagonal_kernel");
 }
 

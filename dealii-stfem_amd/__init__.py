@@ -50,6 +50,11 @@ class _SpaceDesc(C.Structure):
                 ("precision", C.c_int32)]
 
 
+class _StokesSpaceDesc(C.Structure):
+    _fields_ = [("velocity_degree", C.c_int32), ("pressure_space", C.c_int32), ("viscosity", C.c_double),
+                ("reserved", C.c_int32 * 4)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _lib = None
@@ -220,6 +225,13 @@ SIGNATURES = {
     "stfem_last_tile_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
 }
 
+# every symbol the companion header include/stfem_stokes_space.h declares (tests/test_stokes_space_header_cpu.py)
+SPACE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "stfem_stokes_space.h")
+SPACE_SIGNATURES = {
+    "stfem_stokes_create_space": (C.c_int, [C.POINTER(_MeshDesc), C.POINTER(_StokesSpaceDesc), C.POINTER(_vp)]),
+    "stfem_stokes_last_cell_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+}
+
 
 def lib():
     """Loads the HIP library; raises (never falls back) if it has not been built."""
@@ -229,7 +241,7 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: run `make -C dealii-stfem_amd/csrc` "
                               "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(os.environ.get("STFEM_LIB", LIB_PATH))  # STFEM_LIB: experiment builds only
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SPACE_SIGNATURES.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -833,11 +845,12 @@ class StokesMatrixFreeOperator:
     torch.Tensor.data_ptr()): velocity 3 * n_velocity doubles (component-major), pressure n_pressure.
     vmult / st_vmult / st_vmult_slice_add take the convection mode (CONVECTION_FORM / CONVECTION_JACOBIAN) and the linearisation
     velocity `lin` that the reference's set_data hands in; with the defaults they are the linear operator.  delta0 != 0 adds the
-    CIP interior-face stabilisation (operators.h:1605-1633) to all of them, see set_cip."""
+    CIP interior-face stabilisation (operators.h:1605-1633) to all of them, see set_cip.  with_degree(3, ...): FE_Q(3)^3 x FE_Q(2) /
+    FE_DGP(2), the linear cell operator alone."""
 
     def __init__(self, ncell, vertices=None, lower=(0, 0, 0), upper=(1, 1, 1), dirichlet_mask=63,
                  viscosity=1.0, velocity_degree=2, device=0, weak_boundary_ids=(), outflow_boundary_ids=(),
-                 penalty1=20.0, penalty2=10.0, dg_pressure=False, delta0=0.0, cip_weight=CIP_WEIGHT_SOURCE):
+                 penalty1=20.0, penalty2=10.0, dg_pressure=False, delta0=0.0, cip_weight=CIP_WEIGHT_SOURCE, _space=None):
         """weak_boundary_ids / outflow_boundary_ids: boundary ids 0..5 (face 2 d + s) as in the reference's constructor
         (operators.h:1206-1211); penalty1 / penalty2: its Nitsche penalties (gamma1 = viscosity penalty1, gamma2 = penalty2)."""
         m = _MeshDesc()
@@ -852,9 +865,17 @@ class StokesMatrixFreeOperator:
         m.dirichlet_mask = dirichlet_mask
         m.device = device
         h = _vp()
-        # dg_pressure: FE_DGP(1) instead of FE_Q(1) (the reference's dGPressure, tests/tp_03stokes.cc:83-86)
-        _check(lib().stfem_stokes_create_ex(C.byref(m), velocity_degree, 1 if dg_pressure else 0, viscosity, C.byref(h)),
-               "stfem_stokes_create")
+        # dg_pressure: FE_DGP(degree - 1) instead of FE_Q(degree - 1) (the reference's dGPressure, tests/tp_03stokes.cc:83-86)
+        if _space is None:  # the keyword velocity_degree: stfem_stokes_create_ex, which builds degree 2 alone
+            _check(lib().stfem_stokes_create_ex(C.byref(m), velocity_degree, 1 if dg_pressure else 0, viscosity, C.byref(h)),
+                   "stfem_stokes_create")
+        else:               # with_degree: the constructor by descriptor
+            sd = _StokesSpaceDesc()
+            sd.velocity_degree, sd.pressure_space, sd.viscosity = int(_space[0]), 1 if dg_pressure else 0, float(viscosity)
+            sd.reserved[:] = _space[1]
+            _check(lib().stfem_stokes_create_space(C.byref(m), C.byref(sd), C.byref(h)), "stfem_stokes_create_space")
+            velocity_degree = int(_space[0])
+        self.velocity_degree = velocity_degree
         self._h = h
         self.n_velocity = lib().stfem_stokes_n_velocity_dofs(h)
         self.n_pressure = lib().stfem_stokes_n_pressure_dofs(h)
@@ -866,6 +887,23 @@ class StokesMatrixFreeOperator:
         self.delta0, self.cip_weight = 0.0, CIP_WEIGHT_SOURCE
         if delta0 != 0.0 or cip_weight != CIP_WEIGHT_SOURCE:
             self.set_cip(delta0, cip_weight)
+
+    @classmethod
+    def with_degree(cls, velocity_degree, ncell, reserved=(0, 0, 0, 0), **keywords):
+        """The operator through stfem_stokes_create_space; the keywords of the constructor except velocity_degree.  Degree 2: the
+        operator of the constructor, bit for bit.  Degree 3: FE_Q(3)^3 x FE_Q(2), or FE_DGP(2) with dg_pressure (ten DoFs per cell),
+        QGauss(4) - the pair of the reference's time degree 2 - with the linear cell operator alone: vmult, mass_vmult, st_vmult,
+        st_Tvmult, st_vmult_slice_add.  Weak / outflow ids, delta0 != 0, a convection mode and everything else raise StfemError
+        with status -2 and the reason."""
+        assert "velocity_degree" not in keywords and "_space" not in keywords
+        return cls(ncell, _space=(velocity_degree, tuple(int(v) for v in reserved)), **keywords)
+
+    def last_cell_plan(self):
+        """(workgroups, longest run of cells per wave) of the last colour launch of the degree-3 cell kernel; the environment
+        variable STFEM_STOKES_Q3_WORKGROUPS, read at every launch, caps the workgroups"""
+        out = (C.c_int32 * 2)()
+        _check(lib().stfem_stokes_last_cell_plan(self._h, out), "stfem_stokes_last_cell_plan")
+        return tuple(out)
 
     def set_cip(self, delta0, weight=CIP_WEIGHT_SOURCE):
         """The CIP gradient-jump term sum_F int_F delta0 h_F^2 / 2^3.5 (w.n)^2 [d_n u].[d_n v] on the interior faces in every later
@@ -925,7 +963,10 @@ class StokesMatrixFreeOperator:
 
     def face_points(self):
         """quadrature points of the weak faces [point][3], where the Dirichlet function is evaluated (operators.h:1911-1914)"""
-        out = np.zeros((lib().stfem_stokes_n_face_points(self._h), 3))
+        n = lib().stfem_stokes_n_face_points(self._h)
+        if n < 0:
+            raise StfemError(int(n), "stfem_stokes_n_face_points")
+        out = np.zeros((n, 3))
         _check(lib().stfem_stokes_face_points(self._h, _p(out)), "stfem_stokes_face_points")
         return out
 

@@ -93,6 +93,9 @@ struct stfem_stokes_desc {
 int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *out);
 
 #pragma GCC visibility push(hidden)
+// stfem_stokes.hip: every entry point whose kernels hard-code the 27 nodes of FE_Q(2) asks this first.  On a context of another
+// velocity degree (stfem_stokes_create_space): STFEM_ERR_UNSUPPORTED, "<entry> is built for velocity degree 2 only" in the record.
+int stokes_require_q2(const stfem_stokes_ctx *c, const char *entry);
 // stfem_vanka.hip: vanka_invert_kernel<double> on `count` m x m matrices at B (row-major, destroyed), the inverses in the apply's
 // layout [kpad][mpad] from block cell0 of out; *singular (device) is set to 1 by a matrix without a pivot.  `stream`: a hipStream_t.
 int stfem_vanka_invert_launch(double *B, double *out, int m, int mpad, int kpad, long long cell0, unsigned count, int *singular, void *stream);

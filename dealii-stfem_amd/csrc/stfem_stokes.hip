@@ -7,6 +7,8 @@
 // (stfem_stokes_boundary.hip), and with a convection mode (form / jacobian of the Navier-Stokes operator) the convection launches
 // (stfem_stokes_convection.hip), and with delta0 != 0 the CIP interior-face launches (stfem_stokes_cip.hip).  The helpers of the pressure space the solver around the operator needs: stfem_stokes_pressure.hip.
 // Every entry point describes its launches in ONE form, StokesParams (stfem_stokes_internal.h), put together by StokesLaunch below.
+// A context of velocity degree 3 (stfem_stokes_create_space) has one implementation of the linear cell operator, the cell kernel of
+// stfem_stokes_cell_q3.hip, and nothing on top of it: stokes_launch dispatches on the degree, stokes_require_q2 refuses the rest.
 #include "stfem_stokes_internal.h"
 
 #include <mutex>
@@ -41,6 +43,15 @@ static hipStream_t stokes_side_stream(int device)
 
 extern "C" {
 
+int stfem_stokes_last_cell_plan(const stfem_stokes_ctx *c, int32_t out[2])
+{
+  if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  if (!c->q3_launched) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "stfem_stokes_last_cell_plan: this context has not launched the degree-3 cell kernel");
+  out[0] = c->q3_plan[0];
+  out[1] = c->q3_plan[1];
+  return STFEM_OK;
+}
+
 int stfem_stokes_last_sweep_plan(const stfem_stokes_ctx *c, int32_t out[3])
 {
   if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
@@ -53,11 +64,36 @@ int stfem_stokes_create(const stfem_mesh_desc *mesh, int velocity_degree, double
   return stfem_stokes_create_ex(mesh, velocity_degree, 0, viscosity, out);
 }
 
+// The context of velocity degree 2 or 3 behind the three constructors
+static int stokes_create_degree(const stfem_mesh_desc *mesh, int velocity_degree, int pressure_space, double viscosity, stfem_stokes_ctx **out);
+
 int stfem_stokes_create_ex(const stfem_mesh_desc *mesh, int velocity_degree, int pressure_space, double viscosity, stfem_stokes_ctx **out)
 {
   if (!mesh || !out || pressure_space < 0 || pressure_space > 1) return STFEM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (velocity_degree != 2) return STFEM_ERR_UNSUPPORTED; // Q2/Q1 (BASELINE configs[4]) only
+  if (velocity_degree != 2) return STFEM_ERR_UNSUPPORTED; // this constructor: Q2/Q1 (BASELINE configs[4]) only; degree 3: stfem_stokes_create_space
+  return stokes_create_degree(mesh, velocity_degree, pressure_space, viscosity, out);
+}
+
+int stfem_stokes_create_space(const stfem_mesh_desc *mesh, const stfem_stokes_space_desc *space, stfem_stokes_ctx **out)
+{
+  if (!mesh || !space || !out) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_create_space: a null argument");
+  *out = nullptr;
+  for (int i = 0; i < 4; ++i)
+    if (space->reserved[i] != 0)
+      return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_create_space: reserved[%d] = %d, must be 0", i, (int)space->reserved[i]);
+  if (space->pressure_space < 0 || space->pressure_space > 1)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_create_space: pressure_space %d, must be 0 (FE_Q) or 1 (FE_DGP)",
+                           (int)space->pressure_space);
+  if (space->velocity_degree == 2) return stfem_stokes_create_ex(mesh, 2, space->pressure_space, space->viscosity, out);
+  if (space->velocity_degree != 3)
+    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "stfem_stokes_create_space: velocity degree %d is not built (2 and 3 are)",
+                           (int)space->velocity_degree);
+  return stokes_create_degree(mesh, 3, space->pressure_space, space->viscosity, out);
+}
+
+static int stokes_create_degree(const stfem_mesh_desc *mesh, int velocity_degree, int pressure_space, double viscosity, stfem_stokes_ctx **out)
+{
   for (int d = 0; d < 3; ++d)
     if (mesh->ncell[d] < 1) return STFEM_ERR_INVALID_ARGUMENT;
   int ndev = 0;
@@ -78,13 +114,15 @@ int stfem_stokes_create_ex(const stfem_mesh_desc *mesh, int velocity_degree, int
   c->nu = viscosity;
   for (int d = 0; d < 3; ++d) {
     c->nc[d] = mesh->ncell[d];
-    c->ndu[d] = 2 * mesh->ncell[d] + 1;
-    c->ndp[d] = mesh->ncell[d] + 1;
+    c->ndu[d] = velocity_degree * mesh->ncell[d] + 1;
+    c->ndp[d] = (velocity_degree - 1) * mesh->ncell[d] + 1;
   }
+  c->degree = velocity_degree;
   c->Nu = (long long)c->ndu[0] * c->ndu[1] * c->ndu[2];
   c->Np = (long long)c->ndp[0] * c->ndp[1] * c->ndp[2];
   c->pspace = pressure_space;
-  if (pressure_space == 1) c->Np = 4ll * c->nc[0] * c->nc[1] * c->nc[2]; // FE_DGP(1): 1, x, y, z per cell
+  // FE_DGP(1): 1, x, y, z per cell; FE_DGP(2): the ten Legendre products of total degree <= 2
+  if (pressure_space == 1) c->Np = (velocity_degree == 2 ? 4ll : 10ll) * c->nc[0] * c->nc[1] * c->nc[2];
   const size_t nv = size_t(c->nc[0] + 1) * (c->nc[1] + 1) * (c->nc[2] + 1);
   std::vector<double> v(nv * 3);
   if (mesh->vertices) {
@@ -114,14 +152,16 @@ int stfem_stokes_create_ex(const stfem_mesh_desc *mesh, int velocity_degree, int
   // 1D tables: FE_Q(2) and FE_Q(1) on Gauss-Lobatto nodes at the 3 Gauss points
   StokesParams &b = c->base;
   std::memset(&b, 0, sizeof(b));
-  const stfem::ShapeTables tu = stfem::make_shape_tables(2), tp = stfem::make_shape_tables(1);
+  const stfem::ShapeTables tu = stfem::make_shape_tables(velocity_degree), tp = stfem::make_shape_tables(velocity_degree - 1);
   std::vector<double> xq, wq;
-  stfem::gauss_rule(3, xq, wq);
+  stfem::gauss_rule(velocity_degree + 1, xq, wq);
   stfem::Mat Sp, Gp;
   stfem::lagrange_tables(tp.nodes, xq, Sp, Gp);
-  for (int i = 0; i < 9; ++i) { b.Su[i] = tu.S[i]; b.Du[i] = tu.D[i]; }
-  for (int i = 0; i < 6; ++i) b.Sp[i] = Sp[i];
-  for (int i = 0; i < 3; ++i) { b.xq[i] = xq[i]; b.wq[i] = wq[i]; }
+  if (velocity_degree == 2) {
+    for (int i = 0; i < 9; ++i) { b.Su[i] = tu.S[i]; b.Du[i] = tu.D[i]; }
+    for (int i = 0; i < 6; ++i) b.Sp[i] = Sp[i];
+    for (int i = 0; i < 3; ++i) { b.xq[i] = xq[i]; b.wq[i] = wq[i]; }
+  }
   b.vertices = c->d_vertices;
   b.ncx = c->nc[0]; b.ncy = c->nc[1]; b.ncz = c->nc[2];
   for (int d = 0; d < 3; ++d) { b.ndu[d] = c->ndu[d]; b.ndp[d] = c->ndp[d]; }
@@ -140,6 +180,26 @@ int stfem_stokes_create_ex(const stfem_mesh_desc *mesh, int velocity_degree, int
     b.detJ *= h;
   }
   std::memset(&c->coupling, 0, sizeof(c->coupling));
+  std::memset(&c->q3, 0, sizeof(c->q3));
+  if (velocity_degree == 3) { // FE_Q(3) and FE_Q(2) at the four Gauss points; no scalar pencil context: the cell kernel serves boxes too
+    StokesQ3Params &q = c->q3;
+    for (int i = 0; i < 16; ++i) { q.Su[i] = tu.S[i]; q.Du[i] = tu.D[i]; }
+    for (int i = 0; i < 12; ++i) q.Sp[i] = Sp[i];
+    for (int i = 0; i < 4; ++i) {
+      q.xq[i] = xq[i]; q.wq[i] = wq[i];
+      q.l1q[i] = std::sqrt(3.0) * (2.0 * xq[i] - 1.0);
+      q.l2q[i] = std::sqrt(5.0) * (6.0 * xq[i] * xq[i] - 6.0 * xq[i] + 1.0);
+    }
+    q.vertices = c->d_vertices;
+    q.ncx = c->nc[0]; q.ncy = c->nc[1]; q.ncz = c->nc[2];
+    for (int d = 0; d < 3; ++d) { q.ndu[d] = c->ndu[d]; q.ndp[d] = c->ndp[d]; q.hinv[d] = b.hinv[d]; }
+    q.Nu = c->Nu; q.Np = c->Np;
+    q.dmask = c->dmask;
+    q.nu = c->nu;
+    q.detJ = b.detJ;
+    *out = c;
+    return STFEM_OK;
+  }
   if (b.cart) {
     const char *e = getenv("STFEM_STOKES_CELL"); // 1: keep the cell kernel on boxes too (cross-checks, measurements)
     if (!(e && atoi(e) != 0)) {
@@ -198,9 +258,16 @@ void stfem_stokes_destroy(stfem_stokes_ctx *c)
 }
 
 } // extern "C"
+int stokes_require_q2(const stfem_stokes_ctx *c, const char *entry)
+{
+  if (c && c->degree != 2)
+    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "%s is built for velocity degree 2 only (this context has degree %d)", entry, c->degree);
+  return STFEM_OK;
+}
 int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *d)
 {
   if (!c || !d) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_internal_desc")) return rq;
   d->device = c->device; d->cart = c->base.cart; d->pspace = c->pspace; d->dmask = c->dmask;
   d->weak_mask = c->weak_mask; d->outflow_mask = c->outflow_mask;
   for (int k = 0; k < 3; ++k) {
@@ -421,6 +488,7 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
 int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double *const *lin, hipStream_t st)
 {
   // axis-aligned uniform mesh: the Kronecker path; otherwise the cell kernel
+  if (c->degree == 3) return stokes_cell_q3_launch(c, prm, st); // the linear cell operator is all a degree-3 context has
   const int rc = c->scalar ? stokes_cart_launch(c, prm, st) : stokes_cell_launch(c, prm, st);
   if (rc != STFEM_OK) return rc;
   // LoopType::Full: the boundary-face loop of the same vmult (the mass operator has none)
@@ -465,6 +533,8 @@ int stfem_stokes_vmult_convection(stfem_stokes_ctx *c, int mode, double *dst_u, 
     return STFEM_ERR_INVALID_ARGUMENT;
   if (dst_u == src_u || dst_p == src_p) return STFEM_ERR_ALIAS;
   if (mode != STFEM_CONVECTION_NONE && (lin_u == dst_u || lin_u == dst_p)) return STFEM_ERR_ALIAS;
+  if (mode != STFEM_CONVECTION_NONE)
+    if (const int rq = stokes_require_q2(c, "stfem_stokes_vmult_convection with a convection mode")) return rq;
   if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
   STFEM_TRY(hipSetDevice(c->device));
   StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
@@ -521,6 +591,8 @@ int stfem_stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timest
       for (int it = 0; it < ns; ++it)
         for (int d = 0; d < nt; ++d)
           if (dst_blocks[j] == lin_blocks[index(it, 0, d)]) return STFEM_ERR_ALIAS;
+  if (navier)
+    if (const int rq = stokes_require_q2(c, "stfem_stokes_st_vmult_convection with a convection mode")) return rq;
   for (int it = 0; it < ns; ++it)
     for (int d = 0; d < nt; ++d)
       if (const int rg = stokes_cip_source_ready(c, src_blocks[index(it, 0, d)])) return rg;
@@ -589,6 +661,8 @@ int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, in
     if (dst_blocks[j] == src_u || dst_blocks[j] == src_p) return STFEM_ERR_ALIAS;
     if (mode != STFEM_CONVECTION_NONE && dst_blocks[j] == lin_u) return STFEM_ERR_ALIAS;
   }
+  if (mode != STFEM_CONVECTION_NONE)
+    if (const int rq = stokes_require_q2(c, "stfem_stokes_st_vmult_slice_add_convection with a convection mode")) return rq;
   if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
   STFEM_TRY(hipSetDevice(c->device));
   StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);

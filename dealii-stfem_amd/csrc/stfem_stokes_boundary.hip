@@ -260,6 +260,7 @@ int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *c, int weak_mask, int out
 {
   if (!c || weak_mask < 0 || weak_mask > 63 || outflow_mask < 0 || outflow_mask > 63) return STFEM_ERR_INVALID_ARGUMENT;
   // a face in both sets takes the outflow branch in the reference (1680: checked first), i.e. no term in the linear operator
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_set_weak_boundaries")) return rq;
   c->outflow_mask = outflow_mask;
   c->weak_mask = weak_mask & ~outflow_mask;
   c->penalty1 = penalty1;
@@ -286,11 +287,16 @@ int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *c, int weak_mask, int out
   return STFEM_OK;
 }
 
-int64_t stfem_stokes_n_face_points(const stfem_stokes_ctx *c) { return c ? 9ll * c->bnd.foff[6] : 0; }
+int64_t stfem_stokes_n_face_points(const stfem_stokes_ctx *c)
+{
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_n_face_points")) return rq;
+  return c ? 9ll * c->bnd.foff[6] : 0;
+}
 
 int stfem_stokes_face_points(const stfem_stokes_ctx *c, double *out)
 {
   if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_face_points")) return rq;
   std::vector<double> xq, wq;
   stfem::gauss_rule(3, xq, wq);
   const long long nvx = c->nc[0] + 1, nvy = c->nc[1] + 1;
@@ -324,6 +330,7 @@ int stfem_stokes_face_points(const stfem_stokes_ctx *c, double *out)
 int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *c, const double *g_at_face_points, double *dst_u, double *dst_p, void *stream)
 {
   if (!c || !g_at_face_points || !dst_u || !dst_p) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_nitsche_rhs")) return rq;
   const size_t npts = size_t(stfem_stokes_n_face_points(c));
   if (npts == 0) return STFEM_OK; // no Dirichlet functions: vmult does nothing (operators.h:1836)
   STFEM_TRY(hipSetDevice(c->device));

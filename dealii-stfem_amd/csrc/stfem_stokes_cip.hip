@@ -426,6 +426,7 @@ int stfem_stokes_set_cip(stfem_stokes_ctx *c, double delta0, int weight)
 {
   if (!c || !std::isfinite(delta0) || weight < STFEM_CIP_WEIGHT_SOURCE || weight > STFEM_CIP_WEIGHT_LINEARISATION)
     return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_set_cip")) return rq;
   c->cip_delta0 = delta0;
   c->cip_weight = weight;
   return STFEM_OK;
@@ -435,6 +436,7 @@ int stfem_stokes_cip_add(stfem_stokes_ctx *c, double *dst_u, const double *src_u
 {
   if (!c || !dst_u || !src_u || !weight_u || !std::isfinite(delta0)) return STFEM_ERR_INVALID_ARGUMENT;
   if (dst_u == src_u || dst_u == weight_u) return STFEM_ERR_ALIAS;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_cip_add")) return rq;
   STFEM_TRY(hipSetDevice(c->device));
   const StokesParams prm = cip_single(c, dst_u, src_u);
   return cip_launch(c, prm, &weight_u, delta0, nullptr, nullptr, static_cast<hipStream_t>(stream)); // (the faces inside the slab alone)
@@ -444,6 +446,7 @@ int stfem_stokes_set_cip_neighbours(stfem_stokes_ctx *c, int neighbour_mask, con
 {
   if (!c) return STFEM_ERR_INVALID_ARGUMENT;
   if (neighbour_mask & ~48) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "neighbour_mask %d: only bits 4 and 5 name a z neighbour", neighbour_mask);
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_set_cip_neighbours")) return rq;
   const double *given[2] = {lower_vertices, upper_vertices};
   if (!c->base.cart)
     for (int side = 0; side < 2; ++side)
@@ -481,11 +484,16 @@ int stfem_stokes_set_cip_neighbours(stfem_stokes_ctx *c, int neighbour_mask, con
   return STFEM_OK;
 }
 
-int64_t stfem_stokes_cip_ghost_size(const stfem_stokes_ctx *c) { return c ? 6ll * c->ndu[0] * c->ndu[1] : 0; }
+int64_t stfem_stokes_cip_ghost_size(const stfem_stokes_ctx *c)
+{
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_cip_ghost_size")) return rq;
+  return c ? 6ll * c->ndu[0] * c->ndu[1] : 0;
+}
 
 int stfem_stokes_cip_ghost_create(stfem_stokes_ctx *c, double **device_out)
 {
   if (!c || !device_out) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_cip_ghost_create")) return rq;
   *device_out = nullptr;
   STFEM_TRY(hipSetDevice(c->device));
   const size_t bytes = size_t(stfem_stokes_cip_ghost_size(c)) * sizeof(double);
@@ -517,6 +525,7 @@ int stfem_stokes_cip_pack(stfem_stokes_ctx *c, const double *src_u, int side, do
 {
   if (!c || !src_u || !out || side < 0 || side > 1) return STFEM_ERR_INVALID_ARGUMENT;
   if (out == src_u) return STFEM_ERR_ALIAS;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_cip_pack")) return rq;
   STFEM_TRY(hipSetDevice(c->device));
   const long long n = 6ll * c->ndu[0] * c->ndu[1];
   const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 8ll * c->n_cu);
@@ -530,6 +539,7 @@ int stfem_stokes_cip_add_slab(stfem_stokes_ctx *c, double *dst_u, const double *
                               const double *lower_ghost, const double *upper_ghost, void *stream)
 {
   if (!c || !dst_u || !src_u || !weight_u || !std::isfinite(delta0)) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_cip_add_slab")) return rq;
   if (((c->cip_neighbours & 16) && !lower_ghost) || ((c->cip_neighbours & 32) && !upper_ghost))
     return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "CIP term on a slab: ghost planes missing for a side with a neighbour (mask %d)",
                            c->cip_neighbours);
@@ -543,6 +553,7 @@ int stfem_stokes_cip_bind_ghosts(stfem_stokes_ctx *c, const double *src_u, const
 {
   if (!c || !src_u) return STFEM_ERR_INVALID_ARGUMENT;
   if (src_u == lower_ghost || src_u == upper_ghost) return STFEM_ERR_ALIAS;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_cip_bind_ghosts")) return rq;
   auto &b = c->cip_bindings;
   b.erase(std::remove_if(b.begin(), b.end(), [&](const stfem_stokes_ctx::CipBinding &e) { return e.src == src_u; }), b.end());
   if (lower_ghost || upper_ghost) b.push_back({src_u, lower_ghost, upper_ghost});

@@ -42,6 +42,30 @@ struct StokesParams {
   double l1q[3];              // l at the three Gauss points
 };
 
+// The cell kernel of the degree-3 pair FE_Q(3)^3 x FE_Q(2) / FE_DGP(2), QGauss(4) (stfem_stokes_cell_q3.hip): a description of its
+// own, so that StokesParams stays what it is.  The sources, destinations, weights and store flags mean what they mean there and are
+// copied from the StokesParams of the same set.
+struct StokesQ3Params {
+  const double *vertices; // device, (nc+1)^3 * 3
+  int ncx, ncy, ncz;
+  int ndu[3], ndp[3];     // 3 nc + 1, 2 nc + 1
+  long long Nu, Np;
+  int dmask;
+  double nu;
+  int nsrc;
+  const double *us[MAXSRC], *ps[MAXSRC];
+  int nout;
+  double *out_u[MAXOUT], *out_p[MAXOUT];
+  double wKu[MAXSRC][MAXOUT], wKp[MAXSRC][MAXOUT], wM[MAXSRC][MAXOUT];
+  int store_u[MAXOUT], store_p[MAXOUT];
+  double Su[16], Du[16], Sp[12]; // [q*4+a], [q*4+a], [q*3+a]: FE_Q(3) and FE_Q(2) on Gauss-Lobatto nodes at the four Gauss points
+  double xq[4], wq[4];
+  int colour;
+  double hinv[3], detJ;
+  // FE_DGP(2): the two non-constant orthonormal Legendre functions sqrt 3 (2 x - 1), sqrt 5 (6 x^2 - 6 x + 1) at the Gauss points
+  double l1q[4], l2q[4];
+};
+
 // The coupling kernels of the Kronecker path (stfem_stokes_coupling.hip)
 struct CouplingParams {
   int ncx, ncy, ncz;
@@ -139,7 +163,13 @@ struct stfem_stokes_ctx {
   double *d_vertices = nullptr;
   int n_cu = 256;
   StokesParams base;
-  int pspace = 0; // 0 = FE_Q(1), 1 = FE_DGP(1)
+  int pspace = 0; // 0 = FE_Q(degree - 1), 1 = FE_DGP(degree - 1)
+  // velocity degree: 2, or 3 (stfem_stokes_create_space): the linear cell operator alone, through the kernel of
+  // stfem_stokes_cell_q3.hip described by q3 (geometry and tables; `base` then carries sizes and geometry, no tables)
+  int degree = 2;
+  StokesQ3Params q3;
+  bool q3_launched = false;
+  int q3_plan[2] = {0, 0}; // workgroups and longest run of cells per wave of the last colour launch (stfem_stokes_last_cell_plan)
   // axis-aligned uniform meshes: the scalar FE_Q(2) context whose pencil sweep applies nu K + wM M to the velocity components,
   // and the 1D tables of the coupling kernels
   stfem_ctx *scalar = nullptr;
@@ -252,6 +282,8 @@ __device__ __forceinline__ void cip_face_gradient(const double *tS, const double
 void stokes_cip_end_tables(double Eu[6], double EDu[6]);
 // The eight colour launches of the cell kernel (general meshes; stfem_stokes_cell.hip)
 int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st);
+// The same for a context of velocity degree 3, boxes included (stfem_stokes_cell_q3.hip)
+int stokes_cell_q3_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t st);
 // The coupling kernels (stfem_stokes_coupling.hip): out_u -= sum_s wKu B^T p_s; out_p (=, +=) sum_s wKp B u_s.  A failed launch is
 // left to the caller's stfem_launch_end (stokes_cart_launch).
 void stokes_grad_launch(const CouplingParams &k, hipStream_t st);

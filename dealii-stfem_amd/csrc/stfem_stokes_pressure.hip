@@ -105,6 +105,7 @@ extern "C" {
 int stfem_stokes_pressure_ctx(stfem_stokes_ctx *c, stfem_ctx **out)
 {
   if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_pressure_ctx")) return rq;
   *out = nullptr;
   if (!c->pressure_space) {
     stfem_mesh_desc md;
@@ -139,6 +140,7 @@ int stfem_stokes_pressure_ctx(stfem_stokes_ctx *c, stfem_ctx **out)
 int stfem_stokes_pressure_mean_vectors(stfem_stokes_ctx *c, double *ones, double *weights, double *volume)
 {
   if (!c || !ones || !weights || !volume) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_pressure_mean_vectors")) return rq;
   if (!c->base.cart) return STFEM_ERR_UNSUPPORTED;
   const double cell = c->base.detJ;
   const long long ncells = (long long)c->nc[0] * c->nc[1] * c->nc[2];
@@ -163,6 +165,7 @@ int stfem_stokes_pressure_mean_vectors(stfem_stokes_ctx *c, double *ones, double
 int stfem_stokes_pressure_quadrature_points(const stfem_stokes_ctx *c, int nq, double *out)
 {
   if (!c || !out || nq < 1 || nq > 8) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_pressure_quadrature_points")) return rq;
   if (!c->base.cart) return STFEM_ERR_UNSUPPORTED;
   std::vector<double> xq, wq;
   stfem::gauss_rule(nq, xq, wq);
@@ -187,6 +190,7 @@ int stfem_stokes_pressure_quadrature_points(const stfem_stokes_ctx *c, int nq, d
 int stfem_stokes_pressure_difference(stfem_stokes_ctx *c, int nq, const double *p, const double *exact_at_points, double out[2], void *stream)
 {
   if (!c || !p || !exact_at_points || !out || nq < 1 || nq > 8) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_pressure_difference")) return rq;
   if (!c->base.cart) return STFEM_ERR_UNSUPPORTED;
   STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -227,6 +231,8 @@ int stfem_stokes_pressure_difference(stfem_stokes_ctx *c, int nq, const double *
 int stfem_stokes_dgp_prolongate(stfem_stokes_ctx *fine, stfem_stokes_ctx *coarse, double *dst_fine, const double *src_coarse, int add, void *stream)
 {
   if (!fine || !coarse || !dst_fine || !src_coarse) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(fine, "stfem_stokes_dgp_prolongate")) return rq;
+  if (const int rq = stokes_require_q2(coarse, "stfem_stokes_dgp_prolongate")) return rq;
   if (!fine->pspace || !coarse->pspace) return STFEM_ERR_UNSUPPORTED;
   for (int d = 0; d < 3; ++d)
     if (fine->nc[d] != 2 * coarse->nc[d]) return STFEM_ERR_SHAPE_MISMATCH;
@@ -239,6 +245,8 @@ int stfem_stokes_dgp_prolongate(stfem_stokes_ctx *fine, stfem_stokes_ctx *coarse
 int stfem_stokes_dgp_restrict(stfem_stokes_ctx *fine, stfem_stokes_ctx *coarse, double *dst_coarse, const double *src_fine, int add, void *stream)
 {
   if (!fine || !coarse || !dst_coarse || !src_fine) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(fine, "stfem_stokes_dgp_restrict")) return rq;
+  if (const int rq = stokes_require_q2(coarse, "stfem_stokes_dgp_restrict")) return rq;
   if (!fine->pspace || !coarse->pspace) return STFEM_ERR_UNSUPPORTED;
   for (int d = 0; d < 3; ++d)
     if (fine->nc[d] != 2 * coarse->nc[d]) return STFEM_ERR_SHAPE_MISMATCH;

@@ -231,6 +231,7 @@ int64_t stfem_stokes_drag_lift_n_items(const stfem_stokes_ctx *c, int face_mask)
 {
   if (!c) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_drag_lift_n_items: null context");
   if (face_mask < 1 || face_mask > 63) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_drag_lift_n_items: face_mask %d outside 1..63", face_mask);
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_drag_lift_n_items")) return rq;
   int foff[7];
   return traction_offsets(c, face_mask, foff);
 }
@@ -243,6 +244,7 @@ int stfem_stokes_drag_lift(stfem_stokes_ctx *c, int face_mask, double scale, int
   if (n < 1) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_drag_lift: n = %d pairs", n);
   if (face_mask < 1 || face_mask > 63) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_drag_lift: face_mask %d outside 1..63", face_mask);
   if (!std::isfinite(scale)) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_drag_lift: scale is not finite");
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_drag_lift")) return rq;
   for (int i = 0; i < n; ++i)
     if (!u[i] || !p[i]) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_drag_lift: null %s[%d]", !u[i] ? "u" : "p", i);
   TractionParams k;

@@ -322,6 +322,7 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
                               stfem_stokes_vanka **out)
 {
   if (!ctx || !block_variable || !Alpha || !Beta || !out || n_blocks < 1) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(ctx, "stfem_stokes_vanka_create")) return rq;
   *out = nullptr;
   if (n_blocks > VK_MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
   stfem_stokes_desc d;
@@ -364,6 +365,8 @@ static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *b
   if (!ctx || !block_variable || !Alpha || !Beta || n_blocks < 1) return STFEM_ERR_INVALID_ARGUMENT;
   if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_blocks)) return STFEM_ERR_INVALID_ARGUMENT;
   if (n_blocks > VK_MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
+  // (the _cip and _partitioned entries have asked under their own names before they come here)
+  if (const int rq = stokes_require_q2(ctx, "stfem_stokes_vanka_create_linearised")) return rq;
   stfem_stokes_desc d;
   int rc = stfem_stokes_internal_desc(ctx, &d);
   if (rc != STFEM_OK) return rc;
@@ -412,6 +415,7 @@ int stfem_stokes_vanka_create_linearised_cip(stfem_stokes_ctx *ctx, int n_blocks
                                              const double *Beta, int mode, const double *const *lin_blocks, double delta0, stfem_stokes_vanka **out)
 {
   if (!out) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_vanka_create_linearised_cip: out is null");
+  if (const int rq = stokes_require_q2(ctx, "stfem_stokes_vanka_create_linearised_cip")) return rq;
   *out = nullptr;
   if (!std::isfinite(delta0)) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_vanka_create_linearised_cip: delta0 is not finite");
   if (delta0 == 0.0) return stfem_stokes_vanka_create_linearised(ctx, n_blocks, block_variable, Alpha, Beta, mode, lin_blocks, out);
@@ -437,6 +441,8 @@ int stfem_stokes_vanka_create_linearised_partitioned(stfem_stokes_ctx *slab, stf
   if (neighbour_mask & ~48) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: neighbour_mask %d, only bits 4 and 5 name a z neighbour", me, neighbour_mask);
   if (beyond_mask & ~neighbour_mask)
     return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: beyond_mask %d names a side without a neighbour (neighbour_mask %d)", me, beyond_mask, neighbour_mask);
+  if (const int rq = stokes_require_q2(slab, me)) return rq;
+  if (const int rq = stokes_require_q2(extended, me)) return rq;
   stfem_stokes_desc ds, de;
   int rc = stfem_stokes_internal_desc(slab, &ds);
   if (rc == STFEM_OK) rc = stfem_stokes_internal_desc(extended, &de);

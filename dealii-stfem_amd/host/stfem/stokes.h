@@ -158,13 +158,23 @@ public:
     if (!std::isfinite(delta0)) throw Error(STFEM_ERR_INVALID_ARGUMENT, "StokesMatrixFreeOperator: delta0 is not finite");
     if (nonlinear && outflow_penalty != 0.0)
       throw Error(STFEM_ERR_UNSUPPORTED, "StokesMatrixFreeOperator: outflow_penalty != 0 with a nonlinear treatment is not built");
+    // velocity degree 3 (FE_Q(3)^3 x FE_Q(2) / FE_DGP(2), QGauss(4)) has the linear cell operator alone: weak / outflow ids and
+    // delta0 != 0 are refused by the C-ABI below, a nonlinear treatment here (its launches would only be refused at the first vmult)
+    if (velocity_degree != 2 && nonlinear)
+      throw Error(STFEM_ERR_UNSUPPORTED, "StokesMatrixFreeOperator: a nonlinear treatment is built for velocity degree 2 only");
     create(mesh, velocity_degree, viscosity, dg_pressure);
-    int weak = 0, outflow = 0;
-    for (boundary_id f : weak_boundary_ids) weak |= 1 << f;
-    for (boundary_id f : outflow_boundary_ids) outflow |= 1 << f;
-    if (weak || outflow) check(stfem_stokes_set_weak_boundaries(h_, weak, outflow, penalty1, penalty2), "stfem_stokes_set_weak_boundaries");
-    delta0_ = delta0;
-    if (delta0 != 0.0) check(stfem_stokes_set_cip(h_, delta0, STFEM_CIP_WEIGHT_SOURCE), "stfem_stokes_set_cip");
+    try {
+      int weak = 0, outflow = 0;
+      for (boundary_id f : weak_boundary_ids) weak |= 1 << f;
+      for (boundary_id f : outflow_boundary_ids) outflow |= 1 << f;
+      if (weak || outflow) check(stfem_stokes_set_weak_boundaries(h_, weak, outflow, penalty1, penalty2), "stfem_stokes_set_weak_boundaries");
+      delta0_ = delta0;
+      if (delta0 != 0.0) check(stfem_stokes_set_cip(h_, delta0, STFEM_CIP_WEIGHT_SOURCE), "stfem_stokes_set_cip");
+    } catch (...) { // (no destructor runs for a constructor that throws)
+      stfem_stokes_destroy(h_);
+      h_ = nullptr;
+      throw;
+    }
   }
   // Whose velocity weighs the CIP term: STFEM_CIP_WEIGHT_SOURCE (the reference: the source of the vmult, cubic in it) or
   // STFEM_CIP_WEIGHT_LINEARISATION (with a nonlinear treatment the linearisation velocity of set_data: linear in the source, what a
@@ -175,6 +185,7 @@ public:
     cip_weight_ = weight;
   }
   Number delta0() const { return delta0_; }
+  unsigned velocity_degree() const { return velocity_degree_; }
   int cip_weight() const { return cip_weight_; }
   // The CIP term on a z-slab (stfem_stokes_set_cip_neighbours and its companions): neighbour_mask bit 4 / 5 a slab below / above,
   // the vertex plane one cell layer beyond each interface on a general mesh; the ghost planes of a velocity source are what the
@@ -210,7 +221,12 @@ private:
     md.vertices = mesh.vertices.empty() ? nullptr : mesh.vertices.data();
     md.dirichlet_mask = mesh.dirichlet_mask;
     md.device = mesh.device;
-    check(stfem_stokes_create_ex(&md, int(velocity_degree), dg_pressure ? 1 : 0, viscosity, &h_), "stfem_stokes_create");
+    stfem_stokes_space_desc sd{};
+    sd.velocity_degree = int32_t(velocity_degree);
+    sd.pressure_space = dg_pressure ? 1 : 0;
+    sd.viscosity = viscosity;
+    check(stfem_stokes_create_space(&md, &sd, &h_), "stfem_stokes_create_space");
+    velocity_degree_ = velocity_degree;
     n_cells_ = size_t(mesh.ncell[0]) * size_t(mesh.ncell[1]) * size_t(mesh.ncell[2]);
   }
 
@@ -326,6 +342,7 @@ private:
   bool nonlinear;
   mutable const double *lin_ = nullptr; // data_lin[0]
   Number delta0_ = 0.0;
+  unsigned velocity_degree_ = 2;
   mutable int cip_weight_ = STFEM_CIP_WEIGHT_SOURCE;
   size_t n_cells_ = 0;
   mutable StokesVector cells_; // device cell values of compute_divergence, made on demand

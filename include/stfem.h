@@ -402,12 +402,14 @@ int stfem_coefficient_per_cell(const int32_t ncell[3], const double *vertices, d
  * (compute_divergence) through stfem_stokes_divergence, the boundary force (compute_drag_lift) through stfem_stokes_drag_lift; the CIP interior-face term (delta0 != 0, 1603-1638) after
  * stfem_stokes_set_cip.  Not built: the outflow penalty (beta, 1705-1709).  Velocity FE_Q(2)^3, pressure FE_Q(1) (stfem_stokes_create)
  * or FE_DGP(1) (stfem_stokes_create_ex), QGauss(3), MappingQ1 on the mesh of `mesh`; mesh->dirichlet_mask constrains the velocity
- * (homogeneous), the pressure is unconstrained.  fp64.
+ * (homogeneous), the pressure is unconstrained.  fp64.  Velocity degree 3 - FE_Q(3)^3 with FE_Q(2) or FE_DGP(2), QGauss(4) - through
+ * stfem_stokes_create_space: the linear cell operator and nothing else, see there.
  * Layout: a velocity vector is 3 * n_velocity_dofs doubles, component-major, every component in
  * the scalar FE_Q(2) numbering of this header; a pressure vector is n_pressure_dofs doubles in
  * the scalar FE_Q(1) numbering.  All vector arguments are DEVICE pointers. */
 typedef struct stfem_stokes_ctx stfem_stokes_ctx; /* replaces MatrixFree + StokesMatrixFreeOperator state */
-/* StokesMatrixFreeOperator ctor (operators.h:1200-1251); only velocity_degree == 2 is built */
+/* StokesMatrixFreeOperator ctor (operators.h:1200-1251).  This constructor and stfem_stokes_create_ex build velocity_degree == 2
+ * only and refuse every other degree with STFEM_ERR_UNSUPPORTED; degree 3 is reached through stfem_stokes_create_space below. */
 int stfem_stokes_create(const stfem_mesh_desc *mesh, int velocity_degree, double viscosity,
                         stfem_stokes_ctx **out);
 /* the same with the pressure space chosen as tests/tp_03stokes.cc:83-86 does with dGPressure: 0 = FE_Q(degree - 1) (continuous,
@@ -415,6 +417,9 @@ int stfem_stokes_create(const stfem_mesh_desc *mesh, int velocity_degree, double
  * of orthonormal Legendre polynomials on the reference cell (degree 1: 1, l(xi), l(eta), l(zeta), l(x) = sqrt 3 (2 x - 1)), four
  * DoFs per cell numbered cell by cell (p[4 cell + j], cells lexicographic) */
 int stfem_stokes_create_ex(const stfem_mesh_desc *mesh, int velocity_degree, int pressure_space, double viscosity, stfem_stokes_ctx **out);
+/* The constructor by descriptor, stfem_stokes_create_space (velocity degree 2 or 3), its descriptor and the diagnostic of the
+ * degree-3 cell kernel: the companion header, part of this boundary and included here so that a caller of stfem.h has them. */
+#include "stfem_stokes_space.h"
 void stfem_stokes_destroy(stfem_stokes_ctx *ctx);
 int64_t stfem_stokes_n_velocity_dofs(const stfem_stokes_ctx *ctx); /* per component */
 int64_t stfem_stokes_n_pressure_dofs(const stfem_stokes_ctx *ctx);
@@ -603,6 +608,7 @@ int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *ctx, const double *g_at_face_poin
 /* diagnostics: {tiles, workgroups} as stfem_last_sweep_plan of the last velocity sweep (pencil sweep of the scalar FE_Q(2) context:
  * box meshes), and whether that sweep of the last vmult added the pressure gradient itself (1) or the gradient kernel ran (0) */
 int stfem_stokes_last_sweep_plan(const stfem_stokes_ctx *ctx, int32_t out[3]);
+/* (the diagnostic of the degree-3 cell kernel, stfem_stokes_last_cell_plan: stfem_stokes_space.h) */
 
 /* The pressure space by itself - what the solver around the operator needs of it (tests/tp_03stokes.cc:404-425, 1047-1062;
  * include/exact_solution.h:503-649; the pressure transfer of the Stokes multigrid levels, include/stmg.h:557-600).

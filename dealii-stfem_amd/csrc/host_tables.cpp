@@ -299,7 +299,7 @@ void small_gen_eig(int m, Mat K, Mat M, std::vector<double> &lam, Mat &V)
   }
 }
 
-// fills t.fd_W / t.fd_lam (see host_tables.h)
+// fills t.fd_W / t.fd_lam and t.fd_M1 / t.fd_K1 (see host_tables.h)
 void make_fast_diagonalisation(ShapeTables &t)
 {
   const int n = t.n, h = n / 2, ne = n - h;
@@ -312,6 +312,19 @@ void make_fast_diagonalisation(ShapeTables &t)
       }
   std::fill(t.fd_W, t.fd_W + EO_MAX, 0.0);
   std::fill(t.fd_lam, t.fd_lam + 8, 0.0);
+  // M1, K1 in parity form (upper triangles of the even and the odd block, host_tables.h)
+  std::fill(t.fd_M1, t.fd_M1 + EO_MAX, 0.0);
+  std::fill(t.fd_K1, t.fd_K1 + EO_MAX, 0.0);
+  auto pack_parity = [&](const Mat &X, double *out) {
+    const int odd0 = fd_sym_index(ne, ne, ne);
+    for (int i = 0; i < ne; ++i)
+      for (int j = i; j < ne; ++j)
+        out[fd_sym_index(ne, i, j)] = j < h ? 0.5 * (X[i * n + j] + X[i * n + (n - 1 - j)]) : X[i * n + j];
+    for (int i = 0; i < h; ++i)
+      for (int j = i; j < h; ++j) out[odd0 + fd_sym_index(h, i, j)] = 0.5 * (X[i * n + j] - X[i * n + (n - 1 - j)]);
+  };
+  pack_parity(M1, t.fd_M1);
+  pack_parity(K1, t.fd_K1);
   // parity bases: even e_i = (d_i + d_{n-1-i})/sqrt2 (i < h), middle d_h; odd o_i = (d_i - d_{n-1-i})/sqrt2
   const double r2 = std::sqrt(0.5);
   for (int parity = 0; parity < 2; ++parity) {

@@ -43,7 +43,17 @@ struct ShapeTables {
   //   We[m*ne + i], i < ne   (coefficient of u_i + u_{n-1-i}, and of u_{n/2} for the middle)
   //   Wo[m*h + i],  i < h    (coefficient of u_i - u_{n-1-i}),   h = n/2, stored after We
   double fd_W[EO_MAX], fd_lam[8];
+  // M1 and K1 themselves in parity form, for applying them to a line directly (W^T W = M1 and W^T diag(lam) W = K1, but
+  // the tables are packed from the assembled matrices, not from products of the rounded W).  For X = M1 or K1, with
+  //   ae_i = u_i + u_{n-1-i},  ao_i = u_i - u_{n-1-i}  (i < h),  ae_h = u_h for odd n,
+  //   e = Xe ae,  o = Xo ao,   (X u)_i = e_i + o_i,  (X u)_{n-1-i} = e_i - o_i,  (X u)_h = e_h:
+  //   Xe[i][j] = (X[i][j] + X[i][n-1-j]) / 2,  Xo[i][j] = (X[i][j] - X[i][n-1-j]) / 2   (i, j < h; the halves folded in),
+  //   Xe[i][h] = Xe[h][i] = X[i][h],  Xe[h][h] = X[h][h].
+  // Xe (ne x ne) and Xo (h x h) are symmetric; only their upper triangles are stored, row by row, Xe first:
+  // entry (i, j), i <= j, of an m x m block at fd_sym_index(m, i, j); Xo starts at fd_sym_index(ne, ne, ne) = ne (ne + 1) / 2.
+  double fd_M1[EO_MAX], fd_K1[EO_MAX];
 };
+constexpr int fd_sym_index(int m, int i, int j) { return i <= j ? i * m - i * (i - 1) / 2 + (j - i) : fd_sym_index(m, j, i); }
 ShapeTables make_shape_tables(int p);
 
 // ---- temporal matrices ----

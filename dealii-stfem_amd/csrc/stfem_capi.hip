@@ -254,7 +254,11 @@ template <class PR> static void fill_common(const stfem_ctx *c, typename PR::Swe
     prm.eo_Dq[i] = real(c->tab.eo_Dq[i]);
     prm.eo_DqT[i] = real(c->tab.eo_DqT[i]);
   }
-  for (int i = 0; i < EO_N; ++i) prm.fd_W[i] = real(c->tab.fd_W[i]);
+  for (int i = 0; i < EO_N; ++i) {
+    prm.fd_W[i] = real(c->tab.fd_W[i]);
+    prm.fd_Mx[i] = real(c->tab.fd_M1[i]);
+    prm.fd_Kx[i] = real(c->tab.fd_K1[i] / (c->h[0] * c->h[0]));
+  }
   for (int i = 0; i < 8; ++i) {
     prm.fd_lx[i] = real(c->tab.fd_lam[i] / (c->h[0] * c->h[0]));
     prm.fd_ly[i] = real(c->tab.fd_lam[i] / (c->h[1] * c->h[1]));

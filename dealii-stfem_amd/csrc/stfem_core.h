@@ -365,8 +365,11 @@ cell_core_general(const SweepParams &prm, real_t *__restrict__ lds, int cell_in_
 // exchanged; the three phases are separate functions so that the caller can issue the next
 // cell group's src loads between them.
 //   forward : nodal [y][z] -> modal in z, y -> LDS (plane of lane i)
-//   middle  : lane k = z-mode; per y-mode row: read the x-lines of all input blocks, to modal
-//             space in x, diagonal scaling + temporal combination, back to nodal values in x,
+//   middle  : lane k = z-mode; per y-mode row: read the x-lines of all input blocks, combine them
+//             with the temporal weights and apply the x operator itself to the two sums (x is NOT
+//             diagonalised: with F / B the transforms, B F = M1 and B diag(lam) F = K1 exactly, so
+//             B diag(aK (s + lam_x) + aM) F u = Kx (aK u) + Mx ((aK s + aM) u), one product of
+//             transform cost instead of a transform per input block and one back: fd_apply_pair),
 //             written straight back to the slab.  The x = P node of a cell IS the x = 0 node of
 //             the next cell of the wave: its partial sum is added into the neighbour's slot
 //             (ds_add_f64 after the neighbour's own write; LDS operations of one wave execute in
@@ -416,7 +419,7 @@ template <int P, int NBM> struct PencilCore {
   {
     real_t *cb_lds = lds + cb_offset(cell_in_wave, blk);
     const int oz = opaque_zero();
-    const real_t *W = prm.fd_W + oz, *lx = prm.fd_lx + oz, *ly = prm.fd_ly + oz;
+    const real_t *Kx = prm.fd_Kx + oz, *Mx = prm.fd_Mx + oz, *ly = prm.fd_ly + oz;
     // opaque copies: see cell_core
     real_t wK[NBM], wM[NBM];
     STFEM_UNROLL
@@ -442,43 +445,21 @@ template <int P, int NBM> struct PencilCore {
     for (int y = 0; y < N; ++y) {
       row_hook(y);
       if (y + 1 < N) load_row(y + 1, vbuf[(y + 1) & 1]);
+      // out_j = Kx (sum_i aK_ji u_i) + Mx (sum_i (aK_ji s + aM_ji) u_i),  s = lam_z(k) + lam_y(y)
       const real_t sy = lzk + ly[y];
-      real_t acc[N];
-      if (NBM <= 2) {
-        STFEM_UNROLL
-        for (int i = 0; i < NBM; ++i) {
-          if (i == 0 || i < prm.nbi) {
-            real_t t[N];
-            fd_forward<N>(W, vbuf[y & 1][i], t);
-            STFEM_UNROLL
-            for (int x = 0; x < N; ++x) {
-              const real_t d = fma(wK[i], sy + lx[x], wM[i]);
-              acc[x] = i == 0 ? d * t[x] : fma(d, t[x], acc[x]);
-            }
+      real_t ua[N], ub[N], r[N];
+      STFEM_UNROLL
+      for (int i = 0; i < NBM; ++i) {
+        if (i == 0 || i < prm.nbi) {
+          const real_t wB = fma(wK[i], sy, wM[i]);
+          STFEM_UNROLL
+          for (int x = 0; x < N; ++x) {
+            ua[x] = i == 0 ? wK[i] * vbuf[y & 1][i][x] : fma(wK[i], vbuf[y & 1][i][x], ua[x]);
+            ub[x] = i == 0 ? wB * vbuf[y & 1][i][x] : fma(wB, vbuf[y & 1][i][x], ub[x]);
           }
         }
-      } else {
-        real_t ua[N], ub[N];
-        STFEM_UNROLL
-        for (int x = 0; x < N; ++x) ua[x] = ub[x] = real_t(0);
-        STFEM_UNROLL
-        for (int i = 0; i < NBM; ++i) {
-          if (i < prm.nbi) {
-            STFEM_UNROLL
-            for (int x = 0; x < N; ++x) {
-              ua[x] = fma(wK[i], vbuf[y & 1][i][x], ua[x]);
-              ub[x] = fma(wM[i], vbuf[y & 1][i][x], ub[x]);
-            }
-          }
-        }
-        real_t ta[N], tb[N];
-        fd_forward<N>(W, ua, ta);
-        fd_forward<N>(W, ub, tb);
-        STFEM_UNROLL
-        for (int x = 0; x < N; ++x) acc[x] = fma(sy + lx[x], ta[x], tb[x]);
       }
-      real_t r[N];
-      fd_backward<N>(W, acc, r);
+      fd_apply_pair<N>(Kx, Mx, ua, ub, r);
       pin(r);
       if (out_active) {
         STFEM_UNROLL
@@ -496,7 +477,7 @@ template <int P, int NBM> struct PencilCore {
   // ahead) into the two weighted sums ua = sum_i aK(j,i) u_i, ub = sum_i aM(j,i) u_i instead of being held all at once
   // (2 x NBM x N registers), and the weights of this lane's output block come from a small LDS table, wrow[2 i] =
   // aK(j,i) vol, wrow[2 i + 1] = aM(j,i) vol (2 x NBM registers per lane otherwise, for the whole kernel).  The
-  // cell-wise coefficients fK, fM (operators.h:1060-1087) multiply the two sums after the transform.
+  // cell-wise coefficients fK, fM (operators.h:1060-1087) multiply the two sums before the x operator is applied.
   template <class Hook>
   static __device__ __forceinline__ void middle_stream(const SweepParams &prm, real_t *__restrict__ lds, int cell_in_wave,
                                                        int blk, int k, bool out_active, bool is_last, real_t lzk,
@@ -504,7 +485,7 @@ template <int P, int NBM> struct PencilCore {
   {
     real_t *cb_lds = lds + cb_offset(cell_in_wave, blk);
     const int oz = opaque_zero();
-    const real_t *W = prm.fd_W + oz, *lx = prm.fd_lx + oz, *ly = prm.fd_ly + oz;
+    const real_t *Kx = prm.fd_Kx + oz, *Mx = prm.fd_Mx + oz, *ly = prm.fd_ly + oz;
     const int nbi = prm.nbi;
     asm volatile("" : "+v"(lzk), "+v"(fK), "+v"(fM));
     STFEM_UNROLL
@@ -536,13 +517,15 @@ template <int P, int NBM> struct PencilCore {
           }
         }
       }
-      const real_t sy = lzk + ly[y];
-      real_t ta[N], tb[N], acc[N], r[N];
-      fd_forward<N>(W, ua, ta);
-      fd_forward<N>(W, ub, tb);
+      // out = Kx (fK ua) + Mx (fK s ua + fM ub)
+      const real_t fKs = fK * (lzk + ly[y]);
+      real_t r[N];
       STFEM_UNROLL
-      for (int x = 0; x < N; ++x) acc[x] = fma(fK * (sy + lx[x]), ta[x], fM * tb[x]);
-      fd_backward<N>(W, acc, r);
+      for (int x = 0; x < N; ++x) {
+        ub[x] = fma(fKs, ua[x], fM * ub[x]);
+        ua[x] *= fK;
+      }
+      fd_apply_pair<N>(Kx, Mx, ua, ub, r);
       pin(r);
       if (out_active) {
         STFEM_UNROLL

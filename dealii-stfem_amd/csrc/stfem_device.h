@@ -268,6 +268,54 @@ __device__ __forceinline__ void fd_backward(const real_t *__restrict__ c, const 
   }
 }
 
+// r = Kx a + Mx b for the 1D pair itself in parity form (host_tables.h: fd_M1, fd_K1; fd_sym_index there): both products
+// share the parity split of their inputs, one accumulator per output and the recombination.  N = 5: 8 adds, 26
+// multiply-adds, 4 adds - a forward and a backward transform are 17 each.
+template <int N>
+__device__ __forceinline__ void fd_apply_pair(const real_t *__restrict__ kx, const real_t *__restrict__ mx,
+                                              const real_t (&a)[N], const real_t (&b)[N], real_t (&r)[N])
+{
+  constexpr int H = N / 2, NE = N - H, ODD0 = NE * (NE + 1) / 2;
+  auto sym = [](int m, int i, int j) { return i <= j ? i * m - i * (i - 1) / 2 + (j - i) : j * m - j * (j - 1) / 2 + (i - j); };
+  real_t ae[NE], be[NE], ao[H > 0 ? H : 1], bo[H > 0 ? H : 1];
+  STFEM_UNROLL
+  for (int i = 0; i < H; ++i) {
+    ae[i] = a[i] + a[N - 1 - i];
+    ao[i] = a[i] - a[N - 1 - i];
+    be[i] = b[i] + b[N - 1 - i];
+    bo[i] = b[i] - b[N - 1 - i];
+  }
+  if (N & 1) {
+    ae[H] = a[H];
+    be[H] = b[H];
+  }
+  real_t e[NE], o[H > 0 ? H : 1];
+  STFEM_UNROLL
+  for (int i = 0; i < NE; ++i) {
+    real_t s = kx[sym(NE, i, 0)] * ae[0];
+    STFEM_UNROLL
+    for (int j = 1; j < NE; ++j) s = fma(kx[sym(NE, i, j)], ae[j], s);
+    STFEM_UNROLL
+    for (int j = 0; j < NE; ++j) s = fma(mx[sym(NE, i, j)], be[j], s);
+    e[i] = s;
+  }
+  STFEM_UNROLL
+  for (int i = 0; i < H; ++i) {
+    real_t s = kx[ODD0 + sym(H, i, 0)] * ao[0];
+    STFEM_UNROLL
+    for (int j = 1; j < H; ++j) s = fma(kx[ODD0 + sym(H, i, j)], ao[j], s);
+    STFEM_UNROLL
+    for (int j = 0; j < H; ++j) s = fma(mx[ODD0 + sym(H, i, j)], bo[j], s);
+    o[i] = s;
+  }
+  STFEM_UNROLL
+  for (int i = 0; i < H; ++i) {
+    r[i] = e[i] + o[i];
+    r[N - 1 - i] = e[i] - o[i];
+  }
+  if (N & 1) r[H] = e[H];
+}
+
 template <int N, bool FORWARD, bool ALONG_FAST>
 __device__ __forceinline__ void fd_plane(const real_t *__restrict__ c, real_t (&P)[N * N])
 {

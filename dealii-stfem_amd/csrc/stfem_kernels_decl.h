@@ -24,6 +24,9 @@ struct SweepParams {
   // Cartesian fast path: simultaneous diagonalisation of the 1D nodal mass / stiffness pair
   // (host_tables.h: fd_W, fd_lam), eigenvalues pre-scaled by 1/h_d^2 per direction
   real_t fd_W[EO_N], fd_lx[8], fd_ly[8], fd_lz[8];
+  // the x direction of the pencil core applies the 1D pair itself (host_tables.h: fd_M1, fd_K1, parity-packed):
+  // Mx = M1, Kx = K1 / hx^2
+  real_t fd_Mx[EO_N], fd_Kx[EO_N];
   // general-geometry path: plain interpolation S, collocation derivative D and D^T, and the
   // per-quadrature-point metric records [cell][qz][qy][qx][8] = (Gxx,Gxy,Gxz,Gyy,Gyz,Gzz,Mq,pad)
   real_t eo_S[EO_N], eo_Dq[EO_N], eo_DqT[EO_N];

@@ -131,6 +131,9 @@ template <int P, int NBM, int TY> struct PencilGeom {
 
 
 
+// both structures travel by value in the kernel-argument segment
+static_assert(sizeof(SweepParams) + sizeof(PencilPlan) <= 4096, "kernel arguments of st_sweep_pencil exceed 4 KB");
+
 // per-lane roles, kept in ONE register (a bool per role would pin two SGPRs each)
 enum : unsigned {
   LF_IN = 1,    // feeds an input block

@@ -4,7 +4,12 @@
 //                                       header line, then Alpha, Beta, Gamma, Zeta with 17 digits
 //   print_tables blockslice             BlockSlice index / decompose / get_variable tables, one line per
 //                                       entry in the wording of the golden
+//   print_tables fd                     the library's 1D tables of the fast diagonalisation for FE_Q(1) .. FE_Q(5)
+//                                       (csrc/host_tables.h, tests/test_fd_x_operator_cpu.py): a line "p <p> n <n>", then
+//                                       one named line each: nodes, xq, wq, fd_W, fd_lam, fd_M1, fd_K1, 17 digits
 #include "stfem/stokes.h"
+
+#include "../csrc/host_tables.h"
 
 #include <cstdio>
 #include <cstring>
@@ -49,6 +54,27 @@ static void blockslice_table(bool variable_major, unsigned nts, unsigned nv, uns
     }
 }
 
+static void line(const char *name, const double *v, int n)
+{
+  std::printf("%s", name);
+  for (int i = 0; i < n; ++i) std::printf(" %.17g", v[i]);
+  std::printf("\n");
+}
+
+static void fd_section(int p)
+{
+  const ShapeTables t = make_shape_tables(p);
+  const int n = t.n, h = n / 2, ne = n - h;
+  std::printf("p %d n %d\n", p, n);
+  line("nodes", t.nodes.data(), n);
+  line("xq", t.xq.data(), n);
+  line("wq", t.wq.data(), n);
+  line("fd_W", t.fd_W, ne * ne + h * h);
+  line("fd_lam", t.fd_lam, n);
+  line("fd_M1", t.fd_M1, fd_sym_index(ne, ne, ne) + fd_sym_index(h, h, h));
+  line("fd_K1", t.fd_K1, fd_sym_index(ne, ne, ne) + fd_sym_index(h, h, h));
+}
+
 int main(int argc, char **argv)
 {
   if (argc != 2) return 2;
@@ -63,6 +89,10 @@ int main(int argc, char **argv)
       stokes_section(TimeStepType::DG, 1, ns);
       stokes_section(TimeStepType::DG, 2, ns);
     }
+    return 0;
+  }
+  if (!std::strcmp(argv[1], "fd")) {
+    for (int p = 1; p <= 5; ++p) fd_section(p);
     return 0;
   }
   if (!std::strcmp(argv[1], "blockslice")) {

@@ -55,6 +55,11 @@ class _StokesSpaceDesc(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class _StokesVankaSpaceDesc(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("block_variable", C.POINTER(C.c_int32)), ("Alpha", C.POINTER(C.c_double)),
+                ("Beta", C.POINTER(C.c_double)), ("reserved", C.c_int32 * 4)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _lib = None
@@ -232,6 +237,12 @@ SPACE_SIGNATURES = {
     "stfem_stokes_last_cell_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
 }
 
+# every symbol the companion header include/stfem_stokes_vanka_space.h declares (tests/test_stokes_vanka_space_header_cpu.py)
+VANKA_SPACE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "stfem_stokes_vanka_space.h")
+VANKA_SPACE_SIGNATURES = {
+    "stfem_stokes_vanka_create_space": (C.c_int, [_vp, C.POINTER(_StokesVankaSpaceDesc), C.POINTER(_vp)]),
+}
+
 
 def lib():
     """Loads the HIP library; raises (never falls back) if it has not been built."""
@@ -241,7 +252,7 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: run `make -C dealii-stfem_amd/csrc` "
                               "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(os.environ.get("STFEM_LIB", LIB_PATH))  # STFEM_LIB: experiment builds only
-        for name, (res, args) in list(SIGNATURES.items()) + list(SPACE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SPACE_SIGNATURES.items()) + list(VANKA_SPACE_SIGNATURES.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -846,7 +857,7 @@ class StokesMatrixFreeOperator:
     vmult / st_vmult / st_vmult_slice_add take the convection mode (CONVECTION_FORM / CONVECTION_JACOBIAN) and the linearisation
     velocity `lin` that the reference's set_data hands in; with the defaults they are the linear operator.  delta0 != 0 adds the
     CIP interior-face stabilisation (operators.h:1605-1633) to all of them, see set_cip.  with_degree(3, ...): FE_Q(3)^3 x FE_Q(2) /
-    FE_DGP(2), the linear cell operator alone."""
+    FE_DGP(2), the linear cell operator, and StokesPreconditionVanka.for_space over it."""
 
     def __init__(self, ncell, vertices=None, lower=(0, 0, 0), upper=(1, 1, 1), dirichlet_mask=63,
                  viscosity=1.0, velocity_degree=2, device=0, weak_boundary_ids=(), outflow_boundary_ids=(),
@@ -893,8 +904,8 @@ class StokesMatrixFreeOperator:
         """The operator through stfem_stokes_create_space; the keywords of the constructor except velocity_degree.  Degree 2: the
         operator of the constructor, bit for bit.  Degree 3: FE_Q(3)^3 x FE_Q(2), or FE_DGP(2) with dg_pressure (ten DoFs per cell),
         QGauss(4) - the pair of the reference's time degree 2 - with the linear cell operator alone: vmult, mass_vmult, st_vmult,
-        st_Tvmult, st_vmult_slice_add.  Weak / outflow ids, delta0 != 0, a convection mode and everything else raise StfemError
-        with status -2 and the reason."""
+        st_Tvmult, st_vmult_slice_add; its smoother is StokesPreconditionVanka.for_space.  Weak / outflow ids, delta0 != 0, a convection
+        mode and everything else raise StfemError with status -2 and the reason."""
         assert "velocity_degree" not in keywords and "_space" not in keywords
         return cls(ncell, _space=(velocity_degree, tuple(int(v) for v in reserved)), **keywords)
 
@@ -1165,19 +1176,14 @@ class StokesPreconditionVanka:
     (pressure entries may be None); update(lin) rebuilds the blocks for new states.  delta0 != 0 (implies one block per cell): the
     blocks hold the CIP term C(lin_j; .) too, weighted by the linearisation state of the column block in every mode
     (stfem_stokes_vanka_create_linearised_cip); update keeps that delta0.  The defaults are the class blocks of a box (one block per
-    cell on a general mesh)."""
+    cell on a general mesh).  for_space(...): the constructor by descriptor, which also serves an operator of velocity degree 3."""
 
     def __init__(self, op, block_variable, Alpha, Beta, lin=None, mode=0, per_cell=False, delta0=0.0, partition=None):
         """partition=(extended_op, neighbour_mask, beyond_mask): `op` is a z-slab; the per-cell blocks are set up on extended_op (the
         slab plus one ghost cell layer per z neighbour of neighbour_mask, bit 4 below / 5 above; `lin`, also of update, lives there),
         built for the slab's own cells and applied on `op`, partial sums in the interface planes.  beyond_mask: cells beyond a ghost
         layer (read with delta0 != 0).  stfem_stokes_vanka_create_linearised_partitioned."""
-        self.op = op
-        self.partition = partition
-        self.nb = len(block_variable)
-        bv = (C.c_int32 * self.nb)(*[int(v) for v in block_variable])
-        A = np.ascontiguousarray(Alpha, dtype=np.float64); B = np.ascontiguousarray(Beta, dtype=np.float64)
-        assert A.shape == (self.nb, self.nb) and B.shape == (self.nb, self.nb)
+        bv, A, B = self._blocks(op, block_variable, Alpha, Beta, partition)
         h = _vp()
         if partition is not None:
             ext, nmask, bmask = partition
@@ -1198,6 +1204,33 @@ class StokesPreconditionVanka:
         assert rc == 0 or not h.value
         _check(rc, what)
         self._h = h
+
+    @classmethod
+    def for_space(cls, op, block_variable, Alpha, Beta, reserved=(0, 0, 0, 0)):
+        """The smoother through stfem_stokes_vanka_create_space: one block per cell of the linear operator `op`, whatever its
+        velocity degree.  Degree 2: the blocks of per_cell=True with mode 0, bit for bit.  Degree 3 (StokesMatrixFreeOperator.
+        with_degree(3, ...)): 192 velocity and 27 / 10 pressure rows per time dof, at most 512 rows (two time dofs); this is the one
+        constructor that serves it - the plain one raises StfemError with status -2.  vmult / step / update(None) as usual."""
+        self = cls.__new__(cls)
+        bv, A, B = self._blocks(op, block_variable, Alpha, Beta, None)
+        d = _StokesVankaSpaceDesc()
+        d.n_blocks, d.block_variable, d.Alpha, d.Beta = self.nb, bv, _p(A), _p(B)
+        d.reserved[:] = [int(v) for v in reserved]
+        h = _vp()
+        rc = lib().stfem_stokes_vanka_create_space(op._h, C.byref(d), C.byref(h))
+        assert rc == 0 or not h.value
+        _check(rc, "stfem_stokes_vanka_create_space")
+        self._h = h
+        return self
+
+    def _blocks(self, op, block_variable, Alpha, Beta, partition):
+        """what every constructor starts with: the operator, the block count, and the block layout and weights as the C ABI takes them"""
+        self.op, self.partition = op, partition
+        self.nb = len(block_variable)
+        bv = (C.c_int32 * self.nb)(*[int(v) for v in block_variable])
+        A = np.ascontiguousarray(Alpha, dtype=np.float64); B = np.ascontiguousarray(Beta, dtype=np.float64)
+        assert A.shape == (self.nb, self.nb) and B.shape == (self.nb, self.nb)
+        return bv, A, B
 
     def _lin(self, lin):
         if lin is None:

@@ -96,6 +96,9 @@ int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *out
 // stfem_stokes.hip: every entry point whose kernels hard-code the 27 nodes of FE_Q(2) asks this first.  On a context of another
 // velocity degree (stfem_stokes_create_space): STFEM_ERR_UNSUPPORTED, "<entry> is built for velocity degree 2 only" in the record.
 int stokes_require_q2(const stfem_stokes_ctx *c, const char *entry);
+// stfem_stokes.hip: stfem_stokes_internal_desc without that question (stfem_stokes_vanka_create_space serves degree 3 too)
+int stokes_desc_any_degree(const stfem_stokes_ctx *c, stfem_stokes_desc *out);
+int stokes_velocity_degree(const stfem_stokes_ctx *c);
 // stfem_vanka.hip: vanka_invert_kernel<double> on `count` m x m matrices at B (row-major, destroyed), the inverses in the apply's
 // layout [kpad][mpad] from block cell0 of out; *singular (device) is set to 1 by a matrix without a pivot.  `stream`: a hipStream_t.
 int stfem_vanka_invert_launch(double *B, double *out, int m, int mpad, int kpad, long long cell0, unsigned count, int *singular, void *stream);
@@ -111,6 +114,9 @@ struct stokes_cell_vanka_desc {
   // a ghost layer (bit 4 / 5: its outer z face is interior for the CIP term).  nullptr: the context of the apply, all layers own.
   stfem_stokes_ctx *setup;
   int own0, beyond;
+  // velocity degree of the context, set by every caller: 2, or 3 (stfem_stokes_vanka_create_space: mode 0, no CIP term, no slab);
+  // anything else is refused
+  int degree;
 };
 struct stokes_cell_vanka;
 // row table: nblk-block rows -> (vector | variable << 8, element offset from the cell's first DoF of the variable), m entries of two ints

@@ -8,7 +8,8 @@
 // (stfem_stokes_convection.hip), and with delta0 != 0 the CIP interior-face launches (stfem_stokes_cip.hip).  The helpers of the pressure space the solver around the operator needs: stfem_stokes_pressure.hip.
 // Every entry point describes its launches in ONE form, StokesParams (stfem_stokes_internal.h), put together by StokesLaunch below.
 // A context of velocity degree 3 (stfem_stokes_create_space) has one implementation of the linear cell operator, the cell kernel of
-// stfem_stokes_cell_q3.hip, and nothing on top of it: stokes_launch dispatches on the degree, stokes_require_q2 refuses the rest.
+// stfem_stokes_cell_q3.hip, and nothing on top of it: stokes_launch dispatches on the degree, stokes_require_q2 refuses the rest
+// (beside the operator such a context has its per-cell Vanka smoother, stfem_stokes_vanka_create_space in stfem_stokes_vanka.hip).
 #include "stfem_stokes_internal.h"
 
 #include <mutex>
@@ -268,6 +269,11 @@ int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *d)
 {
   if (!c || !d) return STFEM_ERR_INVALID_ARGUMENT;
   if (const int rq = stokes_require_q2(c, "stfem_stokes_internal_desc")) return rq;
+  return stokes_desc_any_degree(c, d);
+}
+int stokes_velocity_degree(const stfem_stokes_ctx *c) { return c->degree; }
+int stokes_desc_any_degree(const stfem_stokes_ctx *c, stfem_stokes_desc *d)
+{
   d->device = c->device; d->cart = c->base.cart; d->pspace = c->pspace; d->dmask = c->dmask;
   d->weak_mask = c->weak_mask; d->outflow_mask = c->outflow_mask;
   for (int k = 0; k < 3; ++k) {

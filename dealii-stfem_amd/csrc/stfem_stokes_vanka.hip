@@ -43,6 +43,7 @@ struct StokesCollectParams {
   const double *y;   // [slot][mpad]
   const int *slot;   // cell -> slot (nullptr: slot = cell, the one-block-per-cell layout)
   int nblk, mpad, pdg;
+  int pu, npc; // velocity degree (2, or 3 with one block per cell), FE_DGP functions per cell (4 / 10)
   int var[VK_MAX_BLOCKS], rowbase[VK_MAX_BLOCKS];
   int nc[3], ndu[3], ndp[3];
   long long Nu, Np;
@@ -61,10 +62,10 @@ __global__ __launch_bounds__(256) void stokes_vanka_collect_kernel(const StokesC
   if (i >= n_dofs) return;
   double s = 0.0;
   if (var == 1 && P.pdg) {
-    const long long cell = i >> 2;
-    s = P.y[size_t(P.slot ? P.slot[cell] : cell) * P.mpad + P.rowbase[b] + int(i & 3)];
+    const long long cell = i / P.npc;
+    s = P.y[size_t(P.slot ? P.slot[cell] : cell) * P.mpad + P.rowbase[b] + int(i - cell * P.npc)];
   } else {
-    const int p = var == 0 ? 2 : 1, np = p + 1;
+    const int p = var == 0 ? P.pu : P.pu - 1, np = p + 1;
     const int *nd = var == 0 ? P.ndu : P.ndp;
     const long long N = var == 0 ? P.Nu : P.Np;
     const int comp = int(i / N);
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256) void stokes_vanka_collect_kernel(const StokesC
     const int idx[3] = {int(node % nd[0]), int((node / nd[0]) % nd[1]), int(node / ((long long)nd[0] * nd[1]))};
     int cc[3][2], ll[3][2], cnt[3];
     node_cells(idx, p, P.nc, cc, ll, cnt);
-    const int rb = P.rowbase[b] + comp * 27;
+    const int rb = P.rowbase[b] + comp * (P.pu + 1) * (P.pu + 1) * (P.pu + 1);
     for (int kz = 0; kz < cnt[2]; ++kz)
       for (int ky = 0; ky < cnt[1]; ++ky)
         for (int kx = 0; kx < cnt[0]; ++kx) {
@@ -108,6 +109,7 @@ struct stfem_stokes_vanka {
   double *d_blocks = nullptr, *d_flat = nullptr;
   int2 *d_rowtab = nullptr;
   int *d_cellu = nullptr, *d_cellp = nullptr, *d_cls = nullptr, *d_slot = nullptr;
+  int degree = 2;                    // velocity degree (3: stfem_stokes_vanka_create_space, one block per cell)
   int mode = 0;                      // convection mode of the per-cell blocks
   double delta0 = 0.0;               // their CIP term (stfem_stokes_vanka_create_linearised_cip)
   stokes_cell_vanka *cell = nullptr; // one block per cell (stfem_stokes_vanka_cell.hip): none of the class arrays above
@@ -233,26 +235,13 @@ int build_class_blocks(stfem_stokes_vanka *v, const vanka::ClassTable &t, int np
 }
 
 // The row table: row -> (vector, variable, element offset from the cell's first DoF of the variable)
-int row_table(const stfem_stokes_vanka *v, int npl, std::vector<int2> &rowtab)
+int row_table(const stfem_stokes_vanka *v, std::vector<int2> &rowtab)
 {
   const stfem_stokes_desc &d = v->d;
+  std::vector<int> xy;
+  if (!vanka::stokes_row_table(v->degree, d.pspace != 0, v->nblk, v->var, v->rowbase, d.Nu, d.ndu, d.ndp, xy)) return STFEM_ERR_UNSUPPORTED;
   rowtab.resize(v->m);
-  for (int i = 0; i < v->nblk; ++i) {
-    if (v->var[i] == 0) {
-      for (int c = 0; c < 3; ++c)
-        for (int n = 0; n < 27; ++n) {
-          const int a = n % 3, b = (n / 3) % 3, e = n / 9;
-          const long long off = c * d.Nu + a + (long long)d.ndu[0] * (b + (long long)d.ndu[1] * e);
-          if (off > 0x7fffffffll) return STFEM_ERR_UNSUPPORTED;
-          rowtab[v->rowbase[i] + c * 27 + n] = make_int2(i, int(off));
-        }
-    } else {
-      for (int n = 0; n < npl; ++n) {
-        const int a = n % 2, b = (n / 2) % 2, e = n / 4;
-        rowtab[v->rowbase[i] + n] = make_int2(i | (1 << 8), d.pspace ? n : a + d.ndp[0] * (b + d.ndp[1] * e));
-      }
-    }
-  }
+  for (int r = 0; r < v->m; ++r) rowtab[r] = make_int2(xy[2 * r], xy[2 * r + 1]);
   return STFEM_OK;
 }
 
@@ -261,7 +250,7 @@ int build_tables(stfem_stokes_vanka *v, const vanka::ClassTable &t, int npl)
 {
   const stfem_stokes_desc &d = v->d;
   std::vector<int2> rowtab;
-  int rc = row_table(v, npl, rowtab);
+  int rc = row_table(v, rowtab);
   if (rc != STFEM_OK) return rc;
   // ---- cells grouped by class into batches of 16, four batches of one class per workgroup
   std::vector<int> firstu(t.cls.size()), firstp(t.cls.size());
@@ -305,17 +294,21 @@ void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v)
 int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v) { return v ? v->nclasses : 0; }
 int stfem_stokes_vanka_setup_batches(const stfem_stokes_vanka *v) { return v ? stokes_cell_vanka_setup_batches(v->cell) : 0; }
 
-// the rows of the cell block: block i holds the 81 velocity or the npl pressure DoFs of the cell from row rowbase[i]
-static int block_rows(stfem_stokes_vanka *v, int n_blocks, const int32_t *block_variable, int npl)
+// the rows of the cell block at velocity degree `degree`: block i holds the cell's velocity DoFs (81, at degree 3 192) or its pressure
+// DoFs from row rowbase[i]
+static int block_rows(stfem_stokes_vanka *v, int n_blocks, const int32_t *block_variable, int degree)
 {
+  const int nvel = vanka::stokes_cell_velocity_dofs(degree), npl = vanka::stokes_cell_pressure_dofs(degree, v->d.pspace != 0);
   v->nblk = n_blocks;
   for (int i = 0; i < n_blocks; ++i) {
     if (block_variable[i] < 0 || block_variable[i] > 1) return STFEM_ERR_INVALID_ARGUMENT;
     v->var[i] = block_variable[i];
     v->rowbase[i] = v->m;
-    v->m += block_variable[i] == 0 ? 81 : npl;
+    v->m += block_variable[i] == 0 ? nvel : npl;
   }
-  return v->m > VK_MAX_ROWS ? STFEM_ERR_UNSUPPORTED : STFEM_OK;
+  if (v->m > VK_MAX_ROWS)
+    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "a cell block of %d rows (%d blocks at velocity degree %d): the limit is %d rows", v->m, n_blocks, degree, VK_MAX_ROWS);
+  return STFEM_OK;
 }
 
 int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta,
@@ -335,7 +328,7 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
   v->ctx = ctx;
   v->d = d;
   const int npl = d.pspace ? 4 : 8;
-  rc = block_rows(v.get(), n_blocks, block_variable, npl);
+  rc = block_rows(v.get(), n_blocks, block_variable, 2);
   if (rc != STFEM_OK) return rc;
   const vanka::TilePlan plan = vanka::stokes_tile_plan((v->m + 15) / 16);
   v->mtw = plan.mtw; v->parts = plan.parts; v->mt = plan.parts * plan.mtw;
@@ -358,7 +351,7 @@ int stfem_stokes_vanka_create(stfem_stokes_ctx *ctx, int n_blocks, const int32_t
 // layers from own0; lin_blocks live there), see stfem_stokes_vanka_create_linearised_partitioned
 static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha, const double *Beta, int mode,
                            const double *const *lin_blocks, double delta0, stfem_stokes_vanka **out, stfem_stokes_ctx *setup = nullptr,
-                           int own0 = 0, int beyond = 0)
+                           int own0 = 0, int beyond = 0, bool any_degree = false)
 {
   if (!out) return STFEM_ERR_INVALID_ARGUMENT;
   *out = nullptr;
@@ -366,16 +359,19 @@ static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *b
   if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_blocks)) return STFEM_ERR_INVALID_ARGUMENT;
   if (n_blocks > VK_MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
   // (the _cip and _partitioned entries have asked under their own names before they come here)
-  if (const int rq = stokes_require_q2(ctx, "stfem_stokes_vanka_create_linearised")) return rq;
+  // any_degree: stfem_stokes_vanka_create_space, the one entry that serves velocity degree 3 (mode 0, no CIP term, no slab)
+  if (!any_degree)
+    if (const int rq = stokes_require_q2(ctx, "stfem_stokes_vanka_create_linearised")) return rq;
+  const int degree = stokes_velocity_degree(ctx);
   stfem_stokes_desc d;
-  int rc = stfem_stokes_internal_desc(ctx, &d);
+  int rc = stokes_desc_any_degree(ctx, &d);
   if (rc != STFEM_OK) return rc;
   std::unique_ptr<stfem_stokes_vanka, void (*)(stfem_stokes_vanka *)> v(new (std::nothrow) stfem_stokes_vanka, stfem_stokes_vanka_destroy);
   if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   v->ctx = ctx;
   v->d = d;
-  const int npl = d.pspace ? 4 : 8;
-  rc = block_rows(v.get(), n_blocks, block_variable, npl);
+  v->degree = degree;
+  rc = block_rows(v.get(), n_blocks, block_variable, degree);
   if (rc != STFEM_OK) return rc;
   if (mode != STFEM_CONVECTION_NONE) // (only the velocity entries are read: operators.h:835-866)
     for (int i = 0; i < n_blocks; ++i)
@@ -385,7 +381,7 @@ static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *b
   v->kpad = ((v->m + 3) / 4) * 4;
   v->nclasses = int((long long)d.nc[0] * d.nc[1] * d.nc[2]);
   std::vector<int2> rowtab;
-  rc = row_table(v.get(), npl, rowtab);
+  rc = row_table(v.get(), rowtab);
   if (rc != STFEM_OK) return rc;
   stokes_cell_vanka_desc cd;
   std::memset(&cd, 0, sizeof(cd));
@@ -393,6 +389,7 @@ static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *b
   v->delta0 = delta0;
   cd.delta0 = delta0;
   cd.setup = setup; cd.own0 = own0; cd.beyond = beyond;
+  cd.degree = degree;
   cd.nblk = n_blocks; cd.m = v->m; cd.mpad = v->mpad; cd.kpad = v->kpad; cd.mode = mode;
   for (int i = 0; i < n_blocks; ++i) cd.var[i] = v->var[i];
   for (int i = 0; i < n_blocks * n_blocks; ++i) { cd.Alpha[i] = Alpha[i]; cd.Beta[i] = Beta[i]; }
@@ -406,6 +403,30 @@ int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, co
                                          int mode, const double *const *lin_blocks, stfem_stokes_vanka **out)
 {
   return create_per_cell(ctx, n_blocks, block_variable, Alpha, Beta, mode, lin_blocks, 0.0, out);
+}
+
+// The constructor by descriptor (include/stfem_stokes_vanka_space.h): velocity degree 2 is stfem_stokes_vanka_create_linearised with
+// STFEM_CONVECTION_NONE on its own path; degree 3 builds the same blocks (stmg.h:704-742, compute_block_matrix.h:50-139) from the cell
+// matrices of stfem_stokes_vanka_cell_q3.hip.  Every refusal is decided on the arguments, before the context or the device is touched.
+int stfem_stokes_vanka_create_space(stfem_stokes_ctx *ctx, const stfem_stokes_vanka_space_desc *desc, stfem_stokes_vanka **out)
+{
+  const char *me = "stfem_stokes_vanka_create_space";
+  if (!out) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: out is null", me);
+  *out = nullptr;
+  if (!ctx) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: ctx is null", me);
+  if (!desc) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: desc is null", me);
+  for (int i = 0; i < 4; ++i)
+    if (desc->reserved[i] != 0) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: reserved[%d] = %d, must be 0", me, i, desc->reserved[i]);
+  if (desc->n_blocks < 1 || desc->n_blocks > VK_MAX_BLOCKS)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: n_blocks = %d, must be 1..%d", me, desc->n_blocks, VK_MAX_BLOCKS);
+  if (!desc->block_variable || !desc->Alpha || !desc->Beta)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: %s is null", me, !desc->block_variable ? "block_variable" : (!desc->Alpha ? "Alpha" : "Beta"));
+  for (int i = 0; i < desc->n_blocks; ++i)
+    if (desc->block_variable[i] < 0 || desc->block_variable[i] > 1)
+      return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: block_variable[%d] = %d, must be 0 (velocity) or 1 (pressure)", me, i, desc->block_variable[i]);
+  if (stokes_velocity_degree(ctx) == 2)
+    return stfem_stokes_vanka_create_linearised(ctx, desc->n_blocks, desc->block_variable, desc->Alpha, desc->Beta, STFEM_CONVECTION_NONE, nullptr, out);
+  return create_per_cell(ctx, desc->n_blocks, desc->block_variable, desc->Alpha, desc->Beta, STFEM_CONVECTION_NONE, nullptr, 0.0, out, nullptr, 0, 0, true);
 }
 
 // The same blocks of the operator WITH the CIP term (stfem_stokes_set_cip, weight STFEM_CIP_WEIGHT_LINEARISATION): K = the assembled
@@ -517,6 +538,7 @@ int stfem_stokes_vanka_step(stfem_stokes_vanka *v, double *const *dst_blocks, do
   std::memset(&cp, 0, sizeof(cp));
   for (int i = 0; i < v->nblk; ++i) { cp.dst[i] = dst_blocks[i]; cp.var[i] = v->var[i]; cp.rowbase[i] = v->rowbase[i]; }
   cp.y = rows; cp.slot = v->d_slot; cp.nblk = v->nblk; cp.mpad = v->mpad; cp.pdg = v->d.pspace;
+  cp.pu = v->degree; cp.npc = vanka::stokes_cell_pressure_dofs(v->degree, true);
   for (int k3 = 0; k3 < 3; ++k3) { cp.nc[k3] = v->d.nc[k3]; cp.ndu[k3] = v->d.ndu[k3]; cp.ndp[k3] = v->d.ndp[k3]; }
   cp.Nu = v->d.Nu; cp.Np = v->d.Np; cp.omega = omega; cp.accumulate = accumulate;
   const long long big = std::max(3 * v->d.Nu, v->d.Np);

@@ -11,6 +11,8 @@
 //   stokes_cell_matrices_kernel   the cell's own (81 + npl)^2 matrix of A(b) and its 27 x 27 scalar mass, in plain matrix form
 //   stokes_vanka_assemble_kernel  restriction of the assembled matrices to the cell's DoFs, constraints, valence, Alpha / Beta
 //   vanka_invert_kernel<double>   (stfem_vanka.hip) Gauss-Jordan, straight into the apply's layout
+// Velocity degree 3 (stfem_stokes_vanka_create_space; FE_Q(3)^3 x FE_Q(2) / FE_DGP(2), the linear operator alone): the cell matrices come
+// from stfem_stokes_vanka_cell_q3.hip, the assembling kernel is instantiated for 64 nodes per component, the apply is told the degree.
 // Apply: stokes_vanka_apply_percell_kernel streams every block from HBM once and leaves the rows in the scratch array; the collecting
 // launch of stfem_stokes_vanka.hip sums them per DoF: two launches, no colours, no atomics, fixed summation order.
 #include "stfem_stokes_internal.h"
@@ -360,7 +362,7 @@ __global__ __launch_bounds__(256) void stokes_cip_cell_matrices_kernel(const Sto
 }
 
 struct StokesAssembleParams {
-  const double *Ac, *Mc;    // cell matrices of the cell layers [zw0, ...): Ac[state][cell of the window][nl][nl], Mc[cell][27][27]
+  const double *Ac, *Mc;    // cell matrices of the cell layers [zw0, ...): Ac[state][cell of the window][nl][nl], Mc[cell][NN][NN]
   const double *Cc;         // CIP matrices Cc[state][cell of the window][27][7][27]; nullptr: no CIP term
   size_t cip_stride;        // doubles between the states of Cc
   int selc[VK_MAX_BLOCKS];  // the state of Cc of every column block
@@ -377,10 +379,13 @@ struct StokesAssembleParams {
 // One workgroup per cell: entry (r, s) of the block = valence(r) (Alpha(i, j) A_j(k, l) + [velocity, velocity] Beta(i, j) M(k, l)) with the
 // ASSEMBLED matrices restricted to the cell's DoFs k, l: the cell's own matrix + what the neighbours holding both DoFs add
 // (compute_block_matrix.h:50-139; cells in z, y, x order); a strongly constrained DoF keeps only the entries with itself.
+// NN: velocity nodes of a cell per component, 27 (FE_Q(2)) or 64 (FE_Q(3), no CIP term).
+template <int NN>
 __global__ __launch_bounds__(256) void stokes_vanka_assemble_kernel(const StokesAssembleParams P)
 {
-  __shared__ double s_val[96];
-  __shared__ int s_con[96];
+  constexpr int NV = 3 * NN;
+  __shared__ double s_val[NV + 32]; // (nl <= NV + 27)
+  __shared__ int s_con[NV + 32];
   const int lc = blockIdx.x, cpl = P.nc[0] * P.nc[1];
   const int cz = P.z0 + lc / cpl, cy = (lc % cpl) / P.nc[0], cx = lc % P.nc[0];
   const int cc[3] = {cx, cy, cz};
@@ -408,7 +413,7 @@ __global__ __launch_bounds__(256) void stokes_vanka_assemble_kernel(const Stokes
     const int i = P.rowblk[r], j = P.rowblk[s], a = P.rowdof[r], b = P.rowdof[s];
     double out = 0.0;
     if (a == b || !(s_con[a] || s_con[b])) {
-      const bool mass = a < 81 && b < 81 && a / 27 == b / 27;
+      const bool mass = a < NV && b < NV && a / NN == b / NN;
       const double *A = P.Ac + size_t(P.sel[j]) * P.state_stride;
       double ks = 0.0, ms = 0.0;
       for (int sh = 0; sh < 27; ++sh) {
@@ -416,9 +421,9 @@ __global__ __launch_bounds__(256) void stokes_vanka_assemble_kernel(const Stokes
         if (a2 < 0 || b2 < 0 || !has_cell(sh)) continue;
         const size_t c2 = size_t(cx + sh % 3 - 1) + size_t(P.nc[0]) * (size_t(cy + (sh / 3) % 3 - 1) + size_t(P.nc[1]) * size_t(cz + sh / 9 - 1 - P.zw0));
         ks += A[c2 * nl2 + size_t(a2) * P.nl + b2];
-        if (mass) ms += P.Mc[c2 * 729 + (a2 % 27) * 27 + b2 % 27];
+        if (mass) ms += P.Mc[c2 * (NN * NN) + (a2 % NN) * NN + b2 % NN];
       }
-      if (P.Cc && mass) {
+      if (NN == 27 && P.Cc && mass) {
         // the assembled CIP matrix: every patch cell K' = K + sh holding a adds its own-side rows - its column group 0 when it holds b
         // too, and for each of its interior faces f the group 1 + f when the neighbour behind that face is a patch cell holding b
         // (only patch cells hold b).  Shifts ascending, group 0 first, faces 0..5: a fixed order.
@@ -460,12 +465,14 @@ struct StokesCellApplyParams {
   const int2 *rowtab;   // row -> (vector | variable << 8, element offset from the cell's first DoF of the variable)
   int m, mpad, kpad, pdg;
   int nc[3], ndu[3], ndp[3];
+  int pu, pp, npc; // velocity degree 2 / 3: cell steps of the velocity and the FE_Q pressure lattice (2, 1 / 3, 2), FE_DGP functions per cell (4 / 10)
 };
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
 // y = B_c^-1 gather(src) per cell, the block streamed from HBM once (the reference's apply: stmg.h:845-867): one workgroup per cell.
-// HBM-bound: kpad * mpad doubles per cell (70 kB at m = 89) against 2 m of DoF traffic.  A thread holds a PAIR of rows (one 16-byte
+// HBM-bound: kpad * mpad doubles per cell (70 kB at m = 89, 1.3 - 1.6 MB at the 404 - 438 rows of degree 3, where the shape below is one
+// group of mpad / 2 threads that walks all k) against 2 m of DoF traffic.  A thread holds a PAIR of rows (one 16-byte
 // load per k) and the threads are dealt over 256 / (mpad / 2) groups that split k between them - at m = 89 five groups of 48 threads,
 // 240 of 256 busy, each step of the k loop reading 5 consecutive k rows = 3840 contiguous bytes (thread r = row r with 8-byte loads,
 // the scalar kernel's shape, would leave 167 threads idle there).  Four loads of a thread are in flight at a time.  The partial sums
@@ -477,8 +484,8 @@ __global__ __launch_bounds__(256) void stokes_vanka_apply_percell_kernel(const S
   const int tid = threadIdx.x;
   const long long cell = blockIdx.x;
   const int cx = int(cell % P.nc[0]), cy = int((cell / P.nc[0]) % P.nc[1]), cz = int(cell / ((long long)P.nc[0] * P.nc[1]));
-  const long long firstu = 2 * cx + (long long)P.ndu[0] * (2 * cy + (long long)P.ndu[1] * 2 * cz);
-  const long long firstp = P.pdg ? 4 * cell : cx + (long long)P.ndp[0] * (cy + (long long)P.ndp[1] * cz);
+  const long long firstu = P.pu * cx + (long long)P.ndu[0] * (P.pu * cy + (long long)P.ndu[1] * P.pu * cz);
+  const long long firstp = P.pdg ? P.npc * cell : P.pp * cx + (long long)P.ndp[0] * (P.pp * cy + (long long)P.ndp[1] * P.pp * cz);
   for (int r = tid; r < P.kpad; r += 256) {
     double v = 0.0;
     if (r < P.m) {
@@ -529,7 +536,7 @@ struct stokes_cell_vanka {
   stfem_stokes_ctx *setup = nullptr; // the context of the set-up (ctx, or a slab's extended context); own layers [own0, own0 + ctx->nc[2])
   int own0 = 0;
   stokes_cell_vanka_desc d;
-  int nl = 0, npl = 0;
+  int nl = 0, npl = 0, nn = 27; // cell DoFs, its pressure DoFs, velocity nodes per component (64 at degree 3)
   int setup_batches = 0; // batches of cell layers the last build_blocks took
   double *d_blocks = nullptr, *d_flat = nullptr;
   int2 *d_rowtab = nullptr;
@@ -559,8 +566,8 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
   int selc[VK_MAX_BLOCKS];
   const double *weight[VK_MAX_BLOCKS];
   const int ncip = cip ? vanka::distinct_states(d.nblk, d.var, lin, selc, weight) : 0;
-  const size_t nl2 = size_t(nl) * nl;
-  const size_t km_layer = (size_t(nstates) * nl2 + 729 + size_t(ncip) * CIP_CELL) * cpl * sizeof(double), b_layer = cpl * size_t(m) * m * sizeof(double);
+  const size_t nl2 = size_t(nl) * nl, nn2 = size_t(v->nn) * v->nn;
+  const size_t km_layer = (size_t(nstates) * nl2 + nn2 + size_t(ncip) * CIP_CELL) * cpl * sizeof(double), b_layer = cpl * size_t(m) * m * sizeof(double);
   STFEM_TRY(hipSetDevice(c->device));
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
@@ -591,7 +598,7 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
     (void)hipFree(d_flag);
   };
   int rc = vk_alloc(reinterpret_cast<void **>(&d_A), size_t(nstates) * win_cells * nl2 * sizeof(double));
-  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_M), win_cells * 729 * sizeof(double));
+  if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_M), win_cells * nn2 * sizeof(double));
   if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_B), cpl * L * size_t(m) * m * sizeof(double));
   if (rc == STFEM_OK && cip) rc = vk_alloc(reinterpret_cast<void **>(&d_C), size_t(ncip) * win_cells * CIP_CELL * sizeof(double));
   if (rc == STFEM_OK) rc = vk_alloc(reinterpret_cast<void **>(&d_flag), sizeof(int));
@@ -630,6 +637,8 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
     for (int i = 0; i < d.nblk; ++i) ap.selc[i] = selc[i];
   }
   const void *cipk = c->base.cart ? reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<false>);
+  const bool q3 = d.degree == 3; // (the linear operator alone: one state, no CIP term)
+  const void *asmk = q3 ? reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<64>) : reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<27>);
   const void *cellk = c->pspace ? reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<false>);
   stfem_launch_begin();
   v->setup_batches = 0;
@@ -642,7 +651,8 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
       mp.b = state[s];
       mp.Ac = d_A + size_t(s) * ap.state_stride;
       mp.Mc = s == 0 ? d_M : nullptr;
-      rc = vk_launch(cellk, dim3((unsigned)wcells), &mp, nullptr, "stokes_cell_matrices_kernel");
+      rc = q3 ? stokes_cell_matrices_q3_launch(c, mp.Ac, mp.Mc, mp.cell0, (unsigned)wcells)
+              : vk_launch(cellk, dim3((unsigned)wcells), &mp, nullptr, "stokes_cell_matrices_kernel");
     }
     for (int s = 0; s < ncip && rc == STFEM_OK; ++s) {
       cp.w = weight[s];
@@ -651,7 +661,7 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
       rc = vk_launch(cipk, dim3((unsigned)wcells), &cp, nullptr, "stokes_cip_cell_matrices_kernel");
     }
     ap.zw0 = zw0; ap.z0 = z0;
-    if (rc == STFEM_OK) rc = vk_launch(reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel), dim3((unsigned)bcells), &ap, nullptr, "stokes_vanka_assemble_kernel");
+    if (rc == STFEM_OK) rc = vk_launch(asmk, dim3((unsigned)bcells), &ap, nullptr, "stokes_vanka_assemble_kernel");
     if (rc == STFEM_OK) rc = stfem_vanka_invert_launch(d_B, v->d_blocks, m, d.mpad, d.kpad, (long long)cpl * (z0 - own0), (unsigned)bcells, d_flag, nullptr);
     if (rc == STFEM_OK) e = hipDeviceSynchronize(); // (the next batch reuses the scratch)
   }
@@ -683,17 +693,23 @@ int stokes_cell_vanka_create(stfem_stokes_ctx *c, const stokes_cell_vanka_desc &
                              stokes_cell_vanka **out)
 {
   *out = nullptr;
+  // the kernels know 27 and 64 velocity nodes per component, nothing else; and the degree is the context's
+  const int degree = d.degree;
+  if ((degree != 2 && degree != 3) || degree != c->degree)
+    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "per-cell Stokes blocks of velocity degree %d on a context of degree %d: built for 2 and 3", degree, c->degree);
   stokes_cell_vanka *v = new (std::nothrow) stokes_cell_vanka;
   if (!v) return STFEM_ERR_OUT_OF_MEMORY;
   v->ctx = c;
   v->setup = d.setup ? d.setup : c;
   v->own0 = d.setup ? d.own0 : 0;
   v->d = d;
-  v->npl = c->pspace ? 4 : 8;
-  v->nl = 81 + v->npl;
-  const vanka::CellDofTables t = vanka::stokes_cell_dof_tables(c->pspace != 0);
+  const int nvel = vanka::stokes_cell_velocity_dofs(degree);
+  v->npl = vanka::stokes_cell_pressure_dofs(degree, c->pspace != 0);
+  v->nn = nvel / 3;
+  v->nl = nvel + v->npl;
+  const vanka::CellDofTables t = vanka::stokes_cell_dof_tables(c->pspace != 0, degree);
   std::vector<int> rowblk, rowdof;
-  vanka::stokes_row_dofs(d.nblk, d.var, v->npl, rowblk, rowdof);
+  vanka::stokes_row_dofs(d.nblk, d.var, v->npl, rowblk, rowdof, nvel);
   std::vector<int2> rowtab(d.m);
   for (int r = 0; r < d.m; ++r) rowtab[r] = make_int2(rowtab_xy[2 * r], rowtab_xy[2 * r + 1]);
   const size_t ncells = size_t(c->nc[0]) * c->nc[1] * c->nc[2];
@@ -724,6 +740,7 @@ int stokes_cell_vanka_apply(stokes_cell_vanka *v, const double *const *src_block
   p.blocks = v->d_blocks; p.flat = v->d_flat; p.rowtab = v->d_rowtab;
   p.m = v->d.m; p.mpad = v->d.mpad; p.kpad = v->d.kpad; p.pdg = c->pspace;
   for (int k = 0; k < 3; ++k) { p.nc[k] = c->nc[k]; p.ndu[k] = c->ndu[k]; p.ndp[k] = c->ndp[k]; }
+  p.pu = v->d.degree; p.pp = v->d.degree - 1; p.npc = c->pspace ? v->npl : 0;
   *rows = v->d_flat;
   const size_t ncells = size_t(c->nc[0]) * c->nc[1] * c->nc[2];
   return vk_launch(reinterpret_cast<const void *>(&stokes_vanka_apply_percell_kernel), dim3((unsigned)ncells), &p, static_cast<hipStream_t>(stream),

@@ -1,7 +1,8 @@
 // Host-side set-up steps shared by the cell-patch smoothers (stfem_vanka.hip: scalar systems; stfem_stokes_vanka.hip: the
 // two-variable Stokes system): block classes of an axis-aligned uniform mesh, cell lists of the apply launches, tile plans, and
 // the way from a combined cell matrix to the stored inverse, and the index tables of the one-block-per-cell Stokes layout
-// (stfem_stokes_vanka_cell.hip).  Plain C++17, no HIP: csrc/test_vanka_setup.cpp and csrc/test_stokes_vanka_setup.cpp run it on the CPU.
+// (stfem_stokes_vanka_cell.hip), at velocity degree 2 and 3.  Plain C++17, no HIP: csrc/test_vanka_setup.cpp, csrc/test_stokes_vanka_setup.cpp and
+// csrc/test_stokes_vanka_setup_q3.cpp run it on the CPU.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -208,27 +209,30 @@ bool finish_block(int m, std::vector<double> &B, const std::vector<int> &dof, co
 }
 
 // ---- one block per cell of the two-variable (Stokes) system: the cell's DoFs and the cells that share them ----
-// Cell DoF k: 0 .. 80 velocity (component k / 27, node k % 27 = a + 3 b + 9 e of the FE_Q(2) cell), 81 .. the pressure DoFs:
-// FE_Q(1) vertices a + 2 b + 4 e, or the four FE_DGP(1) functions of the cell, which no other cell holds.
+// Velocity degree p (2 or 3): the cell holds nn = (p + 1)^3 velocity nodes per component.  Cell DoF k: 0 .. 3 nn - 1 velocity
+// (component k / nn, node k % nn = a + (p + 1) (b + (p + 1) e) of the FE_Q(p) cell), from 3 nn the pressure DoFs: the FE_Q(p - 1)
+// nodes a + p (b + p e), or the FE_DGP(p - 1) functions of the cell (4 at degree 2, 10 at degree 3), which no other cell holds.
+inline int stokes_cell_velocity_dofs(int degree) { return 3 * (degree + 1) * (degree + 1) * (degree + 1); }
+inline int stokes_cell_pressure_dofs(int degree, bool pdg) { return pdg ? (degree == 2 ? 4 : 10) : degree * degree * degree; }
 struct CellDofTables {
-  int nl = 0;            // 81 + pressure DoFs of a cell
+  int nl = 0;            // velocity + pressure DoFs of a cell (degree 2: 81 + 8 or 4, degree 3: 192 + 27 or 10)
   std::vector<int> nbr;  // [nl][27]: the DoF's index in the neighbour cell at shift (sx + 1) + 3 (sy + 1) + 9 (sz + 1), -1: not held there
   std::vector<int> face; // [nl]: bit 2 d / 2 d + 1: a velocity DoF on the cell's lower / upper face of direction d (strong constraints)
 };
-inline CellDofTables stokes_cell_dof_tables(bool pdg)
+inline CellDofTables stokes_cell_dof_tables(bool pdg, int degree = 2)
 {
   CellDofTables t;
-  const int npl = pdg ? 4 : 8;
-  t.nl = 81 + npl;
+  const int nv = stokes_cell_velocity_dofs(degree), nn = nv / 3;
+  t.nl = nv + stokes_cell_pressure_dofs(degree, pdg);
   t.nbr.assign(size_t(t.nl) * 27, -1);
   t.face.assign(t.nl, 0);
   for (int k = 0; k < t.nl; ++k) {
-    const bool vel = k < 81;
+    const bool vel = k < nv;
     if (!vel && pdg) { // a cell function: the cell itself only
       t.nbr[size_t(k) * 27 + 13] = k;
       continue;
     }
-    const int n1 = vel ? 3 : 2, top = n1 - 1, n = vel ? k % 27 : k - 81, base = vel ? k - n : 81;
+    const int n1 = vel ? degree + 1 : degree, top = n1 - 1, n = vel ? k % nn : k - nv, base = vel ? k - n : nv;
     const int idx[3] = {n % n1, (n / n1) % n1, n / (n1 * n1)};
     for (int d = 0; d < 3; ++d)
       if (vel) t.face[k] |= (idx[d] == 0 ? 1 << (2 * d) : 0) | (idx[d] == top ? 2 << (2 * d) : 0);
@@ -248,17 +252,47 @@ inline CellDofTables stokes_cell_dof_tables(bool pdg)
   }
   return t;
 }
-// row of the cell block -> (block of the BlockSlice, cell DoF): block i holds the 81 velocity or the npl pressure DoFs, the blocks
+// row of the cell block -> (block of the BlockSlice, cell DoF): block i holds the nvel velocity or the npl pressure DoFs, the blocks
 // one after the other
-inline void stokes_row_dofs(int nblk, const int *var, int npl, std::vector<int> &rowblk, std::vector<int> &rowdof)
+inline void stokes_row_dofs(int nblk, const int *var, int npl, std::vector<int> &rowblk, std::vector<int> &rowdof, int nvel = 81)
 {
   rowblk.clear();
   rowdof.clear();
   for (int i = 0; i < nblk; ++i)
-    for (int k = 0; k < (var[i] ? npl : 81); ++k) {
+    for (int k = 0; k < (var[i] ? npl : nvel); ++k) {
       rowblk.push_back(i);
-      rowdof.push_back((var[i] ? 81 : 0) + k);
+      rowdof.push_back((var[i] ? nvel : 0) + k);
     }
+}
+// The apply's row table of the one-block-per-cell layout: row -> (block | variable << 8, element offset from the cell's first DoF of
+// the variable); velocity block: component c, node (a, b, e) at c Nu + a + ndu[0] (b + ndu[1] e); pressure block: node (a, b, e) at
+// a + ndp[0] (b + ndp[1] e), or cell function n at n.  false: an offset beyond 2^31.
+inline bool stokes_row_table(int degree, bool pdg, int nblk, const int *var, const int *rowbase, long long Nu, const int ndu[3], const int ndp[3],
+                             std::vector<int> &rowtab_xy)
+{
+  const int n1 = degree + 1, nn = n1 * n1 * n1, npl = stokes_cell_pressure_dofs(degree, pdg);
+  int m = 0;
+  for (int i = 0; i < nblk; ++i) m = rowbase[i] + (var[i] ? npl : 3 * nn) > m ? rowbase[i] + (var[i] ? npl : 3 * nn) : m;
+  rowtab_xy.assign(size_t(2) * m, 0);
+  for (int i = 0; i < nblk; ++i) {
+    if (var[i] == 0) {
+      for (int c = 0; c < 3; ++c)
+        for (int n = 0; n < nn; ++n) {
+          const int a = n % n1, b = (n / n1) % n1, e = n / (n1 * n1);
+          const long long off = c * Nu + a + (long long)ndu[0] * (b + (long long)ndu[1] * e);
+          if (off > 0x7fffffffll) return false;
+          rowtab_xy[2 * (rowbase[i] + c * nn + n)] = i;
+          rowtab_xy[2 * (rowbase[i] + c * nn + n) + 1] = int(off);
+        }
+    } else {
+      for (int n = 0; n < npl; ++n) {
+        const int a = n % degree, b = (n / degree) % degree, e = n / (degree * degree);
+        rowtab_xy[2 * (rowbase[i] + n)] = i | (1 << 8);
+        rowtab_xy[2 * (rowbase[i] + n) + 1] = pdg ? n : a + ndp[0] * (b + ndp[1] * e);
+      }
+    }
+  }
+  return true;
 }
 // The distinct linearisation states of the velocity column blocks: sel[j] = position of lin[j] among the distinct pointers, in the
 // order the blocks meet them (pressure blocks and a null `lin`: 0); returns their number (at least 1)

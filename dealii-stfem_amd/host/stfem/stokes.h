@@ -548,7 +548,8 @@ using NavierStokesOperator =
 // Stokes levels: the assembled Stokes and mass matrices restricted to every cell's velocity and pressure DoFs, combined with
 // Alpha / Beta over the blocks of the BlockSlice (K_mask empty, M_mask(0, 0) only), inverted.  The assembled matrices and DoF
 // handlers of the reference's constructor are not needed: the blocks follow from the operator (stfem_stokes_vanka_create; one block
-// per neighbour pattern on a box, one per cell on a general mesh and, second constructor, for the linearised operator).
+// per neighbour pattern on a box, one per cell on a general mesh and, second constructor, for the linearised operator).  An operator
+// of velocity degree 3 goes through stfem_stokes_vanka_create_space (first constructor only): one block per cell on every mesh.
 template <typename Number> class PreconditionVankaStokes {
   static_assert(std::is_same<Number, double>::value, "fp64");
 
@@ -563,8 +564,18 @@ public:
     std::vector<int32_t> var(nb_);
     for (unsigned i = 0; i < nb_; ++i) var[i] = int32_t(blk_slice.decompose(i)[1]);
     stfem_stokes_vanka *v = nullptr;
-    const int rc = stfem_stokes_vanka_create(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), &v);
-    if (rc != STFEM_OK) throw Error(rc, "stfem_stokes_vanka_create");
+    if (K.velocity_degree() != 2) { // FE_Q(3)^3 x FE_Q(2) / FE_DGP(2): the constructor by descriptor, one block per cell of the linear operator
+      stfem_stokes_vanka_space_desc d{}; // (reserved: 0)
+      d.n_blocks = int32_t(nb_);
+      d.block_variable = var.data();
+      d.Alpha = Alpha.data();
+      d.Beta = Beta.data();
+      const int rc = stfem_stokes_vanka_create_space(K.handle(), &d, &v);
+      if (rc != STFEM_OK) throw Error(rc, "stfem_stokes_vanka_create_space");
+    } else {
+      const int rc = stfem_stokes_vanka_create(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), &v);
+      if (rc != STFEM_OK) throw Error(rc, "stfem_stokes_vanka_create");
+    }
     v_.reset(v, stfem_stokes_vanka_destroy);
   }
   // The smoother of the LINEARISED operator, one block per cell (reinit_asm, stmg.h:929-965: set_data(mg_data[l]), the assembled

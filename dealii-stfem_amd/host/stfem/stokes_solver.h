@@ -288,6 +288,8 @@ struct SynchronisedTimer {
 // reestimate_relaxation is false - at every later one.  The preconditioner interface of TimeIntegratorNavierStokes beside GMGStokes.
 // delta0 != 0 (a nonlinear treatment only): the blocks hold the CIP term weighted by the linearisation
 // (PreconditionVankaStokes, stfem_stokes_vanka_create_linearised_cip); the estimate sees whatever `system` applies.
+// Velocity degree 2 only: `system` stands on StokesSpaces, whose scalar spaces are FE_Q(2) / stfem_stokes_pressure_ctx; over a degree-3
+// operator PreconditionVankaStokes and its step() are what there is.
 template <int dim> class RelaxedVankaStokes {
 public:
   RelaxedVankaStokes(const StokesMatrixFreeOperator<dim, double> &K, const StokesSystem<dim, double> &system, const FullMatrix<double> &Alpha,

@@ -688,6 +688,10 @@ int stfem_stokes_vanka_create_linearised_partitioned(stfem_stokes_ctx *slab, stf
 int stfem_stokes_vanka_create_linearised_cip(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *block_variable, const double *Alpha,
                                              const double *Beta, int mode, const double *const *lin_blocks, double delta0,
                                              stfem_stokes_vanka **out);
+/* The constructor by descriptor, which alone serves a context of velocity degree 3 (one block per cell of the linear operator; at
+ * degree 2 it is create_linearised with STFEM_CONVECTION_NONE): the companion header, part of this boundary and included here, where
+ * its types are declared.  Every function below takes its handle. */
+#include "stfem_stokes_vanka_space.h"
 int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_blocks);
 void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v);
 int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v);

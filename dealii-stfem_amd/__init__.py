@@ -910,8 +910,9 @@ class StokesMatrixFreeOperator:
         return cls(ncell, _space=(velocity_degree, tuple(int(v) for v in reserved)), **keywords)
 
     def last_cell_plan(self):
-        """(workgroups, longest run of cells per wave) of the last colour launch of the degree-3 cell kernel; the environment
-        variable STFEM_STOKES_Q3_WORKGROUPS, read at every launch, caps the workgroups"""
+        """(workgroups, longest run of cells per wave - per half-wave at degree 2) of the last colour launch of the cell kernel, at
+        either degree; the environment variable STFEM_STOKES_Q3_WORKGROUPS, read at every launch, caps the workgroups of the colour
+        launches of the cell kernel at either degree.  A context that has not launched the cell kernel raises status -2."""
         out = (C.c_int32 * 2)()
         _check(lib().stfem_stokes_last_cell_plan(self._h, out), "stfem_stokes_last_cell_plan")
         return tuple(out)

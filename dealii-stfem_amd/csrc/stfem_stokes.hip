@@ -7,8 +7,8 @@
 // (stfem_stokes_boundary.hip), and with a convection mode (form / jacobian of the Navier-Stokes operator) the convection launches
 // (stfem_stokes_convection.hip), and with delta0 != 0 the CIP interior-face launches (stfem_stokes_cip.hip).  The helpers of the pressure space the solver around the operator needs: stfem_stokes_pressure.hip.
 // Every entry point describes its launches in ONE form, StokesParams (stfem_stokes_internal.h), put together by StokesLaunch below.
-// A context of velocity degree 3 (stfem_stokes_create_space) has one implementation of the linear cell operator, the cell kernel of
-// stfem_stokes_cell_q3.hip, and nothing on top of it: stokes_launch dispatches on the degree, stokes_require_q2 refuses the rest
+// A context of velocity degree 3 (stfem_stokes_create_space) has one implementation of the linear cell operator, the same cell kernel
+// at DEG = 3 (stfem_stokes_cell.hip), and nothing on top of it: stokes_launch dispatches on the degree, stokes_require_q2 refuses the rest
 // (beside the operator such a context has its per-cell Vanka smoother, stfem_stokes_vanka_create_space in stfem_stokes_vanka.hip).
 #include "stfem_stokes_internal.h"
 
@@ -42,14 +42,44 @@ static hipStream_t stokes_side_stream(int device)
   return streams[device];
 }
 
+// Geometry and 1D tables of a context, in the launch description of its degree
+template <int DEG, class Table>
+static void stokes_describe(const stfem_stokes_ctx *c, const stfem_mesh_desc *mesh, const Table &Su, const Table &Du, const stfem::Mat &Sp,
+                            const std::vector<double> &xq, const std::vector<double> &wq, StokesParamsT<DEG> &b)
+{
+  for (int i = 0; i < (DEG + 1) * (DEG + 1); ++i) { b.Su[i] = Su[i]; b.Du[i] = Du[i]; }
+  for (int i = 0; i < (DEG + 1) * DEG; ++i) b.Sp[i] = Sp[i];
+  for (int i = 0; i <= DEG; ++i) {
+    b.xq[i] = xq[i]; b.wq[i] = wq[i];
+    b.lq[0][i] = std::sqrt(3.0) * (2.0 * xq[i] - 1.0);
+    if (DEG > 2) b.lq[DEG - 2][i] = std::sqrt(5.0) * (6.0 * xq[i] * xq[i] - 6.0 * xq[i] + 1.0);
+  }
+  b.vertices = c->d_vertices;
+  b.ncx = c->nc[0]; b.ncy = c->nc[1]; b.ncz = c->nc[2];
+  for (int d = 0; d < 3; ++d) { b.ndu[d] = c->ndu[d]; b.ndp[d] = c->ndp[d]; }
+  b.Nu = c->Nu; b.Np = c->Np;
+  b.dmask = c->dmask;
+  b.nu = c->nu;
+  b.cart = mesh->vertices ? 0 : 1;
+  b.pdg = c->pspace;
+  b.interleave = 1;
+  if (const char *e = getenv("STFEM_STOKES_INTERLEAVE")) b.interleave = atoi(e) != 0;
+  b.detJ = 1.0;
+  for (int d = 0; d < 3; ++d) {
+    const double h = (mesh->upper[d] - mesh->lower[d]) / c->nc[d];
+    b.hinv[d] = 1.0 / h;
+    b.detJ *= h;
+  }
+}
+
 extern "C" {
 
 int stfem_stokes_last_cell_plan(const stfem_stokes_ctx *c, int32_t out[2])
 {
   if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
-  if (!c->q3_launched) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "stfem_stokes_last_cell_plan: this context has not launched the degree-3 cell kernel");
-  out[0] = c->q3_plan[0];
-  out[1] = c->q3_plan[1];
+  if (!c->cell_launched) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "stfem_stokes_last_cell_plan: this context has not launched the cell kernel");
+  out[0] = c->cell_plan[0];
+  out[1] = c->cell_plan[1];
   return STFEM_OK;
 }
 
@@ -150,57 +180,22 @@ static int stokes_create_degree(const stfem_mesh_desc *mesh, int velocity_degree
   }
   c->h_vertices = v;
   std::memset(&c->bnd, 0, sizeof(c->bnd));
-  // 1D tables: FE_Q(2) and FE_Q(1) on Gauss-Lobatto nodes at the 3 Gauss points
-  StokesParams &b = c->base;
-  std::memset(&b, 0, sizeof(b));
+  // 1D tables: FE_Q(degree) and FE_Q(degree - 1) on Gauss-Lobatto nodes at the degree + 1 Gauss points
   const stfem::ShapeTables tu = stfem::make_shape_tables(velocity_degree), tp = stfem::make_shape_tables(velocity_degree - 1);
   std::vector<double> xq, wq;
   stfem::gauss_rule(velocity_degree + 1, xq, wq);
   stfem::Mat Sp, Gp;
   stfem::lagrange_tables(tp.nodes, xq, Sp, Gp);
-  if (velocity_degree == 2) {
-    for (int i = 0; i < 9; ++i) { b.Su[i] = tu.S[i]; b.Du[i] = tu.D[i]; }
-    for (int i = 0; i < 6; ++i) b.Sp[i] = Sp[i];
-    for (int i = 0; i < 3; ++i) { b.xq[i] = xq[i]; b.wq[i] = wq[i]; }
-  }
-  b.vertices = c->d_vertices;
-  b.ncx = c->nc[0]; b.ncy = c->nc[1]; b.ncz = c->nc[2];
-  for (int d = 0; d < 3; ++d) { b.ndu[d] = c->ndu[d]; b.ndp[d] = c->ndp[d]; }
-  b.Nu = c->Nu; b.Np = c->Np;
-  b.dmask = c->dmask;
-  b.nu = c->nu;
-  b.cart = mesh->vertices ? 0 : 1;
-  b.pdg = c->pspace;
-  for (int i = 0; i < 3; ++i) b.l1q[i] = std::sqrt(3.0) * (2.0 * xq[i] - 1.0);
-  b.interleave = 1;
-  if (const char *e = getenv("STFEM_STOKES_INTERLEAVE")) b.interleave = atoi(e) != 0;
-  b.detJ = 1.0;
-  for (int d = 0; d < 3; ++d) {
-    const double h = (mesh->upper[d] - mesh->lower[d]) / c->nc[d];
-    b.hinv[d] = 1.0 / h;
-    b.detJ *= h;
-  }
+  std::memset(&c->base, 0, sizeof(c->base));
+  std::memset(&c->base3, 0, sizeof(c->base3));
   std::memset(&c->coupling, 0, sizeof(c->coupling));
-  std::memset(&c->q3, 0, sizeof(c->q3));
-  if (velocity_degree == 3) { // FE_Q(3) and FE_Q(2) at the four Gauss points; no scalar pencil context: the cell kernel serves boxes too
-    StokesQ3Params &q = c->q3;
-    for (int i = 0; i < 16; ++i) { q.Su[i] = tu.S[i]; q.Du[i] = tu.D[i]; }
-    for (int i = 0; i < 12; ++i) q.Sp[i] = Sp[i];
-    for (int i = 0; i < 4; ++i) {
-      q.xq[i] = xq[i]; q.wq[i] = wq[i];
-      q.l1q[i] = std::sqrt(3.0) * (2.0 * xq[i] - 1.0);
-      q.l2q[i] = std::sqrt(5.0) * (6.0 * xq[i] * xq[i] - 6.0 * xq[i] + 1.0);
-    }
-    q.vertices = c->d_vertices;
-    q.ncx = c->nc[0]; q.ncy = c->nc[1]; q.ncz = c->nc[2];
-    for (int d = 0; d < 3; ++d) { q.ndu[d] = c->ndu[d]; q.ndp[d] = c->ndp[d]; q.hinv[d] = b.hinv[d]; }
-    q.Nu = c->Nu; q.Np = c->Np;
-    q.dmask = c->dmask;
-    q.nu = c->nu;
-    q.detJ = b.detJ;
+  if (velocity_degree == 3) { // no scalar pencil context: the cell kernel serves boxes too
+    stokes_describe(c, mesh, tu.S, tu.D, Sp, xq, wq, c->base3);
     *out = c;
     return STFEM_OK;
   }
+  stokes_describe(c, mesh, tu.S, tu.D, Sp, xq, wq, c->base);
+  const StokesParams &b = c->base;
   if (b.cart) {
     const char *e = getenv("STFEM_STOKES_CELL"); // 1: keep the cell kernel on boxes too (cross-checks, measurements)
     if (!(e && atoi(e) != 0)) {
@@ -274,7 +269,7 @@ int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *d)
 int stokes_velocity_degree(const stfem_stokes_ctx *c) { return c->degree; }
 int stokes_desc_any_degree(const stfem_stokes_ctx *c, stfem_stokes_desc *d)
 {
-  d->device = c->device; d->cart = c->base.cart; d->pspace = c->pspace; d->dmask = c->dmask;
+  d->device = c->device; d->cart = c->cart(); d->pspace = c->pspace; d->dmask = c->dmask;
   d->weak_mask = c->weak_mask; d->outflow_mask = c->outflow_mask;
   for (int k = 0; k < 3; ++k) {
     d->nc[k] = c->nc[k]; d->ndu[k] = c->ndu[k]; d->ndp[k] = c->ndp[k];
@@ -337,6 +332,8 @@ namespace {
 int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double *const *lin, hipStream_t st);
 
 // One set of launches in the making: the sources first, then the destination pairs with their weights per source.
+// prm starts as the context's `base`.  On a context of degree 3 that is all zero (geometry and tables are in base3): prm then carries
+// the set part alone, which is all stokes_cell_launch reads of it there - nothing on the degree-3 path may read geometry from prm.
 struct StokesLaunch {
   stfem_stokes_ctx *c;
   hipStream_t st;
@@ -494,7 +491,7 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
 int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double *const *lin, hipStream_t st)
 {
   // axis-aligned uniform mesh: the Kronecker path; otherwise the cell kernel
-  if (c->degree == 3) return stokes_cell_q3_launch(c, prm, st); // the linear cell operator is all a degree-3 context has
+  if (c->degree == 3) return stokes_cell_launch(c, prm, st); // the linear cell operator is all a degree-3 context has
   const int rc = c->scalar ? stokes_cart_launch(c, prm, st) : stokes_cell_launch(c, prm, st);
   if (rc != STFEM_OK) return rc;
   // LoopType::Full: the boundary-face loop of the same vmult (the mass operator has none)

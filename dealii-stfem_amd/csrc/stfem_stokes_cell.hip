@@ -1,5 +1,6 @@
-// Stokes two-field operator, general meshes: the cell kernel.  It replaces, for the cell loop (LoopType::Cell: no weak boundary
-// ids, delta0 = 0):
+// Stokes two-field operator: the cell kernel, for velocity degree DEG = 2 (FE_Q(2)^3 x FE_Q(1) / FE_DGP(1), QGauss(3)) and DEG = 3
+// (FE_Q(3)^3 x FE_Q(2) / FE_DGP(2), QGauss(4), the pair the reference builds for time degree 2, tests/tp_03stokes.cc:79-86).  It
+// replaces, for the cell loop (LoopType::Cell: no weak boundary ids, delta0 = 0):
 //   StokesMatrixFreeOperator::do_cell_integral_range / do_cell_integral_local
 //       (reference include/operators.h:1501-1575, OperatorMode::none):
 //       pressure.submit_value(div u); velocity.submit_gradient(nu grad u - p I)
@@ -10,12 +11,13 @@
 //       wKu_j * (nu K u - B^T p) + wM_j * M u   into every velocity destination block j,
 //       wKp_j * (div u, q)                       into every pressure destination block j
 // in eight launches, one per cell colour (cells of one colour share no DoF), with plain loads and
-// stores: no atomics, no zeroing, bitwise reproducible.  No CPU fallback.
+// stores: no atomics, no zeroing, bitwise reproducible.  No CPU fallback.  At degree 2 it serves general meshes (boxes take the
+// Kronecker path of stfem_stokes.hip unless STFEM_STOKES_CELL=1), at degree 3 every mesh.
 //
-// Thread layout: one wave owns two cells (32 lanes each, 27 = 3^3 active).  Evaluation and
-// integration are sum-factorised (three 1D stages each, see stokes_cell_kernel); the MappingQ1
-// Jacobian is evaluated on the fly from the eight cell vertices (24 doubles per cell instead of a
-// stored metric), or is a constant diagonal on axis-aligned boxes.
+// Thread layout: lane t = a + (DEG + 1) b + (DEG + 1)^2 c of a cell is its velocity node (a, b, c) and its quadrature point (a, b, c).
+// Degree 2: 27 of 32 lanes, one wave owns two cells; degree 3: 64 lanes, one wave is one cell.  Evaluation and integration are
+// sum-factorised (three 1D stages each, see stokes_cell_kernel); the MappingQ1 Jacobian is evaluated on the fly from the eight cell
+// vertices (24 doubles per cell instead of a stored metric), or is a constant diagonal on axis-aligned boxes.
 #include "stfem_stokes_internal.h"
 
 #include <algorithm>
@@ -23,66 +25,130 @@
 
 namespace {
 
-// 256 threads = 4 waves = 8 cells at a time; the workgroups walk over the cells.
-// Sum-factorised: evaluation and integration are three 1D stages each (x, y, z), handed from lane to
-// lane through two wave-private LDS regions per cell that alternate as source and destination.
+// FE_DGP(DEG - 1): function f is l_i(xi) l_j(eta) l_k(zeta) with i + j + k <= DEG - 1, i fastest (l_n: the orthonormal Legendre
+// functions on [0, 1]); d[f] = (i, j, k).  Degree 2: 1, l(xi), l(eta), l(zeta), deal.II's basis.
+template <int DEG> struct DgpDegrees {
+  int d[DEG * (DEG + 1) * (DEG + 2) / 6][3];
+};
+template <int DEG> constexpr DgpDegrees<DEG> dgp_degrees()
+{
+  DgpDegrees<DEG> r{};
+  int f = 0;
+  for (int k = 0; k < DEG; ++k)
+    for (int j = 0; j + k < DEG; ++j)
+      for (int i = 0; i + j + k < DEG; ++i, ++f) { r.d[f][0] = i; r.d[f][1] = j; r.d[f][2] = k; }
+  return r;
+}
+
+// The lane's N coefficients p[0], p[STRIDE], ... of a 1D table in LDS: HELD - copied into registers once, for the whole kernel;
+// otherwise read where they are used.
+template <int N, int STRIDE, bool HELD> struct Coef {
+  const double *p;
+  double r[HELD ? N : 1];
+  __device__ __forceinline__ explicit Coef(const double *q) : p(q)
+  {
+    if constexpr (HELD) {
+#pragma unroll
+      for (int n = 0; n < N; ++n) r[n] = q[n * STRIDE];
+    }
+  }
+  __device__ __forceinline__ double operator[](int n) const
+  {
+    if constexpr (HELD) return r[n];
+    else return p[n * STRIDE];
+  }
+};
+// Which 1D tables a lane holds in registers.  The rows of its quadrature index (evaluation) always.  The columns of its node index
+// (integration) and the pressure tables at degree 2 only: at degree 3 they are 44 doubles more, and with all of them in registers
+// five of the eight instantiations need 256 VGPRs and spills to AGPRs, one wave per SIMD (profiles/stokes_q3.txt).
+template <int DEG> constexpr bool COLUMNS_HELD = DEG == 2;
+
+// sum_n w[n] v[n * stride], ascending, one fma chain.  The values are read last first: the compiler's order of the LDS reads in the
+// integration stages follows the order here, and this one is the faster (profiles/stokes_cell_merge.txt)
+template <int N, class W> __device__ __forceinline__ double dot(const W &w, const double *v, int stride = 1)
+{
+  double x[N];
+#pragma unroll
+  for (int n = N - 1; n >= 0; --n) x[n] = v[n * stride];
+  double s = w[0] * x[0];
+#pragma unroll
+  for (int n = 1; n < N; ++n) s = fma(w[n], x[n], s);
+  return s;
+}
+
+// 256 threads = 8 (degree 2) or 4 (degree 3) cells at a time; the workgroups walk over the cells.
+// Sum-factorised: evaluation and integration are three 1D stages each (x, y, z), handed from lane to lane through two wave-private
+// LDS regions per cell that alternate as source and destination, ordered with wave_fence() (a cell never leaves its wave: no
+// workgroup barrier inside the cell loop).
 //   evaluate : lane (a, b, c) = (q_x, n_y, n_z) -> (q_x, q_y, n_z) -> quadrature point (q_x, q_y, q_z)
-//   integrate: lane (q_x, q_y, n_z) -> (q_x, n_y, n_z) -> velocity node (n_x, n_y, n_z); the eight
-//              lanes with a, b, c < 2 also carry the pressure node (a, b, c)
-// The lane's rows / columns of the 1D tables stay in registers for the whole kernel.
+//   integrate: lane (q_x, q_y, n_z) -> (q_x, n_y, n_z) -> velocity node (n_x, n_y, n_z)
+// The FE_Q(DEG - 1) pressure rides on the lanes with a, b, c < DEG (node (a, b, c)); the other lanes compute on clamped indices and
+// their results are not used.  The FE_DGP(DEG - 1) functions are evaluated directly at the lane's point and integrated by the first
+// lanes of the cell, one function each, as sums over the quadrature points in ascending order.
 // CART: axis-aligned uniform cells (the context was created without vertices): constant diagonal Jacobian.
 // MULTI: several sources per cell, weighted sums in registers (one set per destination pair, up to MAXSRC), one scatter; otherwise
 //        one source (index 0), no sums, the weights applied at scatter time to up to MAXOUT destination pairs (see StokesParams)
-// PDG: FE_DGP(1) pressure (a template parameter: the FE_Q(1) instantiations stay what they were)
-template <bool CART, bool MULTI, bool PDG>
-__global__ __launch_bounds__(256) void stokes_cell_kernel(const StokesParams prm)
+// PDG: FE_DGP pressure (a template parameter: the FE_Q instantiations carry none of it, and the other way round)
+template <int DEG, bool CART, bool MULTI, bool PDG>
+__global__ __launch_bounds__(256) void stokes_cell_kernel(const StokesParamsT<DEG> prm)
 {
-  constexpr int RX = 351, RY = 351; // doubles per cell of the two regions (largest stage: 13 x 27)
-  __shared__ double smem[8 * (RX + RY)];
-  __shared__ double tS[9], tD[9], tP[6], tL[3]; // 1D tables [q*3+a], [q*3+a], [q*2+a]; l at the Gauss points
-  if (threadIdx.x < 9) { tS[threadIdx.x] = prm.Su[threadIdx.x]; tD[threadIdx.x] = prm.Du[threadIdx.x]; }
-  if (threadIdx.x < 6) tP[threadIdx.x] = prm.Sp[threadIdx.x];
-  if (threadIdx.x < 3) tL[threadIdx.x] = prm.l1q[threadIdx.x];
+  constexpr int N1 = DEG + 1, N2 = N1 * N1, NN = N1 * N2; // nodes = quadrature points per direction, per cell: 27 or 64
+  constexpr int LANES = NN <= 32 ? 32 : 64, CELLS = 256 / LANES;
+  constexpr int NDGP = DEG * (DEG + 1) * (DEG + 2) / 6; // 4 or 10
+  constexpr int R = 13 * NN;                            // doubles per cell of each region (largest stage: 13 arrays of NN)
+  constexpr int XP = 3 * NN;                            // the cell's pressure values in the gather: X[XP ..] (nodes or functions)
+  constexpr bool HELD = COLUMNS_HELD<DEG>;
+  // the 1D tables behind the regions, in the same array: [q*N1+a], [q*N1+a], and the pressure's, N1 * DEG doubles either way: FE_Q
+  // [q*DEG+a], FE_DGP the Legendre functions at the Gauss points [degree*N1+q], degree 0 = 1
+  __shared__ double smem[CELLS * 2 * R + 2 * N2 + N1 * DEG];
+  double *const tS = smem + CELLS * 2 * R, *const tD = tS + N2, *const tP = tD + N2, *const tL = tP;
+  if (threadIdx.x < N2) { tS[threadIdx.x] = prm.Su[threadIdx.x]; tD[threadIdx.x] = prm.Du[threadIdx.x]; }
+  if (threadIdx.x < N1 * DEG) tP[threadIdx.x] = !PDG ? prm.Sp[threadIdx.x] : (threadIdx.x < N1 ? 1.0 : prm.lq[threadIdx.x / N1 - 1][threadIdx.x % N1]);
   __syncthreads();
-  const int slot = threadIdx.x >> 5, t32 = threadIdx.x & 31;
-  const bool lane27 = t32 < 27;
-  const int t = lane27 ? t32 : 0;
-  const int a = t % 3, b = (t / 3) % 3, c = t / 9;
-  const int a1 = a < 2 ? a : 1, b1 = b < 2 ? b : 1, c1 = c < 2 ? c : 1; // (pressure stages: clamped, unused where >= 2)
-  double *X = smem + slot * (RX + RY), *Y = X + RX;
+  const int slot = threadIdx.x / LANES, tl = threadIdx.x % LANES;
+  const bool lane_on = NN == LANES || tl < NN;
+  const int t = lane_on ? tl : 0;
+  const int a = t % N1, b = (t / N1) % N1, c = t / N2;
+  const int ap = a < DEG ? a : DEG - 1, bp = b < DEG ? b : DEG - 1, cp = c < DEG ? c : DEG - 1; // (pressure stages: clamped, unused where DEG)
+  double *X = smem + slot * (2 * R), *Y = X + R;
   // evaluation: row of this lane's quadrature index; integration: column of this lane's node index
-  double Sa[3], Da[3], Sb[3], Db[3], Sc[3], Dc[3], SaT[3], DaT[3], SbT[3], DbT[3], ScT[3], DcT[3];
-  double Pa[2], Pb[2], Pc[2], PaT[3], PbT[3], PcT[3];
-#pragma unroll
-  for (int n = 0; n < 3; ++n) {
-    Sa[n] = tS[a * 3 + n]; Da[n] = tD[a * 3 + n]; Sb[n] = tS[b * 3 + n]; Db[n] = tD[b * 3 + n];
-    Sc[n] = tS[c * 3 + n]; Dc[n] = tD[c * 3 + n];
-    SaT[n] = tS[n * 3 + a]; DaT[n] = tD[n * 3 + a]; SbT[n] = tS[n * 3 + b]; DbT[n] = tD[n * 3 + b];
-    ScT[n] = tS[n * 3 + c]; DcT[n] = tD[n * 3 + c];
-    PaT[n] = tP[n * 2 + a1]; PbT[n] = tP[n * 2 + b1]; PcT[n] = tP[n * 2 + c1];
-  }
-#pragma unroll
-  for (int n = 0; n < 2; ++n) { Pa[n] = tP[a * 2 + n]; Pb[n] = tP[b * 2 + n]; Pc[n] = tP[c * 2 + n]; }
+  const Coef<N1, 1, true> Sa(tS + N1 * a), Da(tD + N1 * a), Sb(tS + N1 * b), Db(tD + N1 * b), Sc(tS + N1 * c), Dc(tD + N1 * c);
+  const Coef<N1, N1, HELD> SaT(tS + a), DaT(tD + a), SbT(tS + b), DbT(tD + b), ScT(tS + c), DcT(tD + c);
+  const Coef<DEG, 1, HELD> Pa(tP + DEG * a), Pb(tP + DEG * b), Pc(tP + DEG * c);
+  const Coef<N1, DEG, HELD> PaT(tP + ap), PbT(tP + bp), PcT(tP + cp);
   const double wabc = prm.wq[a] * prm.wq[b] * prm.wq[c];
-  // this lane also carries a pressure DoF of the cell: FE_Q(1) node (a, b, c), or FE_DGP(1) function t
-  const bool pnode = PDG ? t32 < 4 : (lane27 && a < 2 && b < 2 && c < 2);
-  const int pslot = PDG ? t32 : a + 2 * b + 4 * c; // its slot in the cell's pressure values X[81 ..]
-  const double la = PDG ? tL[a] : 0.0, lb = PDG ? tL[b] : 0.0, lc = PDG ? tL[c] : 0.0; // DGP: the linear functions at this lane's quadrature point
+  // this lane also carries a pressure DoF of the cell: FE_Q node (a, b, c), or FE_DGP function tl
+  const bool pnode = PDG ? tl < NDGP : (lane_on && a < DEG && b < DEG && c < DEG);
+  const int pslot = PDG ? (tl < NDGP ? tl : NDGP - 1) : ap + DEG * bp + DEG * DEG * cp; // its slot in the cell's pressure values X[XP ..]
+  // FE_DGP: the functions at this lane's quadrature point, and the degrees of the function this lane integrates
+  auto legendre = [&](int degree, int q) { return degree == 0 ? 1.0 : tL[degree * N1 + q]; }; // (a constant degree 0 folds)
+  double phi[PDG ? NDGP : 1];
+  int ei = 0, ej = 0, ek = 0;
+  if constexpr (PDG) {
+    constexpr DgpDegrees<DEG> dgp = dgp_degrees<DEG>();
+#pragma unroll
+    for (int f = 0; f < NDGP; ++f) {
+      phi[f] = legendre(dgp.d[f][0], a) * legendre(dgp.d[f][1], b) * legendre(dgp.d[f][2], c);
+      if (tl == f) { ei = dgp.d[f][0]; ej = dgp.d[f][1]; ek = dgp.d[f][2]; }
+    }
+  } else {
+    phi[0] = 0.0;
+  }
   // the cells of one colour share no DoF: the eight colours run as eight launches, lowest first, and
   // scatter with plain loads and stores (no atomics, no zeroing of the destinations, deterministic)
   const int px = prm.colour & 1, py = (prm.colour >> 1) & 1, pz = prm.colour >> 2;
   const int ncxc = (prm.ncx - px + 1) / 2, ncyc = (prm.ncy - py + 1) / 2, nczc = (prm.ncz - pz + 1) / 2;
   const long long ncells = (long long)ncxc * ncyc * nczc;
 
-  // every half-wave walks through its own contiguous run of cells: cells sharing nodes are handled one
-  // after the other by the same lanes instead of at the same time by neighbouring ones (their atomics
-  // on the shared nodes would serialise in L2)
-  const long long nhalf = (long long)gridDim.x * 8, run = (ncells + nhalf - 1) / nhalf;
-  // STRIDE = 1: every half-wave walks its own contiguous run of cells; STRIDE = 8: the eight half-waves of the workgroup take eight
-  // consecutive cells of the workgroup's run at a time (their rows are 32 bytes apart: denser sectors per gather / scatter instruction)
-  const long long wg_first = (long long)blockIdx.x * 8 * run, wg_end = wg_first + 8 * run;
-  const int STRIDE = prm.interleave ? 8 : 1;
-  const long long first = prm.interleave ? wg_first + slot : ((long long)blockIdx.x * 8 + slot) * run;
+  // every cell slot (half-wave or wave) walks through its own contiguous run of cells: cells sharing nodes are handled one after the
+  // other by the same lanes instead of at the same time by neighbouring ones.  Degree 2 with prm.interleave: the eight half-waves of
+  // the workgroup take eight consecutive cells of the workgroup's run at a time (their rows are 32 bytes apart: denser sectors per
+  // gather / scatter instruction); degree 3 keeps the contiguous runs
+  const long long nslot = (long long)gridDim.x * CELLS, run = (ncells + nslot - 1) / nslot;
+  const long long wg_first = (long long)blockIdx.x * CELLS * run, wg_end = wg_first + CELLS * run;
+  const bool interleave = DEG == 2 && prm.interleave;
+  const int STRIDE = interleave ? CELLS : 1;
+  const long long first = interleave ? wg_first + slot : ((long long)blockIdx.x * CELLS + slot) * run;
   // the DoFs of a cell are fetched while the previous cell is being computed
   struct CellIds {
     int cx, cy, cz;
@@ -91,21 +157,21 @@ __global__ __launch_bounds__(256) void stokes_cell_kernel(const StokesParams prm
   };
   auto ids = [&](long long cell) {
     CellIds q;
-    q.ok = cell < ncells && (prm.interleave ? cell < wg_end : cell < first + run);
+    q.ok = cell < ncells && (interleave ? cell < wg_end : cell < first + run);
     const long long cc = q.ok ? cell : 0;
     q.cx = 2 * int(cc % ncxc) + px; q.cy = 2 * int((cc / ncxc) % ncyc) + py; q.cz = 2 * int(cc / ((long long)ncxc * ncyc)) + pz;
-    const int ix = 2 * q.cx + a, iy = 2 * q.cy + b, iz = 2 * q.cz + c;
+    const int ix = DEG * q.cx + a, iy = DEG * q.cy + b, iz = DEG * q.cz + c;
     q.con = constrained_u(prm, ix, iy, iz);
     q.gu = ix + (long long)prm.ndu[0] * (iy + (long long)prm.ndu[1] * iz);
-    q.gp = PDG ? (q.cx + (long long)prm.ncx * (q.cy + (long long)prm.ncy * q.cz)) * 4 + (t32 & 3)
-                   : (q.cx + a1) + (long long)prm.ndp[0] * ((q.cy + b1) + (long long)prm.ndp[1] * (q.cz + c1));
+    q.gp = PDG ? (q.cx + (long long)prm.ncx * (q.cy + (long long)prm.ncy * q.cz)) * NDGP + pslot
+               : ((DEG - 1) * q.cx + ap) + (long long)prm.ndp[0] * (((DEG - 1) * q.cy + bp) + (long long)prm.ndp[1] * ((DEG - 1) * q.cz + cp));
     return q;
   };
   double un[3] = {0, 0, 0}, pn = 0.0;
   const int nsrc = MULTI ? prm.nsrc : 1;
   auto fetch = [&](const CellIds &q, int s) { // read_dof_values: constrained velocity entries read as 0
     const double *us = prm.us[MULTI ? s : 0], *ps = prm.ps[MULTI ? s : 0];
-    if (q.ok && lane27 && !q.con) {
+    if (q.ok && lane_on && !q.con) {
 #pragma unroll
       for (int comp = 0; comp < 3; ++comp) un[comp] = us[comp * prm.Nu + q.gu];
     } else {
@@ -122,63 +188,70 @@ __global__ __launch_bounds__(256) void stokes_cell_kernel(const StokesParams prm
     const long long it = it2 / nsrc;
     const int src = int(it2 - it * nsrc);
     const CellIds cur = nxt;
-    const bool cell_ok = cur.ok;
     const int cx = cur.cx, cy = cur.cy, cz = cur.cz;
     const bool con = cur.con;
     const long long gu = cur.gu, gp = cur.gp;
-    const bool active = cell_ok && lane27;
+    const bool active = cur.ok && lane_on;
 
-    // ---- gather: X = u[3][27], p[8]
-    if (lane27) {
+    // ---- gather: X = u[3][NN], p[nodes or functions]
+    if (lane_on) {
 #pragma unroll
-      for (int comp = 0; comp < 3; ++comp) X[comp * 27 + t] = un[comp];
+      for (int comp = 0; comp < 3; ++comp) X[comp * NN + t] = un[comp];
     }
-    if (pnode) X[81 + pslot] = pn;
+    if (pnode) X[XP + pslot] = pn;
     nxt = ids(first + STRIDE * ((it2 + 1) / nsrc));
     fetch(nxt, int((it2 + 1) % nsrc));
     wave_fence();
-    double pdgv[4] = {0, 0, 0, 0};
-    if (PDG) {
+    double pval = 0.0;
+    if constexpr (PDG) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) pdgv[j] = X[81 + j];
+      for (int j = 0; j < NDGP; ++j) pval = fma(phi[j], X[XP + j], pval);
     }
 
     // ---- evaluate, x: (n_x, n_y, n_z) -> (q_x, n_y, n_z): values and x derivatives -> Y
 #pragma unroll
     for (int comp = 0; comp < 3; ++comp) {
-      const double *u = X + comp * 27 + 3 * b + 9 * c;
-      const double u0 = u[0], u1 = u[1], u2 = u[2];
-      Y[(comp * 2) * 27 + t] = fma(Sa[2], u2, fma(Sa[1], u1, Sa[0] * u0));
-      Y[(comp * 2 + 1) * 27 + t] = fma(Da[2], u2, fma(Da[1], u1, Da[0] * u0));
+      const double *up = X + comp * NN + N1 * b + N2 * c;
+      double u[N1];
+#pragma unroll
+      for (int n = 0; n < N1; ++n) u[n] = up[n];
+      Y[(comp * 2) * NN + t] = dot<N1>(Sa, u);
+      Y[(comp * 2 + 1) * NN + t] = dot<N1>(Da, u);
     }
-    Y[162 + t] = fma(Pa[1], X[81 + 1 + 2 * b1 + 4 * c1], Pa[0] * X[81 + 2 * b1 + 4 * c1]); // pressure (n_y, n_z < 2)
+    if constexpr (!PDG) Y[6 * NN + t] = dot<DEG>(Pa, X + XP + DEG * bp + DEG * DEG * cp); // pressure (n_y, n_z < DEG)
     wave_fence();
     // ---- y: -> (q_x, q_y, n_z): value, d/dx, d/dy -> X
 #pragma unroll
     for (int comp = 0; comp < 3; ++comp) {
-      const double *v = Y + (comp * 2) * 27 + a + 9 * c, *d = v + 27;
-      const double v0 = v[0], v1 = v[3], v2 = v[6], d0 = d[0], d1 = d[3], d2 = d[6];
-      X[(comp * 3) * 27 + t] = fma(Sb[2], v2, fma(Sb[1], v1, Sb[0] * v0));
-      X[(comp * 3 + 1) * 27 + t] = fma(Sb[2], d2, fma(Sb[1], d1, Sb[0] * d0));
-      X[(comp * 3 + 2) * 27 + t] = fma(Db[2], v2, fma(Db[1], v1, Db[0] * v0));
+      const double *vp = Y + (comp * 2) * NN + a + N2 * c, *dp = vp + NN;
+      double v[N1], d[N1];
+#pragma unroll
+      for (int n = 0; n < N1; ++n) v[n] = vp[N1 * n];
+#pragma unroll
+      for (int n = 0; n < N1; ++n) d[n] = dp[N1 * n];
+      X[(comp * 3) * NN + t] = dot<N1>(Sb, v);
+      X[(comp * 3 + 1) * NN + t] = dot<N1>(Sb, d);
+      X[(comp * 3 + 2) * NN + t] = dot<N1>(Db, v);
     }
-    X[243 + t] = fma(Pb[1], Y[162 + a + 3 + 9 * c1], Pb[0] * Y[162 + a + 9 * c1]);
+    if constexpr (!PDG) X[9 * NN + t] = dot<DEG>(Pb, Y + 6 * NN + a + N2 * cp, N1);
     wave_fence();
     // ---- z: -> quadrature point (a, b, c): value and reference gradient in registers
     double uval[3], gref[3][3];
 #pragma unroll
     for (int comp = 0; comp < 3; ++comp) {
-      const double *v = X + (comp * 3) * 27 + a + 3 * b, *dx = v + 27, *dy = v + 54;
-      const double v0 = v[0], v1 = v[9], v2 = v[18];
-      uval[comp] = fma(Sc[2], v2, fma(Sc[1], v1, Sc[0] * v0));
-      gref[comp][0] = fma(Sc[2], dx[18], fma(Sc[1], dx[9], Sc[0] * dx[0]));
-      gref[comp][1] = fma(Sc[2], dy[18], fma(Sc[1], dy[9], Sc[0] * dy[0]));
-      gref[comp][2] = fma(Dc[2], v2, fma(Dc[1], v1, Dc[0] * v0));
+      const double *vp = X + (comp * 3) * NN + a + N1 * b;
+      double v[N1];
+#pragma unroll
+      for (int n = 0; n < N1; ++n) v[n] = vp[N2 * n];
+      uval[comp] = dot<N1>(Sc, v);
+      gref[comp][0] = dot<N1>(Sc, vp + NN, N2);
+      gref[comp][1] = dot<N1>(Sc, vp + 2 * NN, N2);
+      gref[comp][2] = dot<N1>(Dc, v);
     }
-    double pval = fma(Pc[1], X[243 + a + 3 * b + 9], Pc[0] * X[243 + a + 3 * b]);
-    if (PDG) pval = pdgv[0] + la * pdgv[1] + lb * pdgv[2] + lc * pdgv[3];
+    if constexpr (!PDG) pval = dot<DEG>(Pc, X + 9 * NN + a + N1 * b, N2);
 
-    // ---- quadrature-point operation (operators.h:1547-1553, 1570; weights applied at scatter time) -> Y
+    // ---- quadrature-point operation (operators.h:1547-1553, 1570; weights applied at scatter time) -> Y:
+    // arrays comp * 3 + e: the flux in reference coordinates, 9: div u, 10 + comp: the mass term
     if (CART) {
       const double JxW = prm.detJ * wabc;
 #pragma unroll
@@ -186,44 +259,15 @@ __global__ __launch_bounds__(256) void stokes_cell_kernel(const StokesParams prm
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
           const double g = gref[comp][e] * prm.hinv[e];
-          Y[(comp * 3 + e) * 27 + t] = (prm.nu * g - (comp == e ? pval : 0.0)) * JxW * prm.hinv[e];
+          Y[(comp * 3 + e) * NN + t] = (prm.nu * g - (comp == e ? pval : 0.0)) * JxW * prm.hinv[e];
         }
-        Y[(10 + comp) * 27 + t] = uval[comp] * JxW;
+        Y[(10 + comp) * NN + t] = uval[comp] * JxW;
       }
-      Y[9 * 27 + t] = (gref[0][0] * prm.hinv[0] + gref[1][1] * prm.hinv[1] + gref[2][2] * prm.hinv[2]) * JxW;
+      Y[9 * NN + t] = (gref[0][0] * prm.hinv[0] + gref[1][1] * prm.hinv[1] + gref[2][2] * prm.hinv[2]) * JxW;
     } else {
-      const double x = prm.xq[a], y = prm.xq[b], z = prm.xq[c];
-      const double fx[2] = {1 - x, x}, fy[2] = {1 - y, y}, fz[2] = {1 - z, z}, dd[2] = {-1.0, 1.0};
-      double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-      const long long nvx = prm.ncx + 1, nvy = prm.ncy + 1;
-#pragma unroll
-      for (int k = 0; k < 2; ++k)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const double *V = prm.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-              const double Vd = V[d];
-              J[d][0] += Vd * dd[i] * fy[j] * fz[k];
-              J[d][1] += Vd * fx[i] * dd[j] * fz[k];
-              J[d][2] += Vd * fx[i] * fy[j] * dd[k];
-            }
-          }
-      const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-                         J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-      const double id = 1.0 / det;
-      double Ji[3][3];
-      Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
-      Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-      Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-      Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
-      Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-      Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-      Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
-      Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-      Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+      const double xi[3] = {prm.xq[a], prm.xq[b], prm.xq[c]};
+      double Ji[3][3], det;
+      cip_jacobian(prm, cx, cy, cz, xi, Ji, det); // (J^-1 and det J of the trilinear mapping at this lane's point)
       const double JxW = det * wabc;
       double divu = 0.0;
 #pragma unroll
@@ -236,63 +280,58 @@ __global__ __launch_bounds__(256) void stokes_cell_kernel(const StokesParams prm
           F[d] = (prm.nu * g - (comp == d ? pval : 0.0)) * JxW;
         }
 #pragma unroll
-        for (int e = 0; e < 3; ++e) Y[(comp * 3 + e) * 27 + t] = Ji[e][0] * F[0] + Ji[e][1] * F[1] + Ji[e][2] * F[2];
-        Y[(10 + comp) * 27 + t] = uval[comp] * JxW;
+        for (int e = 0; e < 3; ++e) Y[(comp * 3 + e) * NN + t] = Ji[e][0] * F[0] + Ji[e][1] * F[1] + Ji[e][2] * F[2];
+        Y[(10 + comp) * NN + t] = uval[comp] * JxW;
       }
-      Y[9 * 27 + t] = divu * JxW;
+      Y[9 * NN + t] = divu * JxW;
     }
     wave_fence();
-    double rPdg = 0.0;
-    if (PDG && t32 < 4) { // (q_j, div u): the cell's own four test functions, summed over the 27 quadrature points
-      const double *fd = Y + 9 * 27;
-      for (int q = 0; q < 27; ++q) {
-        const int qa = q % 3, qb = (q / 3) % 3, qc = q / 9;
-        const double l = t32 == 0 ? 1.0 : tL[t32 == 1 ? qa : (t32 == 2 ? qb : qc)];
-        rPdg = fma(l, fd[q], rPdg);
+    double rP = 0.0;
+    if constexpr (PDG) { // (q_j, div u): the cell's own test functions, each summed over the quadrature points in ascending order
+      if (tl < NDGP) {
+        const double *fd = Y + 9 * NN;
+        for (int qc = 0; qc < N1; ++qc)
+          for (int qb = 0; qb < N1; ++qb) {
+            const double lbc = tL[ej * N1 + qb] * tL[ek * N1 + qc]; // (the lane's degrees: the row of ones where 0, no select)
+#pragma unroll
+            for (int qa = 0; qa < N1; ++qa) rP = fma(tL[ei * N1 + qa] * lbc, fd[qa + N1 * qb + N2 * qc], rP);
+          }
       }
     }
 
-    // ---- integrate, z: quadrature point -> (q_x, q_y, n_z) -> X
+    // ---- integrate, z: quadrature point -> (q_x, q_y, n_z) -> X: per component flux_x, flux_y (values in z), flux_z (derivative), mass
 #pragma unroll
     for (int comp = 0; comp < 3; ++comp) {
-      const double *f0 = Y + (comp * 3) * 27 + a + 3 * b, *f1 = f0 + 27, *f2 = f0 + 54, *fm = Y + (10 + comp) * 27 + a + 3 * b;
-      X[(comp * 4) * 27 + t] = fma(ScT[2], f0[18], fma(ScT[1], f0[9], ScT[0] * f0[0]));
-      X[(comp * 4 + 1) * 27 + t] = fma(ScT[2], f1[18], fma(ScT[1], f1[9], ScT[0] * f1[0]));
-      X[(comp * 4 + 2) * 27 + t] = fma(DcT[2], f2[18], fma(DcT[1], f2[9], DcT[0] * f2[0]));
-      X[(comp * 4 + 3) * 27 + t] = fma(ScT[2], fm[18], fma(ScT[1], fm[9], ScT[0] * fm[0]));
+      const double *f0 = Y + (comp * 3) * NN + a + N1 * b, *fm = Y + (10 + comp) * NN + a + N1 * b;
+      X[(comp * 4) * NN + t] = dot<N1>(ScT, f0, N2);
+      X[(comp * 4 + 1) * NN + t] = dot<N1>(ScT, f0 + NN, N2);
+      X[(comp * 4 + 2) * NN + t] = dot<N1>(DcT, f0 + 2 * NN, N2);
+      X[(comp * 4 + 3) * NN + t] = dot<N1>(ScT, fm, N2);
     }
-    {
-      const double *fd = Y + 9 * 27 + a + 3 * b;
-      X[324 + t] = fma(PcT[2], fd[18], fma(PcT[1], fd[9], PcT[0] * fd[0]));
-    }
+    if constexpr (!PDG) X[12 * NN + t] = dot<N1>(PcT, Y + 9 * NN + a + N1 * b, N2);
     wave_fence();
     // ---- y: -> (q_x, n_y, n_z) -> Y
 #pragma unroll
     for (int comp = 0; comp < 3; ++comp) {
-      const double *g0 = X + (comp * 4) * 27 + a + 9 * c, *g1 = g0 + 27, *g2 = g0 + 54, *gm = g0 + 81;
-      Y[(comp * 3) * 27 + t] = fma(SbT[2], g0[6], fma(SbT[1], g0[3], SbT[0] * g0[0]));
-      Y[(comp * 3 + 1) * 27 + t] = fma(DbT[2], g1[6], fma(DbT[1], g1[3], DbT[0] * g1[0])) +
-                                   fma(SbT[2], g2[6], fma(SbT[1], g2[3], SbT[0] * g2[0]));
-      Y[(comp * 3 + 2) * 27 + t] = fma(SbT[2], gm[6], fma(SbT[1], gm[3], SbT[0] * gm[0]));
+      const double *g0 = X + (comp * 4) * NN + a + N2 * c;
+      Y[(comp * 3) * NN + t] = dot<N1>(SbT, g0, N1);
+      Y[(comp * 3 + 1) * NN + t] = dot<N1>(DbT, g0 + NN, N1) + dot<N1>(SbT, g0 + 2 * NN, N1);
+      Y[(comp * 3 + 2) * NN + t] = dot<N1>(SbT, g0 + 3 * NN, N1);
     }
-    {
-      const double *gd = X + 324 + a + 9 * c;
-      Y[243 + t] = fma(PbT[2], gd[6], fma(PbT[1], gd[3], PbT[0] * gd[0]));
-    }
+    if constexpr (!PDG) Y[9 * NN + t] = dot<N1>(PbT, X + 12 * NN + a + N2 * c, N1);
     wave_fence();
     // ---- x: -> node (a, b, c)
     double rK[3], rM[3];
 #pragma unroll
     for (int comp = 0; comp < 3; ++comp) {
-      const double *h0 = Y + (comp * 3) * 27 + 3 * b + 9 * c, *h1 = h0 + 27, *hm = h0 + 54;
-      rK[comp] = fma(DaT[2], h0[2], fma(DaT[1], h0[1], DaT[0] * h0[0])) + fma(SaT[2], h1[2], fma(SaT[1], h1[1], SaT[0] * h1[0]));
-      rM[comp] = fma(SaT[2], hm[2], fma(SaT[1], hm[1], SaT[0] * hm[0]));
+      const double *h0 = Y + (comp * 3) * NN + N1 * b + N2 * c;
+      rK[comp] = dot<N1>(DaT, h0) + dot<N1>(SaT, h0 + NN);
+      rM[comp] = dot<N1>(SaT, h0 + 2 * NN);
     }
-    const double *hd = Y + 243 + 3 * b + 9 * c;
-    const double rP = PDG ? rPdg : fma(PaT[2], hd[2], fma(PaT[1], hd[1], PaT[0] * hd[0]));
+    if constexpr (!PDG) rP = dot<N1>(PaT, Y + 9 * NN + N1 * b + N2 * c);
 
-    // ---- distribute_local_to_global: constrained velocity rows stay 0.  A DoF on a face shared with a
-    // neighbouring cell is first touched by the cell whose colour bits are 0 in all shared directions.
+    // ---- distribute_local_to_global: constrained velocity rows stay 0.  A DoF on a face shared with a neighbouring cell is first
+    // touched by the cell whose colour bits are 0 in all shared directions (last node index: DEG velocity, DEG - 1 FE_Q pressure).
     if constexpr (MULTI) {
 #pragma unroll
       for (int o = 0; o < MAXSRC; ++o)
@@ -304,12 +343,12 @@ __global__ __launch_bounds__(256) void stokes_cell_kernel(const StokesParams prm
         }
     }
     if (active && src == nsrc - 1) {
-      const bool fu = !((a == 0 && cx > 0 && px) || (a == 2 && cx < prm.ncx - 1 && px) ||
-                        (b == 0 && cy > 0 && py) || (b == 2 && cy < prm.ncy - 1 && py) ||
-                        (c == 0 && cz > 0 && pz) || (c == 2 && cz < prm.ncz - 1 && pz));
-      const bool fp = PDG || !((a == 0 && cx > 0 && px) || (a == 1 && cx < prm.ncx - 1 && px) ||
-                                    (b == 0 && cy > 0 && py) || (b == 1 && cy < prm.ncy - 1 && py) ||
-                                    (c == 0 && cz > 0 && pz) || (c == 1 && cz < prm.ncz - 1 && pz));
+      const bool fu = !((a == 0 && cx > 0 && px) || (a == DEG && cx < prm.ncx - 1 && px) ||
+                        (b == 0 && cy > 0 && py) || (b == DEG && cy < prm.ncy - 1 && py) ||
+                        (c == 0 && cz > 0 && pz) || (c == DEG && cz < prm.ncz - 1 && pz));
+      const bool fp = PDG || !((a == 0 && cx > 0 && px) || (a == DEG - 1 && cx < prm.ncx - 1 && px) ||
+                                    (b == 0 && cy > 0 && py) || (b == DEG - 1 && cy < prm.ncy - 1 && py) ||
+                                    (c == 0 && cz > 0 && pz) || (c == DEG - 1 && cz < prm.ncz - 1 && pz));
       // what destination pair o receives: the sums over the sources, or the one source's results with the pair's weights
       auto valU = [&](int o, int comp) {
         if constexpr (MULTI) return accU[o][comp];
@@ -353,36 +392,59 @@ __global__ __launch_bounds__(256) void stokes_cell_kernel(const StokesParams prm
   }
 }
 
+template <int DEG> const void *cell_kernel(int which) // which = 4 PDG + 2 MULTI + CART
+{
+  const void *const kerns[8] = {
+    (const void *)stokes_cell_kernel<DEG, false, false, false>, (const void *)stokes_cell_kernel<DEG, true, false, false>,
+    (const void *)stokes_cell_kernel<DEG, false, true, false>,  (const void *)stokes_cell_kernel<DEG, true, true, false>,
+    (const void *)stokes_cell_kernel<DEG, false, false, true>,  (const void *)stokes_cell_kernel<DEG, true, false, true>,
+    (const void *)stokes_cell_kernel<DEG, false, true, true>,   (const void *)stokes_cell_kernel<DEG, true, true, true>};
+  return kerns[which];
+}
+
 } // namespace
 
-int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st)
+int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &set, hipStream_t st)
 {
-  const int which = (prm.pdg ? 4 : 0) + (prm.nsrc > 1 ? 2 : 0) + (prm.cart ? 1 : 0);
-  if (prm.nsrc < 1 || prm.nsrc > MAXSRC || prm.nout > (prm.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiation's bounds)
+  if (set.nsrc < 1 || set.nsrc > MAXSRC || set.nout > (set.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiation's bounds)
+  // degree 2: `set` is the kernel's argument; degree 3: the context's description with the sources, destinations and weights of `set`
+  const bool deg3 = c->degree == 3;
+  StokesParamsT<3> wide;
+  if (deg3) {
+    wide = c->base3;
+    stokes_copy_set(wide, set);
+  }
+  const int pdg = deg3 ? wide.pdg : set.pdg, cart = deg3 ? wide.cart : set.cart;
+  int &launch_colour = deg3 ? wide.colour : set.colour;
+  void *args[] = {deg3 ? (void *)&wide : (void *)&set};
+  const int which = (pdg ? 4 : 0) + (set.nsrc > 1 ? 2 : 0) + (cart ? 1 : 0), cells = deg3 ? 4 : 8; // (cells per workgroup)
+  const void *kern = deg3 ? cell_kernel<3>(which) : cell_kernel<2>(which);
+  // persistent workgroups: exactly as many as stay resident, asked once per instantiation, not on the launch path (measured at degree
+  // 2 on 64^3 cells, cG(1): 2 per CU 0.41 ms, 3: 0.50, 4: 0.43, 8: 0.45, one workgroup per 8 cells: 0.52 - long runs keep the prefetch
+  // of the next cell's DoFs going and leave no partial round)
+  static int resident_of[2][8] = {};
+  int &resident = resident_of[deg3][which];
+  if (resident < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, 256, 0) != hipSuccess || resident < 1)) resident = 2;
+  static const int grid_env = [] {
+    const char *e = getenv("STFEM_STOKES_GRID"); // workgroups per CU of a colour launch at degree 2 (experiments)
+    return e ? std::max(1, atoi(e)) : 0;
+  }();
+  // STFEM_STOKES_Q3_WORKGROUPS=<n>, read at every launch: at most n workgroups per colour launch (tests: several cells per wave or
+  // half-wave on a small mesh)
+  long long cap = 0;
+  if (const char *e = getenv("STFEM_STOKES_Q3_WORKGROUPS")) cap = std::max(1ll, atoll(e));
   stfem_launch_begin();
   for (int colour = 0; colour < 8; ++colour) { // ascending: see store_u / store_p
     const long long n = (long long)((c->nc[0] - (colour & 1) + 1) / 2) * ((c->nc[1] - ((colour >> 1) & 1) + 1) / 2) *
                         ((c->nc[2] - (colour >> 2) + 1) / 2);
     if (n == 0) continue;
-    prm.colour = colour;
-    // persistent workgroups: exactly as many as stay resident (measured on 64^3 cells, cG(1): 2 per CU 0.41 ms, 3: 0.50, 4: 0.43,
-    // 8: 0.45, one workgroup per 8 cells: 0.52 - long runs keep the prefetch of the next cell's DoFs going and leave no partial round)
-    static const int grid_env = [] {
-      const char *e = getenv("STFEM_STOKES_GRID"); // workgroups per CU of a colour launch (experiments)
-      return e ? std::max(1, atoi(e)) : 0;
-    }();
-    const void *kerns[8] = {(const void *)stokes_cell_kernel<false, false, false>, (const void *)stokes_cell_kernel<true, false, false>,
-                            (const void *)stokes_cell_kernel<false, true, false>,  (const void *)stokes_cell_kernel<true, true, false>,
-                            (const void *)stokes_cell_kernel<false, false, true>,  (const void *)stokes_cell_kernel<true, false, true>,
-                            (const void *)stokes_cell_kernel<false, true, true>,   (const void *)stokes_cell_kernel<true, true, true>};
-    const void *kern = kerns[which];
-    // resident workgroups per CU of the instantiations, asked once (not on the launch path)
-    static int resident_of[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int &resident = resident_of[which];
-    if (resident < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, 256, 0) != hipSuccess || resident < 1)) resident = 2;
-    const unsigned grid = (unsigned)std::min<long long>((n + 7) / 8, (long long)c->n_cu * (grid_env ? grid_env : resident));
-    void *args[] = {(void *)&prm};
-    (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
+    launch_colour = colour;
+    long long grid = std::min<long long>((n + cells - 1) / cells, (long long)c->n_cu * (grid_env && !deg3 ? grid_env : resident));
+    if (cap) grid = std::min(grid, cap);
+    (void)hipLaunchKernel(kern, dim3((unsigned)grid), dim3(256), args, 0, st);
+    c->cell_launched = true;
+    c->cell_plan[0] = (int)grid;
+    c->cell_plan[1] = (int)((n + grid * cells - 1) / (grid * cells));
   }
   return stfem_launch_end("stokes_cell_kernel");
 }

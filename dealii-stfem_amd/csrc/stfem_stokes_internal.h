@@ -12,10 +12,12 @@ constexpr int MAXOUT = 8; // destination pairs of a launch with one source
 constexpr int MAXSRC = 4; // sources, and destination pairs, of a launch with several sources
 
 // One set of launches:  out_u[o] (=, +=) sum_s wKu[s][o] (nu K u_s - B^T p_s) + wM[s][o] M u_s,  out_p[o] (=, +=) sum_s wKp[s][o] B u_s
-struct StokesParams {
+// DEG: the velocity degree, FE_Q(DEG)^3 x FE_Q(DEG - 1) / FE_DGP(DEG - 1) with QGauss(DEG + 1).  StokesParams, the description of
+// degree 2, is what every kernel of the operator outside the cell kernel takes.
+template <int DEG> struct StokesParamsT {
   const double *vertices; // device, (nc+1)^3 * 3
   int ncx, ncy, ncz;
-  int ndu[3], ndp[3];
+  int ndu[3], ndp[3];     // DEG nc + 1, (DEG - 1) nc + 1
   long long Nu, Np;
   int dmask;
   double nu;
@@ -30,41 +32,36 @@ struct StokesParams {
   // (with the destination index first that walk needed a second scaled index: more scalar registers spilled in the cell kernel)
   double wKu[MAXSRC][MAXOUT], wKp[MAXSRC][MAXOUT], wM[MAXSRC][MAXOUT];
   int store_u[MAXOUT], store_p[MAXOUT]; // 1: the first cell to touch a DoF (lowest colour) stores, the others add; 0: all add
-  double Su[9], Du[9], Sp[6]; // [q*3+a], [q*3+a], [q*2+a]
-  double xq[3], wq[3];
-  int interleave;             // cell -> half-wave assignment (see the cell kernel)
+  // FE_Q(DEG) and FE_Q(DEG - 1) on Gauss-Lobatto nodes at the Gauss points: [q*(DEG+1)+a], [q*(DEG+1)+a], [q*DEG+a]
+  double Su[(DEG + 1) * (DEG + 1)], Du[(DEG + 1) * (DEG + 1)], Sp[(DEG + 1) * DEG];
+  double xq[DEG + 1], wq[DEG + 1];
+  int interleave;             // cell -> half-wave assignment at degree 2 (see the cell kernel)
   int colour;                 // this launch handles the cells with (cx & 1) + 2 (cy & 1) + 4 (cz & 1) == colour
   int cart;                   // axis-aligned uniform cells: constant diagonal Jacobian
   double hinv[3], detJ;       // 1 / h_d, hx hy hz
-  // pressure space: 0 = FE_Q(1) on the vertex lattice, 1 = FE_DGP(1), the reference's dGPressure (tests/tp_03stokes.cc:83-86):
-  // four DoFs per cell, deal.II's basis 1, l(xi), l(eta), l(zeta) with l(x) = sqrt 3 (2 x - 1), p[cell * 4 + j]
+  // pressure space: 0 = FE_Q(DEG - 1) on its node lattice, 1 = FE_DGP(DEG - 1), the reference's dGPressure (tests/tp_03stokes.cc:83-86):
+  // per cell the products l_i(xi) l_j(eta) l_k(zeta), i + j + k <= DEG - 1, i fastest, of the orthonormal Legendre functions
+  // l_1(x) = sqrt 3 (2 x - 1), l_2(x) = sqrt 5 (6 x^2 - 6 x + 1); degree 2: deal.II's basis 1, l(xi), l(eta), l(zeta), p[cell * 4 + j]
   int pdg;
-  double l1q[3];              // l at the three Gauss points
+  double lq[DEG - 1][DEG + 1]; // l_1 (and l_2) at the Gauss points
 };
-
-// The cell kernel of the degree-3 pair FE_Q(3)^3 x FE_Q(2) / FE_DGP(2), QGauss(4) (stfem_stokes_cell_q3.hip): a description of its
-// own, so that StokesParams stays what it is.  The sources, destinations, weights and store flags mean what they mean there and are
-// copied from the StokesParams of the same set.
-struct StokesQ3Params {
-  const double *vertices; // device, (nc+1)^3 * 3
-  int ncx, ncy, ncz;
-  int ndu[3], ndp[3];     // 3 nc + 1, 2 nc + 1
-  long long Nu, Np;
-  int dmask;
-  double nu;
-  int nsrc;
-  const double *us[MAXSRC], *ps[MAXSRC];
-  int nout;
-  double *out_u[MAXOUT], *out_p[MAXOUT];
-  double wKu[MAXSRC][MAXOUT], wKp[MAXSRC][MAXOUT], wM[MAXSRC][MAXOUT];
-  int store_u[MAXOUT], store_p[MAXOUT];
-  double Su[16], Du[16], Sp[12]; // [q*4+a], [q*4+a], [q*3+a]: FE_Q(3) and FE_Q(2) on Gauss-Lobatto nodes at the four Gauss points
-  double xq[4], wq[4];
-  int colour;
-  double hinv[3], detJ;
-  // FE_DGP(2): the two non-constant orthonormal Legendre functions sqrt 3 (2 x - 1), sqrt 5 (6 x^2 - 6 x + 1) at the Gauss points
-  double l1q[4], l2q[4];
-};
+using StokesParams = StokesParamsT<2>;
+// The set part of a description - sources, destinations, weights, store flags - from one degree's description into another's
+template <int TO, int FROM> inline void stokes_copy_set(StokesParamsT<TO> &to, const StokesParamsT<FROM> &from)
+{
+  to.nsrc = from.nsrc; to.nout = from.nout;
+  for (int s = 0; s < MAXSRC; ++s) {
+    to.us[s] = s < from.nsrc ? from.us[s] : nullptr;
+    to.ps[s] = s < from.nsrc ? from.ps[s] : nullptr;
+    for (int o = 0; o < MAXOUT; ++o) { to.wKu[s][o] = from.wKu[s][o]; to.wKp[s][o] = from.wKp[s][o]; to.wM[s][o] = from.wM[s][o]; }
+  }
+  for (int o = 0; o < MAXOUT; ++o) {
+    to.out_u[o] = o < from.nout ? from.out_u[o] : nullptr;
+    to.out_p[o] = o < from.nout ? from.out_p[o] : nullptr;
+    to.store_u[o] = from.store_u[o]; to.store_p[o] = from.store_p[o];
+  }
+}
+static_assert(sizeof(StokesParams) == 1440, "the degree-2 description is the argument of every Stokes kernel: its layout stays");
 
 // The coupling kernels of the Kronecker path (stfem_stokes_coupling.hip)
 struct CouplingParams {
@@ -162,14 +159,15 @@ struct stfem_stokes_ctx {
   double nu = 1.0;
   double *d_vertices = nullptr;
   int n_cu = 256;
-  StokesParams base;
   int pspace = 0; // 0 = FE_Q(degree - 1), 1 = FE_DGP(degree - 1)
-  // velocity degree: 2, or 3 (stfem_stokes_create_space): the linear cell operator alone, through the kernel of
-  // stfem_stokes_cell_q3.hip described by q3 (geometry and tables; `base` then carries sizes and geometry, no tables)
+  // velocity degree: 2, or 3 (stfem_stokes_create_space): the linear cell operator alone.  Geometry and tables are in the description
+  // of that degree, base or base3 (stokes_create_degree fills the one); the other stays zero
   int degree = 2;
-  StokesQ3Params q3;
-  bool q3_launched = false;
-  int q3_plan[2] = {0, 0}; // workgroups and longest run of cells per wave of the last colour launch (stfem_stokes_last_cell_plan)
+  StokesParams base;
+  StokesParamsT<3> base3;
+  bool cart() const { return (degree == 3 ? base3.cart : base.cart) != 0; }
+  bool cell_launched = false;
+  int cell_plan[2] = {0, 0}; // workgroups and longest run of cells per cell slot of the last colour launch (stfem_stokes_last_cell_plan)
   // axis-aligned uniform meshes: the scalar FE_Q(2) context whose pencil sweep applies nu K + wM M to the velocity components,
   // and the 1D tables of the coupling kernels
   stfem_ctx *scalar = nullptr;
@@ -280,10 +278,9 @@ __device__ __forceinline__ void cip_face_gradient(const double *tS, const double
 
 // FE_Q(2) values / derivatives at the end points 0 and 1, [s * 3 + a] (stfem_stokes_cip.hip)
 void stokes_cip_end_tables(double Eu[6], double EDu[6]);
-// The eight colour launches of the cell kernel (general meshes; stfem_stokes_cell.hip)
+// The eight colour launches of the cell kernel (stfem_stokes_cell.hip), at the context's degree: general meshes at degree 2, boxes
+// included at degree 3, where `prm` gives the sources, destinations and weights alone
 int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st);
-// The same for a context of velocity degree 3, boxes included (stfem_stokes_cell_q3.hip)
-int stokes_cell_q3_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t st);
 // The cell matrices of a degree-3 context for the per-cell Vanka blocks (stfem_stokes_vanka_cell_q3.hip): `count` cells from cell0,
 // Ac[cell][nl][nl] with nl = 192 + 27 (FE_Q(2)) or 10 (FE_DGP(2)), Mc[cell][64][64] (nullptr: not wanted)
 int stokes_cell_matrices_q3_launch(const stfem_stokes_ctx *c, double *Ac, double *Mc, long long cell0, unsigned count);

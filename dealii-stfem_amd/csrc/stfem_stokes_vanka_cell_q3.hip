@@ -26,7 +26,7 @@ struct StokesCellMatQ3Params {
   int ncx, ncy, ncz;
   long long cell0;        // first cell of the window
   double nu;
-  double Su[16], Du[16], Sp[12]; // StokesQ3Params: [q*4+a], [q*4+a], [q*3+a]
+  double Su[16], Du[16], Sp[12]; // StokesParamsT<3>: [q*4+a], [q*4+a], [q*3+a]
   double xq[4], wq[4], l1q[4], l2q[4];
 };
 
@@ -121,7 +121,7 @@ int stokes_cell_matrices_q3_launch(const stfem_stokes_ctx *c, double *Ac, double
   const long long ncells = (long long)c->nc[0] * c->nc[1] * c->nc[2];
   if (cell0 < 0 || cell0 + (long long)count > ncells)
     return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stokes_cell_matrices_q3_kernel: cells [%lld, %lld) of %lld", cell0, cell0 + (long long)count, ncells);
-  const StokesQ3Params &q = c->q3;
+  const StokesParamsT<3> &q = c->base3;
   StokesCellMatQ3Params p;
   std::memset(&p, 0, sizeof(p));
   p.vertices = c->d_vertices;
@@ -131,7 +131,7 @@ int stokes_cell_matrices_q3_launch(const stfem_stokes_ctx *c, double *Ac, double
   p.nu = c->nu;
   for (int i = 0; i < 16; ++i) { p.Su[i] = q.Su[i]; p.Du[i] = q.Du[i]; }
   for (int i = 0; i < 12; ++i) p.Sp[i] = q.Sp[i];
-  for (int i = 0; i < 4; ++i) { p.xq[i] = q.xq[i]; p.wq[i] = q.wq[i]; p.l1q[i] = q.l1q[i]; p.l2q[i] = q.l2q[i]; }
+  for (int i = 0; i < 4; ++i) { p.xq[i] = q.xq[i]; p.wq[i] = q.wq[i]; p.l1q[i] = q.lq[0][i]; p.l2q[i] = q.lq[1][i]; }
   const void *k = c->pspace ? reinterpret_cast<const void *>(&stokes_cell_matrices_q3_kernel<true>)
                             : reinterpret_cast<const void *>(&stokes_cell_matrices_q3_kernel<false>);
   return vk_launch(k, dim3(count), &p, nullptr, "stokes_cell_matrices_q3_kernel");

@@ -418,7 +418,7 @@ int stfem_stokes_create(const stfem_mesh_desc *mesh, int velocity_degree, double
  * DoFs per cell numbered cell by cell (p[4 cell + j], cells lexicographic) */
 int stfem_stokes_create_ex(const stfem_mesh_desc *mesh, int velocity_degree, int pressure_space, double viscosity, stfem_stokes_ctx **out);
 /* The constructor by descriptor, stfem_stokes_create_space (velocity degree 2 or 3), its descriptor and the diagnostic of the
- * degree-3 cell kernel: the companion header, part of this boundary and included here so that a caller of stfem.h has them. */
+ * cell kernel: the companion header, part of this boundary and included here so that a caller of stfem.h has them. */
 #include "stfem_stokes_space.h"
 void stfem_stokes_destroy(stfem_stokes_ctx *ctx);
 int64_t stfem_stokes_n_velocity_dofs(const stfem_stokes_ctx *ctx); /* per component */
@@ -608,7 +608,7 @@ int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *ctx, const double *g_at_face_poin
 /* diagnostics: {tiles, workgroups} as stfem_last_sweep_plan of the last velocity sweep (pencil sweep of the scalar FE_Q(2) context:
  * box meshes), and whether that sweep of the last vmult added the pressure gradient itself (1) or the gradient kernel ran (0) */
 int stfem_stokes_last_sweep_plan(const stfem_stokes_ctx *ctx, int32_t out[3]);
-/* (the diagnostic of the degree-3 cell kernel, stfem_stokes_last_cell_plan: stfem_stokes_space.h) */
+/* (the diagnostic of the cell kernel, stfem_stokes_last_cell_plan: stfem_stokes_space.h) */
 
 /* The pressure space by itself - what the solver around the operator needs of it (tests/tp_03stokes.cc:404-425, 1047-1062;
  * include/exact_solution.h:503-649; the pressure transfer of the Stokes multigrid levels, include/stmg.h:557-600).

@@ -34,9 +34,10 @@ typedef struct {
 } stfem_stokes_space_desc;
 int stfem_stokes_create_space(const stfem_mesh_desc *mesh, const stfem_stokes_space_desc *space, stfem_stokes_ctx **out);
 
-/* Diagnostic of the degree-3 cell kernel: out[0] = workgroups of the last colour launch, out[1] = the longest run of cells one wave
- * walked in it.  STFEM_STOKES_Q3_WORKGROUPS=<n> in the environment, read at every launch, caps the workgroups of a colour launch
- * (tests: several cells per wave on a small mesh).  STFEM_ERR_UNSUPPORTED on a context that has never launched that kernel. */
+/* Diagnostic of the cell kernel, at either degree: out[0] = workgroups of the last colour launch, out[1] = the longest run of cells
+ * one wave (degree 3) or half-wave (degree 2) walked in it.  STFEM_STOKES_Q3_WORKGROUPS=<n> in the environment, read at every launch,
+ * caps the workgroups of the colour launches of the cell kernel at either degree (tests: several cells per wave on a small mesh).
+ * STFEM_ERR_UNSUPPORTED on a context that has never launched that kernel (a degree-2 box runs the Kronecker path instead). */
 int stfem_stokes_last_cell_plan(const stfem_stokes_ctx *ctx, int32_t out[2]);
 
 #endif /* STFEM_STOKES_SPACE_H */

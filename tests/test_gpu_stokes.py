@@ -1,6 +1,7 @@
 """GPU parity of the Stokes two-field operator through the C-ABI
 (stfem_stokes_*): against the dense numpy fixtures and against the CPU oracle on a larger seeded
 mesh.  Tolerance rel-L2 <= 1e-12 (fp64)."""
+import functools
 import importlib
 import os
 
@@ -259,6 +260,106 @@ def test_stokes_vmult_slice_add_many_destinations(npairs, cart, stfem):
         assert (ju, jp) == (2 * it, 2 * it + 1)
         assert rel(dst[ju].download(), init[ju] + Gamma[ju] * ku.reshape(-1) + Zeta[ju] * mu.reshape(-1)) < TOL
         assert rel(dst[jp].download(), init[jp] + Gamma[jp] * kp) < TOL
+
+
+# ---- the cell kernel's walk over several cells per half-wave, on small meshes (STFEM_STOKES_Q3_WORKGROUPS caps the workgroups of a
+# colour launch at either degree; last_cell_plan reports the last colour launch)
+SEVERAL_CELLS = {"perturbed": ((6, 6, 6), 0.12, 9), "box": ((5, 4, 3), 0.0, 0)}  # cells, distortion, seed
+SEVERAL_MASK, SEVERAL_NU = 0b011110, 0.9
+
+
+@functools.lru_cache(maxsize=None)
+def _several_cells_reference(mesh, dgp):
+    """cG(2) x 1 step, two sources and four destination blocks, and the oracle's result: computed once per mesh and pressure space"""
+    from oracle import oracle
+    stfem = importlib.import_module("dealii-stfem_amd")
+    nc, distort, seed = SEVERAL_CELLS[mesh]
+    verts = stfem.mesh_vertices(nc, distort=distort, seed=seed) if distort else stfem.mesh_vertices(nc)
+    orc = oracle.StokesOracle(nc, verts, SEVERAL_MASK, SEVERAL_NU, dg_pressure=dgp)
+    Alpha, Beta, _, _ = stfem.get_fe_time_weights_stokes(stfem.CGP, 2, 1.0 / 16, 1)
+    rng = np.random.default_rng(4)
+    blocks, var = [None] * 4, [0, 0, 1, 1]
+    for d in range(2):
+        blocks[stfem.stokes_block_index(2, 0, 0, d)] = rng.uniform(-1, 1, 3 * orc.n_u)
+        blocks[stfem.stokes_block_index(2, 0, 1, d)] = rng.uniform(-1, 1, orc.n_p)
+    want = orc.st_vmult(Alpha, Beta, 1, 2, blocks, True)
+    for x in blocks + list(want):
+        x.setflags(write=False)
+    return verts, Alpha, Beta, blocks, var, want
+
+
+def _several_cells_run(op, Alpha, Beta, blocks, var):
+    src = [op.initialize_dof_vector(v, b) for v, b in zip(var, blocks)]
+    dst = [op.initialize_dof_vector(v, np.full(b.size, 11.0)) for v, b in zip(var, blocks)]  # st_vmult overwrites
+    op.st_vmult(Alpha, Beta, 1, 2, dst, src)
+    return [d.download() for d in dst]
+
+
+@pytest.mark.parametrize("interleave", ["1", "0"])
+@pytest.mark.parametrize("dgp", [False, True], ids=["FE_Q1", "FE_DGP1"])
+def test_cell_kernel_several_cells_per_half_wave(dgp, interleave, stfem, monkeypatch):
+    """6^3 perturbed cells, both cell -> half-wave assignments.  The launcher gives a colour of n cells min(ceil(n / 8), resident)
+    workgroups of 8 half-waves and every half-wave a run of ceil(n / (8 workgroups)) cells.  Every colour has 3^3 = 27 cells.
+    Uncapped: ceil(27 / 8) = 4 workgroups, runs of ceil(27 / 32) = 1 cell - the plan of the last launch (colour 7) is (4, 1), where the
+    degree-3 test has (7, 1).  Capped at one workgroup: 27 cells on 8 half-waves, runs of ceil(27 / 8) = 4 - the plan is (1, 4).  The
+    capped and a repeated run equal the uncapped one bit for bit (the cell -> half-wave assignment changes no sum), and it is the oracle's."""
+    monkeypatch.delenv("STFEM_STOKES_Q3_WORKGROUPS", raising=False)
+    monkeypatch.setenv("STFEM_STOKES_INTERLEAVE", interleave)  # (read when the context is created)
+    verts, Alpha, Beta, blocks, var, want = _several_cells_reference("perturbed", dgp)
+    op = stfem.StokesMatrixFreeOperator(SEVERAL_CELLS["perturbed"][0], vertices=verts, dirichlet_mask=SEVERAL_MASK, viscosity=SEVERAL_NU,
+                                        dg_pressure=dgp)
+    with pytest.raises(stfem.StfemError) as e:
+        op.last_cell_plan()  # a context that has not launched the kernel
+    assert e.value.status == -2
+    free = _several_cells_run(op, Alpha, Beta, blocks, var)
+    plan = op.last_cell_plan()
+    assert plan == (4, 1), plan
+    again = _several_cells_run(op, Alpha, Beta, blocks, var)
+    monkeypatch.setenv("STFEM_STOKES_Q3_WORKGROUPS", "1")
+    capped = _several_cells_run(op, Alpha, Beta, blocks, var)
+    plan = op.last_cell_plan()
+    assert plan == (1, 4), plan
+    for j in range(4):
+        assert np.array_equal(again[j], free[j]), j
+        assert np.array_equal(capped[j], free[j]), j
+        print(dgp, interleave, j, "%.2e" % rel(free[j], want[j]))
+        assert np.linalg.norm(want[j]) > 0 and rel(free[j], want[j]) < TOL, j
+
+
+@pytest.mark.parametrize("interleave", ["1", "0"])
+@pytest.mark.parametrize("dgp", [False, True], ids=["FE_Q1", "FE_DGP1"])
+def test_cell_kernel_several_cells_per_half_wave_box(dgp, interleave, stfem, monkeypatch):
+    """The same on a box of 5 x 4 x 3 cells without vertices, STFEM_STOKES_CELL=1: the constant-Jacobian instantiations.  The colours
+    have 12, 8, 12, 8, 6, 4, 6, 4 cells: capped at one workgroup, colours 0 and 2 give every half-wave a run of ceil(12 / 8) = 2 cells,
+    four of those 16 places beyond the colour's end, and the colours below 8 cells leave half-waves idle.  The last
+    launch (colour 7, 4 cells) has one workgroup and runs of one cell either way, so its plan cannot show whether the cap acts on these
+    instantiations: a 6^3 box does, as the perturbed 6^3 mesh above ((4, 1) uncapped, (1, 4) capped), bit for bit against its own
+    uncapped run (no oracle: the 5 x 4 x 3 mesh has it)."""
+    monkeypatch.delenv("STFEM_STOKES_Q3_WORKGROUPS", raising=False)
+    monkeypatch.setenv("STFEM_STOKES_INTERLEAVE", interleave)
+    monkeypatch.setenv("STFEM_STOKES_CELL", "1")  # (read when the context is created: no Kronecker path)
+    _, Alpha, Beta, blocks, var, want = _several_cells_reference("box", dgp)
+    op = stfem.StokesMatrixFreeOperator(SEVERAL_CELLS["box"][0], dirichlet_mask=SEVERAL_MASK, viscosity=SEVERAL_NU, dg_pressure=dgp)
+    free = _several_cells_run(op, Alpha, Beta, blocks, var)
+    assert op.last_cell_plan() == (1, 1)  # (the cell kernel ran: the Kronecker path leaves no plan)
+    monkeypatch.setenv("STFEM_STOKES_Q3_WORKGROUPS", "1")
+    capped = _several_cells_run(op, Alpha, Beta, blocks, var)
+    assert op.last_cell_plan() == (1, 1)
+    for j in range(4):
+        assert np.array_equal(capped[j], free[j]), j
+        print(dgp, interleave, j, "%.2e" % rel(free[j], want[j]))
+        assert np.linalg.norm(want[j]) > 0 and rel(free[j], want[j]) < TOL, j
+    monkeypatch.delenv("STFEM_STOKES_Q3_WORKGROUPS")
+    cube = stfem.StokesMatrixFreeOperator((6, 6, 6), dirichlet_mask=SEVERAL_MASK, viscosity=SEVERAL_NU, dg_pressure=dgp)
+    rng = np.random.default_rng(6)
+    cube_blocks = [rng.uniform(-1, 1, 3 * cube.n_velocity if v == 0 else cube.n_pressure) for v in var]
+    free = _several_cells_run(cube, Alpha, Beta, cube_blocks, var)
+    assert cube.last_cell_plan() == (4, 1)
+    monkeypatch.setenv("STFEM_STOKES_Q3_WORKGROUPS", "1")
+    capped = _several_cells_run(cube, Alpha, Beta, cube_blocks, var)
+    assert cube.last_cell_plan() == (1, 4)
+    for j in range(4):
+        assert np.linalg.norm(free[j]) > 0 and np.array_equal(capped[j], free[j]), j
 
 
 # ---- weak (Nitsche) boundary faces: StokesMatrixFreeOperator with weak_boundary_ids (LoopType::Full) and

@@ -1,5 +1,5 @@
 """GPU parity of the Stokes two-field operator at velocity degree 3, FE_Q(3)^3 x FE_Q(2) / FE_DGP(2) with QGauss(4)
-(stfem_stokes_create_space, csrc/stfem_stokes_cell_q3.hip): against the dense numpy fixtures tests/golden/stokes_q3_*.npz and
+(stfem_stokes_create_space, csrc/stfem_stokes_cell.hip at DEG = 3): against the dense numpy fixtures tests/golden/stokes_q3_*.npz and
 against the CPU oracle at pu = 3.  Tolerance rel-L2 <= 1e-12 per block (fp64).  The largest mesh has 6^3 cells."""
 import ctypes as C
 import functools

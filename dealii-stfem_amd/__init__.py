@@ -243,6 +243,15 @@ VANKA_SPACE_SIGNATURES = {
     "stfem_stokes_vanka_create_space": (C.c_int, [_vp, C.POINTER(_StokesVankaSpaceDesc), C.POINTER(_vp)]),
 }
 
+# every symbol the companion header include/stfem_stokes_convection_space.h declares (tests/test_stokes_convection_space_header_cpu.py)
+CONVECTION_SPACE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "stfem_stokes_convection_space.h")
+CONVECTION_SPACE_SIGNATURES = {
+    "stfem_stokes_vmult_convection_space": SIGNATURES["stfem_stokes_vmult_convection"],
+    "stfem_stokes_st_vmult_convection_space": SIGNATURES["stfem_stokes_st_vmult_convection"],
+    "stfem_stokes_st_vmult_slice_add_convection_space": SIGNATURES["stfem_stokes_st_vmult_slice_add_convection"],
+    "stfem_stokes_last_convection_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+}
+
 
 def lib():
     """Loads the HIP library; raises (never falls back) if it has not been built."""
@@ -252,7 +261,8 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: run `make -C dealii-stfem_amd/csrc` "
                               "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(os.environ.get("STFEM_LIB", LIB_PATH))  # STFEM_LIB: experiment builds only
-        for name, (res, args) in list(SIGNATURES.items()) + list(SPACE_SIGNATURES.items()) + list(VANKA_SPACE_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(SPACE_SIGNATURES.items()) + list(VANKA_SPACE_SIGNATURES.items()) +
+                                  list(CONVECTION_SPACE_SIGNATURES.items())):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -857,7 +867,8 @@ class StokesMatrixFreeOperator:
     vmult / st_vmult / st_vmult_slice_add take the convection mode (CONVECTION_FORM / CONVECTION_JACOBIAN) and the linearisation
     velocity `lin` that the reference's set_data hands in; with the defaults they are the linear operator.  delta0 != 0 adds the
     CIP interior-face stabilisation (operators.h:1605-1633) to all of them, see set_cip.  with_degree(3, ...): FE_Q(3)^3 x FE_Q(2) /
-    FE_DGP(2), the linear cell operator, and StokesPreconditionVanka.for_space over it."""
+    FE_DGP(2), the linear cell operator with the convection modes (cell term; no weak faces), and StokesPreconditionVanka.for_space
+    over the linear operator."""
 
     def __init__(self, ncell, vertices=None, lower=(0, 0, 0), upper=(1, 1, 1), dirichlet_mask=63,
                  viscosity=1.0, velocity_degree=2, device=0, weak_boundary_ids=(), outflow_boundary_ids=(),
@@ -887,6 +898,8 @@ class StokesMatrixFreeOperator:
             _check(lib().stfem_stokes_create_space(C.byref(m), C.byref(sd), C.byref(h)), "stfem_stokes_create_space")
             velocity_degree = int(_space[0])
         self.velocity_degree = velocity_degree
+        # with_degree: vmult / st_vmult / st_vmult_slice_add with lin= / mode= go through the _space entries (stfem_stokes_convection_space.h)
+        self._space_entries = _space is not None
         self._h = h
         self.n_velocity = lib().stfem_stokes_n_velocity_dofs(h)
         self.n_pressure = lib().stfem_stokes_n_pressure_dofs(h)
@@ -903,9 +916,11 @@ class StokesMatrixFreeOperator:
     def with_degree(cls, velocity_degree, ncell, reserved=(0, 0, 0, 0), **keywords):
         """The operator through stfem_stokes_create_space; the keywords of the constructor except velocity_degree.  Degree 2: the
         operator of the constructor, bit for bit.  Degree 3: FE_Q(3)^3 x FE_Q(2), or FE_DGP(2) with dg_pressure (ten DoFs per cell),
-        QGauss(4) - the pair of the reference's time degree 2 - with the linear cell operator alone: vmult, mass_vmult, st_vmult,
-        st_Tvmult, st_vmult_slice_add; its smoother is StokesPreconditionVanka.for_space.  Weak / outflow ids, delta0 != 0, a convection
-        mode and everything else raise StfemError with status -2 and the reason."""
+        QGauss(4) - the pair of the reference's time degree 2 - with the cell operator alone: vmult, mass_vmult, st_vmult, st_Tvmult,
+        st_vmult_slice_add, with the convection modes (lin=, mode=: the cell term); its smoother is StokesPreconditionVanka.for_space,
+        over the linear operator.  Weak / outflow ids, delta0 != 0 and everything else raise StfemError with status -2 and the reason.
+        An operator made here sends lin= / mode= through the _space entries of include/stfem_stokes_convection_space.h (at degree 2
+        the entries of the constructor's operator, bit for bit)."""
         assert "velocity_degree" not in keywords and "_space" not in keywords
         return cls(ncell, _space=(velocity_degree, tuple(int(v) for v in reserved)), **keywords)
 
@@ -915,6 +930,14 @@ class StokesMatrixFreeOperator:
         launches of the cell kernel at either degree.  A context that has not launched the cell kernel raises status -2."""
         out = (C.c_int32 * 2)()
         _check(lib().stfem_stokes_last_cell_plan(self._h, out), "stfem_stokes_last_cell_plan")
+        return tuple(out)
+
+    def last_convection_plan(self):
+        """(workgroups, longest run of cells per wave - per half-wave at degree 2) of the last convection colour launch; at degree 3
+        STFEM_STOKES_Q3_WORKGROUPS caps the workgroups of those launches too.  A context that has launched no convection kernel
+        raises status -2."""
+        out = (C.c_int32 * 2)()
+        _check(lib().stfem_stokes_last_convection_plan(self._h, out), "stfem_stokes_last_convection_plan")
         return tuple(out)
 
     def set_cip(self, delta0, weight=CIP_WEIGHT_SOURCE):
@@ -998,8 +1021,11 @@ class StokesMatrixFreeOperator:
         if mode == 0 and lin is None:
             _check(lib().stfem_stokes_vmult(self._h, dst_u, dst_p, src_u, src_p, stream), "stfem_stokes_vmult")
             return
-        _check(lib().stfem_stokes_vmult_convection(self._h, int(mode), dst_u, dst_p, src_u, src_p, getattr(lin, "ptr", lin), stream),
-               "stfem_stokes_vmult_convection")
+        args = (self._h, int(mode), dst_u, dst_p, src_u, src_p, getattr(lin, "ptr", lin), stream)
+        if self._space_entries:
+            _check(lib().stfem_stokes_vmult_convection_space(*args), "stfem_stokes_vmult_convection_space")
+        else:
+            _check(lib().stfem_stokes_vmult_convection(*args), "stfem_stokes_vmult_convection")
 
     @property
     def last_sweep_plan(self):
@@ -1028,8 +1054,11 @@ class StokesMatrixFreeOperator:
             return
         assert lin is None or len(lin) == nb
         l_ = None if lin is None else (_vp * nb)(*[getattr(v, "ptr", v) for v in lin])
-        _check(lib().stfem_stokes_st_vmult_convection(self._h, int(mode), n_timesteps_at_once, n_timedofs, int(variable_major),
-                                                      _p(A), _p(B), d, s_, l_, stream), "stfem_stokes_st_vmult_convection")
+        args = (self._h, int(mode), n_timesteps_at_once, n_timedofs, int(variable_major), _p(A), _p(B), d, s_, l_, stream)
+        if self._space_entries:
+            _check(lib().stfem_stokes_st_vmult_convection_space(*args), "stfem_stokes_st_vmult_convection_space")
+        else:
+            _check(lib().stfem_stokes_st_vmult_convection(*args), "stfem_stokes_st_vmult_convection")
 
     def st_Tvmult(self, Alpha, Beta, n_timesteps_at_once, n_timedofs, dst_blocks, src_blocks, variable_major=True, stream=None):
         """SystemMatrixStokes::Tvmult AS THE REFERENCE HAS IT (operators.h:708-745): its scatter overload (operators.h:111-123)
@@ -1066,10 +1095,12 @@ class StokesMatrixFreeOperator:
                                                          getattr(src_p, "ptr", src_p), stream),
                    "stfem_stokes_st_vmult_slice_add")
             return
-        _check(lib().stfem_stokes_st_vmult_slice_add_convection(self._h, int(mode), n_timesteps_at_once, n_timedofs,
-                                                                int(variable_major), _p(g), _p(z), d, getattr(src_u, "ptr", src_u),
-                                                                getattr(src_p, "ptr", src_p), getattr(lin, "ptr", lin), stream),
-               "stfem_stokes_st_vmult_slice_add_convection")
+        args = (self._h, int(mode), n_timesteps_at_once, n_timedofs, int(variable_major), _p(g), _p(z), d, getattr(src_u, "ptr", src_u),
+                getattr(src_p, "ptr", src_p), getattr(lin, "ptr", lin), stream)
+        if self._space_entries:
+            _check(lib().stfem_stokes_st_vmult_slice_add_convection_space(*args), "stfem_stokes_st_vmult_slice_add_convection_space")
+        else:
+            _check(lib().stfem_stokes_st_vmult_slice_add_convection(*args), "stfem_stokes_st_vmult_slice_add_convection")
 
     @property
     def n_cells(self):

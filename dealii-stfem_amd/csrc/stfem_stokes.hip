@@ -8,7 +8,9 @@
 // (stfem_stokes_convection.hip), and with delta0 != 0 the CIP interior-face launches (stfem_stokes_cip.hip).  The helpers of the pressure space the solver around the operator needs: stfem_stokes_pressure.hip.
 // Every entry point describes its launches in ONE form, StokesParams (stfem_stokes_internal.h), put together by StokesLaunch below.
 // A context of velocity degree 3 (stfem_stokes_create_space) has one implementation of the linear cell operator, the same cell kernel
-// at DEG = 3 (stfem_stokes_cell.hip), and nothing on top of it: stokes_launch dispatches on the degree, stokes_require_q2 refuses the rest
+// at DEG = 3 (stfem_stokes_cell.hip), and on top of it the convection launches of the Navier-Stokes modes alone
+// (stfem_stokes_convection_q3.hip), reached through the _space entries of stfem_stokes_convection_space.h: stokes_launch dispatches on
+// the degree, stokes_require_q2 refuses the rest
 // (beside the operator such a context has its per-cell Vanka smoother, stfem_stokes_vanka_create_space in stfem_stokes_vanka.hip).
 #include "stfem_stokes_internal.h"
 
@@ -80,6 +82,16 @@ int stfem_stokes_last_cell_plan(const stfem_stokes_ctx *c, int32_t out[2])
   if (!c->cell_launched) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "stfem_stokes_last_cell_plan: this context has not launched the cell kernel");
   out[0] = c->cell_plan[0];
   out[1] = c->cell_plan[1];
+  return STFEM_OK;
+}
+
+int stfem_stokes_last_convection_plan(const stfem_stokes_ctx *c, int32_t out[2])
+{
+  if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  if (!c->convection_launched)
+    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "stfem_stokes_last_convection_plan: this context has not launched a convection kernel");
+  out[0] = c->convection_plan[0];
+  out[1] = c->convection_plan[1];
   return STFEM_OK;
 }
 
@@ -491,7 +503,11 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
 int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double *const *lin, hipStream_t st)
 {
   // axis-aligned uniform mesh: the Kronecker path; otherwise the cell kernel
-  if (c->degree == 3) return stokes_cell_launch(c, prm, st); // the linear cell operator is all a degree-3 context has
+  if (c->degree == 3) { // the linear cell operator, then the convection colours: all a degree-3 context has
+    const int rc = stokes_cell_launch(c, prm, st);
+    if (rc != STFEM_OK || mode == STFEM_CONVECTION_NONE) return rc;
+    return stokes_convection_q3_launch(c, prm, lin, mode, st);
+  }
   const int rc = c->scalar ? stokes_cart_launch(c, prm, st) : stokes_cell_launch(c, prm, st);
   if (rc != STFEM_OK) return rc;
   // LoopType::Full: the boundary-face loop of the same vmult (the mass operator has none)
@@ -518,6 +534,35 @@ int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double
 // BlockSlice::index, fe_time.h:956-967
 int block_index(int nt, int variable_major, int it, int v, int d) { return variable_major ? it * (2 * nt) + v * nt + d : it * (2 * nt) + d * 2 + v; }
 
+// The three entries that take a convection mode, in the form behind both their names: require_q2 - the entry of stfem.h, which refuses
+// a mode on a context of degree 3 (stokes_require_q2); otherwise the _space entry of stfem_stokes_convection_space.h, which runs it.
+int stokes_vmult_convection(stfem_stokes_ctx *c, int mode, double *dst_u, double *dst_p, const double *src_u, const double *src_p,
+                            const double *lin_u, void *stream, bool require_q2)
+{
+  if (!c || !dst_u || !dst_p || !src_u || !src_p) return STFEM_ERR_INVALID_ARGUMENT;
+  if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_u))
+    return STFEM_ERR_INVALID_ARGUMENT;
+  if (dst_u == src_u || dst_p == src_p) return STFEM_ERR_ALIAS;
+  if (mode != STFEM_CONVECTION_NONE && (lin_u == dst_u || lin_u == dst_p)) return STFEM_ERR_ALIAS;
+  if (mode != STFEM_CONVECTION_NONE && require_q2)
+    if (const int rq = stokes_require_q2(c, "stfem_stokes_vmult_convection with a convection mode")) return rq;
+  if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
+  STFEM_TRY(hipSetDevice(c->device));
+  StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
+  launch.add_source(src_u, src_p, lin_u);
+  const double one = 1.0, zero = 0.0;
+  char written[2] = {0, 0}; // dst is overwritten
+  const int rc = launch.add_destination(dst_u, dst_p, &one, &one, &zero, &written[0], &written[1]);
+  return rc != STFEM_OK ? rc : launch.flush();
+}
+
+int stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timesteps_at_once, int n_timedofs, int variable_major,
+                               const double *Alpha, const double *Beta, double *const *dst_blocks, const double *const *src_blocks,
+                               const double *const *lin_blocks, void *stream, bool require_q2);
+int stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, int n_timesteps_at_once, int n_timedofs, int variable_major,
+                                         const double *Gamma, const double *Zeta, double *const *dst_blocks, const double *src_u,
+                                         const double *src_p, const double *lin_u, void *stream, bool require_q2);
+
 } // namespace
 
 extern "C" {
@@ -531,21 +576,13 @@ int stfem_stokes_vmult(stfem_stokes_ctx *c, double *dst_u, double *dst_p, const 
 int stfem_stokes_vmult_convection(stfem_stokes_ctx *c, int mode, double *dst_u, double *dst_p, const double *src_u,
                                   const double *src_p, const double *lin_u, void *stream)
 {
-  if (!c || !dst_u || !dst_p || !src_u || !src_p) return STFEM_ERR_INVALID_ARGUMENT;
-  if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_u))
-    return STFEM_ERR_INVALID_ARGUMENT;
-  if (dst_u == src_u || dst_p == src_p) return STFEM_ERR_ALIAS;
-  if (mode != STFEM_CONVECTION_NONE && (lin_u == dst_u || lin_u == dst_p)) return STFEM_ERR_ALIAS;
-  if (mode != STFEM_CONVECTION_NONE)
-    if (const int rq = stokes_require_q2(c, "stfem_stokes_vmult_convection with a convection mode")) return rq;
-  if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
-  STFEM_TRY(hipSetDevice(c->device));
-  StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
-  launch.add_source(src_u, src_p, lin_u);
-  const double one = 1.0, zero = 0.0;
-  char written[2] = {0, 0}; // dst is overwritten
-  const int rc = launch.add_destination(dst_u, dst_p, &one, &one, &zero, &written[0], &written[1]);
-  return rc != STFEM_OK ? rc : launch.flush();
+  return stokes_vmult_convection(c, mode, dst_u, dst_p, src_u, src_p, lin_u, stream, true);
+}
+
+int stfem_stokes_vmult_convection_space(stfem_stokes_ctx *c, int mode, double *dst_u, double *dst_p, const double *src_u,
+                                        const double *src_p, const double *lin_u, void *stream)
+{
+  return stokes_vmult_convection(c, mode, dst_u, dst_p, src_u, src_p, lin_u, stream, false);
 }
 
 int stfem_stokes_mass_vmult(stfem_stokes_ctx *c, double *dst_u, const double *src_u, void *stream)
@@ -573,6 +610,26 @@ int stfem_stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timest
                                      const double *Alpha, const double *Beta, double *const *dst_blocks,
                                      const double *const *src_blocks, const double *const *lin_blocks, void *stream)
 {
+  return stokes_st_vmult_convection(c, mode, n_timesteps_at_once, n_timedofs, variable_major, Alpha, Beta, dst_blocks, src_blocks, lin_blocks,
+                                    stream, true);
+}
+
+int stfem_stokes_st_vmult_convection_space(stfem_stokes_ctx *c, int mode, int n_timesteps_at_once, int n_timedofs, int variable_major,
+                                           const double *Alpha, const double *Beta, double *const *dst_blocks,
+                                           const double *const *src_blocks, const double *const *lin_blocks, void *stream)
+{
+  return stokes_st_vmult_convection(c, mode, n_timesteps_at_once, n_timedofs, variable_major, Alpha, Beta, dst_blocks, src_blocks, lin_blocks,
+                                    stream, false);
+}
+
+} // extern "C"
+
+namespace {
+
+int stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timesteps_at_once, int n_timedofs, int variable_major,
+                               const double *Alpha, const double *Beta, double *const *dst_blocks, const double *const *src_blocks,
+                               const double *const *lin_blocks, void *stream, bool require_q2)
+{
   if (!c || !Alpha || !Beta || !dst_blocks || !src_blocks || n_timesteps_at_once < 1 || n_timedofs < 1)
     return STFEM_ERR_INVALID_ARGUMENT;
   if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_blocks))
@@ -594,7 +651,7 @@ int stfem_stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timest
       for (int it = 0; it < ns; ++it)
         for (int d = 0; d < nt; ++d)
           if (dst_blocks[j] == lin_blocks[index(it, 0, d)]) return STFEM_ERR_ALIAS;
-  if (navier)
+  if (navier && require_q2)
     if (const int rq = stokes_require_q2(c, "stfem_stokes_st_vmult_convection with a convection mode")) return rq;
   for (int it = 0; it < ns; ++it)
     for (int d = 0; d < nt; ++d)
@@ -638,6 +695,10 @@ int stfem_stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timest
   return STFEM_OK;
 }
 
+} // namespace
+
+extern "C" {
+
 // SystemMatrixStokes::vmult_slice_add (operators.h:748-781): the n x 1 case used for the right-hand
 // side: src = one (velocity, pressure) pair, dst[index(it,v,id)] += Gamma(index(it,v,id), 0) * (K_S src)_v
 // and dst[index(it,0,id)] += Zeta(index(it,0,id), 0) * M u.  dst is NOT zeroed.
@@ -654,6 +715,27 @@ int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, in
                                                double *const *dst_blocks, const double *src_u, const double *src_p,
                                                const double *lin_u, void *stream)
 {
+  return stokes_st_vmult_slice_add_convection(c, mode, n_timesteps_at_once, n_timedofs, variable_major, Gamma, Zeta, dst_blocks, src_u, src_p,
+                                              lin_u, stream, true);
+}
+
+int stfem_stokes_st_vmult_slice_add_convection_space(stfem_stokes_ctx *c, int mode, int n_timesteps_at_once, int n_timedofs,
+                                                     int variable_major, const double *Gamma, const double *Zeta,
+                                                     double *const *dst_blocks, const double *src_u, const double *src_p,
+                                                     const double *lin_u, void *stream)
+{
+  return stokes_st_vmult_slice_add_convection(c, mode, n_timesteps_at_once, n_timedofs, variable_major, Gamma, Zeta, dst_blocks, src_u, src_p,
+                                              lin_u, stream, false);
+}
+
+} // extern "C"
+
+namespace {
+
+int stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, int n_timesteps_at_once, int n_timedofs, int variable_major,
+                                         const double *Gamma, const double *Zeta, double *const *dst_blocks, const double *src_u,
+                                         const double *src_p, const double *lin_u, void *stream, bool require_q2)
+{
   if (!c || !Gamma || !Zeta || !dst_blocks || !src_u || !src_p || n_timesteps_at_once < 1 || n_timedofs < 1)
     return STFEM_ERR_INVALID_ARGUMENT;
   if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_u))
@@ -664,7 +746,7 @@ int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, in
     if (dst_blocks[j] == src_u || dst_blocks[j] == src_p) return STFEM_ERR_ALIAS;
     if (mode != STFEM_CONVECTION_NONE && dst_blocks[j] == lin_u) return STFEM_ERR_ALIAS;
   }
-  if (mode != STFEM_CONVECTION_NONE)
+  if (mode != STFEM_CONVECTION_NONE && require_q2)
     if (const int rq = stokes_require_q2(c, "stfem_stokes_st_vmult_slice_add_convection with a convection mode")) return rq;
   if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
   STFEM_TRY(hipSetDevice(c->device));
@@ -679,4 +761,4 @@ int stfem_stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, in
   return launch.flush();
 }
 
-} // extern "C"
+} // namespace

@@ -40,41 +40,10 @@ template <int DEG> constexpr DgpDegrees<DEG> dgp_degrees()
   return r;
 }
 
-// The lane's N coefficients p[0], p[STRIDE], ... of a 1D table in LDS: HELD - copied into registers once, for the whole kernel;
-// otherwise read where they are used.
-template <int N, int STRIDE, bool HELD> struct Coef {
-  const double *p;
-  double r[HELD ? N : 1];
-  __device__ __forceinline__ explicit Coef(const double *q) : p(q)
-  {
-    if constexpr (HELD) {
-#pragma unroll
-      for (int n = 0; n < N; ++n) r[n] = q[n * STRIDE];
-    }
-  }
-  __device__ __forceinline__ double operator[](int n) const
-  {
-    if constexpr (HELD) return r[n];
-    else return p[n * STRIDE];
-  }
-};
-// Which 1D tables a lane holds in registers.  The rows of its quadrature index (evaluation) always.  The columns of its node index
+// Which 1D tables a lane holds in registers (Coef, with dot in stfem_stokes_internal.h).  The rows of its quadrature index (evaluation) always.  The columns of its node index
 // (integration) and the pressure tables at degree 2 only: at degree 3 they are 44 doubles more, and with all of them in registers
 // five of the eight instantiations need 256 VGPRs and spills to AGPRs, one wave per SIMD (profiles/stokes_q3.txt).
 template <int DEG> constexpr bool COLUMNS_HELD = DEG == 2;
-
-// sum_n w[n] v[n * stride], ascending, one fma chain.  The values are read last first: the compiler's order of the LDS reads in the
-// integration stages follows the order here, and this one is the faster (profiles/stokes_cell_merge.txt)
-template <int N, class W> __device__ __forceinline__ double dot(const W &w, const double *v, int stride = 1)
-{
-  double x[N];
-#pragma unroll
-  for (int n = N - 1; n >= 0; --n) x[n] = v[n * stride];
-  double s = w[0] * x[0];
-#pragma unroll
-  for (int n = 1; n < N; ++n) s = fma(w[n], x[n], s);
-  return s;
-}
 
 // 256 threads = 8 (degree 2) or 4 (degree 3) cells at a time; the workgroups walk over the cells.
 // Sum-factorised: evaluation and integration are three 1D stages each (x, y, z), handed from lane to lane through two wave-private

@@ -464,6 +464,9 @@ int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const
     const unsigned grid = (unsigned)std::min<long long>((n + 7) / 8, (long long)c->n_cu * resident);
     void *args[] = {(void *)&k};
     (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
+    c->convection_launched = true; // (stfem_stokes_last_convection_plan)
+    c->convection_plan[0] = (int)grid;
+    c->convection_plan[1] = (int)((n + 8ll * grid - 1) / (8ll * grid));
   }
   const long long items = k.weak_mask ? k.foff[6] : 0;
   if (items > 0) {

@@ -114,6 +114,25 @@ struct ConvectionParams {
   double Eu[6];
 };
 
+// The same at velocity degree 3 (stfem_stokes_convection_q3.hip): FE_Q(3) tables at the four Gauss points.  A degree-3 context has no
+// weak faces, so there is no inflow term and no face data.
+struct ConvectionQ3Params {
+  const double *vertices;
+  int ncx, ncy, ncz;
+  int ndu[3];
+  long long Nu;
+  int dmask;
+  int nsrc;
+  const double *us[MAXSRC], *bs[MAXSRC];
+  int nout;
+  double *out_u[MAXOUT];
+  double wKu[MAXSRC][MAXOUT];
+  double Su[16], Du[16]; // [q*4+a]
+  double xq[4], wq[4];
+  int colour, cart;
+  double hinv[3], detJ;
+};
+
 // The CIP interior-face launches (stfem_stokes_cip.hip), again a description of their own:
 //   out_u[o] += sum_s wKu[s][o] C(w_s; u_s),   C(w; u)(v) = sum_F int_F delta0 h_F^2 / pa (w.n)^2 [d_n u] . [d_n v] dA
 // Geometry, tables and the weights are copied from the StokesParams of the same set; only destinations with a non-zero wKu are listed.
@@ -160,7 +179,7 @@ struct stfem_stokes_ctx {
   double *d_vertices = nullptr;
   int n_cu = 256;
   int pspace = 0; // 0 = FE_Q(degree - 1), 1 = FE_DGP(degree - 1)
-  // velocity degree: 2, or 3 (stfem_stokes_create_space): the linear cell operator alone.  Geometry and tables are in the description
+  // velocity degree: 2, or 3 (stfem_stokes_create_space): the linear cell operator and the convection term of the Navier-Stokes modes.  Geometry and tables are in the description
   // of that degree, base or base3 (stokes_create_degree fills the one); the other stays zero
   int degree = 2;
   StokesParams base;
@@ -168,6 +187,8 @@ struct stfem_stokes_ctx {
   bool cart() const { return (degree == 3 ? base3.cart : base.cart) != 0; }
   bool cell_launched = false;
   int cell_plan[2] = {0, 0}; // workgroups and longest run of cells per cell slot of the last colour launch (stfem_stokes_last_cell_plan)
+  bool convection_launched = false;
+  int convection_plan[2] = {0, 0}; // the same of the last convection colour launch (stfem_stokes_last_convection_plan)
   // axis-aligned uniform meshes: the scalar FE_Q(2) context whose pencil sweep applies nu K + wM M to the velocity components,
   // and the 1D tables of the coupling kernels
   stfem_ctx *scalar = nullptr;
@@ -217,6 +238,38 @@ __device__ __forceinline__ void wave_fence()
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// What the sum-factorised cell kernels (stfem_stokes_cell.hip, stfem_stokes_convection_q3.hip) share.
+// The lane's N coefficients p[0], p[STRIDE], ... of a 1D table in LDS: HELD - copied into registers once, for the whole kernel;
+// otherwise read where they are used.
+template <int N, int STRIDE, bool HELD> struct Coef {
+  const double *p;
+  double r[HELD ? N : 1];
+  __device__ __forceinline__ explicit Coef(const double *q) : p(q)
+  {
+    if constexpr (HELD) {
+#pragma unroll
+      for (int n = 0; n < N; ++n) r[n] = q[n * STRIDE];
+    }
+  }
+  __device__ __forceinline__ double operator[](int n) const
+  {
+    if constexpr (HELD) return r[n];
+    else return p[n * STRIDE];
+  }
+};
+// sum_n w[n] v[n * stride], ascending, one fma chain.  The values are read last first: the compiler's order of the LDS reads in the
+// integration stages follows the order here, and this one is the faster (profiles/stokes_cell_merge.txt)
+template <int N, class W> __device__ __forceinline__ double dot(const W &w, const double *v, int stride = 1)
+{
+  double x[N];
+#pragma unroll
+  for (int n = N - 1; n >= 0; --n) x[n] = v[n * stride];
+  double s = w[0] * x[0];
+#pragma unroll
+  for (int n = 1; n < N; ++n) s = fma(w[n], x[n], s);
+  return s;
 }
 
 // What the CIP kernel of the operator (stfem_stokes_cip.hip) and the CIP cell matrices of the per-cell Vanka blocks
@@ -294,6 +347,10 @@ int stokes_boundary_launch(stfem_stokes_ctx *c, StokesParams &prm, const double 
 // faces, eight of the inflow-face kernel.  mode: STFEM_CONVECTION_FORM / _JACOBIAN; lin[s]: the linearisation velocity of source s.
 // Nothing is launched when all wKu of the set are zero.
 int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *lin, int mode, hipStream_t st);
+// The convection launches of a degree-3 context after the cell launches of `prm` (stfem_stokes_convection_q3.hip): eight colour launches,
+// geometry and tables from the context's base3, sources, destinations and weights from `prm`; mode and lin as above.
+// STFEM_STOKES_Q3_WORKGROUPS=<n>, read at every launch, caps their workgroups.
+int stokes_convection_q3_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *lin, int mode, hipStream_t st);
 // The CIP launches after those (stfem_stokes_cip.hip): eight colour launches; weight[s]: the weight velocity of source s.  Nothing is
 // launched with delta0 == 0, on a mesh without interior faces, for a colour without cells or when all wKu of the set are zero.
 int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, hipStream_t st);

@@ -2,7 +2,8 @@
 // SystemMatrixStokes, 1193-1766 StokesMatrixFreeOperator, 1768-1951 StokesNitscheMatrixFreeOperator;
 // include/fe_time.h:901-1221 BlockSlice, 1242-1285 get_fe_time_weights_stokes) on the C-ABI (stfem_stokes_*):
 // cell loop and, for weak boundary ids, the boundary-face loop; with a NonlinearTreatment the convection modes of the Navier-Stokes
-// operator (OperatorMode::form / jacobian) and the NavierStokesOperator alias over PDE<> (operators.h:2052-2063).
+// operator (OperatorMode::form / jacobian) and the NavierStokesOperator alias over PDE<> (operators.h:2052-2063).  Velocity degree 3
+// with a NonlinearTreatment: the constructor by descriptor (StokesSpace).
 #pragma once
 #include "fe_time.h"
 #include "operators.h"
@@ -136,6 +137,15 @@ inline void rhs_minus(std::vector<StokesVector> &dst, const std::vector<StokesVe
   check(stfem_axpby_many(pc, int(nb), len.data(), 1.0, px.data(), -1.0, py.data(), nullptr), "PDE::residual");
 }
 
+// The operator by descriptor: what the second constructor of StokesMatrixFreeOperator takes.  velocity_degree 2 or 3; at degree 3 the
+// cell operator with the convection term of the nonlinear treatment (no weak faces, no CIP: a degree-3 context has neither).
+template <typename Number> struct StokesSpace {
+  unsigned velocity_degree = 2;
+  bool dg_pressure = false;
+  Number viscosity = 1;
+  NonlinearTreatment nonlinear_treatment = NonlinearTreatment::None;
+};
+
 // operators.h:1193-1766: cell loop + boundary-face loop for the weak (Nitsche) ids.  Same constructor arguments after the mesh as
 // the reference (1199-1213), with dg_pressure before the nonlinear treatment.  delta0 != 0 switches the CIP interior-face term on
 // (1605-1633, stfem_stokes_set_cip), weighted with the source of every vmult as in the reference; set_cip_weight chooses the
@@ -176,6 +186,16 @@ public:
       throw;
     }
   }
+  // By descriptor: a nonlinear treatment is accepted at velocity degree 3 too.  vmult, form and the SystemMatrixStokes calls over this
+  // operator go through the _space entries of stfem_stokes_convection_space.h, which run a convection mode at either degree (degree 2:
+  // the entries of the first constructor's operator, bit for bit).
+  StokesMatrixFreeOperator(const Mesh &mesh, const StokesSpace<Number> &space)
+    : nonlinear_treatment(space.nonlinear_treatment), nonlinear(space.nonlinear_treatment != NonlinearTreatment::None), space_entries_(true)
+  {
+    create(mesh, space.velocity_degree, space.viscosity, space.dg_pressure);
+  }
+  // whether the convection entries of this operator are the _space forms (the constructor by descriptor)
+  bool space_entries() const { return space_entries_; }
   // Whose velocity weighs the CIP term: STFEM_CIP_WEIGHT_SOURCE (the reference: the source of the vmult, cubic in it) or
   // STFEM_CIP_WEIGHT_LINEARISATION (with a nonlinear treatment the linearisation velocity of set_data: linear in the source, what a
   // Krylov method needs).  form(x) about x itself is the same with both.  The state of the device context, like set_data.
@@ -334,12 +354,14 @@ private:
   void apply(int mode, BlockVectorType &dst, const BlockVectorType &src, void *stream) const
   {
     if (mode != STFEM_CONVECTION_NONE && !lin_) throw Error(STFEM_ERR_INVALID_ARGUMENT, "StokesMatrixFreeOperator: no linearization set");
-    check(stfem_stokes_vmult_convection(h_, mode, dst.at(0).data(), dst.at(1).data(), src.at(0).data(), src.at(1).data(), lin_, stream),
+    check((space_entries_ ? stfem_stokes_vmult_convection_space : stfem_stokes_vmult_convection)(
+            h_, mode, dst.at(0).data(), dst.at(1).data(), src.at(0).data(), src.at(1).data(), lin_, stream),
           "StokesMatrixFreeOperator::vmult");
   }
   stfem_stokes_ctx *h_ = nullptr;
   NonlinearTreatment nonlinear_treatment;
   bool nonlinear;
+  bool space_entries_ = false;
   mutable const double *lin_ = nullptr; // data_lin[0]
   Number delta0_ = 0.0;
   unsigned velocity_degree_ = 2;
@@ -462,9 +484,9 @@ private:
           const unsigned i = blk_slice.index(it, 0, id);
           l[i] = (*solution_linearization)[i].data();
         }
-    check(stfem_stokes_st_vmult_convection(K.handle(), mode, int(blk_slice.n_timesteps_at_once()), int(blk_slice.n_timedofs()),
-                                           blk_slice.variable_major() ? 1 : 0, Alpha.data(), Beta.data(), d.data(), s.data(),
-                                           l.empty() ? nullptr : l.data(), stream),
+    check((K.space_entries() ? stfem_stokes_st_vmult_convection_space : stfem_stokes_st_vmult_convection)(
+            K.handle(), mode, int(blk_slice.n_timesteps_at_once()), int(blk_slice.n_timedofs()), blk_slice.variable_major() ? 1 : 0,
+            Alpha.data(), Beta.data(), d.data(), s.data(), l.empty() ? nullptr : l.data(), stream),
           "SystemMatrixStokes::vmult");
   }
 
@@ -519,10 +541,10 @@ private:
     for (unsigned i = 0; i < nb; ++i) d[i] = dst[i].data();
     // (759-761: set_linearization_data_slice - one linearisation pair for the one source pair)
     const std::vector<const double *> l = linearization(mode, 2, "SystemMatrixStokes::vmult_slice_add");
-    check(stfem_stokes_st_vmult_slice_add_convection(K.handle(), mode, int(blk_slice.n_timesteps_at_once()), int(blk_slice.n_timedofs()),
-                                                     blk_slice.variable_major() ? 1 : 0, Alpha.data(), Beta.data(), d.data(),
-                                                     src[0].data(), src[1].data(), l.empty() ? nullptr : (*solution_linearization)[0].data(),
-                                                     stream),
+    check((K.space_entries() ? stfem_stokes_st_vmult_slice_add_convection_space : stfem_stokes_st_vmult_slice_add_convection)(
+            K.handle(), mode, int(blk_slice.n_timesteps_at_once()), int(blk_slice.n_timedofs()), blk_slice.variable_major() ? 1 : 0,
+            Alpha.data(), Beta.data(), d.data(), src[0].data(), src[1].data(),
+            l.empty() ? nullptr : (*solution_linearization)[0].data(), stream),
           "SystemMatrixStokes::vmult_slice_add");
   }
 

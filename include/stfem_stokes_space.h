@@ -16,14 +16,15 @@
  *     (1,1,0), (0,2,0), (0,0,1), (1,0,1), (0,1,1), (0,0,2).  QGauss(4), MappingQ1 from the mesh vertices (a constant diagonal
  *     Jacobian without vertices); dirichlet_mask constrains the velocity, the pressure is free; fp64.
  *     A degree-3 context has the LINEAR CELL OPERATOR and its per-cell Vanka smoother (stfem_stokes_vanka_create_space,
- *     stfem_stokes_vanka_space.h: the one Vanka constructor that serves it), and nothing else: n_velocity_dofs / n_pressure_dofs, the vector functions,
+ *     stfem_stokes_vanka_space.h: the one Vanka constructor that serves it), and of the entries declared in stfem.h itself nothing else: n_velocity_dofs / n_pressure_dofs, the vector functions,
  *     stfem_stokes_vmult, _mass_vmult, _st_vmult, _st_vmult_slice_add (and with them the reference's Tvmult) and their _convection
  *     forms with STFEM_CONVECTION_NONE, all through one cell kernel (one wave per cell, eight colour launches, bitwise reproducible;
  *     boxes included: no Kronecker path).  Every other entry point that takes a Stokes context - weak / outflow faces, the convection
  *     modes, CIP, divergence, drag / lift, the face-point and Nitsche functions, the pressure helpers, the FE_DGP transfers, the Vanka
  *     constructors of stfem.h itself (stfem_stokes_vanka_create and the three _create_linearised forms) - returns STFEM_ERR_UNSUPPORTED with "<entry> is built for velocity degree 2 only" in stfem_last_error, before it
- *     touches the device and with its operands untouched (the int64_t counts return that status as their value).  Not built at
- *     degree 3 either: GMGStokes and the drivers, slabs (untested, unclaimed), fp32.
+ *     touches the device and with its operands untouched (the int64_t counts return that status as their value).  The convection
+ *     modes at degree 3 run through entries of their own, the _space forms of the three _convection entries
+ *     (stfem_stokes_convection_space.h).  Not built at degree 3 either: GMGStokes and the drivers, slabs (untested, unclaimed), fp32.
  *   Any other degree: STFEM_ERR_UNSUPPORTED; non-zero reserved or a pressure_space outside 0..1: STFEM_ERR_INVALID_ARGUMENT; both
  *   with their reason in stfem_last_error. */
 typedef struct {

@@ -60,6 +60,12 @@ class _StokesVankaSpaceDesc(C.Structure):
                 ("Beta", C.POINTER(C.c_double)), ("reserved", C.c_int32 * 4)]
 
 
+class _StokesVankaLinearisedSpaceDesc(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("block_variable", C.POINTER(C.c_int32)), ("Alpha", C.POINTER(C.c_double)),
+                ("Beta", C.POINTER(C.c_double)), ("mode", C.c_int32), ("lin_blocks", C.POINTER(C.c_void_p)),
+                ("reserved", C.c_int32 * 4)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _lib = None
@@ -252,6 +258,13 @@ CONVECTION_SPACE_SIGNATURES = {
     "stfem_stokes_last_convection_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
 }
 
+# every symbol the companion header include/stfem_stokes_vanka_linearised_space.h declares
+# (tests/test_stokes_vanka_linearised_space_header_cpu.py)
+VANKA_LINEARISED_SPACE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "stfem_stokes_vanka_linearised_space.h")
+VANKA_LINEARISED_SPACE_SIGNATURES = {
+    "stfem_stokes_vanka_create_linearised_space": (C.c_int, [_vp, C.POINTER(_StokesVankaLinearisedSpaceDesc), C.POINTER(_vp)]),
+}
+
 
 def lib():
     """Loads the HIP library; raises (never falls back) if it has not been built."""
@@ -262,7 +275,7 @@ def lib():
                               "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(os.environ.get("STFEM_LIB", LIB_PATH))  # STFEM_LIB: experiment builds only
         for name, (res, args) in (list(SIGNATURES.items()) + list(SPACE_SIGNATURES.items()) + list(VANKA_SPACE_SIGNATURES.items()) +
-                                  list(CONVECTION_SPACE_SIGNATURES.items())):
+                                  list(CONVECTION_SPACE_SIGNATURES.items()) + list(VANKA_LINEARISED_SPACE_SIGNATURES.items())):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -1238,13 +1251,26 @@ class StokesPreconditionVanka:
         self._h = h
 
     @classmethod
-    def for_space(cls, op, block_variable, Alpha, Beta, reserved=(0, 0, 0, 0)):
+    def for_space(cls, op, block_variable, Alpha, Beta, reserved=(0, 0, 0, 0), lin=None, mode=0):
         """The smoother through stfem_stokes_vanka_create_space: one block per cell of the linear operator `op`, whatever its
         velocity degree.  Degree 2: the blocks of per_cell=True with mode 0, bit for bit.  Degree 3 (StokesMatrixFreeOperator.
-        with_degree(3, ...)): 192 velocity and 27 / 10 pressure rows per time dof, at most 512 rows (two time dofs); this is the one
-        constructor that serves it - the plain one raises StfemError with status -2.  vmult / step / update(None) as usual."""
+        with_degree(3, ...)): 192 velocity and 27 / 10 pressure rows per time dof, at most 512 rows (two time dofs); this is the
+        constructor that serves it - the plain one raises StfemError with status -2.  vmult / step / update(None) as usual.
+        With `lin` or a convection mode: through stfem_stokes_vanka_create_linearised_space, the blocks of the operator linearised
+        about `lin` (device vectors in BlockSlice order, pressure entries may be None) at either degree; update(lin) rebuilds them."""
         self = cls.__new__(cls)
         bv, A, B = self._blocks(op, block_variable, Alpha, Beta, None)
+        if lin is not None or mode != 0:
+            d = _StokesVankaLinearisedSpaceDesc()
+            d.n_blocks, d.block_variable, d.Alpha, d.Beta, d.mode = self.nb, bv, _p(A), _p(B), int(mode)
+            d.lin_blocks = self._lin(lin)
+            d.reserved[:] = [int(v) for v in reserved]
+            h = _vp()
+            rc = lib().stfem_stokes_vanka_create_linearised_space(op._h, C.byref(d), C.byref(h))
+            assert rc == 0 or not h.value
+            _check(rc, "stfem_stokes_vanka_create_linearised_space")
+            self._h = h
+            return self
         d = _StokesVankaSpaceDesc()
         d.n_blocks, d.block_variable, d.Alpha, d.Beta = self.nb, bv, _p(A), _p(B)
         d.reserved[:] = [int(v) for v in reserved]

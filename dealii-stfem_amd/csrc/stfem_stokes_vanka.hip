@@ -359,10 +359,13 @@ static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *b
   if (mode < STFEM_CONVECTION_NONE || mode > STFEM_CONVECTION_JACOBIAN || (mode != STFEM_CONVECTION_NONE && !lin_blocks)) return STFEM_ERR_INVALID_ARGUMENT;
   if (n_blocks > VK_MAX_BLOCKS) return STFEM_ERR_UNSUPPORTED;
   // (the _cip and _partitioned entries have asked under their own names before they come here)
-  // any_degree: stfem_stokes_vanka_create_space, the one entry that serves velocity degree 3 (mode 0, no CIP term, no slab)
+  // any_degree: stfem_stokes_vanka_create_space and _create_linearised_space, the entries that serve velocity degree 3 (every mode, no
+  // CIP term, no slab)
   if (!any_degree)
     if (const int rq = stokes_require_q2(ctx, "stfem_stokes_vanka_create_linearised")) return rq;
   const int degree = stokes_velocity_degree(ctx);
+  if (degree != 2 && delta0 != 0.0)
+    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "per-cell Stokes blocks with delta0 = %g at velocity degree %d: a context of that degree has no CIP term", delta0, degree);
   stfem_stokes_desc d;
   int rc = stokes_desc_any_degree(ctx, &d);
   if (rc != STFEM_OK) return rc;
@@ -427,6 +430,39 @@ int stfem_stokes_vanka_create_space(stfem_stokes_ctx *ctx, const stfem_stokes_va
   if (stokes_velocity_degree(ctx) == 2)
     return stfem_stokes_vanka_create_linearised(ctx, desc->n_blocks, desc->block_variable, desc->Alpha, desc->Beta, STFEM_CONVECTION_NONE, nullptr, out);
   return create_per_cell(ctx, desc->n_blocks, desc->block_variable, desc->Alpha, desc->Beta, STFEM_CONVECTION_NONE, nullptr, 0.0, out, nullptr, 0, 0, true);
+}
+
+// The same constructor for the operator linearised about lin_blocks (include/stfem_stokes_vanka_linearised_space.h): velocity degree 2
+// is stfem_stokes_vanka_create_linearised on its own path; degree 3 builds the blocks of A(b_j) per column block from the cell matrices
+// of stfem_stokes_vanka_cell_q3.hip in the mode, a launch per distinct state.  The refusals of stfem_stokes_vanka_create_space, then
+// those of the mode, all decided on the arguments before the context or the device is touched.
+int stfem_stokes_vanka_create_linearised_space(stfem_stokes_ctx *ctx, const stfem_stokes_vanka_linearised_space_desc *desc, stfem_stokes_vanka **out)
+{
+  const char *me = "stfem_stokes_vanka_create_linearised_space";
+  if (!out) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: out is null", me);
+  *out = nullptr;
+  if (!ctx) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: ctx is null", me);
+  if (!desc) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: desc is null", me);
+  for (int i = 0; i < 4; ++i)
+    if (desc->reserved[i] != 0) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: reserved[%d] = %d, must be 0", me, i, desc->reserved[i]);
+  if (desc->n_blocks < 1 || desc->n_blocks > VK_MAX_BLOCKS)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: n_blocks = %d, must be 1..%d", me, desc->n_blocks, VK_MAX_BLOCKS);
+  if (!desc->block_variable || !desc->Alpha || !desc->Beta)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: %s is null", me, !desc->block_variable ? "block_variable" : (!desc->Alpha ? "Alpha" : "Beta"));
+  for (int i = 0; i < desc->n_blocks; ++i)
+    if (desc->block_variable[i] < 0 || desc->block_variable[i] > 1)
+      return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: block_variable[%d] = %d, must be 0 (velocity) or 1 (pressure)", me, i, desc->block_variable[i]);
+  if (desc->mode < STFEM_CONVECTION_NONE || desc->mode > STFEM_CONVECTION_JACOBIAN)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: mode = %d, must be 0 (none), 1 (form) or 2 (jacobian)", me, desc->mode);
+  if (desc->mode != STFEM_CONVECTION_NONE) {
+    if (!desc->lin_blocks) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: mode = %d needs lin_blocks, the linearisation states", me, desc->mode);
+    for (int i = 0; i < desc->n_blocks; ++i)
+      if (desc->block_variable[i] == 0 && !desc->lin_blocks[i])
+        return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "%s: mode = %d and lin_blocks[%d] of a velocity block is null", me, desc->mode, i);
+  }
+  if (stokes_velocity_degree(ctx) == 2)
+    return stfem_stokes_vanka_create_linearised(ctx, desc->n_blocks, desc->block_variable, desc->Alpha, desc->Beta, desc->mode, desc->lin_blocks, out);
+  return create_per_cell(ctx, desc->n_blocks, desc->block_variable, desc->Alpha, desc->Beta, desc->mode, desc->lin_blocks, 0.0, out, nullptr, 0, 0, true);
 }
 
 // The same blocks of the operator WITH the CIP term (stfem_stokes_set_cip, weight STFEM_CIP_WEIGHT_LINEARISATION): K = the assembled

@@ -11,8 +11,9 @@
 //   stokes_cell_matrices_kernel   the cell's own (81 + npl)^2 matrix of A(b) and its 27 x 27 scalar mass, in plain matrix form
 //   stokes_vanka_assemble_kernel  restriction of the assembled matrices to the cell's DoFs, constraints, valence, Alpha / Beta
 //   vanka_invert_kernel<double>   (stfem_vanka.hip) Gauss-Jordan, straight into the apply's layout
-// Velocity degree 3 (stfem_stokes_vanka_create_space; FE_Q(3)^3 x FE_Q(2) / FE_DGP(2), the linear operator alone): the cell matrices come
-// from stfem_stokes_vanka_cell_q3.hip, the assembling kernel is instantiated for 64 nodes per component, the apply is told the degree.
+// Velocity degree 3 (stfem_stokes_vanka_create_space, _create_linearised_space; FE_Q(3)^3 x FE_Q(2) / FE_DGP(2), no weak faces, no CIP term):
+// the cell matrices of A(b) come from stfem_stokes_vanka_cell_q3.hip, a launch per state, the assembling kernel is instantiated for 64
+// nodes per component, the apply is told the degree.
 // Apply: stokes_vanka_apply_percell_kernel streams every block from HBM once and leaves the rows in the scratch array; the collecting
 // launch of stfem_stokes_vanka.hip sums them per DoF: two launches, no colours, no atomics, fixed summation order.
 #include "stfem_stokes_internal.h"
@@ -637,7 +638,7 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
     for (int i = 0; i < d.nblk; ++i) ap.selc[i] = selc[i];
   }
   const void *cipk = c->base.cart ? reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<false>);
-  const bool q3 = d.degree == 3; // (the linear operator alone: one state, no CIP term)
+  const bool q3 = d.degree == 3; // (no CIP term)
   const void *asmk = q3 ? reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<64>) : reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<27>);
   const void *cellk = c->pspace ? reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<false>);
   stfem_launch_begin();
@@ -651,7 +652,7 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
       mp.b = state[s];
       mp.Ac = d_A + size_t(s) * ap.state_stride;
       mp.Mc = s == 0 ? d_M : nullptr;
-      rc = q3 ? stokes_cell_matrices_q3_launch(c, mp.Ac, mp.Mc, mp.cell0, (unsigned)wcells)
+      rc = q3 ? stokes_cell_matrices_q3_launch(c, mp.Ac, mp.Mc, mp.cell0, (unsigned)wcells, d.mode, state[s])
               : vk_launch(cellk, dim3((unsigned)wcells), &mp, nullptr, "stokes_cell_matrices_kernel");
     }
     for (int s = 0; s < ncip && rc == STFEM_OK; ++s) {

@@ -571,7 +571,8 @@ using NavierStokesOperator =
 // Alpha / Beta over the blocks of the BlockSlice (K_mask empty, M_mask(0, 0) only), inverted.  The assembled matrices and DoF
 // handlers of the reference's constructor are not needed: the blocks follow from the operator (stfem_stokes_vanka_create; one block
 // per neighbour pattern on a box, one per cell on a general mesh and, second constructor, for the linearised operator).  An operator
-// of velocity degree 3 goes through stfem_stokes_vanka_create_space (first constructor only): one block per cell on every mesh.
+// of velocity degree 3 goes through stfem_stokes_vanka_create_space (first constructor) or stfem_stokes_vanka_create_linearised_space
+// (second constructor, delta0 == 0 only): one block per cell on every mesh.
 template <typename Number> class PreconditionVankaStokes {
   static_assert(std::is_same<Number, double>::value, "fp64");
 
@@ -619,6 +620,20 @@ public:
                      : nonlinear_treatment == NonlinearTreatment::Explicit ? STFEM_CONVECTION_FORM : STFEM_CONVECTION_JACOBIAN;
     const std::vector<const double *> l = linearization(solution_linearization);
     stfem_stokes_vanka *v = nullptr;
+    if (K.velocity_degree() != 2) { // FE_Q(3)^3 x FE_Q(2) / FE_DGP(2): the constructor by descriptor of the linearised blocks
+      if (delta0 != 0) throw Error(STFEM_ERR_UNSUPPORTED, "PreconditionVankaStokes: delta0 != 0 at velocity degree 3 (an operator of that degree has no CIP term)");
+      stfem_stokes_vanka_linearised_space_desc d{}; // (reserved: 0)
+      d.n_blocks = int32_t(nb_);
+      d.block_variable = var.data();
+      d.Alpha = Alpha.data();
+      d.Beta = Beta.data();
+      d.mode = mode;
+      d.lin_blocks = l.data();
+      const int rc = stfem_stokes_vanka_create_linearised_space(K.handle(), &d, &v);
+      if (rc != STFEM_OK) throw Error(rc, "stfem_stokes_vanka_create_linearised_space");
+      v_.reset(v, stfem_stokes_vanka_destroy);
+      return;
+    }
     const int rc = delta0 != 0 ? stfem_stokes_vanka_create_linearised_cip(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), mode, l.data(), delta0, &v)
                                : stfem_stokes_vanka_create_linearised(K.handle(), int(nb_), var.data(), Alpha.data(), Beta.data(), mode, l.data(), &v);
     if (rc != STFEM_OK) throw Error(rc, delta0 != 0 ? "stfem_stokes_vanka_create_linearised_cip" : "stfem_stokes_vanka_create_linearised");

@@ -20,8 +20,9 @@
  *     (operators.h:1554-1567).  A degree-3 context has no weak faces: there is no inflow term.  Pressure rows and constrained velocity
  *     rows are those of the linear operator, bit for bit.  One wave per cell, eight colour launches, plain loads and stores: no atomics,
  *     bitwise reproducible.  STFEM_CONVECTION_NONE: the entry of stfem.h, launch for launch.
- * Not built at degree 3: the convection term in the Vanka blocks (stfem_stokes_vanka_create_space stays linear), weak faces with their
- * inflow term, CIP, GMGStokes and the drivers, slabs, fp32. */
+ * The Vanka blocks of the operator in these modes: stfem_stokes_vanka_create_linearised_space (stfem_stokes_vanka_linearised_space.h;
+ * stfem_stokes_vanka_create_space stays linear).
+ * Not built at degree 3: weak faces with their inflow term, CIP, GMGStokes and the drivers, slabs, fp32. */
 int stfem_stokes_vmult_convection_space(stfem_stokes_ctx *ctx, int mode, double *dst_u, double *dst_p, const double *src_u,
                                         const double *src_p, const double *lin_u, void *stream);
 int stfem_stokes_st_vmult_convection_space(stfem_stokes_ctx *ctx, int mode, int n_timesteps_at_once, int n_timedofs,

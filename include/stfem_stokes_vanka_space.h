@@ -29,7 +29,9 @@
  * outside 0..1: STFEM_ERR_INVALID_ARGUMENT.
  * The handle is an ordinary stfem_stokes_vanka: stfem_stokes_vanka_step, _vmult, _update (lin_blocks is not read: the same blocks again,
  * bit for bit), _setup_batches, _n_classes (the cell count) and _destroy work on it unchanged.
- * Not built at degree 3: class blocks, convection modes, the CIP term, weak faces (a degree-3 context has none of them), slabs, fp32. */
+ * The blocks of the operator linearised about a velocity (the convection modes) come from the companion
+ * stfem_stokes_vanka_linearised_space.h (stfem_stokes_vanka_create_linearised_space); this entry stays linear.
+ * Not built at degree 3: class blocks, the CIP term, weak faces (a degree-3 context has neither), slabs, fp32. */
 typedef struct {
   int32_t n_blocks;
   const int32_t *block_variable; /* n_blocks entries, 0 velocity / 1 pressure, BlockSlice order */

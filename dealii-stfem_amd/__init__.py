@@ -946,8 +946,8 @@ class StokesMatrixFreeOperator:
         return tuple(out)
 
     def last_convection_plan(self):
-        """(workgroups, longest run of cells per wave - per half-wave at degree 2) of the last convection colour launch; at degree 3
-        STFEM_STOKES_Q3_WORKGROUPS caps the workgroups of those launches too.  A context that has launched no convection kernel
+        """(workgroups, longest run of cells per wave - per half-wave at degree 2) of the last convection colour launch;
+        STFEM_STOKES_Q3_WORKGROUPS caps the workgroups of those launches too, at either degree.  A context that has launched no convection kernel
         raises status -2."""
         out = (C.c_int32 * 2)()
         _check(lib().stfem_stokes_last_convection_plan(self._h, out), "stfem_stokes_last_convection_plan")

@@ -9,7 +9,7 @@
 // Every entry point describes its launches in ONE form, StokesParams (stfem_stokes_internal.h), put together by StokesLaunch below.
 // A context of velocity degree 3 (stfem_stokes_create_space) has one implementation of the linear cell operator, the same cell kernel
 // at DEG = 3 (stfem_stokes_cell.hip), and on top of it the convection launches of the Navier-Stokes modes alone
-// (stfem_stokes_convection_q3.hip), reached through the _space entries of stfem_stokes_convection_space.h: stokes_launch dispatches on
+// (the same kernel at DEG = 3, stfem_stokes_convection.hip), reached through the _space entries of stfem_stokes_convection_space.h: stokes_launch dispatches on
 // the degree, stokes_require_q2 refuses the rest
 // (beside the operator such a context has its per-cell Vanka smoother, stfem_stokes_vanka_create_space in stfem_stokes_vanka.hip).
 #include "stfem_stokes_internal.h"
@@ -506,7 +506,7 @@ int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double
   if (c->degree == 3) { // the linear cell operator, then the convection colours: all a degree-3 context has
     const int rc = stokes_cell_launch(c, prm, st);
     if (rc != STFEM_OK || mode == STFEM_CONVECTION_NONE) return rc;
-    return stokes_convection_q3_launch(c, prm, lin, mode, st);
+    return stokes_convection_launch(c, prm, lin, mode, st);
   }
   const int rc = c->scalar ? stokes_cart_launch(c, prm, st) : stokes_cell_launch(c, prm, st);
   if (rc != STFEM_OK) return rc;

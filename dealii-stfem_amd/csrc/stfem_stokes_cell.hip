@@ -40,11 +40,6 @@ template <int DEG> constexpr DgpDegrees<DEG> dgp_degrees()
   return r;
 }
 
-// Which 1D tables a lane holds in registers (Coef, with dot in stfem_stokes_internal.h).  The rows of its quadrature index (evaluation) always.  The columns of its node index
-// (integration) and the pressure tables at degree 2 only: at degree 3 they are 44 doubles more, and with all of them in registers
-// five of the eight instantiations need 256 VGPRs and spills to AGPRs, one wave per SIMD (profiles/stokes_q3.txt).
-template <int DEG> constexpr bool COLUMNS_HELD = DEG == 2;
-
 // 256 threads = 8 (degree 2) or 4 (degree 3) cells at a time; the workgroups walk over the cells.
 // Sum-factorised: evaluation and integration are three 1D stages each (x, y, z), handed from lane to lane through two wave-private
 // LDS regions per cell that alternate as source and destination, ordered with wave_fence() (a cell never leaves its wave: no
@@ -392,28 +387,16 @@ int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &set, hipStream_t st)
   // 2 on 64^3 cells, cG(1): 2 per CU 0.41 ms, 3: 0.50, 4: 0.43, 8: 0.45, one workgroup per 8 cells: 0.52 - long runs keep the prefetch
   // of the next cell's DoFs going and leave no partial round)
   static int resident_of[2][8] = {};
-  int &resident = resident_of[deg3][which];
-  if (resident < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, 256, 0) != hipSuccess || resident < 1)) resident = 2;
+  const int resident = stokes_resident(resident_of[deg3][which], kern);
   static const int grid_env = [] {
     const char *e = getenv("STFEM_STOKES_GRID"); // workgroups per CU of a colour launch at degree 2 (experiments)
     return e ? std::max(1, atoi(e)) : 0;
   }();
-  // STFEM_STOKES_Q3_WORKGROUPS=<n>, read at every launch: at most n workgroups per colour launch (tests: several cells per wave or
-  // half-wave on a small mesh)
-  long long cap = 0;
-  if (const char *e = getenv("STFEM_STOKES_Q3_WORKGROUPS")) cap = std::max(1ll, atoll(e));
   stfem_launch_begin();
-  for (int colour = 0; colour < 8; ++colour) { // ascending: see store_u / store_p
-    const long long n = (long long)((c->nc[0] - (colour & 1) + 1) / 2) * ((c->nc[1] - ((colour >> 1) & 1) + 1) / 2) *
-                        ((c->nc[2] - (colour >> 2) + 1) / 2);
-    if (n == 0) continue;
-    launch_colour = colour;
-    long long grid = std::min<long long>((n + cells - 1) / cells, (long long)c->n_cu * (grid_env && !deg3 ? grid_env : resident));
-    if (cap) grid = std::min(grid, cap);
-    (void)hipLaunchKernel(kern, dim3((unsigned)grid), dim3(256), args, 0, st);
+  stokes_colour_launches(c, cells, grid_env && !deg3 ? grid_env : resident, c->cell_plan, [&](int colour, unsigned grid) {
+    launch_colour = colour; // (ascending: see store_u / store_p)
+    (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
     c->cell_launched = true;
-    c->cell_plan[0] = (int)grid;
-    c->cell_plan[1] = (int)((n + grid * cells - 1) / (grid * cells));
-  }
+  });
   return stfem_launch_end("stokes_cell_kernel");
 }

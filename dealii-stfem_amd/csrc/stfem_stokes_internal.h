@@ -5,7 +5,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 constexpr int MAXOUT = 8; // destination pairs of a launch with one source
@@ -92,8 +94,9 @@ struct BoundaryParams {
 // the by-value argument of every kernel of the linear operator, stays what it is.
 //   out_u[o] += sum_s wKu[s][o] C(b_s, u_s),   C = C_form(b, u) (form) or C_form(b, u) + C_form(u, b) (jacobian),
 //   C_form(b, u)(v) = - int (u (x) b) : grad v  - int_{weak faces} min(b.n, 0) u.v
-// Geometry, tables and the weights are copied from the StokesParams of the same set; only destinations with a non-zero wKu are listed.
-struct ConvectionParams {
+// Geometry and tables are copied from the context's description of its degree, sources and weights from the StokesParams of the same
+// set; only destinations with a non-zero wKu are listed.  DEG: the velocity degree, as in StokesParamsT.
+template <int DEG> struct ConvectionParamsT {
   const double *vertices;
   int ncx, ncy, ncz;
   int ndu[3];
@@ -104,33 +107,18 @@ struct ConvectionParams {
   int nout;
   double *out_u[MAXOUT];
   double wKu[MAXSRC][MAXOUT];
-  double Su[9], Du[9];
-  double xq[3], wq[3];
+  double Su[(DEG + 1) * (DEG + 1)], Du[(DEG + 1) * (DEG + 1)]; // [q*(DEG+1)+a]
+  double xq[DEG + 1], wq[DEG + 1];
   int interleave, colour, cart;
   double hinv[3], detJ;
-  // the inflow term on the weak faces
+};
+// Degree 2 with the inflow term on the weak faces (a degree-3 context has none): what the launcher fills and the inflow kernel takes.
+// Not members of the common part: behind the degree-3 description they move the hidden kernel arguments (the grid size, read in
+// the prologue) into a 64-byte line of their own, 2 us per vmult on 32^3 cells of a box (profiles/stokes_convection_merge.txt)
+struct ConvectionParams : ConvectionParamsT<2> {
   int weak_mask;
   int foff[7];
   double Eu[6];
-};
-
-// The same at velocity degree 3 (stfem_stokes_convection_q3.hip): FE_Q(3) tables at the four Gauss points.  A degree-3 context has no
-// weak faces, so there is no inflow term and no face data.
-struct ConvectionQ3Params {
-  const double *vertices;
-  int ncx, ncy, ncz;
-  int ndu[3];
-  long long Nu;
-  int dmask;
-  int nsrc;
-  const double *us[MAXSRC], *bs[MAXSRC];
-  int nout;
-  double *out_u[MAXOUT];
-  double wKu[MAXSRC][MAXOUT];
-  double Su[16], Du[16]; // [q*4+a]
-  double xq[4], wq[4];
-  int colour, cart;
-  double hinv[3], detJ;
 };
 
 // The CIP interior-face launches (stfem_stokes_cip.hip), again a description of their own:
@@ -224,7 +212,7 @@ struct stfem_stokes_ctx {
   std::vector<CipBinding> cip_bindings;
 };
 
-template <typename Params> // (StokesParams or ConvectionParams)
+template <typename Params> // (StokesParamsT or ConvectionParamsT)
 __device__ __forceinline__ bool constrained_u(const Params &prm, int ix, int iy, int iz)
 {
   return ((prm.dmask & 1) && ix == 0) || ((prm.dmask & 2) && ix == prm.ndu[0] - 1) ||
@@ -240,7 +228,13 @@ __device__ __forceinline__ void wave_fence()
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// What the sum-factorised cell kernels (stfem_stokes_cell.hip, stfem_stokes_convection_q3.hip) share.
+// What the sum-factorised cell kernels (stokes_cell_kernel in stfem_stokes_cell.hip, stokes_convection_kernel in
+// stfem_stokes_convection.hip) share.
+// Which 1D tables a lane holds in registers (Coef, with dot below).  The rows of its quadrature index (evaluation) always.  The columns
+// of its node index (integration) and the pressure tables at degree 2 only: at degree 3 they are 44 doubles more, and with all of them
+// in registers five of the eight instantiations of the cell kernel need 256 VGPRs and spills to AGPRs, one wave per SIMD
+// (profiles/stokes_q3.txt).
+template <int DEG> constexpr bool COLUMNS_HELD = DEG == 2;
 // The lane's N coefficients p[0], p[STRIDE], ... of a 1D table in LDS: HELD - copied into registers once, for the whole kernel;
 // otherwise read where they are used.
 template <int N, int STRIDE, bool HELD> struct Coef {
@@ -270,6 +264,32 @@ template <int N, class W> __device__ __forceinline__ double dot(const W &w, cons
 #pragma unroll
   for (int n = 1; n < N; ++n) s = fma(w[n], x[n], s);
   return s;
+}
+// Their launchers: persistent workgroups, exactly as many as stay resident - asked once per instantiation (`cached`), not on the
+// launch path
+inline int stokes_resident(int &cached, const void *kern)
+{
+  if (cached < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&cached, kern, 256, 0) != hipSuccess || cached < 1)) cached = 2;
+  return cached;
+}
+// and the eight colour launches, ascending, like every colour sequence of the operator: launch(colour, grid) for every colour that has
+// cells, with min(ceil(n / cells), n_cu * per_cu) workgroups of `cells` cells at a time; plan = (workgroups, longest run of cells per
+// cell slot) of the last one.  STFEM_STOKES_Q3_WORKGROUPS=<n>, read at every call: at most n workgroups per colour launch (tests:
+// several cells per wave or half-wave on a small mesh)
+template <class Launch> inline void stokes_colour_launches(const stfem_stokes_ctx *c, int cells, int per_cu, int plan[2], Launch launch)
+{
+  long long cap = 0;
+  if (const char *e = getenv("STFEM_STOKES_Q3_WORKGROUPS")) cap = std::max(1ll, atoll(e));
+  for (int colour = 0; colour < 8; ++colour) {
+    const long long n = (long long)((c->nc[0] - (colour & 1) + 1) / 2) * ((c->nc[1] - ((colour >> 1) & 1) + 1) / 2) *
+                        ((c->nc[2] - (colour >> 2) + 1) / 2);
+    if (n == 0) continue;
+    long long grid = std::min<long long>((n + cells - 1) / cells, (long long)c->n_cu * per_cu);
+    if (cap) grid = std::min(grid, cap);
+    launch(colour, (unsigned)grid);
+    plan[0] = (int)grid;
+    plan[1] = (int)((n + grid * cells - 1) / (grid * cells));
+  }
 }
 
 // What the CIP kernel of the operator (stfem_stokes_cip.hip) and the CIP cell matrices of the per-cell Vanka blocks
@@ -343,14 +363,12 @@ void stokes_grad_launch(const CouplingParams &k, hipStream_t st);
 void stokes_div_launch(const CouplingParams &k, long long Np, hipStream_t st);
 // The eight colour launches of the boundary kernel (stfem_stokes_boundary.hip); d_g: the Dirichlet data of the rhs mode, or nullptr
 int stokes_boundary_launch(stfem_stokes_ctx *c, StokesParams &prm, const double *d_g, hipStream_t st);
-// The convection launches after those of `prm` (stfem_stokes_convection.hip): eight colour launches of the cell kernel, then, with weak
-// faces, eight of the inflow-face kernel.  mode: STFEM_CONVECTION_FORM / _JACOBIAN; lin[s]: the linearisation velocity of source s.
-// Nothing is launched when all wKu of the set are zero.
+// The convection launches after those of `prm` (stfem_stokes_convection.hip), at the context's degree: eight colour launches of the
+// cell kernel, then, with weak faces (degree 2), eight of the inflow-face kernel.  mode: STFEM_CONVECTION_FORM / _JACOBIAN; lin[s]: the
+// linearisation velocity of source s.  At degree 3 geometry and tables come from the context's base3 and `prm` gives the sources,
+// destinations and weights alone.  Nothing is launched when all wKu of the set are zero.  STFEM_STOKES_Q3_WORKGROUPS=<n>, read at
+// every launch, caps the workgroups of the colour launches at either degree, as it caps those of stokes_cell_launch.
 int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *lin, int mode, hipStream_t st);
-// The convection launches of a degree-3 context after the cell launches of `prm` (stfem_stokes_convection_q3.hip): eight colour launches,
-// geometry and tables from the context's base3, sources, destinations and weights from `prm`; mode and lin as above.
-// STFEM_STOKES_Q3_WORKGROUPS=<n>, read at every launch, caps their workgroups.
-int stokes_convection_q3_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *lin, int mode, hipStream_t st);
 // The CIP launches after those (stfem_stokes_cip.hip): eight colour launches; weight[s]: the weight velocity of source s.  Nothing is
 // launched with delta0 == 0, on a mesh without interior faces, for a colour without cells or when all wKu of the set are zero.
 int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, hipStream_t st);

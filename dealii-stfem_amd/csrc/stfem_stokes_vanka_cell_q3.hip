@@ -8,7 +8,7 @@
 //   Mc[cell][64][64]:        its scalar mass
 // With a convection mode (template parameter MODE, the linearisation velocity b of the state in the parameters) the velocity-velocity
 // entries are those of A(b): + C_form(b, .) (form) / + C_form(b, .) + C_form(., b) (jacobian), C_form(b, u)(v) = - int (u (x) b) : grad v
-// (operators.h:1554-1567), the forms stokes_convection_q3_kernel applies and phase 0 of stokes_cell_matrices_kernel holds at degree 2.
+// (operators.h:1554-1567), the forms stokes_convection_kernel<3, ...> applies and phase 0 of stokes_cell_matrices_kernel holds at degree 2.
 // b is read as read_dof_values reads it: an entry on a strongly constrained DoF is selected as 0, never loaded.  MODE 0 is the linear
 // operator alone and holds none of this.  A degree-3 context has no weak faces and no CIP term.
 //

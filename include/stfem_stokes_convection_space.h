@@ -36,9 +36,9 @@ int stfem_stokes_st_vmult_slice_add_convection_space(stfem_stokes_ctx *ctx, int 
 
 /* Diagnostic of the convection cell kernel, at either degree: out[0] = workgroups of the last convection colour launch of the context,
  * out[1] = the longest run of cells one wave (degree 3) or half-wave (degree 2) walked in it.  STFEM_STOKES_Q3_WORKGROUPS=<n> in the
- * environment, read at every launch, caps the workgroups of the convection colour launches at degree 3 (tests: several cells per wave
- * on a small mesh); those of degree 2 do not read it.  STFEM_ERR_UNSUPPORTED, with its reason in stfem_last_error, on a context that
- * has launched no convection kernel. */
+ * environment, read at every launch, caps the workgroups of the convection colour launches at either degree (tests: several cells per
+ * wave or half-wave on a small mesh).  STFEM_ERR_UNSUPPORTED, with its reason in stfem_last_error, on a context that has launched no
+ * convection kernel. */
 int stfem_stokes_last_convection_plan(const stfem_stokes_ctx *ctx, int32_t out[2]);
 
 #endif /* STFEM_STOKES_CONVECTION_SPACE_H */

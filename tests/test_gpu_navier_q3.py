@@ -1,5 +1,5 @@
 """GPU parity of the Navier-Stokes modes (form / jacobian) of the Stokes operator at velocity degree 3, FE_Q(3)^3 x FE_Q(2) / FE_DGP(2)
-with QGauss(4): csrc/stfem_stokes_convection_q3.hip through the _space entries of include/stfem_stokes_convection_space.h.
+with QGauss(4): stokes_convection_kernel<3, ...> of csrc/stfem_stokes_convection.hip through the _space entries of include/stfem_stokes_convection_space.h.
 
 Expected value: the linear part from the CPU oracle at pu = 3 (as tests/test_gpu_stokes_q3.py) plus the dense numpy restatement of the
 term (tests/navier_q3_reference.py).  Two bars, per block:

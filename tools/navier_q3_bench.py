@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""What the Navier-Stokes modes add to the degree-3 Stokes operator (FE_Q(3)^3 x FE_Q(2) / FE_DGP(2),
-StokesMatrixFreeOperator.with_degree(3, ...)): time per vmult and per cG(2) st_vmult in mode none / form / jacobian on 48^3 cells,
-box and perturbed mesh, both pressure spaces.  The yardstick is the linear vmult (mode none) of the same context in the same run; the
+"""What the Navier-Stokes modes add to the Stokes operator of velocity degree 3 (FE_Q(3)^3 x FE_Q(2) / FE_DGP(2), the default) or 2
+(FE_Q(2)^3 x FE_Q(1) / FE_DGP(1)), StokesMatrixFreeOperator.with_degree(degree, ...): time per vmult and per cG(2) st_vmult in mode
+none / form / jacobian on 48^3 cells, box and perturbed mesh, both pressure spaces.  The yardstick is the linear vmult (mode none) of the same context in the same run; the
 added time of a mode is reported as a fraction of it (for st_vmult: of the linear st_vmult beside it, and of the linear vmult).
 
 A window is `calls` back-to-back calls ended by a blocking download of one pressure vector, host clock; `calls` is chosen per variant
 from a first window so that a window lasts about WINDOW seconds.  Per configuration: a warm-up window per variant, then ROUNDS rounds
 alternating over the six variants; median (min .. max) over the rounds.  Run with no other GPU work in the same call:
-    python tools/navier_q3_bench.py [cells per direction ...]"""
+    python tools/navier_q3_bench.py [--degree 2|3] [cells per direction ...]"""
 import importlib
 import os
 import sys
@@ -23,10 +23,10 @@ MODES = (("none", 0), ("form", 1), ("jacobian", 2))
 Alpha, Beta, _, _ = stfem.get_fe_time_weights_stokes(stfem.CGP, 2, 1.0 / 64, 1)
 
 
-def measure(N, dg, perturbed):
+def measure(degree, N, dg, perturbed):
     nc = (N, N, N)
     verts = stfem.mesh_vertices(nc, distort=0.1, seed=7) if perturbed else None
-    op = stfem.StokesMatrixFreeOperator.with_degree(3, nc, vertices=verts, viscosity=0.01, dg_pressure=dg)
+    op = stfem.StokesMatrixFreeOperator.with_degree(degree, nc, vertices=verts, viscosity=0.01, dg_pressure=dg)
     rng = np.random.default_rng(0)
     var = [0, 0, 1, 1]
     src = [op.initialize_dof_vector(v, rng.uniform(-1, 1, 3 * op.n_velocity if v == 0 else op.n_pressure)) for v in var]
@@ -60,14 +60,17 @@ def measure(N, dg, perturbed):
 
 
 def main():
-    sizes = [int(a) for a in sys.argv[1:]] or [48]
+    args, degree = sys.argv[1:], 3
+    if args[:1] == ["--degree"]:
+        degree, args = int(args[1]), args[2:]
+    sizes = [int(a) for a in args] or [48]
     print(f"median (min .. max) of {ROUNDS} alternating rounds, a window of `calls` calls each (about {WINDOW} s); "
           "added = (mode - none) / linear vmult of the same context")
     for N in sizes:
         for perturbed in (False, True):
             for dg in (False, True):
-                op, calls, t = measure(N, dg, perturbed)
-                head = f"{N}^3 cells {'perturbed' if perturbed else 'box      '} Q3/{'FE_DGP2' if dg else 'FE_Q2':7s}"
+                op, calls, t = measure(degree, N, dg, perturbed)
+                head = f"{N}^3 cells {'perturbed' if perturbed else 'box      '} Q{degree}/{f'FE_DGP{degree - 1}' if dg else f'FE_Q{degree - 1}':7s}"
                 yard = t["vmult none"][0]
                 for name in t:
                     med, lo, hi = t[name]
@@ -79,7 +82,11 @@ def main():
                         if kind == "st_vmult":
                             line += f", {added / t['st_vmult none'][0]:5.2f} of the linear st_vmult"
                     print(line, flush=True)
-                print(f"{head} plans: cell {op.last_cell_plan()}, convection {op.last_convection_plan()}", flush=True)
+                try:
+                    cell = op.last_cell_plan()
+                except stfem.StfemError:  # (degree 2 on a box: the Kronecker path, no cell launch)
+                    cell = None
+                print(f"{head} plans: cell {cell}, convection {op.last_convection_plan()}", flush=True)
 
 
 if __name__ == "__main__":

@@ -354,9 +354,9 @@ void stokes_cip_end_tables(double Eu[6], double EDu[6]);
 // The eight colour launches of the cell kernel (stfem_stokes_cell.hip), at the context's degree: general meshes at degree 2, boxes
 // included at degree 3, where `prm` gives the sources, destinations and weights alone
 int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st);
-// The cell matrices of a degree-3 context for the per-cell Vanka blocks (stfem_stokes_vanka_cell_q3.hip): `count` cells from cell0,
-// Ac[cell][nl][nl] with nl = 192 + 27 (FE_Q(2)) or 10 (FE_DGP(2)), Mc[cell][64][64] (nullptr: not wanted)
-int stokes_cell_matrices_q3_launch(const stfem_stokes_ctx *c, double *Ac, double *Mc, long long cell0, unsigned count, int mode, const double *b);
+// The cell matrices of A(b) for the per-cell Vanka blocks (stfem_stokes_vanka_cell.hip), at the context's degree: `count` cells from cell0,
+// Ac[cell][nl][nl] with nl = 81 + 8 / 4 or 192 + 27 / 10 (FE_Q / FE_DGP pressure), Mc[cell][27 or 64][.] (nullptr: not wanted)
+int stokes_cell_matrices_launch(const stfem_stokes_ctx *c, double *Ac, double *Mc, long long cell0, unsigned count, int mode, const double *b);
 // The coupling kernels (stfem_stokes_coupling.hip): out_u -= sum_s wKu B^T p_s; out_p (=, +=) sum_s wKp B u_s.  A failed launch is
 // left to the caller's stfem_launch_end (stokes_cart_launch).
 void stokes_grad_launch(const CouplingParams &k, hipStream_t st);

@@ -410,7 +410,7 @@ int stfem_stokes_vanka_create_linearised(stfem_stokes_ctx *ctx, int n_blocks, co
 
 // The constructor by descriptor (include/stfem_stokes_vanka_space.h): velocity degree 2 is stfem_stokes_vanka_create_linearised with
 // STFEM_CONVECTION_NONE on its own path; degree 3 builds the same blocks (stmg.h:704-742, compute_block_matrix.h:50-139) from the cell
-// matrices of stfem_stokes_vanka_cell_q3.hip.  Every refusal is decided on the arguments, before the context or the device is touched.
+// matrices of the same kernel's degree-3 instantiations (stfem_stokes_vanka_cell.hip).  Every refusal is decided on the arguments, before the context or the device is touched.
 int stfem_stokes_vanka_create_space(stfem_stokes_ctx *ctx, const stfem_stokes_vanka_space_desc *desc, stfem_stokes_vanka **out)
 {
   const char *me = "stfem_stokes_vanka_create_space";
@@ -434,7 +434,7 @@ int stfem_stokes_vanka_create_space(stfem_stokes_ctx *ctx, const stfem_stokes_va
 
 // The same constructor for the operator linearised about lin_blocks (include/stfem_stokes_vanka_linearised_space.h): velocity degree 2
 // is stfem_stokes_vanka_create_linearised on its own path; degree 3 builds the blocks of A(b_j) per column block from the cell matrices
-// of stfem_stokes_vanka_cell_q3.hip in the mode, a launch per distinct state.  The refusals of stfem_stokes_vanka_create_space, then
+// of the same kernel's degree-3 instantiations in the mode, a launch per distinct state.  The refusals of stfem_stokes_vanka_create_space, then
 // those of the mode, all decided on the arguments before the context or the device is touched.
 int stfem_stokes_vanka_create_linearised_space(stfem_stokes_ctx *ctx, const stfem_stokes_vanka_linearised_space_desc *desc, stfem_stokes_vanka **out)
 {

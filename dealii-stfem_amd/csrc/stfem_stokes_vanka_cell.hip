@@ -8,12 +8,12 @@
 //   A(b) = [[nu K, -B^T], [B, 0]] + Nitsche terms of the weak faces + C_form(b, .) (form) / C_form(b, .) + C_form(., b) (jacobian),
 //   C_form(b, u)(v) = - int (u (x) b) : grad v - int_{weak faces} min(b.n, 0) u.v            (operators.h:1554-1567, 1738-1743).
 // Set-up on the device, a few cell layers at a time, in the stages of the scalar smoother (stfem_vanka.hip):
-//   stokes_cell_matrices_kernel   the cell's own (81 + npl)^2 matrix of A(b) and its 27 x 27 scalar mass, in plain matrix form
+//   stokes_cell_matrices_kernel   the cell's own (81 + npl)^2 matrix of A(b) and its 27 x 27 scalar mass, in plain matrix form, a launch per state
 //   stokes_vanka_assemble_kernel  restriction of the assembled matrices to the cell's DoFs, constraints, valence, Alpha / Beta
 //   vanka_invert_kernel<double>   (stfem_vanka.hip) Gauss-Jordan, straight into the apply's layout
-// Velocity degree 3 (stfem_stokes_vanka_create_space, _create_linearised_space; FE_Q(3)^3 x FE_Q(2) / FE_DGP(2), no weak faces, no CIP term):
-// the cell matrices of A(b) come from stfem_stokes_vanka_cell_q3.hip, a launch per state, the assembling kernel is instantiated for 64
-// nodes per component, the apply is told the degree.
+// Velocity degree 3 (stfem_stokes_vanka_create_space, _create_linearised_space; FE_Q(3)^3 x FE_Q(2) / FE_DGP(2) with QGauss(4), no weak
+// faces, no CIP term): the same kernels - the cell matrices (192 + npl)^2 and 64 x 64 from the degree's instantiation of the one
+// degree-templated kernel, the assembling kernel instantiated for 64 nodes per component, the apply told the degree.
 // Apply: stokes_vanka_apply_percell_kernel streams every block from HBM once and leaves the rows in the scratch array; the collecting
 // launch of stfem_stokes_vanka.hip sums them per DoF: two launches, no colours, no atomics, fixed summation order.
 #include "stfem_stokes_internal.h"
@@ -31,195 +31,250 @@ namespace vanka = stfem::vanka;
 
 namespace {
 
-struct StokesCellMatParams {
+// The description of stokes_cell_matrices_kernel: geometry and 1D tables are copied from the context's StokesParamsT<DEG>
+template <int DEG> struct StokesCellMatParamsT {
   const double *vertices; // (nc + 1)^3 x 3
-  const double *b;        // linearisation velocity (3 Nu, component-major); nullptr: none
-  double *Ac, *Mc;        // [cell of the window][nl][nl], [cell of the window][27][27] (nullptr: not wanted)
-  int nc[3], ndu[3];
-  long long Nu, cell0;    // first cell of the window
-  int dmask, weak_mask, mode;
-  double nu, gamma1, gamma2;
-  double xq[3], wq[3];
+  double *Ac, *Mc;        // [cell of the window][NL][NL], [cell of the window][NN][NN] (nullptr: not wanted)
+  int ncx, ncy, ncz;
+  long long cell0;        // first cell of the window
+  double nu;
+  double Su[(DEG + 1) * (DEG + 1)], Du[(DEG + 1) * (DEG + 1)], Sp[(DEG + 1) * DEG]; // [q*(DEG+1)+a], [q*(DEG+1)+a], [q*DEG+a]
+  double xq[DEG + 1], wq[DEG + 1], lq[DEG - 1][DEG + 1];
+  // read with a convection mode only (behind everything the linear kernel reads)
+  const double *b;        // linearisation velocity (3 Nu, component-major)
+  long long Nu;
+  int ndu[3], dmask;
 };
+// Degree 2 with the weak faces (a degree-3 context has none), as ConvectionParams holds them
+struct StokesCellMatParams : StokesCellMatParamsT<2> {
+  int weak_mask;
+  double gamma1, gamma2;
+  double Eu[6], EDu[6], Ep[4]; // the end-point tables of BoundaryParams
+};
+template <int DEG> using StokesCellMat = std::conditional_t<DEG == 2, StokesCellMatParams, StokesCellMatParamsT<DEG>>;
 
-// FE_Q(2) on the nodes 0, 1/2, 1 and FE_Q(1), value and derivative of node n at x
-__device__ __forceinline__ double q2v(int n, double x) { return n == 0 ? (2 * x - 1) * (x - 1) : (n == 1 ? 4 * x * (1 - x) : x * (2 * x - 1)); }
-__device__ __forceinline__ double q2d(int n, double x) { return n == 0 ? 4 * x - 3 : (n == 1 ? 4 - 8 * x : 4 * x - 1); }
-__device__ __forceinline__ double q1v(int n, double x) { return n == 0 ? 1 - x : x; }
-
-// One workgroup per cell; a thread takes entries (row, column) of the cell matrix.  Phase 0: the cell term at the operator's 3 x 3 x 3
-// Gauss points (MappingQ1 Jacobian from the eight vertices); phases 1 - 6: the Nitsche and inflow terms of the cell's weak faces at
-// their 3 x 3 points, h = sqrt(face area) (get_h_face, operators.h:184-209).  Set-up code: plain matrix form, not tuned.
-template <bool PDG>
-__global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesCellMatParams P)
+// Ac[cell][NL][NL]: the cell's own matrix of A(b), rows / columns: 3 x NN velocity DoFs (component-major, node a + N1 b + N1^2 c on the
+// Gauss-Lobatto nodes), then the DEG^3 FE_Q(DEG - 1) nodes or the FE_DGP(DEG - 1) functions in the order include/stfem_stokes_space.h
+// documents; Mc[cell][NN][NN]: its scalar mass.  MODE: 0 the linear operator alone, which holds nothing of b; 1 / 2 the forms
+// stokes_convection_kernel applies, b read as read_dof_values reads it: an entry on a strongly constrained DoF is selected as 0.
+// One workgroup per cell, plain matrix form: the physical gradients, values and pressure functions of all points are tabulated in LDS
+// from the 1D tables of the context - the ones its cell kernel applies, no closed form typed again -, then every thread takes entries
+// (row, column) and sums over the points in ascending order: a fixed summation order.  Degree 3: G 96 KiB + PH 32 KiB + PS 13.5 KiB +
+// geometry 5 KiB = 146.7 KiB of the 160 KiB a workgroup may declare on gfx950, one workgroup per CU; a mode adds b at the cell's nodes and
+// at the points, 1.5 KiB each.  Phase 0: the cell term at the operator's N1^3 Gauss points (MappingQ1 Jacobian from the eight vertices);
+// phases 1 - 6, degree 2 only: the Nitsche and inflow terms of the cell's weak faces at their 3 x 3 points, h = sqrt(face area)
+// (get_h_face, operators.h:184-209); there the 1D factor of the face's normal direction comes from the end-point tables.
+// Set-up code, not tuned.
+template <int DEG, bool PDG, int MODE>
+__global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesCellMat<DEG> P)
 {
-  constexpr int NPL = PDG ? 4 : 8, NL = 81 + NPL;
-  __shared__ double G[27][27][3]; // physical gradient of velocity node n at point q
-  __shared__ double PH[27][27];   // its value
-  __shared__ double PS[27][NPL];  // pressure functions
-  __shared__ double JI[27][9], W[27], NR[9][3], BQ[27][3], INF[9];
-  __shared__ double bl[81], V[8][3];
+  constexpr int N1 = DEG + 1, NQ = N1 * N1 * N1, NN = NQ, NV = 3 * NN;
+  constexpr int NPL = PDG ? (DEG == 2 ? 4 : 10) : DEG * DEG * DEG, NL = NV + NPL;
+  constexpr bool FACES = DEG == 2; // (a degree-3 context has no weak faces)
+  constexpr int NF = FACES ? 9 : 1;
+  __shared__ double G[NQ][NN][3]; // physical gradient of velocity node n at point q
+  __shared__ double PH[NQ][NN];   // its value
+  __shared__ double PS[NQ][NPL];  // pressure functions
+  __shared__ double JI[NQ][9], W[NQ];
+  __shared__ double tS[N1 * N1], tD[N1 * N1], tP[N1 * DEG], tL[DEG * N1], tX[N1], tW[N1]; // the 1D tables; Legendre [degree * N1 + q], degree 0 = 1
+  __shared__ double tE[FACES ? 6 : 1], tED[FACES ? 6 : 1], tEp[FACES ? 4 : 1], NR[NF][3];   // end-point tables [s * n + a]; normals of a face
+  __shared__ double bl[MODE ? NV : 1], BQ[MODE ? NQ : 1][3], INF[MODE ? NF : 1]; // b at the cell's nodes [component * NN + n] and at the points; inflow
   const int tid = threadIdx.x;
   const long long cell = P.cell0 + blockIdx.x;
-  const int cx = int(cell % P.nc[0]), cy = int((cell / P.nc[0]) % P.nc[1]), cz = int(cell / ((long long)P.nc[0] * P.nc[1]));
-  const int cc[3] = {cx, cy, cz};
-  double *Ac = P.Ac + (size_t)blockIdx.x * NL * NL;
-  if (tid < 24) {
-    const int v = tid / 3, d = tid % 3;
-    const long long nvx = P.nc[0] + 1, nvy = P.nc[1] + 1;
-    V[v][d] = P.vertices[3 * ((cx + (v & 1)) + nvx * ((cy + ((v >> 1) & 1)) + nvy * (long long)(cz + (v >> 2)))) + d];
+  const int cx = int(cell % P.ncx), cy = int((cell / P.ncx) % P.ncy), cz = int(cell / ((long long)P.ncx * P.ncy));
+  if (tid < N1 * N1) { tS[tid] = P.Su[tid]; tD[tid] = P.Du[tid]; }
+  if (tid < N1 * DEG) tP[tid] = P.Sp[tid];
+  if (tid < N1) {
+    tL[tid] = 1.0;
+#pragma unroll
+    for (int k = 1; k < DEG; ++k) tL[k * N1 + tid] = P.lq[k - 1][tid];
+    tX[tid] = P.xq[tid]; tW[tid] = P.wq[tid];
   }
-  if (tid < 81) { // read_dof_values: entries on strongly constrained DoFs read as 0
-    const int comp = tid / 27, n = tid % 27;
-    const int ix = 2 * cx + n % 3, iy = 2 * cy + (n / 3) % 3, iz = 2 * cz + n / 9;
-    const bool con = ((P.dmask & 1) && ix == 0) || ((P.dmask & 2) && ix == P.ndu[0] - 1) || ((P.dmask & 4) && iy == 0) ||
-                     ((P.dmask & 8) && iy == P.ndu[1] - 1) || ((P.dmask & 16) && iz == 0) || ((P.dmask & 32) && iz == P.ndu[2] - 1);
-    bl[tid] = (P.b && P.mode && !con) ? P.b[comp * P.Nu + ix + (long long)P.ndu[0] * (iy + (long long)P.ndu[1] * iz)] : 0.0;
+  if constexpr (FACES) {
+    if (tid < 6) { tE[tid] = P.Eu[tid]; tED[tid] = P.EDu[tid]; }
+    if (tid < 4) tEp[tid] = P.Ep[tid];
+  }
+  if constexpr (MODE != 0) {
+    if (tid < NV) { // read_dof_values: entries on strongly constrained DoFs read as 0
+      const int comp = tid / NN, n = tid % NN;
+      const int ix = DEG * cx + n % N1, iy = DEG * cy + (n / N1) % N1, iz = DEG * cz + n / (N1 * N1);
+      bl[tid] = constrained_u(P, ix, iy, iz) ? 0.0 : P.b[comp * P.Nu + ix + (long long)P.ndu[0] * (iy + (long long)P.ndu[1] * iz)];
+    }
   }
   __syncthreads();
-  for (int phase = 0; phase < 7; ++phase) {
-    const int f = phase - 1, fd = f >> 1, fs = f & 1; // the face of phases 1 - 6
-    if (phase > 0 && !((P.weak_mask >> f & 1) && cc[fd] == (fs ? P.nc[fd] - 1 : 0))) continue; // (uniform)
-    const int npts = phase == 0 ? 27 : 9;
-    const int t1 = fd == 0 ? 1 : 0;
-    // reference coordinates of point q
-    auto point = [&](int q, double (&xi)[3]) {
-      if (phase == 0) {
-        xi[0] = P.xq[q % 3]; xi[1] = P.xq[(q / 3) % 3]; xi[2] = P.xq[q / 9];
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xi[k] = k == fd ? double(fs) : P.xq[k == t1 ? q % 3 : q / 3];
-      }
+  double *Ac = P.Ac + (size_t)blockIdx.x * NL * NL;
+  for (int phase = 0; phase < (FACES ? 7 : 1); ++phase) {
+    const bool face = FACES && phase > 0;
+    const int f = phase - 1, fd = f >> 1, fs = f & 1, t1 = fd == 0 ? 1 : 0; // the face of phases 1 - 6, its lower tangential direction
+    if constexpr (FACES) {
+      const int cd = fd == 0 ? cx : (fd == 1 ? cy : cz), ncd = fd == 0 ? P.ncx : (fd == 1 ? P.ncy : P.ncz);
+      if (face && !((P.weak_mask >> f & 1) && cd == (fs ? ncd - 1 : 0))) continue; // (uniform)
+    }
+    // (the sums of the entries run to npts, not to NQ: at degree 2, where it is a run-time value, the compiler then leaves them rolled -
+    // unrolled over the 27 points they take 256 VGPRs, one wave per SIMD for three or four, and an update of the blocks of 32^3 cells
+    // 92 ms for 75: profiles/stokes_cell_matrices_merge.txt, section 3)
+    const int npts = face ? NF : NQ;
+    // direction k is the normal one of the face: the 1D factors there are the end-point tables'; in every other direction those of
+    // the 1D Gauss point of point q, q = qa + N1 qb + N1^2 qc in the cell and lower tangential index fastest on a face
+    auto normal = [&](int k) { return face && k == fd; };
+    auto q1d = [&](int q, int k) {
+      if (face) return k == t1 ? q % 3 : q / 3;
+      return k == 0 ? q % N1 : (k == 1 ? (q / N1) % N1 : q / (N1 * N1));
     };
-    // ---- geometry of the points
+    auto su = [&](int q, int k, int a) { return normal(k) ? tE[fs * 3 + a] : tS[q1d(q, k) * N1 + a]; };
+    auto du = [&](int q, int k, int a) { return normal(k) ? tED[fs * 3 + a] : tD[q1d(q, k) * N1 + a]; };
+    auto sp = [&](int q, int k, int a) { return normal(k) ? tEp[fs * DEG + a] : tP[q1d(q, k) * DEG + a]; };
+    auto lv = [&](int q, int k, int dg) { return normal(k) ? (dg ? (fs ? sqrt(3.0) : -sqrt(3.0)) : 1.0) : tL[dg * N1 + q1d(q, k)]; }; // l_1(s) = sqrt 3 (2 s - 1)
+    // ---- geometry of the points: MappingQ1 from the eight vertices
     if (tid < npts) {
-      double xi[3];
-      point(tid, xi);
-      const double fx[2] = {1 - xi[0], xi[0]}, fy[2] = {1 - xi[1], xi[1]}, fz[2] = {1 - xi[2], xi[2]}, dd[2] = {-1.0, 1.0};
-      double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-      for (int k = 0; k < 2; ++k)
-        for (int j = 0; j < 2; ++j)
-          for (int i = 0; i < 2; ++i)
-            for (int d = 0; d < 3; ++d) {
-              const double Vd = V[i + 2 * j + 4 * k][d];
-              J[d][0] += Vd * dd[i] * fy[j] * fz[k];
-              J[d][1] += Vd * fx[i] * dd[j] * fz[k];
-              J[d][2] += Vd * fx[i] * fy[j] * dd[k];
-            }
-      const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-                         J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-      const double id = 1.0 / det;
-      double *Ji = JI[tid]; // Ji[3 e + d] = d xi_e / d x_d
-      Ji[0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
-      Ji[1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-      Ji[2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-      Ji[3] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
-      Ji[4] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-      Ji[5] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-      Ji[6] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
-      Ji[7] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-      Ji[8] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-      if (phase == 0) {
-        W[tid] = det * P.wq[tid % 3] * P.wq[(tid / 3) % 3] * P.wq[tid / 9];
+      double xi[3], Ji[3][3], det;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) xi[k] = normal(k) ? double(fs) : tX[q1d(tid, k)];
+      cip_jacobian(P, cx, cy, cz, xi, Ji, det);
+#pragma unroll
+      for (int e = 0; e < 3; ++e)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) JI[tid][3 * e + d] = Ji[e][d]; // d xi_e / d x_d
+      if (!face) {
+        W[tid] = det * tW[q1d(tid, 0)] * tW[q1d(tid, 1)] * tW[q1d(tid, 2)];
       } else {
         double mm[3], len = 0.0;
         for (int k = 0; k < 3; ++k) {
-          mm[k] = (fs ? 1.0 : -1.0) * Ji[3 * fd + k];
+          mm[k] = (fs ? 1.0 : -1.0) * JI[tid][3 * fd + k];
           len += mm[k] * mm[k];
         }
         len = sqrt(len);
         for (int k = 0; k < 3; ++k) NR[tid][k] = mm[k] / len;
-        W[tid] = fabs(det) * len * P.wq[tid % 3] * P.wq[tid / 3];
+        W[tid] = fabs(det) * len * tW[tid % 3] * tW[tid / 3];
       }
     }
     __syncthreads();
     // ---- the functions at the points
-    for (int e = tid; e < npts * 27; e += 256) {
-      const int q = e / 27, n = e % 27, a = n % 3, b = (n / 3) % 3, c = n / 9;
-      double xi[3];
-      point(q, xi);
-      const double sx = q2v(a, xi[0]), sy = q2v(b, xi[1]), sz = q2v(c, xi[2]);
-      const double gr[3] = {q2d(a, xi[0]) * sy * sz, sx * q2d(b, xi[1]) * sz, sx * sy * q2d(c, xi[2])};
+    for (int e = tid; e < npts * NN; e += 256) {
+      const int q = e / NN, n = e % NN, a = n % N1, b = (n / N1) % N1, c = n / (N1 * N1);
+      const double sx = su(q, 0, a), sy = su(q, 1, b), sz = su(q, 2, c);
+      const double gr[3] = {du(q, 0, a) * sy * sz, sx * du(q, 1, b) * sz, sx * sy * du(q, 2, c)};
       const double *Ji = JI[q];
       PH[q][n] = sx * sy * sz;
+#pragma unroll
       for (int d = 0; d < 3; ++d) G[q][n][d] = gr[0] * Ji[d] + gr[1] * Ji[3 + d] + gr[2] * Ji[6 + d];
     }
     for (int e = tid; e < npts * NPL; e += 256) {
       const int q = e / NPL, l = e % NPL;
-      double xi[3];
-      point(q, xi);
-      // FE_DGP(1): deal.II's basis 1, l(xi), l(eta), l(zeta), l(x) = sqrt 3 (2 x - 1)
-      if (PDG) PS[q][l] = l == 0 ? 1.0 : 1.7320508075688772 * (2.0 * xi[l - 1] - 1.0);
-      else PS[q][l] = q1v(l & 1, xi[0]) * q1v((l >> 1) & 1, xi[1]) * q1v(l >> 2, xi[2]);
+      if (PDG) { // l_i(xi) l_j(eta) l_k(zeta), i + j + k <= DEG - 1, i fastest; degree 2: deal.II's basis 1, l_1(xi), l_1(eta), l_1(zeta)
+        const int di = DEG == 2 ? l == 1 : ((l == 1 || l == 4 || l == 7) ? 1 : (l == 2 ? 2 : 0));
+        const int dj = DEG == 2 ? l == 2 : ((l == 3 || l == 4 || l == 8) ? 1 : (l == 5 ? 2 : 0));
+        const int dk = DEG == 2 ? l == 3 : ((l == 6 || l == 7 || l == 8) ? 1 : (l == 9 ? 2 : 0));
+        PS[q][l] = lv(q, 0, di) * lv(q, 1, dj) * lv(q, 2, dk);
+      } else {
+        PS[q][l] = sp(q, 0, l % DEG) * sp(q, 1, (l / DEG) % DEG) * sp(q, 2, l / (DEG * DEG));
+      }
     }
     __syncthreads();
-    if (tid < npts * 3) {
-      const int q = tid / 3, comp = tid % 3;
-      double s = 0.0;
-      for (int n = 0; n < 27; ++n) s += PH[q][n] * bl[comp * 27 + n];
-      BQ[q][comp] = s;
-    }
-    __syncthreads();
-    double h = 1.0;
-    if (phase > 0) {
-      double area = 0.0;
-      for (int q = 0; q < 9; ++q) area += W[q];
-      h = sqrt(area);
-      if (tid < 9) INF[tid] = P.mode ? -fmin(BQ[tid][0] * NR[tid][0] + BQ[tid][1] * NR[tid][1] + BQ[tid][2] * NR[tid][2], 0.0) * W[tid] : 0.0;
+    if constexpr (MODE != 0) { // ---- b at the points, nodes ascending
+      if (tid < npts * 3) {
+        const int q = tid / 3, comp = tid % 3;
+        double s = 0.0;
+        for (int n = 0; n < NN; ++n) s += PH[q][n] * bl[comp * NN + n];
+        BQ[q][comp] = s;
+      }
       __syncthreads();
     }
-    const double g1h = P.gamma1 / h, g2h = P.gamma2 / h;
+    double g1h = 0.0, g2h = 0.0;
+    if constexpr (FACES) {
+      if (face) {
+        double area = 0.0;
+        for (int q = 0; q < 9; ++q) area += W[q];
+        const double h = sqrt(area);
+        g1h = P.gamma1 / h;
+        g2h = P.gamma2 / h;
+        if constexpr (MODE != 0) {
+          if (tid < 9) INF[tid] = -fmin(BQ[tid][0] * NR[tid][0] + BQ[tid][1] * NR[tid][1] + BQ[tid][2] * NR[tid][2], 0.0) * W[tid];
+          __syncthreads();
+        }
+      }
+    }
     // ---- the entries
     for (int e = tid; e < NL * NL; e += 256) {
       const int r = e / NL, c = e % NL;
       double acc = 0.0;
-      if (r < 81 && c < 81) {
-        const int ci = r / 27, a = r % 27, cj = c / 27, b = c % 27;
-        for (int q = 0; q < npts; ++q) {
-          const double *ga = G[q][a], *gb = G[q][b];
-          const double pa = PH[q][a], pb = PH[q][b];
-          double t = 0.0;
-          if (phase == 0) {
-            if (ci == cj) {
-              t = P.nu * (ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2]);
-              if (P.mode) t -= pb * (BQ[q][0] * ga[0] + BQ[q][1] * ga[1] + BQ[q][2] * ga[2]); // - (u (x) b) : grad v
-            }
-            if (P.mode == 2) t -= BQ[q][ci] * pb * ga[cj];                                    // - (b (x) u) : grad v
-            acc += W[q] * t;
-          } else {
-            const double *n = NR[q];
+      if (r < NV && c < NV) {
+        const int ci = r / NN, a = r % NN, cj = c / NN, b = c % NN;
+        if (face) {
+          for (int q = 0; q < npts; ++q) {
+            const double *ga = G[q][a], *gb = G[q][b], *n = NR[q];
+            const double pa = PH[q][a], pb = PH[q][b];
+            double t = 0.0;
             if (ci == cj) {
               const double dna = ga[0] * n[0] + ga[1] * n[1] + ga[2] * n[2], dnb = gb[0] * n[0] + gb[1] * n[1] + gb[2] * n[2];
               t = -P.nu * dnb * pa + g1h * pa * pb - P.nu * pb * dna;
             }
             t += g2h * n[ci] * n[cj] * pa * pb;
             acc += W[q] * t;
-            if (ci == cj) acc += INF[q] * pa * pb; // - min(b.n, 0) u.v
+            if (MODE != 0 && ci == cj) acc += INF[q] * pa * pb; // - min(b.n, 0) u.v
           }
+        } else if constexpr (MODE == 0) {
+          if (ci == cj)
+            for (int q = 0; q < npts; ++q) {
+              const double *ga = G[q][a], *gb = G[q][b];
+              acc += W[q] * (P.nu * (ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2]));
+            }
+        } else if (ci == cj) {
+          for (int q = 0; q < npts; ++q) {
+            const double *ga = G[q][a], *gb = G[q][b], *bq = BQ[q];
+            const double pb = PH[q][b];
+            const double visc = P.nu * (ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2]), bga = bq[0] * ga[0] + bq[1] * ga[1] + bq[2] * ga[2];
+            // - (u (x) b) : grad v.  Which of the two products is fused into the subtraction decides the last bit: left to the compiler it
+            // is the first, and the blocks of degree 3 are those; the blocks of degree 2 have the second fused, and every result recorded
+            // for them is compared bit for bit (profiles/stokes_cell_matrices_merge.txt, section 2)
+            double t = DEG == 2 ? fma(-pb, bga, visc) : visc - pb * bga;
+            if (MODE == 2) t -= bq[ci] * pb * ga[cj];                  // - (b (x) u) : grad v
+            acc += W[q] * t;
+          }
+        } else if (MODE == 2) {
+          for (int q = 0; q < npts; ++q) acc += W[q] * -(BQ[q][ci] * PH[q][b] * G[q][a][cj]);
         }
-      } else if (r < 81) { // - p div v; faces: p n.v
-        const int ci = r / 27, a = r % 27, l = c - 81;
-        for (int q = 0; q < npts; ++q)
-          acc += phase == 0 ? -W[q] * PS[q][l] * G[q][a][ci] : W[q] * PS[q][l] * NR[q][ci] * PH[q][a];
-      } else if (c < 81) { // q div u; faces: - q u.n
-        const int cj = c / 27, b = c % 27, l = r - 81;
-        for (int q = 0; q < npts; ++q)
-          acc += phase == 0 ? W[q] * PS[q][l] * G[q][b][cj] : -W[q] * PS[q][l] * NR[q][cj] * PH[q][b];
+      } else if (r < NV) { // - p div v; faces: p n.v
+        const int ci = r / NN, a = r % NN, l = c - NV;
+        for (int q = 0; q < npts; ++q) acc += face ? W[q] * PS[q][l] * NR[q][ci] * PH[q][a] : -W[q] * PS[q][l] * G[q][a][ci];
+      } else if (c < NV) { // q div u; faces: - q u.n
+        const int cj = c / NN, b = c % NN, l = r - NV;
+        for (int q = 0; q < npts; ++q) acc += face ? -W[q] * PS[q][l] * NR[q][cj] * PH[q][b] : W[q] * PS[q][l] * G[q][b][cj];
       }
-      if (phase == 0) Ac[e] = acc;
+      if (!face) Ac[e] = acc;
       else Ac[e] += acc; // (the same thread wrote the entry in the phases before)
     }
-    if (phase == 0 && P.Mc) {
-      double *Mc = P.Mc + (size_t)blockIdx.x * 729;
-      for (int e = tid; e < 729; e += 256) {
-        const int a = e / 27, b = e % 27;
+    if (!face && P.Mc) {
+      double *Mc = P.Mc + (size_t)blockIdx.x * NN * NN;
+      for (int e = tid; e < NN * NN; e += 256) {
+        const int a = e / NN, b = e % NN;
         double s = 0.0;
-        for (int q = 0; q < 27; ++q) s += W[q] * PH[q][a] * PH[q][b];
+        for (int q = 0; q < NQ; ++q) s += W[q] * PH[q][a] * PH[q][b];
         Mc[e] = s;
       }
     }
-    __syncthreads(); // the next phase rewrites the tables
+    if constexpr (FACES) __syncthreads(); // the next phase rewrites the tables
   }
+}
+
+template <int DEG>
+void cell_matrices_describe(StokesCellMatParamsT<DEG> &p, const stfem_stokes_ctx *c, const StokesParamsT<DEG> &g, double *Ac, double *Mc, long long cell0, const double *b)
+{
+  constexpr int N1 = DEG + 1;
+  p.vertices = c->d_vertices;
+  p.Ac = Ac; p.Mc = Mc;
+  p.ncx = c->nc[0]; p.ncy = c->nc[1]; p.ncz = c->nc[2];
+  p.cell0 = cell0;
+  p.nu = c->nu;
+  for (int i = 0; i < N1 * N1; ++i) { p.Su[i] = g.Su[i]; p.Du[i] = g.Du[i]; }
+  for (int i = 0; i < N1 * DEG; ++i) p.Sp[i] = g.Sp[i];
+  for (int i = 0; i < N1; ++i) {
+    p.xq[i] = g.xq[i]; p.wq[i] = g.wq[i];
+    for (int k = 0; k < DEG - 1; ++k) p.lq[k][i] = g.lq[k][i];
+  }
+  p.b = b;
+  p.Nu = c->Nu; p.dmask = c->dmask;
+  for (int i = 0; i < 3; ++i) p.ndu[i] = c->ndu[i];
 }
 
 constexpr int CIP_CELL = 27 * 7 * 27; // doubles of a cell's CIP matrix
@@ -532,6 +587,38 @@ __global__ __launch_bounds__(256) void stokes_vanka_apply_percell_kernel(const S
 
 } // namespace
 
+int stokes_cell_matrices_launch(const stfem_stokes_ctx *c, double *Ac, double *Mc, long long cell0, unsigned count, int mode, const double *b)
+{
+  // the window must lie in the mesh: the kernel reads the vertices of cells [cell0, cell0 + count)
+  const long long ncells = (long long)c->nc[0] * c->nc[1] * c->nc[2];
+  if (cell0 < 0 || cell0 + (long long)count > ncells)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stokes_cell_matrices_kernel: cells [%lld, %lld) of %lld", cell0, cell0 + (long long)count, ncells);
+  if (mode < 0 || mode > 2 || (mode != 0 && !b))
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stokes_cell_matrices_kernel: mode %d%s", mode, mode >= 0 && mode <= 2 ? " without its linearisation velocity" : "");
+#define STFEM_CELL_MATRICES(DEG, PDG) \
+  {reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<DEG, PDG, 0>), reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<DEG, PDG, 1>), \
+   reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<DEG, PDG, 2>)}
+  static const void *const kernels[2][2][3] = {{STFEM_CELL_MATRICES(2, false), STFEM_CELL_MATRICES(2, true)},
+                                               {STFEM_CELL_MATRICES(3, false), STFEM_CELL_MATRICES(3, true)}}; // [degree - 2][pspace][mode]
+#undef STFEM_CELL_MATRICES
+  StokesCellMatParams p2;
+  StokesCellMatParamsT<3> p3;
+  std::memset(&p2, 0, sizeof(p2));
+  std::memset(&p3, 0, sizeof(p3));
+  const bool q3 = c->degree == 3;
+  if (q3) {
+    cell_matrices_describe(p3, c, c->base3, Ac, Mc, cell0, mode ? b : nullptr);
+  } else {
+    cell_matrices_describe(p2, c, c->base, Ac, Mc, cell0, mode ? b : nullptr);
+    const BoundaryParams &w = c->bnd; // (all zero until stfem_stokes_set_weak_boundaries)
+    p2.weak_mask = w.weak_mask; p2.gamma1 = w.gamma1; p2.gamma2 = w.gamma2;
+    for (int i = 0; i < 6; ++i) { p2.Eu[i] = w.Eu[i]; p2.EDu[i] = w.EDu[i]; }
+    for (int i = 0; i < 4; ++i) p2.Ep[i] = w.Ep[i];
+  }
+  return vk_launch(kernels[q3][c->pspace ? 1 : 0][mode], dim3(count), q3 ? static_cast<void *>(&p3) : static_cast<void *>(&p2), nullptr,
+                   "stokes_cell_matrices_kernel");
+}
+
 struct stokes_cell_vanka {
   stfem_stokes_ctx *ctx = nullptr;   // the context of the apply: its cells index the blocks
   stfem_stokes_ctx *setup = nullptr; // the context of the set-up (ctx, or a slab's extended context); own layers [own0, own0 + ctx->nc[2])
@@ -608,12 +695,6 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
     return rc;
   }
   hipError_t e = hipMemset(d_flag, 0, sizeof(int));
-  StokesCellMatParams mp;
-  std::memset(&mp, 0, sizeof(mp));
-  mp.vertices = c->d_vertices;
-  for (int k = 0; k < 3; ++k) { mp.nc[k] = c->nc[k]; mp.ndu[k] = c->ndu[k]; mp.xq[k] = c->base.xq[k]; mp.wq[k] = c->base.wq[k]; }
-  mp.Nu = c->Nu; mp.dmask = c->dmask; mp.weak_mask = c->weak_mask; mp.mode = d.mode;
-  mp.nu = c->nu; mp.gamma1 = c->nu * c->penalty1; mp.gamma2 = c->penalty2;
   StokesAssembleParams ap;
   std::memset(&ap, 0, sizeof(ap));
   ap.Ac = d_A; ap.Mc = d_M; ap.state_stride = win_cells * nl2; ap.B = d_B;
@@ -640,21 +721,14 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
   const void *cipk = c->base.cart ? reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<false>);
   const bool q3 = d.degree == 3; // (no CIP term)
   const void *asmk = q3 ? reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<64>) : reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<27>);
-  const void *cellk = c->pspace ? reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<false>);
   stfem_launch_begin();
   v->setup_batches = 0;
   for (int z0 = own0; z0 < own1 && e == hipSuccess && rc == STFEM_OK; z0 += L) {
     ++v->setup_batches;
     const int z1 = std::min(own1, z0 + L), zw0 = std::max(0, z0 - 1), zw1 = std::min(ncz, z1 + 1);
     const size_t wcells = cpl * size_t(zw1 - zw0), bcells = cpl * size_t(z1 - z0);
-    mp.cell0 = (long long)cpl * zw0;
-    for (int s = 0; s < nstates && rc == STFEM_OK; ++s) {
-      mp.b = state[s];
-      mp.Ac = d_A + size_t(s) * ap.state_stride;
-      mp.Mc = s == 0 ? d_M : nullptr;
-      rc = q3 ? stokes_cell_matrices_q3_launch(c, mp.Ac, mp.Mc, mp.cell0, (unsigned)wcells, d.mode, state[s])
-              : vk_launch(cellk, dim3((unsigned)wcells), &mp, nullptr, "stokes_cell_matrices_kernel");
-    }
+    for (int s = 0; s < nstates && rc == STFEM_OK; ++s)
+      rc = stokes_cell_matrices_launch(c, d_A + size_t(s) * ap.state_stride, s == 0 ? d_M : nullptr, (long long)cpl * zw0, (unsigned)wcells, d.mode, state[s]);
     for (int s = 0; s < ncip && rc == STFEM_OK; ++s) {
       cp.w = weight[s];
       cp.Cc = d_C + size_t(s) * ap.cip_stride;

@@ -143,6 +143,10 @@ CASES = {
     "box223_form_dgp": ((2, 2, 3), False, 1, True, 1, 1, 1, 63, 0, True),
     "box222_jac_dgp_2steps": ((2, 2, 2), False, 2, True, 1, 1, 2, 63, 0, True),  # 8 blocks, 340 rows
     "cell_jac_dgp": ((1, 1, 1), False, 2, True, 0, 1, 1, 0, 0, True),        # one unconstrained cell: the exact inverse
+    # the weak-face terms beyond the x faces of pert322_jac_weak: y and z faces, both sides, FE_DGP on a face, every mode on a face
+    "pert222_form_dgp_weak_all": ((2, 2, 2), True, 1, True, 0, 1, 1, 0, 63, True),  # all six faces weak, FE_DGP, form
+    "pert222_lin_weak_yz": ((2, 2, 2), True, 0, False, 0, 1, 1, 3, 60, True),       # y and z faces weak, no mode, x faces strong
+    "pert222_jac_weak_all": ((2, 2, 2), True, 2, False, 0, 1, 1, 0, 63, True),      # all six faces weak, FE_Q, jacobian
 }
 RELAX = ((3, 3, 2), True, 2, True, 0, 1, 1, 63, 0, True)
 RELAX_NU, RELAX_B, RELAX_OMEGA, RELAX_SWEEPS = 1.0, 0.5, 0.5, 8

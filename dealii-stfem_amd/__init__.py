@@ -265,6 +265,20 @@ VANKA_LINEARISED_SPACE_SIGNATURES = {
     "stfem_stokes_vanka_create_linearised_space": (C.c_int, [_vp, C.POINTER(_StokesVankaLinearisedSpaceDesc), C.POINTER(_vp)]),
 }
 
+# every symbol the companion header include/stfem_stokes_pressure_space.h declares (tests/test_stokes_pressure_space_header_cpu.py)
+PRESSURE_SPACE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "stfem_stokes_pressure_space.h")
+PRESSURE_SPACE_SIGNATURES = {
+    "stfem_stokes_get_space": (C.c_int, [_vp, C.POINTER(_StokesSpaceDesc)]),
+    "stfem_stokes_pressure_ctx_space": SIGNATURES["stfem_stokes_pressure_ctx"],
+    "stfem_stokes_pressure_mean_vectors_space": SIGNATURES["stfem_stokes_pressure_mean_vectors"],
+    "stfem_stokes_pressure_quadrature_points_space": SIGNATURES["stfem_stokes_pressure_quadrature_points"],
+    "stfem_stokes_pressure_difference_space": SIGNATURES["stfem_stokes_pressure_difference"],
+    "stfem_stokes_dgp_prolongate_space": SIGNATURES["stfem_stokes_dgp_prolongate"],
+    "stfem_stokes_dgp_restrict_space": SIGNATURES["stfem_stokes_dgp_restrict"],
+    "stfem_stokes_divergence_space": SIGNATURES["stfem_stokes_divergence"],
+    "stfem_stokes_last_divergence_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+}
+
 
 def lib():
     """Loads the HIP library; raises (never falls back) if it has not been built."""
@@ -275,7 +289,8 @@ def lib():
                               "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(os.environ.get("STFEM_LIB", LIB_PATH))  # STFEM_LIB: experiment builds only
         for name, (res, args) in (list(SIGNATURES.items()) + list(SPACE_SIGNATURES.items()) + list(VANKA_SPACE_SIGNATURES.items()) +
-                                  list(CONVECTION_SPACE_SIGNATURES.items()) + list(VANKA_LINEARISED_SPACE_SIGNATURES.items())):
+                                  list(CONVECTION_SPACE_SIGNATURES.items()) + list(VANKA_LINEARISED_SPACE_SIGNATURES.items()) +
+                                  list(PRESSURE_SPACE_SIGNATURES.items())):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -880,8 +895,8 @@ class StokesMatrixFreeOperator:
     vmult / st_vmult / st_vmult_slice_add take the convection mode (CONVECTION_FORM / CONVECTION_JACOBIAN) and the linearisation
     velocity `lin` that the reference's set_data hands in; with the defaults they are the linear operator.  delta0 != 0 adds the
     CIP interior-face stabilisation (operators.h:1605-1633) to all of them, see set_cip.  with_degree(3, ...): FE_Q(3)^3 x FE_Q(2) /
-    FE_DGP(2), the linear cell operator with the convection modes (cell term; no weak faces), and StokesPreconditionVanka.for_space
-    over the linear operator."""
+    FE_DGP(2), the linear cell operator with the convection modes (cell term; no weak faces), StokesPreconditionVanka.for_space
+    over it, the pressure space helpers and divergence_space."""
 
     def __init__(self, ncell, vertices=None, lower=(0, 0, 0), upper=(1, 1, 1), dirichlet_mask=63,
                  viscosity=1.0, velocity_degree=2, device=0, weak_boundary_ids=(), outflow_boundary_ids=(),
@@ -932,8 +947,11 @@ class StokesMatrixFreeOperator:
         QGauss(4) - the pair of the reference's time degree 2 - with the cell operator alone: vmult, mass_vmult, st_vmult, st_Tvmult,
         st_vmult_slice_add, with the convection modes (lin=, mode=: the cell term); its smoother is StokesPreconditionVanka.for_space,
         over the linear operator.  Weak / outflow ids, delta0 != 0 and everything else raise StfemError with status -2 and the reason.
-        An operator made here sends lin= / mode= through the _space entries of include/stfem_stokes_convection_space.h (at degree 2
-        the entries of the constructor's operator, bit for bit)."""
+        An operator made here sends lin= / mode= through the _space entries of include/stfem_stokes_convection_space.h, and
+        pressure_mean_vectors, pressure_quadrature_points, pressure_difference, pressure_ctx and (between two such operators)
+        stokes_dgp_prolongate / stokes_dgp_restrict through those of include/stfem_stokes_pressure_space.h (at degree 2 the entries of
+        the constructor's operator, bit for bit).  divergence_space is the divergence at either degree; divergence stays the entry of
+        stfem.h, which refuses degree 3."""
         assert "velocity_degree" not in keywords and "_space" not in keywords
         return cls(ncell, _space=(velocity_degree, tuple(int(v) for v in reserved)), **keywords)
 
@@ -1122,7 +1140,10 @@ class StokesMatrixFreeOperator:
     def pressure_quadrature_points(self, nq):
         """[n_cells, nq^3, 3]: QGauss(nq)^3 on the cells (axis-aligned uniform meshes)"""
         out = np.zeros((self.n_cells, max(int(nq), 1) ** 3, 3))
-        _check(lib().stfem_stokes_pressure_quadrature_points(self._h, nq, _p(out)), "stfem_stokes_pressure_quadrature_points")
+        if self._space_entries:
+            _check(lib().stfem_stokes_pressure_quadrature_points_space(self._h, nq, _p(out)), "stfem_stokes_pressure_quadrature_points_space")
+        else:
+            _check(lib().stfem_stokes_pressure_quadrature_points(self._h, nq, _p(out)), "stfem_stokes_pressure_quadrature_points")
         return out
 
     def pressure_difference(self, nq, p, exact, stream=None):
@@ -1131,14 +1152,26 @@ class StokesMatrixFreeOperator:
         if 1 <= nq <= 8:
             assert e.size == self.n_cells * nq ** 3
         out = np.zeros(2)
-        _check(lib().stfem_stokes_pressure_difference(self._h, nq, getattr(p, "ptr", p), _p(e), _p(out), stream),
-               "stfem_stokes_pressure_difference")
+        args = (self._h, nq, getattr(p, "ptr", p), _p(e), _p(out), stream)
+        if self._space_entries:
+            _check(lib().stfem_stokes_pressure_difference_space(*args), "stfem_stokes_pressure_difference_space")
+        else:
+            _check(lib().stfem_stokes_pressure_difference(*args), "stfem_stokes_pressure_difference")
         return out
 
     def divergence(self, u, cells=False, stream=None):
         """StokesMatrixFreeOperator::compute_divergence (operators.h:1391-1439): sqrt(sum_cells int (div u_h)^2) of the device
         velocity vector u at the operator's Gauss points, the values read plain (constrained entries count as stored).
-        cells=True: (total, [n_cells] cell values, cells lexicographic); cells=<device pointer>: the cell values are written there."""
+        cells=True: (total, [n_cells] cell values, cells lexicographic); cells=<device pointer>: the cell values are written there.
+        stfem_stokes_divergence: velocity degree 2 only, on every operator (a degree-3 operator is refused; divergence_space runs)."""
+        return self._divergence(lambda *args: lib().stfem_stokes_divergence(*args), "stfem_stokes_divergence", u, cells, stream)
+
+    def divergence_space(self, u, cells=False, stream=None):
+        """divergence through stfem_stokes_divergence_space (include/stfem_stokes_pressure_space.h): either velocity degree; at degree 2
+        the bits of divergence"""
+        return self._divergence(lambda *args: lib().stfem_stokes_divergence_space(*args), "stfem_stokes_divergence_space", u, cells, stream)
+
+    def _divergence(self, entry, name, u, cells, stream):
         total = C.c_double(0.0)
         scratch = None
         if cells is True:  # (a pressure vector holds the cell values: either pressure space has at least one DoF per cell)
@@ -1146,7 +1179,7 @@ class StokesMatrixFreeOperator:
             dptr = scratch.ptr
         else:
             dptr = None if cells is False or cells is None else getattr(cells, "ptr", cells)
-        _check(lib().stfem_stokes_divergence(self._h, getattr(u, "ptr", u), dptr, C.byref(total), stream), "stfem_stokes_divergence")
+        _check(entry(self._h, getattr(u, "ptr", u), dptr, C.byref(total), stream), name)
         return (total.value, scratch.download()[:self.n_cells].copy()) if scratch is not None else total.value
 
     def drag_lift_n_items(self, faces):
@@ -1196,21 +1229,53 @@ class StokesMatrixFreeOperator:
     def pressure_mean_vectors(self):
         """(ones, weights, volume): coefficients of p = 1, (1, psi_j), and the volume: mean(p) = weights . p / volume"""
         ones, weights, volume = np.zeros(self.n_pressure), np.zeros(self.n_pressure), C.c_double(0.0)
-        _check(lib().stfem_stokes_pressure_mean_vectors(self._h, _p(ones), _p(weights), C.byref(volume)),
-               "stfem_stokes_pressure_mean_vectors")
+        args = (self._h, _p(ones), _p(weights), C.byref(volume))
+        if self._space_entries:
+            _check(lib().stfem_stokes_pressure_mean_vectors_space(*args), "stfem_stokes_pressure_mean_vectors_space")
+        else:
+            _check(lib().stfem_stokes_pressure_mean_vectors(*args), "stfem_stokes_pressure_mean_vectors")
         return ones, weights, volume.value
+
+    def space(self):
+        """(velocity degree, pressure space 0 = FE_Q / 1 = FE_DGP, viscosity) the context was made with (stfem_stokes_get_space)"""
+        sd = _StokesSpaceDesc()
+        _check(lib().stfem_stokes_get_space(self._h, C.byref(sd)), "stfem_stokes_get_space")
+        return int(sd.velocity_degree), int(sd.pressure_space), float(sd.viscosity)
+
+    def pressure_ctx(self):
+        """The handle of the scalar context behind the pressure vectors (owned by the operator): for FE_Q the pressure space on the
+        mesh, for FE_DGP a carrier for the vector arithmetic alone.  For stfem_vector_wrap, stfem_dot, stfem_vector_axpby ..."""
+        h = _vp()
+        if self._space_entries:
+            _check(lib().stfem_stokes_pressure_ctx_space(self._h, C.byref(h)), "stfem_stokes_pressure_ctx_space")
+        else:
+            _check(lib().stfem_stokes_pressure_ctx(self._h, C.byref(h)), "stfem_stokes_pressure_ctx")
+        return h
+
+    def last_divergence_plan(self):
+        """(workgroups, longest run of cells per wave or half-wave) of the last divergence launch"""
+        out = (C.c_int32 * 2)()
+        _check(lib().stfem_stokes_last_divergence_plan(self._h, out), "stfem_stokes_last_divergence_plan")
+        return int(out[0]), int(out[1])
 
 
 def stokes_dgp_prolongate(fine, coarse, dst, src, add=False, stream=None):
-    """FE_DGP(1) pressure: dst_fine (+)= embedding of src_coarse; `fine` has twice the cells of `coarse` per direction"""
-    _check(lib().stfem_stokes_dgp_prolongate(fine._h, coarse._h, getattr(dst, "ptr", dst), getattr(src, "ptr", src), int(bool(add)), stream),
-           "stfem_stokes_dgp_prolongate")
+    """FE_DGP(1) pressure (FE_DGP(2) between two operators of velocity degree 3 made by with_degree): dst_fine (+)= embedding of
+    src_coarse; `fine` has twice the cells of `coarse` per direction"""
+    args = (fine._h, coarse._h, getattr(dst, "ptr", dst), getattr(src, "ptr", src), int(bool(add)), stream)
+    if fine._space_entries and coarse._space_entries:
+        _check(lib().stfem_stokes_dgp_prolongate_space(*args), "stfem_stokes_dgp_prolongate_space")
+    else:
+        _check(lib().stfem_stokes_dgp_prolongate(*args), "stfem_stokes_dgp_prolongate")
 
 
 def stokes_dgp_restrict(fine, coarse, dst, src, add=False, stream=None):
     """dst_coarse (+)= the transpose of the embedding applied to src_fine"""
-    _check(lib().stfem_stokes_dgp_restrict(fine._h, coarse._h, getattr(dst, "ptr", dst), getattr(src, "ptr", src), int(bool(add)), stream),
-           "stfem_stokes_dgp_restrict")
+    args = (fine._h, coarse._h, getattr(dst, "ptr", dst), getattr(src, "ptr", src), int(bool(add)), stream)
+    if fine._space_entries and coarse._space_entries:
+        _check(lib().stfem_stokes_dgp_restrict_space(*args), "stfem_stokes_dgp_restrict_space")
+    else:
+        _check(lib().stfem_stokes_dgp_restrict(*args), "stfem_stokes_dgp_restrict")
 
 
 class StokesPreconditionVanka:

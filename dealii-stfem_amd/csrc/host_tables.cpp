@@ -927,4 +927,32 @@ void line_matrices(int nc_f, int p_f, int nc_c, int p_c, std::vector<double> &P,
   }
 }
 
+void legendre01(double x, double out[3])
+{
+  out[0] = 1.0;
+  out[1] = std::sqrt(3.0) * (2.0 * x - 1.0);
+  out[2] = std::sqrt(5.0) * ((6.0 * x - 6.0) * x + 1.0);
+}
+
+void lagrange_q2_01(double x, double out[3])
+{
+  out[0] = (2.0 * x - 1.0) * (x - 1.0);
+  out[1] = 4.0 * x * (1.0 - x);
+  out[2] = x * (2.0 * x - 1.0);
+}
+
+void dgp_child_tables(double T[2][3][3])
+{
+  for (int s = 0; s < 2; ++s) {
+    const double sign = s ? 1.0 : -1.0;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) T[s][i][j] = 0.0;
+    T[s][0][0] = 1.0;
+    T[s][1][0] = sign * std::sqrt(3.0) / 2.0;
+    T[s][1][1] = 0.5;
+    T[s][2][1] = sign * std::sqrt(15.0) / 4.0;
+    T[s][2][2] = 0.25;
+  }
+}
+
 } // namespace stfem

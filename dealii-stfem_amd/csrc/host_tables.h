@@ -86,6 +86,15 @@ void cell_of(int i, int p, int n, int &cell, int &j);
 // interpolation I[n_c x n_f] (the fine function at the coarse nodes); nc_f / nc_c = fine cells per coarse cell
 void line_matrices(int nc_f, int p_f, int nc_c, int p_c, std::vector<double> &P, std::vector<double> &I);
 
+// ---- the 1D functions of the degree-2 pressure spaces on [0, 1] ----
+// the orthonormal Legendre functions l_0 = 1, l_1 = sqrt 3 (2 x - 1), l_2 = sqrt 5 (6 x^2 - 6 x + 1) of FE_DGP at x
+void legendre01(double x, double out[3]);
+// the Lagrange functions of FE_Q(2) on the nodes 0, 1/2, 1 at x
+void lagrange_q2_01(double x, double out[3]);
+// The parent's Legendre functions on child s of [0, 1] halved, x = (s + xi) / 2:  l_i(x) = sum_j T[s][i][j] l_j(xi) - lower triangular:
+//   l_0 = l_0,  l_1 = 1/2 l_1 + (2 s - 1) (sqrt 3 / 2) l_0,  l_2 = 1/4 l_2 + (2 s - 1) (sqrt 15 / 4) l_1
+void dgp_child_tables(double T[2][3][3]);
+
 // ---- mesh / coefficient ----
 void mesh_vertices(const int32_t gn[3], const double lo[3], const double up[3], double distort,
                    uint64_t seed, int32_t z0, int32_t z1, double *out);

@@ -167,7 +167,8 @@ struct stfem_stokes_ctx {
   double *d_vertices = nullptr;
   int n_cu = 256;
   int pspace = 0; // 0 = FE_Q(degree - 1), 1 = FE_DGP(degree - 1)
-  // velocity degree: 2, or 3 (stfem_stokes_create_space): the linear cell operator and the convection term of the Navier-Stokes modes.  Geometry and tables are in the description
+  // velocity degree: 2, or 3 (stfem_stokes_create_space): the linear cell operator, the convection term of the Navier-Stokes modes,
+  // the divergence functional and the pressure space helpers.  Geometry and tables are in the description
   // of that degree, base or base3 (stokes_create_degree fills the one); the other stays zero
   int degree = 2;
   StokesParams base;
@@ -177,6 +178,8 @@ struct stfem_stokes_ctx {
   int cell_plan[2] = {0, 0}; // workgroups and longest run of cells per cell slot of the last colour launch (stfem_stokes_last_cell_plan)
   bool convection_launched = false;
   int convection_plan[2] = {0, 0}; // the same of the last convection colour launch (stfem_stokes_last_convection_plan)
+  bool divergence_launched = false;
+  int divergence_plan[2] = {0, 0}; // workgroups and longest run of cells per cell slot of the last divergence launch (stfem_stokes_last_divergence_plan)
   // axis-aligned uniform meshes: the scalar FE_Q(2) context whose pencil sweep applies nu K + wM M to the velocity components,
   // and the 1D tables of the coupling kernels
   stfem_ctx *scalar = nullptr;

@@ -133,7 +133,7 @@ inline void rhs_minus(std::vector<StokesVector> &dst, const std::vector<StokesVe
     py[i] = dst[i].data();
   }
   stfem_ctx *pc = nullptr; // (any scalar context of the device serves the vector arithmetic: the pressure space's is at hand)
-  check(stfem_stokes_pressure_ctx(dst[0].context(), &pc), "stfem_stokes_pressure_ctx");
+  check(stfem_stokes_pressure_ctx_space(dst[0].context(), &pc), "stfem_stokes_pressure_ctx_space"); // (either velocity degree)
   check(stfem_axpby_many(pc, int(nb), len.data(), 1.0, px.data(), -1.0, py.data(), nullptr), "PDE::residual");
 }
 
@@ -301,7 +301,7 @@ public:
     // (the cell values land in a pressure vector: either pressure space has at least one DoF per cell)
     if (!cells_.data()) cells_ = StokesVector(h_, 1);
     Number total = 0;
-    check(stfem_stokes_divergence(h_, velocity.data(), cells_.data(), &total, stream), "stfem_stokes_divergence");
+    check(divergence_entry()(h_, velocity.data(), cells_.data(), &total, stream), divergence_entry_name());
     const std::vector<double> h = cells_.copy_to_host();
     cell_vector.assign(h.begin(), h.begin() + (long long)n_cells_);
     return total;
@@ -309,8 +309,17 @@ public:
   Number compute_divergence(const StokesVector &velocity, void *stream = nullptr) const // (the total alone)
   {
     Number total = 0;
-    check(stfem_stokes_divergence(h_, velocity.data(), nullptr, &total, stream), "stfem_stokes_divergence");
+    check(divergence_entry()(h_, velocity.data(), nullptr, &total, stream), divergence_entry_name());
     return total;
+  }
+  // (an operator by descriptor or of velocity degree 3: the _space form of stfem_stokes_pressure_space.h, which runs at either degree)
+  decltype(&stfem_stokes_divergence) divergence_entry() const
+  {
+    return space_entries_ || velocity_degree_ != 2 ? stfem_stokes_divergence_space : stfem_stokes_divergence;
+  }
+  const char *divergence_entry_name() const
+  {
+    return space_entries_ || velocity_degree_ != 2 ? "stfem_stokes_divergence_space" : "stfem_stokes_divergence";
   }
   // operators.h:1344-1389: scale * sum over the boundary faces of obstacle_id of int (p n - nu (grad u + grad u^T) n) dA for the pair
   // src = {velocity, pressure}, the reference's argument order.  Velocity entries on strongly constrained DoFs read as 0 as in the

@@ -1,6 +1,9 @@
 // The solver side of the Stokes slab problem (tests/tp_03stokes.cc:536-560, 840-1090) over the C-ABI: the two-variable block vector
 // with the vector arithmetic of the Krylov solver, the relaxation smoother around the two-variable Vanka smoother, and the first-order
 // time integrator of include/time_integrators.h:30-336 with a velocity force, for FE_Q(2)^3 x FE_Q(1) (BASELINE configs[4]).
+// Over an operator of velocity degree 3 (FE_Q(3)^3 x FE_Q(2) / FE_DGP(2)): StokesSpaces, StokesBlockVector, StokesSystem,
+// RelaxedVankaStokes, PressureErrorCalculator and the zero-mean shift of StokesSlab, through the _space entries of
+// include/stfem_stokes_pressure_space.h; GMGStokes, the time integrators and partitions refuse it.
 // Control flow only: every vector operation, integral and operator application is a call into libstfem_hip.so.
 #pragma once
 #include "stmg.h"
@@ -14,23 +17,31 @@
 
 namespace stfem {
 
-// The scalar spaces behind the two variables: a velocity component is a FE_Q(2) function (with the velocity's strong constraints),
-// the pressure a FE_Q(1) function without constraints.  Their contexts serve the vector arithmetic, the load vectors, the
-// interpolation and the error norms of the Stokes vectors (VectorTools::* per variable in the reference).
+// The scalar spaces behind the two variables, for the velocity degree k = 2 or 3 the Stokes context was made with
+// (stfem_stokes_get_space): a velocity component is a FE_Q(k) function (with the velocity's strong constraints), the pressure a
+// FE_Q(k - 1) function without constraints.  Their contexts serve the vector arithmetic, the load vectors, the interpolation and
+// the error norms of the Stokes vectors (VectorTools::* per variable in the reference).
 struct StokesSpaces {
-  std::shared_ptr<Context> q2, q1; // q1: the pressure space's context (FE_Q(1): a real one; FE_DGP(1): a carrier for the vector arithmetic)
+  // q2: the scalar FE_Q(k) space of a velocity component; q1: the pressure space's context (FE_Q(k - 1): a real one; FE_DGP(k - 1): a
+  // carrier for the vector arithmetic).  (The names are those of k = 2.)
+  std::shared_ptr<Context> q2, q1;
   stfem_stokes_ctx *stokes;
   StokesSpaces(const Mesh &mesh, stfem_stokes_ctx *stokes_) : stokes(stokes_)
   {
-    MatrixFreeOperator<3, 1, double> a(mesh, 2, 0.0, 1.0);
+    stfem_stokes_space_desc sd{};
+    check(stfem_stokes_get_space(stokes, &sd), "stfem_stokes_get_space");
+    velocity_degree = unsigned(sd.velocity_degree);
+    MatrixFreeOperator<3, 1, double> a(mesh, velocity_degree, 0.0, 1.0);
     q2 = a.context();
     stfem_ctx *pc = nullptr;
-    check(stfem_stokes_pressure_ctx(stokes, &pc), "stfem_stokes_pressure_ctx");
+    check(stfem_stokes_pressure_ctx_space(stokes, &pc), "stfem_stokes_pressure_ctx_space");
     q1 = std::make_shared<Context>(pc, false);
-    q1->degree = 1;
+    const int pressure_degree = sd.velocity_degree - 1;
     int32_t nd[3];
     check(stfem_n_dofs_1d(pc, nd), "stfem_n_dofs_1d");
-    carrier = nd[0] != mesh.ncell[0] + 1 || nd[1] != mesh.ncell[1] + 1 || nd[2] != mesh.ncell[2] + 1; // (FE_DGP(1): 2 x 2 x n_cells)
+    // (FE_DGP(1): 2 x 2 x n_cells, FE_DGP(2): 2 x 5 x n_cells; FE_Q(k - 1): (k - 1) ncell + 1 nodes per direction)
+    carrier = nd[0] != pressure_degree * mesh.ncell[0] + 1 || nd[1] != pressure_degree * mesh.ncell[1] + 1 || nd[2] != pressure_degree * mesh.ncell[2] + 1;
+    q1->degree = carrier ? 1 : unsigned(pressure_degree);
     box = mesh.vertices.empty();
   }
   // z-slab partition (the mesh is this rank's slab, interface faces taken out of its Dirichlet mask): the operator leaves partial
@@ -47,6 +58,7 @@ struct StokesSpaces {
   void set_partition(const std::shared_ptr<Communicator> &comm, int lower_rank, int upper_rank, const double *lower_vertices = nullptr,
                      const double *upper_vertices = nullptr)
   {
+    if (velocity_degree != 2) throw Error(STFEM_ERR_UNSUPPORTED, "StokesSpaces::set_partition: slabs are not built at velocity degree 3");
     for (auto &c : {q2, q1}) {
       const bool exchanges = c == q2 || !carrier;
       c->comm = comm;
@@ -57,7 +69,8 @@ struct StokesSpaces {
     cip_neighbours = comm && planes ? (lower_rank >= 0 ? 16 : 0) | (upper_rank >= 0 ? 32 : 0) : 0;
     check(stfem_stokes_set_cip_neighbours(stokes, cip_neighbours, lower_vertices, upper_vertices), "stfem_stokes_set_cip_neighbours");
   }
-  bool carrier = false; // q1 is the FE_DGP(1) carrier context
+  unsigned velocity_degree = 2;
+  bool carrier = false; // q1 is the FE_DGP carrier context
   bool box = true;      // axis-aligned uniform mesh (no vertex array)
   int cip_neighbours = 0;
 };
@@ -288,8 +301,8 @@ struct SynchronisedTimer {
 // reestimate_relaxation is false - at every later one.  The preconditioner interface of TimeIntegratorNavierStokes beside GMGStokes.
 // delta0 != 0 (a nonlinear treatment only): the blocks hold the CIP term weighted by the linearisation
 // (PreconditionVankaStokes, stfem_stokes_vanka_create_linearised_cip); the estimate sees whatever `system` applies.
-// Velocity degree 2 only: `system` stands on StokesSpaces, whose scalar spaces are FE_Q(2) / stfem_stokes_pressure_ctx; over a degree-3
-// operator PreconditionVankaStokes and its step() are what there is.
+// Either velocity degree: over a degree-3 operator the smoother is the per-cell one of stfem_stokes_vanka_create_space /
+// _create_linearised_space (delta0 == 0 only: such an operator has no CIP term).
 template <int dim> class RelaxedVankaStokes {
 public:
   RelaxedVankaStokes(const StokesMatrixFreeOperator<dim, double> &K, const StokesSystem<dim, double> &system, const FullMatrix<double> &Alpha,
@@ -567,6 +580,11 @@ private:
   BlockVectorT<double> foreign_view(const StokesBlockVector &x, unsigned b) const
   {
     const StokesSpaces &sp = *levels_.back().spaces;
+    // (the levels are degree-2 operators made from the mesh: a vector over a degree-3 operator is not theirs)
+    if (!x.spaces() || x.spaces()->velocity_degree != sp.velocity_degree)
+      throw Error(STFEM_ERR_UNSUPPORTED, "GMGStokes is built for velocity degree 2 only: its level operators are FE_Q(2)^3 x FE_Q(1) / FE_DGP(1) on the "
+                                         "mesh, and vmult / set_data were given a vector that is not over such an operator (velocity degree 3 has "
+                                         "RelaxedVankaStokes as its preconditioner)");
     BlockVectorT<double> v;
     double *base = x.blocks()[b].data();
     if (levels_.back().slice.decompose(b)[1] == 0) {
@@ -666,7 +684,7 @@ public:
     numeric.reinit(spaces->q1, 1);
     const size_t ncells = size_t(stfem_n_cells(spaces->q2->h));
     qpoints.resize(ncells * nq * nq * nq * 3);
-    check(stfem_stokes_pressure_quadrature_points(spaces->stokes, nq, qpoints.data()), "stfem_stokes_pressure_quadrature_points");
+    check(stfem_stokes_pressure_quadrature_points_space(spaces->stokes, nq, qpoints.data()), "stfem_stokes_pressure_quadrature_points_space");
   }
   // {L2^2 contribution, Linfty} of the slab; x: the pressure blocks of the time dofs (views on the pressure space), prev: the previous one
   std::array<double, 2> evaluate_error(double time, double time_step, const BlockVectorT<double> &x, const BlockVectorT<double> &prev)
@@ -685,8 +703,9 @@ public:
       }
       exact(time + tq[q] * time_step, qpoints, pe);
       double out[2];
-      check(stfem_stokes_pressure_difference(spaces->stokes, nq, static_cast<const double *>(stfem_vector_block(numeric.handle(), 0)), pe.data(), out, nullptr),
-            "stfem_stokes_pressure_difference");
+      check(stfem_stokes_pressure_difference_space(spaces->stokes, nq, static_cast<const double *>(stfem_vector_block(numeric.handle(), 0)), pe.data(), out,
+                                                   nullptr),
+            "stfem_stokes_pressure_difference_space");
       err[0] += time_step * tw[q] * out[0];
       err[1] = std::max(err[1], out[1]);
     }
@@ -721,6 +740,8 @@ public:
   void assemble_force(StokesBlockVector &rhs, double time, double time_step)
   {
     const StokesSpaces &sp = *rhs.spaces();
+    if (sp.velocity_degree != 2) // (the load vectors below are those of FE_Q(2) with QGauss(3))
+      throw Error(STFEM_ERR_UNSUPPORTED, "StokesSlab::assemble_force: the time integrators are built for velocity degree 2 only");
     if (qpoints.empty()) {
       qpoints.resize(size_t(stfem_n_cells(sp.q2->h)) * 27 * 3);
       check(stfem_quadrature_points(sp.q2->h, 3, qpoints.data()), "stfem_quadrature_points");
@@ -751,7 +772,7 @@ public:
       weights.reinit(sp.q1, 1);
       ones.reinit(sp.q1, 1);
       std::vector<std::vector<double>> h1(1, std::vector<double>(ones.block_size())), hw(1, std::vector<double>(ones.block_size()));
-      check(stfem_stokes_pressure_mean_vectors(sp.stokes, h1[0].data(), hw[0].data(), &volume), "stfem_stokes_pressure_mean_vectors");
+      check(stfem_stokes_pressure_mean_vectors_space(sp.stokes, h1[0].data(), hw[0].data(), &volume), "stfem_stokes_pressure_mean_vectors_space");
       ones.copy_from_host(h1);
       weights.copy_from_host(hw);
     }

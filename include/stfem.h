@@ -698,6 +698,10 @@ int stfem_stokes_vanka_create_linearised_cip(stfem_stokes_ctx *ctx, int n_blocks
 /* The constructor by descriptor of the smoother of the LINEARISED operator for a context of either degree (at degree 3
  * create_linearised above refuses; this entry builds the blocks of A(b_j) there): the companion header, part of this boundary. */
 #include "stfem_stokes_vanka_linearised_space.h"
+/* The pressure space helpers, the FE_DGP transfers and the divergence functional for a context of either degree (at degree 3 the
+ * entries above refuse; the _space entries run), the getter of a context's space and the diagnostic of the divergence kernel: the
+ * companion header, part of this boundary and included here. */
+#include "stfem_stokes_pressure_space.h"
 int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_blocks);
 void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v);
 int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v);

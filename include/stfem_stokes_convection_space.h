@@ -22,6 +22,7 @@
  *     bitwise reproducible.  STFEM_CONVECTION_NONE: the entry of stfem.h, launch for launch.
  * The Vanka blocks of the operator in these modes: stfem_stokes_vanka_create_linearised_space (stfem_stokes_vanka_linearised_space.h;
  * stfem_stokes_vanka_create_space stays linear).
+ * The pressure space helpers and the divergence of such a context: stfem_stokes_pressure_space.h.
  * Not built at degree 3: weak faces with their inflow term, CIP, GMGStokes and the drivers, slabs, fp32. */
 int stfem_stokes_vmult_convection_space(stfem_stokes_ctx *ctx, int mode, double *dst_u, double *dst_p, const double *src_u,
                                         const double *src_p, const double *lin_u, void *stream);

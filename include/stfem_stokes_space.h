@@ -25,7 +25,9 @@
  *     touches the device and with its operands untouched (the int64_t counts return that status as their value).  The convection
  *     modes at degree 3 run through entries of their own, the _space forms of the three _convection entries
  *     (stfem_stokes_convection_space.h), and the Vanka smoother of the linear and of the linearised operator through
- *     stfem_stokes_vanka_create_space and _create_linearised_space (stfem_stokes_vanka_space.h, stfem_stokes_vanka_linearised_space.h).
+ *     stfem_stokes_vanka_create_space and _create_linearised_space (stfem_stokes_vanka_space.h, stfem_stokes_vanka_linearised_space.h);
+ *     the pressure helpers, the FE_DGP transfers and the divergence likewise through the _space forms of their entries, with the
+ *     getter stfem_stokes_get_space (stfem_stokes_pressure_space.h).
  *     Not built at degree 3 either: GMGStokes and the drivers, slabs (untested, unclaimed), fp32.
  *   Any other degree: STFEM_ERR_UNSUPPORTED; non-zero reserved or a pressure_space outside 0..1: STFEM_ERR_INVALID_ARGUMENT; both
  *   with their reason in stfem_last_error. */

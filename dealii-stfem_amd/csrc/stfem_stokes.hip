@@ -6,11 +6,14 @@
 // General meshes: the cell kernel (stfem_stokes_cell.hip).  On top of either: the weak (Nitsche) boundary faces
 // (stfem_stokes_boundary.hip), and with a convection mode (form / jacobian of the Navier-Stokes operator) the convection launches
 // (stfem_stokes_convection.hip), and with delta0 != 0 the CIP interior-face launches (stfem_stokes_cip.hip).  The helpers of the pressure space the solver around the operator needs: stfem_stokes_pressure.hip.
-// Every entry point describes its launches in ONE form, StokesParams (stfem_stokes_internal.h), put together by StokesLaunch below.
+// Every entry point describes its launches in ONE form, a StokesSet (stfem_stokes_set.h: sources, destinations, weights, store flags -
+// nothing of the mesh or the degree), put together by the builder of stokes_set_builder below.  A launcher writes the set into the
+// context's description of its degree (stokes_params<DEG>, stfem_stokes_internal.h); the degree becomes a template parameter in
+// stokes_with_degree alone.
 // A context of velocity degree 3 (stfem_stokes_create_space) has one implementation of the linear cell operator, the same cell kernel
 // at DEG = 3 (stfem_stokes_cell.hip), and on top of it the convection launches of the Navier-Stokes modes alone
-// (the same kernel at DEG = 3, stfem_stokes_convection.hip), reached through the _space entries of stfem_stokes_convection_space.h: stokes_launch dispatches on
-// the degree, stokes_require_q2 refuses the rest
+// (the same kernel at DEG = 3, stfem_stokes_convection.hip), reached through the _space entries of stfem_stokes_convection_space.h:
+// stokes_require_q2 refuses the rest, so that stokes_launch finds nothing else to launch there
 // (beside the operator such a context has its per-cell Vanka smoother, stfem_stokes_vanka_create_space in stfem_stokes_vanka.hip).
 #include "stfem_stokes_internal.h"
 
@@ -20,7 +23,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <new>
 
 static int stokes_lowest_priority()
@@ -44,9 +46,9 @@ static hipStream_t stokes_side_stream(int device)
   return streams[device];
 }
 
-// Geometry and 1D tables of a context, in the launch description of its degree
+// Geometry and 1D tables of a context, in the launch description of its degree; what does not depend on the degree on the context too
 template <int DEG, class Table>
-static void stokes_describe(const stfem_stokes_ctx *c, const stfem_mesh_desc *mesh, const Table &Su, const Table &Du, const stfem::Mat &Sp,
+static void stokes_describe(stfem_stokes_ctx *c, const stfem_mesh_desc *mesh, const Table &Su, const Table &Du, const stfem::Mat &Sp,
                             const std::vector<double> &xq, const std::vector<double> &wq, StokesParamsT<DEG> &b)
 {
   for (int i = 0; i < (DEG + 1) * (DEG + 1); ++i) { b.Su[i] = Su[i]; b.Du[i] = Du[i]; }
@@ -72,6 +74,8 @@ static void stokes_describe(const stfem_stokes_ctx *c, const stfem_mesh_desc *me
     b.hinv[d] = 1.0 / h;
     b.detJ *= h;
   }
+  c->cart = b.cart != 0; c->detJ = b.detJ;
+  for (int d = 0; d < 3; ++d) c->hinv[d] = b.hinv[d];
 }
 
 extern "C" {
@@ -198,17 +202,10 @@ static int stokes_create_degree(const stfem_mesh_desc *mesh, int velocity_degree
   stfem::gauss_rule(velocity_degree + 1, xq, wq);
   stfem::Mat Sp, Gp;
   stfem::lagrange_tables(tp.nodes, xq, Sp, Gp);
-  std::memset(&c->base, 0, sizeof(c->base));
-  std::memset(&c->base3, 0, sizeof(c->base3));
   std::memset(&c->coupling, 0, sizeof(c->coupling));
-  if (velocity_degree == 3) { // no scalar pencil context: the cell kernel serves boxes too
-    stokes_describe(c, mesh, tu.S, tu.D, Sp, xq, wq, c->base3);
-    *out = c;
-    return STFEM_OK;
-  }
-  stokes_describe(c, mesh, tu.S, tu.D, Sp, xq, wq, c->base);
-  const StokesParams &b = c->base;
-  if (b.cart) {
+  if (velocity_degree == 3) stokes_describe(c, mesh, tu.S, tu.D, Sp, xq, wq, c->base3);
+  else stokes_describe(c, mesh, tu.S, tu.D, Sp, xq, wq, c->base);
+  if (c->cart && velocity_degree == 2) { // (degree 3: no scalar pencil context, the cell kernel serves boxes too)
     const char *e = getenv("STFEM_STOKES_CELL"); // 1: keep the cell kernel on boxes too (cross-checks, measurements)
     if (!(e && atoi(e) != 0)) {
       stfem_mesh_desc md = *mesh;
@@ -281,7 +278,7 @@ int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *d)
 int stokes_velocity_degree(const stfem_stokes_ctx *c) { return c->degree; }
 int stokes_desc_any_degree(const stfem_stokes_ctx *c, stfem_stokes_desc *d)
 {
-  d->device = c->device; d->cart = c->cart(); d->pspace = c->pspace; d->dmask = c->dmask;
+  d->device = c->device; d->cart = c->cart; d->pspace = c->pspace; d->dmask = c->dmask;
   d->weak_mask = c->weak_mask; d->outflow_mask = c->outflow_mask;
   for (int k = 0; k < 3; ++k) {
     d->nc[k] = c->nc[k]; d->ndu[k] = c->ndu[k]; d->ndp[k] = c->ndp[k];
@@ -341,81 +338,35 @@ int stfem_stokes_vector_download(stfem_stokes_ctx *c, int variable, const double
 
 namespace {
 
-int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double *const *lin, hipStream_t st);
+int stokes_launch(stfem_stokes_ctx *c, const StokesSet &set, int mode, const double *const *lin, hipStream_t st);
 
-// One set of launches in the making: the sources first, then the destination pairs with their weights per source.
-// prm starts as the context's `base`.  On a context of degree 3 that is all zero (geometry and tables are in base3): prm then carries
-// the set part alone, which is all stokes_cell_launch reads of it there - nothing on the degree-3 path may read geometry from prm.
-struct StokesLaunch {
-  stfem_stokes_ctx *c;
-  hipStream_t st;
-  StokesParams prm;
-  int mode;                  // STFEM_CONVECTION_*: what follows the launches of the linear operator
-  const double *lin[MAXSRC]; // the linearisation velocity of every source (mode != none)
-  StokesLaunch(stfem_stokes_ctx *c_, hipStream_t st_, int mode_ = STFEM_CONVECTION_NONE) : c(c_), st(st_), prm(c_->base), mode(mode_)
-  {
-    prm.nsrc = prm.nout = 0;
-  }
-  void add_source(const double *u, const double *p, const double *b = nullptr) // (p == nullptr: mass only; b: linearisation velocity)
-  {
-    lin[prm.nsrc] = b;
-    prm.us[prm.nsrc] = u;
-    prm.ps[prm.nsrc++] = p;
-  }
-  // The pair (u, p) receives  sum_s aU[s] (nu K u_s - B^T p_s) + bM[s] M u_s  and  sum_s aP[s] B u_s.  Weights up to 10 eps count
-  // as zero (internal::scatter, operators.h:91-110); a part all of whose weights are zero is not touched (its pointer is null in the
-  // launch), a pair of two such parts is left out.  written_u / written_p: whether an earlier launch has written that part - if
-  // not, this one overwrites it and sets the flag; nullptr: the part is accumulated into.  Launches once the set is full.
-  int add_destination(double *u, double *p, const double *aU, const double *aP, const double *bM, char *written_u, char *written_p)
-  {
-    const double eps10 = 10 * std::numeric_limits<double>::epsilon();
-    const int o = prm.nout;
-    bool use_u = false, use_p = false;
-    for (int s = 0; s < prm.nsrc; ++s) {
-      prm.wKu[s][o] = std::abs(aU[s]) > eps10 ? aU[s] : 0.0;
-      prm.wKp[s][o] = std::abs(aP[s]) > eps10 ? aP[s] : 0.0;
-      prm.wM[s][o] = std::abs(bM[s]) > eps10 ? bM[s] : 0.0;
-      use_u = use_u || prm.wKu[s][o] != 0.0 || prm.wM[s][o] != 0.0;
-      use_p = use_p || prm.wKp[s][o] != 0.0;
-    }
-    if (!use_u && !use_p) return STFEM_OK;
-    prm.out_u[o] = use_u ? u : nullptr;
-    prm.out_p[o] = use_p ? p : nullptr;
-    prm.store_u[o] = use_u && written_u && !*written_u;
-    prm.store_p[o] = use_p && written_p && !*written_p;
-    if (use_u && written_u) *written_u = 1;
-    if (use_p && written_p) *written_p = 1;
-    return ++prm.nout == (prm.nsrc > 1 ? MAXSRC : MAXOUT) ? flush() : STFEM_OK;
-  }
-  int flush()
-  {
-    if (prm.nout == 0) return STFEM_OK;
-    const int rc = stokes_launch(c, prm, mode, lin, st);
-    prm.nout = 0;
-    return rc;
-  }
-};
+// One set of launches in the making (StokesSetBuilder, stfem_stokes_set.h), bound to stokes_launch on a context and a stream.
+// mode: STFEM_CONVECTION_*, what follows the launches of the linear operator.
+auto stokes_set_builder(stfem_stokes_ctx *c, hipStream_t st, int mode = STFEM_CONVECTION_NONE)
+{
+  return StokesSetBuilder([=](const StokesSet &set, const double *const *lin) { return stokes_launch(c, set, mode, lin, st); });
+}
 
 // The Kronecker path of stokes_launch (axis-aligned uniform meshes, see stfem_stokes_coupling.hip): the same arguments, three steps.
-int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t st)
+int stokes_cart_launch(stfem_stokes_ctx *c, const StokesSet &set, hipStream_t st)
 {
-  const int nsrc = prm.nsrc, nout = prm.nout;
+  const int nsrc = set.nsrc, nout = set.nout;
   if (nsrc < 1 || nsrc > MAXSRC || nout > MAXOUT) return STFEM_ERR_UNSUPPORTED;
   // ---- the coupling, in gather form: parameters
   CouplingParams k = c->coupling;
   k.nsrc = nsrc; k.nout = nout;
-  for (int q = 0; q < nsrc; ++q) { k.u[q] = prm.us[q]; k.p[q] = prm.ps[q]; }
+  for (int q = 0; q < nsrc; ++q) { k.u[q] = set.us[q]; k.p[q] = set.ps[q]; }
   bool k_u = false, any_p = false; // (any_p: a destination that is overwritten is written even with zero weights)
   int n_store_u = 0, n_add_u = 0;
   for (int o = 0; o < nout; ++o) {
-    k.out_u[o] = prm.out_u[o]; k.out_p[o] = prm.out_p[o];
-    k.store_p[o] = prm.store_p[o];
-    if (prm.out_u[o]) (prm.store_u[o] ? n_store_u : n_add_u)++;
-    any_p = any_p || prm.out_p[o];
+    k.out_u[o] = set.out_u[o]; k.out_p[o] = set.out_p[o];
+    k.store_p[o] = set.store_p[o];
+    if (set.out_u[o]) (set.store_u[o] ? n_store_u : n_add_u)++;
+    any_p = any_p || set.out_p[o];
     for (int q = 0; q < nsrc; ++q) {
-      k.wKu[o][q] = prm.ps[q] ? prm.wKu[q][o] : 0.0;
-      k.wKp[o][q] = prm.wKp[q][o];
-      k_u = k_u || (prm.out_u[o] && k.wKu[o][q] != 0.0);
+      k.wKu[o][q] = set.ps[q] ? set.wKu[q][o] : 0.0;
+      k.wKp[o][q] = set.wKp[q][o];
+      k_u = k_u || (set.out_u[o] && k.wKu[o][q] != 0.0);
     }
   }
   stfem_launch_begin();
@@ -445,7 +396,7 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
   for (int pass = 0; pass < 2; ++pass) { // destinations that are overwritten, then those that are accumulated into
     int rows[MAXOUT], nr = 0;
     for (int o = 0; o < nout; ++o)
-      if (prm.out_u[o] && (prm.store_u[o] != 0) == (pass == 0)) rows[nr++] = o;
+      if (set.out_u[o] && (set.store_u[o] != 0) == (pass == 0)) rows[nr++] = o;
     if (nr == 0) continue;
     const int ncomp_blocks = (nr == 1 && nsrc == 1) ? 3 : 1; // components as blocks of one launch, or one launch per component
     for (int c0 = 0; c0 < 3; c0 += ncomp_blocks) {
@@ -453,12 +404,12 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
       std::vector<void *> dptr(nbo), sptr(nbi);
       std::vector<double> a(size_t(nbo) * nbi, 0.0), b(size_t(nbo) * nbi, 0.0);
       for (int cc = 0; cc < ncomp_blocks; ++cc) {
-        for (int r = 0; r < nr; ++r) dptr[cc * nr + r] = prm.out_u[rows[r]] + (c0 + cc) * c->Nu;
-        for (int q = 0; q < nsrc; ++q) sptr[cc * nsrc + q] = const_cast<double *>(prm.us[q]) + (c0 + cc) * c->Nu;
+        for (int r = 0; r < nr; ++r) dptr[cc * nr + r] = set.out_u[rows[r]] + (c0 + cc) * c->Nu;
+        for (int q = 0; q < nsrc; ++q) sptr[cc * nsrc + q] = const_cast<double *>(set.us[q]) + (c0 + cc) * c->Nu;
         for (int r = 0; r < nr; ++r)
           for (int q = 0; q < nsrc; ++q) {
-            a[size_t(cc * nr + r) * nbi + cc * nsrc + q] = c->nu * prm.wKu[q][rows[r]];
-            b[size_t(cc * nr + r) * nbi + cc * nsrc + q] = prm.wM[q][rows[r]];
+            a[size_t(cc * nr + r) * nbi + cc * nsrc + q] = c->nu * set.wKu[q][rows[r]];
+            b[size_t(cc * nr + r) * nbi + cc * nsrc + q] = set.wM[q][rows[r]];
           }
       }
       stfem_vec *vd = nullptr, *vs = nullptr;
@@ -472,7 +423,7 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
               w[d][0][a3][j] = c->coupling.C[a3][j];
               w[d][1][a3][j] = c->coupling.h[d] * c->coupling.N[a3][j];
             }
-        rc = stfem_internal_set_gradient(c->scalar, prm.ps[0], w, -prm.wKu[0][rows[0]]);
+        rc = stfem_internal_set_gradient(c->scalar, set.ps[0], w, -set.wKu[0][rows[0]]);
       }
       if (rc == STFEM_OK) rc = stfem_st_vmult(c->scalar, nbo, nbi, a.data(), b.data(), 0, pass, vd, vs, st);
       if (grad_in_sweep) {
@@ -500,33 +451,30 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesParams &prm, hipStream_t
 // In this fixed order: the linear part (Kronecker path or cell kernel), its boundary launches, then - with a convection mode - the
 // convection colours 0..7 and the inflow colours (stfem_stokes_convection.hip), which add to what the linear part has written, then -
 // with delta0 != 0 - the CIP colours 0..7 (stfem_stokes_cip.hip).
-int stokes_launch(stfem_stokes_ctx *c, StokesParams &prm, int mode, const double *const *lin, hipStream_t st)
+int stokes_launch(stfem_stokes_ctx *c, const StokesSet &set, int mode, const double *const *lin, hipStream_t st)
 {
-  // axis-aligned uniform mesh: the Kronecker path; otherwise the cell kernel
-  if (c->degree == 3) { // the linear cell operator, then the convection colours: all a degree-3 context has
-    const int rc = stokes_cell_launch(c, prm, st);
-    if (rc != STFEM_OK || mode == STFEM_CONVECTION_NONE) return rc;
-    return stokes_convection_launch(c, prm, lin, mode, st);
-  }
-  const int rc = c->scalar ? stokes_cart_launch(c, prm, st) : stokes_cell_launch(c, prm, st);
+  // axis-aligned uniform mesh at degree 2: the Kronecker path; otherwise the cell kernel.  (A context of degree 3 has no scalar
+  // context, no weak faces and no CIP term - their entry points are kept to degree 2: the cell operator, then the convection colours)
+  assert(c->degree == 2 || (!c->scalar && !c->weak_mask && c->cip_delta0 == 0.0));
+  const int rc = c->scalar ? stokes_cart_launch(c, set, st) : stokes_cell_launch(c, set, st);
   if (rc != STFEM_OK) return rc;
   // LoopType::Full: the boundary-face loop of the same vmult (the mass operator has none)
   bool k_part = false;
-  for (int o = 0; o < prm.nout; ++o)
-    for (int q = 0; q < prm.nsrc; ++q) k_part = k_part || prm.wKu[q][o] != 0.0 || prm.wKp[q][o] != 0.0;
+  for (int o = 0; o < set.nout; ++o)
+    for (int q = 0; q < set.nsrc; ++q) k_part = k_part || set.wKu[q][o] != 0.0 || set.wKp[q][o] != 0.0;
   if (c->weak_mask && k_part) {
-    const int rb = stokes_boundary_launch(c, prm, nullptr, st);
+    const int rb = stokes_boundary_launch(c, set, nullptr, st);
     if (rb != STFEM_OK) return rb;
   }
   if (mode != STFEM_CONVECTION_NONE) {
-    const int rv = stokes_convection_launch(c, prm, lin, mode, st);
+    const int rv = stokes_convection_launch(c, set, lin, mode, st);
     if (rv != STFEM_OK) return rv;
   }
   if (c->cip_delta0 != 0.0) { // last: the CIP interior faces (stfem_stokes_set_cip); without it exactly the launches above
     const double *w[MAXSRC];
     const bool from_lin = c->cip_weight == STFEM_CIP_WEIGHT_LINEARISATION && mode != STFEM_CONVECTION_NONE;
-    for (int s = 0; s < prm.nsrc; ++s) w[s] = from_lin && lin[s] ? lin[s] : prm.us[s];
-    return stokes_cip_launch(c, prm, w, c->cip_delta0, st);
+    for (int s = 0; s < set.nsrc; ++s) w[s] = from_lin && lin[s] ? lin[s] : set.us[s];
+    return stokes_cip_launch(c, set, w, c->cip_delta0, st);
   }
   return STFEM_OK;
 }
@@ -548,7 +496,7 @@ int stokes_vmult_convection(stfem_stokes_ctx *c, int mode, double *dst_u, double
     if (const int rq = stokes_require_q2(c, "stfem_stokes_vmult_convection with a convection mode")) return rq;
   if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
   STFEM_TRY(hipSetDevice(c->device));
-  StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
+  auto launch = stokes_set_builder(c, static_cast<hipStream_t>(stream), mode);
   launch.add_source(src_u, src_p, lin_u);
   const double one = 1.0, zero = 0.0;
   char written[2] = {0, 0}; // dst is overwritten
@@ -590,7 +538,7 @@ int stfem_stokes_mass_vmult(stfem_stokes_ctx *c, double *dst_u, const double *sr
   if (!c || !dst_u || !src_u) return STFEM_ERR_INVALID_ARGUMENT;
   if (dst_u == src_u) return STFEM_ERR_ALIAS;
   STFEM_TRY(hipSetDevice(c->device));
-  StokesLaunch launch(c, static_cast<hipStream_t>(stream));
+  auto launch = stokes_set_builder(c, static_cast<hipStream_t>(stream));
   launch.add_source(src_u, nullptr);
   const double one = 1.0, zero = 0.0;
   char written = 0; // dst is overwritten
@@ -669,7 +617,7 @@ int stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timesteps_at
   }();
   const int group = (fused_ok && ns * nt <= MAXSRC) ? ns * nt : 1;
   for (int s0 = 0; s0 < ns * nt; s0 += group) {
-    StokesLaunch launch(c, st, mode);
+    auto launch = stokes_set_builder(c, st, mode);
     for (int s = s0; s < s0 + group; ++s)
       launch.add_source(src_blocks[index(s / nt, 0, s % nt)], src_blocks[index(s / nt, 1, s % nt)],
                         navier ? lin_blocks[index(s / nt, 0, s % nt)] : nullptr);
@@ -750,7 +698,7 @@ int stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, int n_ti
     if (const int rq = stokes_require_q2(c, "stfem_stokes_st_vmult_slice_add_convection with a convection mode")) return rq;
   if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
   STFEM_TRY(hipSetDevice(c->device));
-  StokesLaunch launch(c, static_cast<hipStream_t>(stream), mode);
+  auto launch = stokes_set_builder(c, static_cast<hipStream_t>(stream), mode);
   launch.add_source(src_u, src_p, lin_u);
   for (int it = 0; it < ns; ++it)
     for (int id = 0; id < nt; ++id) {

@@ -236,13 +236,14 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
 }
 } // namespace
 
-int stokes_boundary_launch(stfem_stokes_ctx *c, StokesParams &prm, const double *d_g, hipStream_t st)
+int stokes_boundary_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *d_g, hipStream_t st)
 {
-  if (prm.nsrc < 1 || prm.nsrc > MAXSRC || prm.nout > (prm.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiation's bounds)
+  if (set.nsrc < 1 || set.nsrc > MAXSRC || set.nout > (set.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiation's bounds)
   BoundaryParams bp = c->bnd;
   bp.g = d_g;
   const long long items = bp.foff[6];
   if (items == 0) return STFEM_OK;
+  StokesParams prm = stokes_params<2>(c, set); // (weak faces: degree 2, stfem_stokes_set_weak_boundaries)
   const unsigned grid = (unsigned)std::min<long long>((items + 7) / 8, 4ll * c->n_cu);
   stfem_launch_begin();
   for (int colour = 0; colour < 8; ++colour) {
@@ -344,12 +345,10 @@ int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *c, const double *g_at_face_points
   }
   STFEM_TRY(hipMemcpyAsync(c->d_g, g_at_face_points, npts * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   STFEM_TRY(hipStreamSynchronize(st)); // (the caller's host array may go away)
-  StokesParams prm = c->base; // no source: the data takes its place
-  prm.nsrc = 1;
-  prm.nout = 1;
-  prm.out_u[0] = dst_u; prm.out_p[0] = dst_p;
-  prm.wKu[0][0] = prm.wKp[0][0] = 1.0;
-  return stokes_boundary_launch(c, prm, c->d_g, st);
+  StokesSet set = stokes_single_set(nullptr, dst_u); // no source: the data takes its place
+  set.out_p[0] = dst_p;
+  set.wKp[0][0] = 1.0;
+  return stokes_boundary_launch(c, set, c->d_g, st);
 }
 
 } // extern "C"

@@ -366,37 +366,34 @@ template <int DEG> const void *cell_kernel(int which) // which = 4 PDG + 2 MULTI
   return kerns[which];
 }
 
-} // namespace
-
-int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &set, hipStream_t st)
+template <int DEG> int cell_launch(stfem_stokes_ctx *c, const StokesSet &set, hipStream_t st)
 {
   if (set.nsrc < 1 || set.nsrc > MAXSRC || set.nout > (set.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiation's bounds)
-  // degree 2: `set` is the kernel's argument; degree 3: the context's description with the sources, destinations and weights of `set`
-  const bool deg3 = c->degree == 3;
-  StokesParamsT<3> wide;
-  if (deg3) {
-    wide = c->base3;
-    stokes_copy_set(wide, set);
-  }
-  const int pdg = deg3 ? wide.pdg : set.pdg, cart = deg3 ? wide.cart : set.cart;
-  int &launch_colour = deg3 ? wide.colour : set.colour;
-  void *args[] = {deg3 ? (void *)&wide : (void *)&set};
-  const int which = (pdg ? 4 : 0) + (set.nsrc > 1 ? 2 : 0) + (cart ? 1 : 0), cells = deg3 ? 4 : 8; // (cells per workgroup)
-  const void *kern = deg3 ? cell_kernel<3>(which) : cell_kernel<2>(which);
+  StokesParamsT<DEG> prm = stokes_params<DEG>(c, set);
+  void *args[] = {&prm};
+  const int which = (prm.pdg ? 4 : 0) + (set.nsrc > 1 ? 2 : 0) + (prm.cart ? 1 : 0), cells = DEG == 3 ? 4 : 8; // (cells per workgroup)
+  const void *kern = cell_kernel<DEG>(which);
   // persistent workgroups: exactly as many as stay resident, asked once per instantiation, not on the launch path (measured at degree
   // 2 on 64^3 cells, cG(1): 2 per CU 0.41 ms, 3: 0.50, 4: 0.43, 8: 0.45, one workgroup per 8 cells: 0.52 - long runs keep the prefetch
   // of the next cell's DoFs going and leave no partial round)
-  static int resident_of[2][8] = {};
-  const int resident = stokes_resident(resident_of[deg3][which], kern);
+  static int resident_of[8] = {};
+  const int resident = stokes_resident(resident_of[which], kern);
   static const int grid_env = [] {
     const char *e = getenv("STFEM_STOKES_GRID"); // workgroups per CU of a colour launch at degree 2 (experiments)
     return e ? std::max(1, atoi(e)) : 0;
   }();
   stfem_launch_begin();
-  stokes_colour_launches(c, cells, grid_env && !deg3 ? grid_env : resident, c->cell_plan, [&](int colour, unsigned grid) {
-    launch_colour = colour; // (ascending: see store_u / store_p)
+  stokes_colour_launches(c, cells, grid_env && DEG == 2 ? grid_env : resident, c->cell_plan, [&](int colour, unsigned grid) {
+    prm.colour = colour; // (ascending: see store_u / store_p)
     (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
     c->cell_launched = true;
   });
   return stfem_launch_end("stokes_cell_kernel");
+}
+
+} // namespace
+
+int stokes_cell_launch(stfem_stokes_ctx *c, const StokesSet &set, hipStream_t st)
+{
+  return stokes_with_degree(c, [&](auto deg) { return cell_launch<deg()>(c, set, st); });
 }

@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256) void stokes_cip_pack_kernel(const double *__re
 }
 
 // the eight colour launches; ghost_lo / ghost_hi: per source the neighbours' planes (read for the sides of c->cip_neighbours only)
-int cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, const double *const *ghost_lo,
+int cip_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *weight, double delta0, const double *const *ghost_lo,
                const double *const *ghost_hi, hipStream_t st);
 
 } // namespace
@@ -319,74 +319,62 @@ int stokes_cip_source_ready(const stfem_stokes_ctx *c, const double *src_u)
                                                      "(stfem_stokes_cip_bind_ghosts)");
 }
 
-int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, hipStream_t st)
+int stokes_cip_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *weight, double delta0, hipStream_t st)
 {
-  if (delta0 == 0.0 || !c->cip_neighbours) return cip_launch(c, prm, weight, delta0, nullptr, nullptr, st);
+  if (delta0 == 0.0 || !c->cip_neighbours) return cip_launch(c, set, weight, delta0, nullptr, nullptr, st);
   const double *lo[MAXSRC] = {}, *hi[MAXSRC] = {};
-  for (int s = 0; s < prm.nsrc && s < MAXSRC; ++s) {
-    const int rc = stokes_cip_source_ready(c, prm.us[s]);
+  for (int s = 0; s < set.nsrc && s < MAXSRC; ++s) {
+    const int rc = stokes_cip_source_ready(c, set.us[s]);
     if (rc != STFEM_OK) return rc;
     for (const auto &b : c->cip_bindings)
-      if (b.src == prm.us[s]) { lo[s] = b.lower; hi[s] = b.upper; }
+      if (b.src == set.us[s]) { lo[s] = b.lower; hi[s] = b.upper; }
   }
-  return cip_launch(c, prm, weight, delta0, lo, hi, st);
+  return cip_launch(c, set, weight, delta0, lo, hi, st);
 }
 
 namespace {
 
-int cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, const double *const *ghost_lo,
+int cip_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *weight, double delta0, const double *const *ghost_lo,
                const double *const *ghost_hi, hipStream_t st)
 {
   if (delta0 == 0.0) return STFEM_OK;
   const int neighbours = ghost_lo && ghost_hi ? c->cip_neighbours : 0;
   if (c->nc[0] < 2 && c->nc[1] < 2 && c->nc[2] < 2 && !neighbours) return STFEM_OK; // no interior face
-  if (prm.nsrc < 1 || prm.nsrc > MAXSRC || prm.nout > (prm.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiations' bounds)
+  if (set.nsrc < 1 || set.nsrc > MAXSRC || set.nout > (set.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiations' bounds)
+  const StokesParams &g = c->desc<2>(); // (the entry points have kept the term to degree 2)
   CipSlabParams k; // (the instantiations without SLAB read its CipParams part alone)
   k.neighbours = neighbours;
   for (int side = 0; side < 2; ++side) k.ghost_vertices[side] = c->d_cip_vertices[side];
   for (int s = 0; s < MAXSRC; ++s) {
-    k.ghost_lo[s] = neighbours && s < prm.nsrc ? ghost_lo[s] : nullptr;
-    k.ghost_hi[s] = neighbours && s < prm.nsrc ? ghost_hi[s] : nullptr;
-    if (s < prm.nsrc && (((neighbours & 16) && !k.ghost_lo[s]) || ((neighbours & 32) && !k.ghost_hi[s])))
+    k.ghost_lo[s] = neighbours && s < set.nsrc ? ghost_lo[s] : nullptr;
+    k.ghost_hi[s] = neighbours && s < set.nsrc ? ghost_hi[s] : nullptr;
+    if (s < set.nsrc && (((neighbours & 16) && !k.ghost_lo[s]) || ((neighbours & 32) && !k.ghost_hi[s])))
       return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "CIP term on a slab: ghost planes missing for a side with a neighbour");
   }
-  if (neighbours && !prm.cart)
+  if (neighbours && !g.cart)
     for (int side = 0; side < 2; ++side)
       if ((neighbours >> (4 + side) & 1) && !k.ghost_vertices[side])
         return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "CIP term on a slab: no ghost vertex plane on side %d", side);
-  k.vertices = prm.vertices;
-  k.ncx = prm.ncx; k.ncy = prm.ncy; k.ncz = prm.ncz;
-  for (int d = 0; d < 3; ++d) { k.ndu[d] = prm.ndu[d]; k.xq[d] = prm.xq[d]; k.wq[d] = prm.wq[d]; k.hinv[d] = prm.hinv[d]; }
-  k.Nu = prm.Nu;
-  k.dmask = prm.dmask;
-  for (int i = 0; i < 9; ++i) { k.Su[i] = prm.Su[i]; k.Du[i] = prm.Du[i]; }
+  k.vertices = g.vertices;
+  k.ncx = g.ncx; k.ncy = g.ncy; k.ncz = g.ncz;
+  for (int d = 0; d < 3; ++d) { k.ndu[d] = g.ndu[d]; k.xq[d] = g.xq[d]; k.wq[d] = g.wq[d]; k.hinv[d] = g.hinv[d]; }
+  k.Nu = g.Nu;
+  k.dmask = g.dmask;
+  for (int i = 0; i < 9; ++i) { k.Su[i] = g.Su[i]; k.Du[i] = g.Du[i]; }
   stokes_cip_end_tables(k.Eu, k.EDu);
-  k.colour = 0; k.cart = prm.cart;
-  k.detJ = prm.detJ;
+  k.colour = 0; k.cart = g.cart;
+  k.detJ = g.detJ;
   k.scale = delta0 / (8.0 * std::sqrt(2.0)); // pa = degree^3.5, degree 2 (operators.h:1614-1615)
-  k.nsrc = prm.nsrc;
+  k.nsrc = set.nsrc;
   for (int s = 0; s < MAXSRC; ++s) {
-    k.us[s] = s < prm.nsrc ? prm.us[s] : nullptr;
-    k.ws[s] = s < prm.nsrc ? weight[s] : nullptr;
-    if (s < prm.nsrc && (!prm.us[s] || !weight[s])) return STFEM_ERR_INVALID_ARGUMENT;
+    k.us[s] = s < set.nsrc ? set.us[s] : nullptr;
+    k.ws[s] = s < set.nsrc ? weight[s] : nullptr;
+    if (s < set.nsrc && (!set.us[s] || !weight[s])) return STFEM_ERR_INVALID_ARGUMENT;
   }
-  // the destinations that receive the term: those with a non-zero weight of the K part
-  k.nout = 0;
-  for (int o = 0; o < MAXOUT; ++o) {
-    k.out_u[o] = nullptr;
-    for (int s = 0; s < MAXSRC; ++s) k.wKu[s][o] = 0.0;
-  }
-  for (int o = 0; o < prm.nout; ++o) {
-    bool use = false;
-    for (int s = 0; s < prm.nsrc; ++s) use = use || prm.wKu[s][o] != 0.0;
-    if (!use || !prm.out_u[o]) continue;
-    k.out_u[k.nout] = prm.out_u[o];
-    for (int s = 0; s < prm.nsrc; ++s) k.wKu[s][k.nout] = prm.wKu[s][o];
-    ++k.nout;
-  }
+  k.nout = stokes_k_destinations(set, k.out_u, k.wKu); // those with a non-zero weight of the K part receive the term
   if (k.nout == 0) return STFEM_OK;
 
-  const bool multi = prm.nsrc > 1;
+  const bool multi = set.nsrc > 1;
   const int which = (multi ? 2 : 0) + (k.cart ? 1 : 0);
   const void *kerns[4] = {(const void *)stokes_cip_kernel<false, false>, (const void *)stokes_cip_kernel<true, false>,
                           (const void *)stokes_cip_kernel<false, true>, (const void *)stokes_cip_kernel<true, true>};
@@ -405,17 +393,6 @@ int cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const
     (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
   }
   return stfem_launch_end("stokes_cip_kernel");
-}
-
-// the term by itself: one source, one destination, weight 1
-StokesParams cip_single(const stfem_stokes_ctx *c, double *dst_u, const double *src_u)
-{
-  StokesParams prm = c->base;
-  prm.nsrc = 1; prm.nout = 1;
-  prm.us[0] = src_u; prm.ps[0] = nullptr;
-  prm.out_u[0] = dst_u; prm.out_p[0] = nullptr;
-  prm.wKu[0][0] = 1.0;
-  return prm;
 }
 
 } // namespace
@@ -438,8 +415,8 @@ int stfem_stokes_cip_add(stfem_stokes_ctx *c, double *dst_u, const double *src_u
   if (dst_u == src_u || dst_u == weight_u) return STFEM_ERR_ALIAS;
   if (const int rq = stokes_require_q2(c, "stfem_stokes_cip_add")) return rq;
   STFEM_TRY(hipSetDevice(c->device));
-  const StokesParams prm = cip_single(c, dst_u, src_u);
-  return cip_launch(c, prm, &weight_u, delta0, nullptr, nullptr, static_cast<hipStream_t>(stream)); // (the faces inside the slab alone)
+  const StokesSet set = stokes_single_set(src_u, dst_u); // the term by itself
+  return cip_launch(c, set, &weight_u, delta0, nullptr, nullptr, static_cast<hipStream_t>(stream)); // (the faces inside the slab alone)
 }
 
 int stfem_stokes_set_cip_neighbours(stfem_stokes_ctx *c, int neighbour_mask, const double *lower_vertices, const double *upper_vertices)
@@ -448,14 +425,14 @@ int stfem_stokes_set_cip_neighbours(stfem_stokes_ctx *c, int neighbour_mask, con
   if (neighbour_mask & ~48) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "neighbour_mask %d: only bits 4 and 5 name a z neighbour", neighbour_mask);
   if (const int rq = stokes_require_q2(c, "stfem_stokes_set_cip_neighbours")) return rq;
   const double *given[2] = {lower_vertices, upper_vertices};
-  if (!c->base.cart)
+  if (!c->cart)
     for (int side = 0; side < 2; ++side)
       if ((neighbour_mask >> (4 + side) & 1) && !given[side])
         return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "general mesh: the %s neighbour needs its vertex plane", side ? "upper" : "lower");
   STFEM_TRY(hipSetDevice(c->device));
   // the new arrays first, then the swap: a failure leaves the context as it was
   double *fresh[2] = {nullptr, nullptr};
-  if (!c->base.cart) {
+  if (!c->cart) {
     const size_t plane = size_t(c->nc[0] + 1) * (c->nc[1] + 1) * 3;
     std::vector<double> two(2 * plane);
     for (int side = 0; side < 2; ++side) {
@@ -545,8 +522,8 @@ int stfem_stokes_cip_add_slab(stfem_stokes_ctx *c, double *dst_u, const double *
                            c->cip_neighbours);
   if (dst_u == src_u || dst_u == weight_u || dst_u == lower_ghost || dst_u == upper_ghost) return STFEM_ERR_ALIAS;
   STFEM_TRY(hipSetDevice(c->device));
-  const StokesParams prm = cip_single(c, dst_u, src_u);
-  return cip_launch(c, prm, &weight_u, delta0, &lower_ghost, &upper_ghost, static_cast<hipStream_t>(stream));
+  const StokesSet set = stokes_single_set(src_u, dst_u); // the term by itself
+  return cip_launch(c, set, &weight_u, delta0, &lower_ghost, &upper_ghost, static_cast<hipStream_t>(stream));
 }
 
 int stfem_stokes_cip_bind_ghosts(stfem_stokes_ctx *c, const double *src_u, const double *lower_ghost, const double *upper_ghost)

@@ -355,12 +355,15 @@ template <int DEG> const void *convection_kernel(int which) // which = 4 JACOBIA
   return kerns[which];
 }
 
-// The description of the launches: geometry and tables from `g`, the context's description of its degree, sources and weights from
-// `set`, lin[s] beside source s.  The destinations that receive the term are those with a non-zero weight of the K part: k.nout == 0
-// afterwards means that nothing is to be launched.
-template <int DEG>
-int convection_describe(ConvectionParamsT<DEG> &k, const StokesParamsT<DEG> &g, const StokesParams &set, const double *const *lin)
+// The kernel argument at degree DEG: with the inflow fields at degree 2
+template <int DEG> using Convection = std::conditional_t<DEG == 2, ConvectionParams, ConvectionParamsT<DEG>>;
+
+// The launches of `set` at degree DEG: geometry and tables from the context's description of that degree, sources and weights from
+// `set`, lin[s] beside source s.  The destinations that receive the term are those with a non-zero weight of the K part.
+template <int DEG> int convection_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *lin, int mode, hipStream_t st)
 {
+  const StokesParamsT<DEG> &g = c->desc<DEG>();
+  Convection<DEG> k;
   k.vertices = g.vertices;
   k.ncx = g.ncx; k.ncy = g.ncy; k.ncz = g.ncz;
   for (int d = 0; d < 3; ++d) { k.ndu[d] = g.ndu[d]; k.hinv[d] = g.hinv[d]; }
@@ -376,59 +379,45 @@ int convection_describe(ConvectionParamsT<DEG> &k, const StokesParamsT<DEG> &g, 
     k.bs[s] = s < set.nsrc ? lin[s] : nullptr;
     if (s < set.nsrc && !lin[s]) return STFEM_ERR_INVALID_ARGUMENT;
   }
-  k.nout = 0;
-  for (int o = 0; o < MAXOUT; ++o) {
-    k.out_u[o] = nullptr;
-    for (int s = 0; s < MAXSRC; ++s) k.wKu[s][o] = 0.0;
+  k.nout = stokes_k_destinations(set, k.out_u, k.wKu);
+  if (k.nout == 0) return STFEM_OK;
+  if constexpr (DEG == 2) { // the inflow term on the weak faces
+    k.weak_mask = c->bnd.weak_mask;
+    for (int f = 0; f < 7; ++f) k.foff[f] = c->bnd.foff[f];
+    for (int i = 0; i < 6; ++i) k.Eu[i] = c->bnd.Eu[i];
   }
-  for (int o = 0; o < set.nout; ++o) {
-    bool use = false;
-    for (int s = 0; s < set.nsrc; ++s) use = use || set.wKu[s][o] != 0.0;
-    if (!use || !set.out_u[o]) continue;
-    k.out_u[k.nout] = set.out_u[o];
-    for (int s = 0; s < set.nsrc; ++s) k.wKu[s][k.nout] = set.wKu[s][o];
-    ++k.nout;
+  void *args[] = {&k};
+
+  const bool multi = set.nsrc > 1, jac = mode == STFEM_CONVECTION_JACOBIAN;
+  const int which = (jac ? 4 : 0) + (multi ? 2 : 0) + (k.cart ? 1 : 0);
+  const void *kern = convection_kernel<DEG>(which);
+  static int resident_of[8] = {};
+  const int resident = stokes_resident(resident_of[which], kern);
+  stfem_launch_begin();
+  stokes_colour_launches(c, DEG == 3 ? 4 : 8, resident, c->convection_plan, [&](int colour, unsigned grid) {
+    k.colour = colour;
+    (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
+    c->convection_launched = true; // (stfem_stokes_last_convection_plan)
+  });
+  if constexpr (DEG == 2) {
+    const long long items = k.weak_mask ? k.foff[6] : 0;
+    if (items > 0) {
+      const unsigned grid = (unsigned)std::min<long long>((items + 7) / 8, 4ll * c->n_cu);
+      for (int colour = 0; colour < 8; ++colour) {
+        k.colour = colour;
+        if (multi) hipLaunchKernelGGL(stokes_inflow_kernel<true>, dim3(grid), dim3(256), 0, st, k);
+        else hipLaunchKernelGGL(stokes_inflow_kernel<false>, dim3(grid), dim3(256), 0, st, k);
+      }
+    }
   }
-  return STFEM_OK;
+  return stfem_launch_end("stokes_convection_kernel");
 }
 
 } // namespace
 
-int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *lin, int mode, hipStream_t st)
+int stokes_convection_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *lin, int mode, hipStream_t st)
 {
   if (mode != STFEM_CONVECTION_FORM && mode != STFEM_CONVECTION_JACOBIAN) return STFEM_ERR_INVALID_ARGUMENT;
-  if (prm.nsrc < 1 || prm.nsrc > MAXSRC || prm.nout > (prm.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiations' bounds)
-  // degree 2: `prm` holds geometry and set; degree 3: the context's description holds the geometry, `prm` the set alone
-  const bool deg3 = c->degree == 3;
-  ConvectionParams k2;
-  ConvectionParamsT<3> k3;
-  if (const int rd = deg3 ? convection_describe(k3, c->base3, prm, lin) : convection_describe<2>(k2, prm, prm, lin)) return rd;
-  if ((deg3 ? k3.nout : k2.nout) == 0) return STFEM_OK;
-  k2.weak_mask = c->bnd.weak_mask; // the inflow term (0 on a degree-3 context: it has no weak faces)
-  for (int f = 0; f < 7; ++f) k2.foff[f] = c->bnd.foff[f];
-  for (int i = 0; i < 6; ++i) k2.Eu[i] = c->bnd.Eu[i];
-  int &launch_colour = deg3 ? k3.colour : k2.colour;
-  void *args[] = {deg3 ? (void *)&k3 : (void *)&k2};
-
-  const bool multi = prm.nsrc > 1, jac = mode == STFEM_CONVECTION_JACOBIAN;
-  const int which = (jac ? 4 : 0) + (multi ? 2 : 0) + ((deg3 ? k3.cart : k2.cart) ? 1 : 0);
-  const void *kern = deg3 ? convection_kernel<3>(which) : convection_kernel<2>(which);
-  static int resident_of[2][8] = {};
-  const int resident = stokes_resident(resident_of[deg3][which], kern);
-  stfem_launch_begin();
-  stokes_colour_launches(c, deg3 ? 4 : 8, resident, c->convection_plan, [&](int colour, unsigned grid) {
-    launch_colour = colour;
-    (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
-    c->convection_launched = true; // (stfem_stokes_last_convection_plan)
-  });
-  const long long items = k2.weak_mask ? k2.foff[6] : 0;
-  if (items > 0) {
-    const unsigned grid = (unsigned)std::min<long long>((items + 7) / 8, 4ll * c->n_cu);
-    for (int colour = 0; colour < 8; ++colour) {
-      k2.colour = colour;
-      if (multi) hipLaunchKernelGGL(stokes_inflow_kernel<true>, dim3(grid), dim3(256), 0, st, k2);
-      else hipLaunchKernelGGL(stokes_inflow_kernel<false>, dim3(grid), dim3(256), 0, st, k2);
-    }
-  }
-  return stfem_launch_end("stokes_convection_kernel");
+  if (set.nsrc < 1 || set.nsrc > MAXSRC || set.nout > (set.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiations' bounds)
+  return stokes_with_degree(c, [&](auto deg) { return convection_launch<deg()>(c, set, lin, mode, st); });
 }

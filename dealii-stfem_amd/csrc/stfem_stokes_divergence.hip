@@ -161,18 +161,31 @@ __global__ __launch_bounds__(256) void stokes_divergence_finish(long long ncells
   if (threadIdx.x == 0) out[0] = red[0];
 }
 
-// The description of the launch from the context's description of its degree
-template <int DEG>
-void divergence_describe(DivergenceParamsT<DEG> &k, const stfem_stokes_ctx *c, const StokesParamsT<DEG> &g, const double *u, double *cell_out)
+// The cell launch at degree DEG, with its plan (stfem_stokes_last_divergence_plan).  Degree 2: four workgroups of eight cells at a time
+// per CU.  Degree 3: persistent workgroups of four waves, as many as stay resident; STFEM_STOKES_Q3_WORKGROUPS=<n>, read at every
+// launch, caps them (tests: several cells per wave on a small mesh)
+template <int DEG> void divergence_launch(stfem_stokes_ctx *c, const double *u, double *cells, long long ncells, hipStream_t st)
 {
+  constexpr int per = DEG == 3 ? 4 : 8; // cells of a workgroup at a time
+  const StokesParamsT<DEG> &g = c->desc<DEG>();
+  DivergenceParamsT<DEG> k;
   k.vertices = c->d_vertices;
   k.u = u;
-  k.cell_out = cell_out;
+  k.cell_out = cells;
   k.ncx = c->nc[0]; k.ncy = c->nc[1]; k.ncz = c->nc[2];
   k.ndu[0] = c->ndu[0]; k.ndu[1] = c->ndu[1];
   k.Nu = c->Nu;
   for (int i = 0; i < (DEG + 1) * (DEG + 1); ++i) { k.Su[i] = g.Su[i]; k.Du[i] = g.Du[i]; }
   for (int i = 0; i < DEG + 1; ++i) { k.xq[i] = g.xq[i]; k.wq[i] = g.wq[i]; }
+  long long grid = std::min<long long>((ncells + per - 1) / per, 4ll * c->n_cu);
+  if constexpr (DEG == 3) {
+    static int resident = 0;
+    grid = std::min<long long>((ncells + per - 1) / per, (long long)c->n_cu * stokes_resident(resident, (const void *)stokes_divergence_kernel<3>));
+    if (const char *e = getenv("STFEM_STOKES_Q3_WORKGROUPS")) grid = std::min(grid, std::max(1ll, atoll(e)));
+  }
+  hipLaunchKernelGGL(stokes_divergence_kernel<DEG>, dim3((unsigned)grid), dim3(256), 0, st, k);
+  c->divergence_plan[0] = (int)grid;
+  c->divergence_plan[1] = (int)((ncells + grid * per - 1) / (grid * per));
 }
 
 // The functional at the context's degree (the entry points have checked their arguments)
@@ -190,25 +203,7 @@ int stokes_divergence(stfem_stokes_ctx *c, const double *u, double *cell_out, do
   }
   double *cells = cell_out ? cell_out : c->d_div;
   stfem_launch_begin();
-  if (c->degree == 3) {
-    // persistent workgroups of four waves, as many as stay resident; STFEM_STOKES_Q3_WORKGROUPS=<n>, read at every launch, caps them
-    // (tests: several cells per wave on a small mesh)
-    DivergenceParamsT<3> k;
-    divergence_describe(k, c, c->base3, u, cells);
-    static int resident = 0;
-    long long grid = std::min<long long>((ncells + 3) / 4, (long long)c->n_cu * stokes_resident(resident, (const void *)stokes_divergence_kernel<3>));
-    if (const char *e = getenv("STFEM_STOKES_Q3_WORKGROUPS")) grid = std::min(grid, std::max(1ll, atoll(e)));
-    hipLaunchKernelGGL(stokes_divergence_kernel<3>, dim3((unsigned)grid), dim3(256), 0, st, k);
-    c->divergence_plan[0] = (int)grid;
-    c->divergence_plan[1] = (int)((ncells + grid * 4 - 1) / (grid * 4));
-  } else {
-    DivergenceParamsT<2> k;
-    divergence_describe(k, c, c->base, u, cells);
-    const unsigned grid = (unsigned)std::min<long long>((ncells + 7) / 8, 4ll * c->n_cu);
-    hipLaunchKernelGGL(stokes_divergence_kernel<2>, dim3(grid), dim3(256), 0, st, k);
-    c->divergence_plan[0] = (int)grid;
-    c->divergence_plan[1] = (int)((ncells + grid * 8ll - 1) / (grid * 8ll));
-  }
+  stokes_with_degree(c, [&](auto deg) { divergence_launch<deg()>(c, u, cells, ncells, st); });
   c->divergence_launched = true; // (stfem_stokes_last_divergence_plan)
   hipLaunchKernelGGL(stokes_divergence_finish, dim3(1), dim3(256), 0, st, ncells, (const double *)cells, c->d_div + ncells);
   if (const int rc = stfem_launch_end("stokes_divergence_kernel")) return rc;

@@ -2,18 +2,21 @@
 // pressure,convection,cip,divergence,traction}.hip): the description of a launch, the context and the launchers.  Not part of the boundary.
 #pragma once
 #include "stfem_internal.h"
+#include "stfem_stokes_set.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
-constexpr int MAXOUT = 8; // destination pairs of a launch with one source
-constexpr int MAXSRC = 4; // sources, and destination pairs, of a launch with several sources
-
-// One set of launches:  out_u[o] (=, +=) sum_s wKu[s][o] (nu K u_s - B^T p_s) + wM[s][o] M u_s,  out_p[o] (=, +=) sum_s wKp[s][o] B u_s
+// The kernel argument of the linear operator at velocity degree DEG: the geometry and 1D tables of a context (constant, filled once
+// by stokes_describe) around the set of one launch (stfem_stokes_set.h; stokes_params<DEG> below writes a StokesSet into it):
+//   out_u[o] (=, +=) sum_s wKu[s][o] (nu K u_s - B^T p_s) + wM[s][o] M u_s,  out_p[o] (=, +=) sum_s wKp[s][o] B u_s
 // DEG: the velocity degree, FE_Q(DEG)^3 x FE_Q(DEG - 1) / FE_DGP(DEG - 1) with QGauss(DEG + 1).  StokesParams, the description of
 // degree 2, is what every kernel of the operator outside the cell kernel takes.
 template <int DEG> struct StokesParamsT {
@@ -23,9 +26,7 @@ template <int DEG> struct StokesParamsT {
   long long Nu, Np;
   int dmask;
   double nu;
-  // nsrc >= 1 sources (ps[s] == nullptr: u_s is read alone, mass only).  With several sources (SystemMatrixStokes::vmult with up to
-  // MAXSRC source time dofs and up to MAXSRC destination pairs in ONE set of launches) a cell is evaluated for every source in turn,
-  // the weighted results are summed in registers and scattered once; with one source the weights are applied at scatter time.
+  // the set of this launch, member for member a StokesSet
   int nsrc;
   const double *us[MAXSRC], *ps[MAXSRC];
   int nout;
@@ -48,22 +49,10 @@ template <int DEG> struct StokesParamsT {
   double lq[DEG - 1][DEG + 1]; // l_1 (and l_2) at the Gauss points
 };
 using StokesParams = StokesParamsT<2>;
-// The set part of a description - sources, destinations, weights, store flags - from one degree's description into another's
-template <int TO, int FROM> inline void stokes_copy_set(StokesParamsT<TO> &to, const StokesParamsT<FROM> &from)
-{
-  to.nsrc = from.nsrc; to.nout = from.nout;
-  for (int s = 0; s < MAXSRC; ++s) {
-    to.us[s] = s < from.nsrc ? from.us[s] : nullptr;
-    to.ps[s] = s < from.nsrc ? from.ps[s] : nullptr;
-    for (int o = 0; o < MAXOUT; ++o) { to.wKu[s][o] = from.wKu[s][o]; to.wKp[s][o] = from.wKp[s][o]; to.wM[s][o] = from.wM[s][o]; }
-  }
-  for (int o = 0; o < MAXOUT; ++o) {
-    to.out_u[o] = o < from.nout ? from.out_u[o] : nullptr;
-    to.out_p[o] = o < from.nout ? from.out_p[o] : nullptr;
-    to.store_u[o] = from.store_u[o]; to.store_p[o] = from.store_p[o];
-  }
-}
 static_assert(sizeof(StokesParams) == 1440, "the degree-2 description is the argument of every Stokes kernel: its layout stays");
+static_assert(sizeof(StokesParamsT<3>) == 1656, "the degree-3 description is the argument of the degree-3 cell kernel: its layout stays");
+static_assert(offsetof(StokesParams, nsrc) == 80 && offsetof(StokesParamsT<3>, nsrc) == 80, "the set follows the mesh part");
+static_assert(offsetof(StokesParams, Su) == 1120 && offsetof(StokesParamsT<3>, Su) == 1120, "the 1D tables follow the set");
 
 // The coupling kernels of the Kronecker path (stfem_stokes_coupling.hip)
 struct CouplingParams {
@@ -94,8 +83,8 @@ struct BoundaryParams {
 // the by-value argument of every kernel of the linear operator, stays what it is.
 //   out_u[o] += sum_s wKu[s][o] C(b_s, u_s),   C = C_form(b, u) (form) or C_form(b, u) + C_form(u, b) (jacobian),
 //   C_form(b, u)(v) = - int (u (x) b) : grad v  - int_{weak faces} min(b.n, 0) u.v
-// Geometry and tables are copied from the context's description of its degree, sources and weights from the StokesParams of the same
-// set; only destinations with a non-zero wKu are listed.  DEG: the velocity degree, as in StokesParamsT.
+// Geometry and tables are copied from the context's description of its degree, sources and weights from the StokesSet of the same
+// launches; only destinations with a non-zero wKu are listed (stokes_k_destinations).  DEG: the velocity degree, as in StokesParamsT.
 template <int DEG> struct ConvectionParamsT {
   const double *vertices;
   int ncx, ncy, ncz;
@@ -123,7 +112,8 @@ struct ConvectionParams : ConvectionParamsT<2> {
 
 // The CIP interior-face launches (stfem_stokes_cip.hip), again a description of their own:
 //   out_u[o] += sum_s wKu[s][o] C(w_s; u_s),   C(w; u)(v) = sum_F int_F delta0 h_F^2 / pa (w.n)^2 [d_n u] . [d_n v] dA
-// Geometry, tables and the weights are copied from the StokesParams of the same set; only destinations with a non-zero wKu are listed.
+// Geometry and tables are copied from the context's description, the weights from the StokesSet of the same launches; only destinations
+// with a non-zero wKu are listed (stokes_k_destinations).
 struct CipParams {
   const double *vertices;
   int ncx, ncy, ncz;
@@ -168,12 +158,22 @@ struct stfem_stokes_ctx {
   int n_cu = 256;
   int pspace = 0; // 0 = FE_Q(degree - 1), 1 = FE_DGP(degree - 1)
   // velocity degree: 2, or 3 (stfem_stokes_create_space): the linear cell operator, the convection term of the Navier-Stokes modes,
-  // the divergence functional and the pressure space helpers.  Geometry and tables are in the description
-  // of that degree, base or base3 (stokes_create_degree fills the one); the other stays zero
+  // the divergence functional and the pressure space helpers.
   int degree = 2;
-  StokesParams base;
-  StokesParamsT<3> base3;
-  bool cart() const { return (degree == 3 ? base3.cart : base.cart) != 0; }
+  // what does not depend on the degree (stokes_describe): axis-aligned uniform cells, and on those 1 / h_d and hx hy hz
+  bool cart = false;
+  double hinv[3] = {0, 0, 0}, detJ = 0;
+  // Geometry and 1D tables as the kernels of degree DEG take them: the description of the context's own degree, the only one
+  // stokes_create_degree fills.  Everything outside it reaches the two through desc<DEG>(), under stokes_with_degree or on a path that
+  // stokes_require_q2 has kept to degree 2.
+  StokesParams base{};
+  StokesParamsT<3> base3{};
+  template <int DEG> const StokesParamsT<DEG> &desc() const
+  {
+    assert(degree == DEG);
+    if constexpr (DEG == 3) return base3;
+    else return base;
+  }
   bool cell_launched = false;
   int cell_plan[2] = {0, 0}; // workgroups and longest run of cells per cell slot of the last colour launch (stfem_stokes_last_cell_plan)
   bool convection_launched = false;
@@ -214,6 +214,30 @@ struct stfem_stokes_ctx {
   struct CipBinding { const double *src, *lower, *upper; };
   std::vector<CipBinding> cip_bindings;
 };
+
+// The one place where the context's degree becomes a template parameter: f(std::integral_constant<int, DEG>) at the context's DEG
+template <class F> inline auto stokes_with_degree(const stfem_stokes_ctx *c, F &&f)
+{
+  return c->degree == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 2>{});
+}
+
+// The kernel argument of a launch: the context's description of degree DEG with `set` written into it, unused slots null
+template <int DEG> inline StokesParamsT<DEG> stokes_params(const stfem_stokes_ctx *c, const StokesSet &set)
+{
+  StokesParamsT<DEG> prm = c->desc<DEG>();
+  prm.nsrc = set.nsrc; prm.nout = set.nout;
+  for (int s = 0; s < MAXSRC; ++s) {
+    prm.us[s] = s < set.nsrc ? set.us[s] : nullptr;
+    prm.ps[s] = s < set.nsrc ? set.ps[s] : nullptr;
+    for (int o = 0; o < MAXOUT; ++o) { prm.wKu[s][o] = set.wKu[s][o]; prm.wKp[s][o] = set.wKp[s][o]; prm.wM[s][o] = set.wM[s][o]; }
+  }
+  for (int o = 0; o < MAXOUT; ++o) {
+    prm.out_u[o] = o < set.nout ? set.out_u[o] : nullptr;
+    prm.out_p[o] = o < set.nout ? set.out_p[o] : nullptr;
+    prm.store_u[o] = set.store_u[o]; prm.store_p[o] = set.store_p[o];
+  }
+  return prm;
+}
 
 template <typename Params> // (StokesParamsT or ConvectionParamsT)
 __device__ __forceinline__ bool constrained_u(const Params &prm, int ix, int iy, int iz)
@@ -354,9 +378,10 @@ __device__ __forceinline__ void cip_face_gradient(const double *tS, const double
 
 // FE_Q(2) values / derivatives at the end points 0 and 1, [s * 3 + a] (stfem_stokes_cip.hip)
 void stokes_cip_end_tables(double Eu[6], double EDu[6]);
+// Every launcher takes the set of its launches and builds its kernel argument from the context's description of its degree.
 // The eight colour launches of the cell kernel (stfem_stokes_cell.hip), at the context's degree: general meshes at degree 2, boxes
-// included at degree 3, where `prm` gives the sources, destinations and weights alone
-int stokes_cell_launch(stfem_stokes_ctx *c, StokesParams &prm, hipStream_t st);
+// included at degree 3
+int stokes_cell_launch(stfem_stokes_ctx *c, const StokesSet &set, hipStream_t st);
 // The cell matrices of A(b) for the per-cell Vanka blocks (stfem_stokes_vanka_cell.hip), at the context's degree: `count` cells from cell0,
 // Ac[cell][nl][nl] with nl = 81 + 8 / 4 or 192 + 27 / 10 (FE_Q / FE_DGP pressure), Mc[cell][27 or 64][.] (nullptr: not wanted)
 int stokes_cell_matrices_launch(const stfem_stokes_ctx *c, double *Ac, double *Mc, long long cell0, unsigned count, int mode, const double *b);
@@ -365,16 +390,16 @@ int stokes_cell_matrices_launch(const stfem_stokes_ctx *c, double *Ac, double *M
 void stokes_grad_launch(const CouplingParams &k, hipStream_t st);
 void stokes_div_launch(const CouplingParams &k, long long Np, hipStream_t st);
 // The eight colour launches of the boundary kernel (stfem_stokes_boundary.hip); d_g: the Dirichlet data of the rhs mode, or nullptr
-int stokes_boundary_launch(stfem_stokes_ctx *c, StokesParams &prm, const double *d_g, hipStream_t st);
-// The convection launches after those of `prm` (stfem_stokes_convection.hip), at the context's degree: eight colour launches of the
-// cell kernel, then, with weak faces (degree 2), eight of the inflow-face kernel.  mode: STFEM_CONVECTION_FORM / _JACOBIAN; lin[s]: the
-// linearisation velocity of source s.  At degree 3 geometry and tables come from the context's base3 and `prm` gives the sources,
-// destinations and weights alone.  Nothing is launched when all wKu of the set are zero.  STFEM_STOKES_Q3_WORKGROUPS=<n>, read at
-// every launch, caps the workgroups of the colour launches at either degree, as it caps those of stokes_cell_launch.
-int stokes_convection_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *lin, int mode, hipStream_t st);
+int stokes_boundary_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *d_g, hipStream_t st);
+// The convection launches after those of the linear operator (stfem_stokes_convection.hip), at the context's degree: eight colour
+// launches of the cell kernel, then, with weak faces (degree 2), eight of the inflow-face kernel.  mode: STFEM_CONVECTION_FORM /
+// _JACOBIAN; lin[s]: the linearisation velocity of source s.  Nothing is launched when all wKu of the set are zero.
+// STFEM_STOKES_Q3_WORKGROUPS=<n>, read at every launch, caps the workgroups of the colour launches at either degree, as it caps
+// those of stokes_cell_launch.
+int stokes_convection_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *lin, int mode, hipStream_t st);
 // The CIP launches after those (stfem_stokes_cip.hip): eight colour launches; weight[s]: the weight velocity of source s.  Nothing is
 // launched with delta0 == 0, on a mesh without interior faces, for a colour without cells or when all wKu of the set are zero.
-int stokes_cip_launch(stfem_stokes_ctx *c, const StokesParams &prm, const double *const *weight, double delta0, hipStream_t st);
+int stokes_cip_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *weight, double delta0, hipStream_t st);
 // On a slab with neighbours (stfem_stokes_set_cip_neighbours) and delta0 != 0 that launch looks up the ghost planes bound to each
 // source; the entry points ask this before anything touches the device: STFEM_ERR_INVALID_ARGUMENT, with its reason, for a velocity
 // source without a binding or with a binding that lacks a side

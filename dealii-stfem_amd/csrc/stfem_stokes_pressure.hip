@@ -195,7 +195,7 @@ int pressure_ctx(stfem_stokes_ctx *c, stfem_ctx **out)
         md.lower[d] = c->h_vertices[d];
         md.upper[d] = c->h_vertices[c->h_vertices.size() - 3 + d];
       }
-      if (!c->cart()) md.vertices = c->h_vertices.data();
+      if (!c->cart) md.vertices = c->h_vertices.data();
     }
     stfem_space_desc sd{1, 2, 1, 0}; // (the carrier is a degree-1 context whatever the pressure degree)
     if (!c->pspace) { sd.degree = c->degree - 1; sd.n_q_points_1d = c->degree; }
@@ -208,8 +208,8 @@ int pressure_ctx(stfem_stokes_ctx *c, stfem_ctx **out)
 
 int pressure_mean_vectors(stfem_stokes_ctx *c, double *ones, double *weights, double *volume)
 {
-  if (!c->cart()) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "the pressure mean vectors are built for axis-aligned uniform meshes");
-  const double cell = c->degree == 3 ? c->base3.detJ : c->base.detJ;
+  if (!c->cart) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "the pressure mean vectors are built for axis-aligned uniform meshes");
+  const double cell = c->detJ;
   const long long ncells = (long long)c->nc[0] * c->nc[1] * c->nc[2];
   *volume = cell * double(ncells);
   if (c->pspace) { // psi_0 = 1, the others have zero mean on a box
@@ -240,11 +240,11 @@ int pressure_mean_vectors(stfem_stokes_ctx *c, double *ones, double *weights, do
 
 int pressure_quadrature_points(const stfem_stokes_ctx *c, int nq, double *out)
 {
-  if (!c->cart()) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "the pressure quadrature points are built for axis-aligned uniform meshes");
+  if (!c->cart) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "the pressure quadrature points are built for axis-aligned uniform meshes");
   std::vector<double> xq, wq;
   stfem::gauss_rule(nq, xq, wq);
   double lo[3], h[3];
-  for (int d = 0; d < 3; ++d) { lo[d] = c->h_vertices[d]; h[d] = 1.0 / (c->degree == 3 ? c->base3.hinv[d] : c->base.hinv[d]); }
+  for (int d = 0; d < 3; ++d) { lo[d] = c->h_vertices[d]; h[d] = 1.0 / c->hinv[d]; }
   size_t o = 0;
   for (int cz = 0; cz < c->nc[2]; ++cz)
     for (int cy = 0; cy < c->nc[1]; ++cy)
@@ -261,7 +261,7 @@ int pressure_quadrature_points(const stfem_stokes_ctx *c, int nq, double *out)
 
 int pressure_difference(stfem_stokes_ctx *c, int nq, const double *p, const double *exact_at_points, double out[2], void *stream)
 {
-  if (!c->cart()) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "the pressure difference is built for axis-aligned uniform meshes");
+  if (!c->cart) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "the pressure difference is built for axis-aligned uniform meshes");
   STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long ncells = (long long)c->nc[0] * c->nc[1] * c->nc[2];
@@ -292,18 +292,14 @@ int pressure_difference(stfem_stokes_ctx *c, int nq, const double *p, const doub
   STFEM_TRY(hipMemcpyAsync(c->d_pq, exact_at_points, npts * sizeof(double), hipMemcpyHostToDevice, st));
   STFEM_TRY(hipMemcpyAsync(c->d_pq + npts, rule.data(), rule.size() * sizeof(double), hipMemcpyHostToDevice, st));
   stfem_launch_begin();
-  const double detJ = c->degree == 3 ? c->base3.detJ : c->base.detJ;
   auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)ncells), dim3(64), 0, st, c->nc[0], c->nc[1], c->nc[2], nq, detJ, (const double *)(c->d_pq + npts),
+    hipLaunchKernelGGL(kern, dim3((unsigned)ncells), dim3(64), 0, st, c->nc[0], c->nc[1], c->nc[2], nq, c->detJ, (const double *)(c->d_pq + npts),
                        (const double *)(c->d_pq + npts + nq), p, (const double *)c->d_pq, c->d_pred);
   };
-  if (c->degree == 3) {
-    if (c->pspace) launch(pressure_difference_kernel<true, 3>);
-    else launch(pressure_difference_kernel<false, 3>);
-  } else {
-    if (c->pspace) launch(pressure_difference_kernel<true, 2>);
-    else launch(pressure_difference_kernel<false, 2>);
-  }
+  stokes_with_degree(c, [&](auto deg) {
+    if (c->pspace) launch(pressure_difference_kernel<true, deg()>);
+    else launch(pressure_difference_kernel<false, deg()>);
+  });
   hipLaunchKernelGGL(pressure_difference_finish, dim3(1), dim3(256), 0, st, ncells, c->d_pred, c->d_pred + 2 * ncells);
   if (const int rc = stfem_launch_end("pressure_difference_kernel")) return rc;
   STFEM_TRY(hipMemcpyAsync(out, c->d_pred + 2 * ncells, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -322,16 +318,18 @@ int dgp_transfer(const char *me, stfem_stokes_ctx *fine, stfem_stokes_ctx *coars
   STFEM_TRY(hipSetDevice(fine->device));
   const long long nc = (long long)coarse->nc[0] * coarse->nc[1] * coarse->nc[2];
   const dim3 grid((unsigned)((nc + 255) / 256));
-  if (fine->degree == 3) {
-    DgpTables tab;
-    stfem::dgp_child_tables(tab.T);
-    hipLaunchKernelGGL(dgp2_transfer_kernel<RESTRICT>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), coarse->nc[0], coarse->nc[1], coarse->nc[2],
-                       dst, src, add, tab);
-    return stfem_launch_end(RESTRICT ? "dgp2_transfer_kernel<true>" : "dgp2_transfer_kernel<false>");
-  }
-  hipLaunchKernelGGL(dgp_transfer_kernel<RESTRICT>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), coarse->nc[0], coarse->nc[1], coarse->nc[2], dst,
-                     src, add);
-  return stfem_launch_end(RESTRICT ? "dgp_transfer_kernel<true>" : "dgp_transfer_kernel<false>");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return stokes_with_degree(fine, [&](auto deg) {
+    if constexpr (deg() == 3) {
+      DgpTables tab;
+      stfem::dgp_child_tables(tab.T);
+      hipLaunchKernelGGL(dgp2_transfer_kernel<RESTRICT>, grid, dim3(256), 0, st, coarse->nc[0], coarse->nc[1], coarse->nc[2], dst, src, add, tab);
+      return stfem_launch_end(RESTRICT ? "dgp2_transfer_kernel<true>" : "dgp2_transfer_kernel<false>");
+    } else {
+      hipLaunchKernelGGL(dgp_transfer_kernel<RESTRICT>, grid, dim3(256), 0, st, coarse->nc[0], coarse->nc[1], coarse->nc[2], dst, src, add);
+      return stfem_launch_end(RESTRICT ? "dgp_transfer_kernel<true>" : "dgp_transfer_kernel<false>");
+    }
+  });
 }
 } // namespace
 

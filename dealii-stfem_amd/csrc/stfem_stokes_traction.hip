@@ -266,7 +266,7 @@ int stfem_stokes_drag_lift(stfem_stokes_ctx *c, int face_mask, double scale, int
     c->trac_cap = need;
   }
   double *items = item_out ? item_out : c->d_trac, *sums = c->d_trac + size_t(nitems) * 3 * size_t(n);
-  const StokesParams &b = c->base;
+  const StokesParams &b = c->desc<2>();
   k.vertices = c->d_vertices;
   k.ncx = c->nc[0]; k.ncy = c->nc[1]; k.ncz = c->nc[2];
   for (int d = 0; d < 3; ++d) { k.ndu[d] = c->ndu[d]; k.ndp[d] = c->ndp[d]; k.xq[d] = b.xq[d]; k.wq[d] = b.wq[d]; }

@@ -257,26 +257,6 @@ __global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesC
   }
 }
 
-template <int DEG>
-void cell_matrices_describe(StokesCellMatParamsT<DEG> &p, const stfem_stokes_ctx *c, const StokesParamsT<DEG> &g, double *Ac, double *Mc, long long cell0, const double *b)
-{
-  constexpr int N1 = DEG + 1;
-  p.vertices = c->d_vertices;
-  p.Ac = Ac; p.Mc = Mc;
-  p.ncx = c->nc[0]; p.ncy = c->nc[1]; p.ncz = c->nc[2];
-  p.cell0 = cell0;
-  p.nu = c->nu;
-  for (int i = 0; i < N1 * N1; ++i) { p.Su[i] = g.Su[i]; p.Du[i] = g.Du[i]; }
-  for (int i = 0; i < N1 * DEG; ++i) p.Sp[i] = g.Sp[i];
-  for (int i = 0; i < N1; ++i) {
-    p.xq[i] = g.xq[i]; p.wq[i] = g.wq[i];
-    for (int k = 0; k < DEG - 1; ++k) p.lq[k][i] = g.lq[k][i];
-  }
-  p.b = b;
-  p.Nu = c->Nu; p.dmask = c->dmask;
-  for (int i = 0; i < 3; ++i) p.ndu[i] = c->ndu[i];
-}
-
 constexpr int CIP_CELL = 27 * 7 * 27; // doubles of a cell's CIP matrix
 
 struct StokesCipCellParams {
@@ -585,6 +565,44 @@ __global__ __launch_bounds__(256) void stokes_vanka_apply_percell_kernel(const S
   }
 }
 
+template <int DEG>
+int cell_matrices_launch(const stfem_stokes_ctx *c, double *Ac, double *Mc, long long cell0, unsigned count, int mode, const double *b)
+{
+  // (the table names the kernels of both degrees, degree 2 first, whatever DEG: the order in which the host code first names the
+  // kernels is the order in which they stand in the code object, which stays that of profiles/stokes_launch_set.txt)
+#define STFEM_CELL_MATRICES(D, PDG) \
+  {reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<D, PDG, 0>), reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<D, PDG, 1>), \
+   reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<D, PDG, 2>)}
+  static const void *const kernels[2][2][3] = {{STFEM_CELL_MATRICES(2, false), STFEM_CELL_MATRICES(2, true)},
+                                               {STFEM_CELL_MATRICES(3, false), STFEM_CELL_MATRICES(3, true)}}; // [degree - 2][pspace][mode]
+#undef STFEM_CELL_MATRICES
+  StokesCellMat<DEG> p;
+  std::memset(&p, 0, sizeof(p));
+  const StokesParamsT<DEG> &g = c->desc<DEG>();
+  constexpr int N1 = DEG + 1;
+  p.vertices = c->d_vertices;
+  p.Ac = Ac; p.Mc = Mc;
+  p.ncx = c->nc[0]; p.ncy = c->nc[1]; p.ncz = c->nc[2];
+  p.cell0 = cell0;
+  p.nu = c->nu;
+  for (int i = 0; i < N1 * N1; ++i) { p.Su[i] = g.Su[i]; p.Du[i] = g.Du[i]; }
+  for (int i = 0; i < N1 * DEG; ++i) p.Sp[i] = g.Sp[i];
+  for (int i = 0; i < N1; ++i) {
+    p.xq[i] = g.xq[i]; p.wq[i] = g.wq[i];
+    for (int k = 0; k < DEG - 1; ++k) p.lq[k][i] = g.lq[k][i];
+  }
+  p.b = mode ? b : nullptr;
+  p.Nu = c->Nu; p.dmask = c->dmask;
+  for (int i = 0; i < 3; ++i) p.ndu[i] = c->ndu[i];
+  if constexpr (DEG == 2) {
+    const BoundaryParams &w = c->bnd; // (all zero until stfem_stokes_set_weak_boundaries)
+    p.weak_mask = w.weak_mask; p.gamma1 = w.gamma1; p.gamma2 = w.gamma2;
+    for (int i = 0; i < 6; ++i) { p.Eu[i] = w.Eu[i]; p.EDu[i] = w.EDu[i]; }
+    for (int i = 0; i < 4; ++i) p.Ep[i] = w.Ep[i];
+  }
+  return vk_launch(kernels[DEG - 2][c->pspace ? 1 : 0][mode], dim3(count), &p, nullptr, "stokes_cell_matrices_kernel");
+}
+
 } // namespace
 
 int stokes_cell_matrices_launch(const stfem_stokes_ctx *c, double *Ac, double *Mc, long long cell0, unsigned count, int mode, const double *b)
@@ -595,28 +613,7 @@ int stokes_cell_matrices_launch(const stfem_stokes_ctx *c, double *Ac, double *M
     return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stokes_cell_matrices_kernel: cells [%lld, %lld) of %lld", cell0, cell0 + (long long)count, ncells);
   if (mode < 0 || mode > 2 || (mode != 0 && !b))
     return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stokes_cell_matrices_kernel: mode %d%s", mode, mode >= 0 && mode <= 2 ? " without its linearisation velocity" : "");
-#define STFEM_CELL_MATRICES(DEG, PDG) \
-  {reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<DEG, PDG, 0>), reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<DEG, PDG, 1>), \
-   reinterpret_cast<const void *>(&stokes_cell_matrices_kernel<DEG, PDG, 2>)}
-  static const void *const kernels[2][2][3] = {{STFEM_CELL_MATRICES(2, false), STFEM_CELL_MATRICES(2, true)},
-                                               {STFEM_CELL_MATRICES(3, false), STFEM_CELL_MATRICES(3, true)}}; // [degree - 2][pspace][mode]
-#undef STFEM_CELL_MATRICES
-  StokesCellMatParams p2;
-  StokesCellMatParamsT<3> p3;
-  std::memset(&p2, 0, sizeof(p2));
-  std::memset(&p3, 0, sizeof(p3));
-  const bool q3 = c->degree == 3;
-  if (q3) {
-    cell_matrices_describe(p3, c, c->base3, Ac, Mc, cell0, mode ? b : nullptr);
-  } else {
-    cell_matrices_describe(p2, c, c->base, Ac, Mc, cell0, mode ? b : nullptr);
-    const BoundaryParams &w = c->bnd; // (all zero until stfem_stokes_set_weak_boundaries)
-    p2.weak_mask = w.weak_mask; p2.gamma1 = w.gamma1; p2.gamma2 = w.gamma2;
-    for (int i = 0; i < 6; ++i) { p2.Eu[i] = w.Eu[i]; p2.EDu[i] = w.EDu[i]; }
-    for (int i = 0; i < 4; ++i) p2.Ep[i] = w.Ep[i];
-  }
-  return vk_launch(kernels[q3][c->pspace ? 1 : 0][mode], dim3(count), q3 ? static_cast<void *>(&p3) : static_cast<void *>(&p2), nullptr,
-                   "stokes_cell_matrices_kernel");
+  return stokes_with_degree(c, [&](auto deg) { return cell_matrices_launch<deg()>(c, Ac, Mc, cell0, count, mode, b); });
 }
 
 struct stokes_cell_vanka {
@@ -706,21 +703,22 @@ int build_blocks(stokes_cell_vanka *v, const double *const *lin, bool fresh)
   StokesCipCellParams cp;
   std::memset(&cp, 0, sizeof(cp));
   if (cip) {
-    const StokesParams &b = c->base;
+    const StokesParams &b = c->desc<2>(); // (the CIP term is built for degree 2)
     cp.vertices = c->d_vertices;
     cp.ncx = ncx; cp.ncy = ncy; cp.ncz = ncz;
-    for (int k = 0; k < 3; ++k) { cp.ndu[k] = c->ndu[k]; cp.xq[k] = b.xq[k]; cp.wq[k] = b.wq[k]; cp.hinv[k] = b.hinv[k]; }
+    for (int k = 0; k < 3; ++k) { cp.ndu[k] = c->ndu[k]; cp.xq[k] = b.xq[k]; cp.wq[k] = b.wq[k]; cp.hinv[k] = c->hinv[k]; }
     for (int i = 0; i < 9; ++i) { cp.Su[i] = b.Su[i]; cp.Du[i] = b.Du[i]; }
     stokes_cip_end_tables(cp.Eu, cp.EDu);
-    cp.Nu = c->Nu; cp.dmask = c->dmask; cp.detJ = b.detJ;
+    cp.Nu = c->Nu; cp.dmask = c->dmask; cp.detJ = c->detJ;
     cp.scale = d.delta0 / (8.0 * std::sqrt(2.0)); // pa = degree^3.5, degree 2 (operators.h:1614-1615)
     cp.beyond = d.beyond;
     ap.Cc = d_C; ap.cip_stride = win_cells * CIP_CELL;
     for (int i = 0; i < d.nblk; ++i) ap.selc[i] = selc[i];
   }
-  const void *cipk = c->base.cart ? reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<false>);
-  const bool q3 = d.degree == 3; // (no CIP term)
-  const void *asmk = q3 ? reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<64>) : reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<27>);
+  const void *cipk = c->cart ? reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<true>) : reinterpret_cast<const void *>(&stokes_cip_cell_matrices_kernel<false>);
+  // (64 named before 27: the order of the two kernels in the code object, see cell_matrices_launch; degree 3 has no CIP term)
+  const void *asmk = reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<64>);
+  if (d.degree == 2) asmk = reinterpret_cast<const void *>(&stokes_vanka_assemble_kernel<27>);
   stfem_launch_begin();
   v->setup_batches = 0;
   for (int z0 = own0; z0 < own1 && e == hipSuccess && rc == STFEM_OK; z0 += L) {

@@ -1,6 +1,6 @@
 // What the slab driver needs around the operator: load vectors, nodal interpolation points
 // and error norms.  None of it is on the vmult hot path; the kernels are plain (one workgroup
-// per cell, the MappingQ1 Jacobian from the eight cell vertices on the fly).
+// per cell, the MappingQ1 Jacobian and the mapped points from the eight cell vertices on the fly: stfem_mapping_q1.h).
 //
 // Replaces, for the structured meshes of this library:
 //   VectorTools::create_right_hand_side(mapping, dof_handler, quad, f, rhs, constraints)  (tests/tp_01.cc:382-392)
@@ -11,6 +11,7 @@
 //       (include/exact_solution.h:534-600)                                                -> stfem_integrate_difference
 //   the vector arithmetic of SolverFGMRES / TimeIntegrator (add, sadd, equ)               -> stfem_vector_axpby (stfem_vector.hip)
 #include "stfem_internal.h"
+#include "stfem_mapping_q1.h"
 
 #include <hip/hip_runtime.h>
 
@@ -38,65 +39,12 @@ std::vector<double> host_vertices(const stfem_ctx *c)
   return v;
 }
 
-// trilinear map of the reference point xi in cell (cx, cy, cz)
-void map_point(const stfem_ctx *c, const std::vector<double> &v, int cx, int cy, int cz, const double xi[3], double out[3])
-{
-  const size_t nvx = c->nc[0] + 1, nvy = c->nc[1] + 1;
-  out[0] = out[1] = out[2] = 0.0;
-  for (int k = 0; k < 2; ++k)
-    for (int j = 0; j < 2; ++j)
-      for (int i = 0; i < 2; ++i) {
-        const double w = (i ? xi[0] : 1 - xi[0]) * (j ? xi[1] : 1 - xi[1]) * (k ? xi[2] : 1 - xi[2]);
-        const double *X = v.data() + 3 * ((cx + i) + nvx * ((cy + j) + nvy * size_t(cz + k)));
-        for (int d = 0; d < 3; ++d) out[d] += w * X[d];
-      }
-}
-
 struct CellGeomParams {
   const double *vertices; // device
   int ncx, ncy, ncz, nx, ny, p, nq, dmask;
   const double *S, *D;    // [nq][n]: nodal basis and its reference derivative at the quadrature points (device)
   const double *xq, *wq;  // [nq] (device)
 };
-
-// Jacobian of the trilinear map at the reference point: J[d][e] = d x_d / d xi_e
-__device__ void jacobian(const CellGeomParams &g, int cx, int cy, int cz, const double xi[3], double J[3][3])
-{
-  const long long nvx = g.ncx + 1, nvy = g.ncy + 1;
-  for (int d = 0; d < 3; ++d)
-    for (int e = 0; e < 3; ++e) J[d][e] = 0.0;
-  for (int k = 0; k < 2; ++k)
-    for (int j = 0; j < 2; ++j)
-      for (int i = 0; i < 2; ++i) {
-        const double *X = g.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
-        const double fx = i ? xi[0] : 1 - xi[0], fy = j ? xi[1] : 1 - xi[1], fz = k ? xi[2] : 1 - xi[2];
-        const double dx = i ? 1.0 : -1.0, dy = j ? 1.0 : -1.0, dz = k ? 1.0 : -1.0;
-        for (int d = 0; d < 3; ++d) {
-          J[d][0] += X[d] * dx * fy * fz;
-          J[d][1] += X[d] * fx * dy * fz;
-          J[d][2] += X[d] * fx * fy * dz;
-        }
-      }
-}
-__device__ double det3(const double J[3][3])
-{
-  return J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-         J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-}
-
-// the trilinear map of the reference point xi in cell (cx, cy, cz)
-__device__ void map_point_dev(const CellGeomParams &g, int cx, int cy, int cz, const double xi[3], double x[3])
-{
-  const long long nvx = g.ncx + 1, nvy = g.ncy + 1;
-  x[0] = x[1] = x[2] = 0.0;
-  for (int k = 0; k < 2; ++k)
-    for (int j = 0; j < 2; ++j)
-      for (int i = 0; i < 2; ++i) {
-        const double w = (i ? xi[0] : 1 - xi[0]) * (j ? xi[1] : 1 - xi[1]) * (k ? xi[2] : 1 - xi[2]);
-        const double *V = g.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
-        for (int d = 0; d < 3; ++d) x[d] += w * V[d];
-      }
-}
 
 // f(x) = amplitude * prod_d sin(2 pi frequency x_d): the separable functions of the reference's convergence tests (exact solutions and
 // right-hand sides of include/exact_solution.h:27-81, 147-197 at a fixed time), evaluated on the device instead of handed in point by point
@@ -135,14 +83,14 @@ __global__ __launch_bounds__(256) void integrate_rhs_kernel(const CellGeomParams
     const int qx = q % nq, qy = (q / nq) % nq, qz = q / (nq * nq);
     const double xi[3] = {g.xq[qx], g.xq[qy], g.xq[qz]};
     double J[3][3];
-    jacobian(g, cx, cy, cz, xi, J);
+    mapping_q1_jacobian(g.vertices, g.ncx, g.ncy, cx, cy, cz, xi, J);
     double fv;
     if (pf.on) {
       double x[3];
-      map_point_dev(g, cx, cy, cz, xi, x);
+      mapping_q1_point(g.vertices, g.ncx, g.ncy, cx, cy, cz, xi, x);
       fv = product_value(pf, x, nullptr);
     } else fv = fq[cell * nq3 + q];
-    sm[q] = det3(J) * g.wq[qx] * g.wq[qy] * g.wq[qz] * fv;
+    sm[q] = mapping_q1_det(J) * g.wq[qx] * g.wq[qy] * g.wq[qz] * fv;
   }
   __syncthreads();
   for (int a = threadIdx.x; a < nloc; a += 256) {
@@ -182,8 +130,8 @@ __global__ __launch_bounds__(256) void integrate_difference_kernel(const CellGeo
     const int qx = q % nq, qy = (q / nq) % nq, qz = q / (nq * nq);
     const double xi[3] = {g.xq[qx], g.xq[qy], g.xq[qz]};
     double J[3][3];
-    jacobian(g, cx, cy, cz, xi, J);
-    const double det = det3(J), JxW = det * g.wq[qx] * g.wq[qy] * g.wq[qz];
+    mapping_q1_jacobian(g.vertices, g.ncx, g.ncy, cx, cy, cz, xi, J);
+    const double det = mapping_q1_det(J), JxW = det * g.wq[qx] * g.wq[qy] * g.wq[qz];
     double val = 0.0, gr[3] = {0, 0, 0};
     for (int az = 0; az < n; ++az)
       for (int ay = 0; ay < n; ++ay)
@@ -198,7 +146,7 @@ __global__ __launch_bounds__(256) void integrate_difference_kernel(const CellGeo
     double ex, exg[3] = {0, 0, 0};
     if (pf.on) {
       double x[3];
-      map_point_dev(g, cx, cy, cz, xi, x);
+      mapping_q1_point(g.vertices, g.ncx, g.ncy, cx, cy, cz, xi, x);
       ex = product_value(pf, x, exg);
     } else {
       ex = exact[cell * nq3 + q];
@@ -210,13 +158,8 @@ __global__ __launch_bounds__(256) void integrate_difference_kernel(const CellGeo
     l8 = fmax(l8, fabs(e));
     if (exact_grad || pf.on) {
       // physical gradient = J^-T reference gradient
-      const double id = 1.0 / det;
       double Ji[3][3];
-      Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id; Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-      Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id; Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
-      Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id; Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-      Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id; Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-      Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+      mapping_q1_inverse(J, Ji);
       for (int d = 0; d < 3; ++d) {
         const double gd = gr[0] * Ji[0][d] + gr[1] * Ji[1][d] + gr[2] * Ji[2][d] - exg[d];
         h1 += JxW * gd * gd;
@@ -285,7 +228,7 @@ int stfem_support_points(const stfem_ctx *c, double *out)
       for (int ix = 0; ix < c->nd[0]; ++ix) {
         const int cx = std::min(ix / p, c->nc[0] - 1), cy = std::min(iy / p, c->nc[1] - 1), cz = std::min(iz / p, c->nc[2] - 1);
         const double xi[3] = {c->tab.nodes[ix - p * cx], c->tab.nodes[iy - p * cy], c->tab.nodes[iz - p * cz]};
-        map_point(c, v, cx, cy, cz, xi, out + 3 * (ix + size_t(c->nd[0]) * (iy + size_t(c->nd[1]) * iz)));
+        mapping_q1_point(v.data(), c->nc[0], c->nc[1], cx, cy, cz, xi, out + 3 * (ix + size_t(c->nd[0]) * (iy + size_t(c->nd[1]) * iz)));
       }
   return STFEM_OK;
 }
@@ -304,7 +247,7 @@ int stfem_quadrature_points(const stfem_ctx *c, int nq, double *out)
           for (int qy = 0; qy < nq; ++qy)
             for (int qx = 0; qx < nq; ++qx, ++o) {
               const double xi[3] = {xq[qx], xq[qy], xq[qz]};
-              map_point(c, v, cx, cy, cz, xi, out + 3 * o);
+              mapping_q1_point(v.data(), c->nc[0], c->nc[1], cx, cy, cz, xi, out + 3 * o);
             }
   return STFEM_OK;
 }

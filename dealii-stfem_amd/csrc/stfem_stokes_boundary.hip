@@ -6,6 +6,7 @@
 // The same kernel evaluates StokesNitscheMatrixFreeOperator::vmult (1898-1940): the functional of the Dirichlet data g.
 // One half-wave per boundary CELL (a cell on several weak faces is handled once, by its lowest face, for all of them);
 // eight colour launches after the cell loop's, plain read-add-write: no atomics, reproducible.
+// Face geometry: stfem_mapping_q1.h.
 #include "stfem_stokes_internal.h"
 
 #include <algorithm>
@@ -95,39 +96,8 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
         if (on && t32 < 9) { // geometry of this lane's face point
           double xi[3];
           xi[d] = s; xi[t1] = tX[q1]; xi[t2] = tX[q2];
-          const double fx[2] = {1 - xi[0], xi[0]}, fy[2] = {1 - xi[1], xi[1]}, fz[2] = {1 - xi[2], xi[2]}, dd[2] = {-1.0, 1.0};
-          double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-          const long long nvx = prm.ncx + 1, nvy = prm.ncy + 1;
-          for (int k = 0; k < 2; ++k)
-            for (int j = 0; j < 2; ++j)
-              for (int i = 0; i < 2; ++i) {
-                const double *V = prm.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
-                for (int e = 0; e < 3; ++e) {
-                  const double Ve = V[e];
-                  J[e][0] += Ve * dd[i] * fy[j] * fz[k];
-                  J[e][1] += Ve * fx[i] * dd[j] * fz[k];
-                  J[e][2] += Ve * fx[i] * fy[j] * dd[k];
-                }
-              }
-          const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-                             J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-          const double id = 1.0 / det;
-          Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
-          Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-          Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-          Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
-          Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-          Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-          Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
-          Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-          Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-          double m[3], len = 0.0;
-          for (int k = 0; k < 3; ++k) {
-            m[k] = (s ? 1.0 : -1.0) * (d == 0 ? Ji[0][k] : (d == 1 ? Ji[1][k] : Ji[2][k]));
-            len += m[k] * m[k];
-          }
-          len = sqrt(len);
-          for (int k = 0; k < 3; ++k) nrm[k] = m[k] / len;
+          const double det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx, cy, cz, xi, Ji);
+          const double len = mapping_q1_face_normal(Ji, d, s ? 1 : -1, nrm);
           JxW = fabs(det) * len * tW[q1] * tW[q2];
           sJ[slot][t32] = JxW;
         }
@@ -300,7 +270,6 @@ int stfem_stokes_face_points(const stfem_stokes_ctx *c, double *out)
   if (const int rq = stokes_require_q2(c, "stfem_stokes_face_points")) return rq;
   std::vector<double> xq, wq;
   stfem::gauss_rule(3, xq, wq);
-  const long long nvx = c->nc[0] + 1, nvy = c->nc[1] + 1;
   size_t pt = 0;
   for (int f = 0; f < 6; ++f) {
     if (!(c->weak_mask >> f & 1)) continue;
@@ -313,15 +282,7 @@ int stfem_stokes_face_points(const stfem_stokes_ctx *c, double *out)
           for (int q1 = 0; q1 < 3; ++q1, ++pt) {
             double xi[3];
             xi[d] = s; xi[t1] = xq[q1]; xi[t2] = xq[q2];
-            double x[3] = {0, 0, 0};
-            for (int k = 0; k < 2; ++k)
-              for (int j = 0; j < 2; ++j)
-                for (int i = 0; i < 2; ++i) {
-                  const double w = (i ? xi[0] : 1 - xi[0]) * (j ? xi[1] : 1 - xi[1]) * (k ? xi[2] : 1 - xi[2]);
-                  const double *V = c->h_vertices.data() + 3 * ((cc[0] + i) + nvx * ((cc[1] + j) + nvy * (long long)(cc[2] + k)));
-                  for (int e = 0; e < 3; ++e) x[e] += w * V[e];
-                }
-            for (int e = 0; e < 3; ++e) out[3 * pt + e] = x[e];
+            mapping_q1_point(c->h_vertices.data(), c->nc[0], c->nc[1], cc[0], cc[1], cc[2], xi, out + 3 * pt);
           }
       }
   }

@@ -230,8 +230,8 @@ __global__ __launch_bounds__(256) void stokes_cell_kernel(const StokesParamsT<DE
       Y[9 * NN + t] = (gref[0][0] * prm.hinv[0] + gref[1][1] * prm.hinv[1] + gref[2][2] * prm.hinv[2]) * JxW;
     } else {
       const double xi[3] = {prm.xq[a], prm.xq[b], prm.xq[c]};
-      double Ji[3][3], det;
-      cip_jacobian(prm, cx, cy, cz, xi, Ji, det); // (J^-1 and det J of the trilinear mapping at this lane's point)
+      double Ji[3][3];
+      const double det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx, cy, cz, xi, Ji); // (at this lane's point)
       const double JxW = det * wabc;
       double divu = 0.0;
 #pragma unroll

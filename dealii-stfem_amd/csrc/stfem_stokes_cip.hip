@@ -157,13 +157,8 @@ __global__ __launch_bounds__(256) void stokes_cip_kernel(const std::conditional_
             double xi[3], Ji[3][3], det;
 #pragma unroll
             for (int k = 0; k < 3; ++k) xi[k] = k == d ? double(s) : tX[k == t1 ? q1 : q2];
-            cip_jacobian(prm, cx, cy, cz, xi, Ji, det);
-            double len = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { nrm[k] = Ji[d][k]; len += nrm[k] * nrm[k]; } // J^-T e_d
-            len = sqrt(len);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) nrm[k] /= len;
+            det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx, cy, cz, xi, Ji);
+            const double len = mapping_q1_face_normal(Ji, d, 0, nrm); // J^-T e_d, unsigned
             JxW = fabs(det) * len * tW[q1] * tW[q2];
 #pragma unroll
             for (int e = 0; e < 3; ++e) go[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
@@ -173,10 +168,10 @@ __global__ __launch_bounds__(256) void stokes_cip_kernel(const std::conditional_
               // 0 of the side's two vertex planes: reads 3 ((cx + i) + (ncx + 1) ((cy + j) + (ncy + 1) k)), k in {0, 1}, inside
               // 2 (ncx + 1) (ncy + 1) * 3
               const bool below = ncz_ < 0, beyond = below || ncz_ >= prm.ncz;
-              const CipGhostGeometry geo = {beyond ? prm.ghost_vertices[below ? 0 : 1] : prm.vertices, prm.ncx, prm.ncy};
-              cip_jacobian(geo, ncx_, ncy_, beyond ? 0 : ncz_, xi, Ji, det);
+              const double *vertices = beyond ? prm.ghost_vertices[below ? 0 : 1] : prm.vertices;
+              det = mapping_q1_inverse(vertices, prm.ncx, prm.ncy, ncx_, ncy_, beyond ? 0 : ncz_, xi, Ji);
             } else {
-              cip_jacobian(prm, ncx_, ncy_, ncz_, xi, Ji, det);
+              det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, ncx_, ncy_, ncz_, xi, Ji);
             }
 #pragma unroll
             for (int e = 0; e < 3; ++e) gnb[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];

@@ -132,8 +132,8 @@ __global__ __launch_bounds__(256) void stokes_convection_kernel(const Convection
         }
     } else {
       const double xi[3] = {prm.xq[a], prm.xq[b], prm.xq[c]};
-      double Ji[3][3], det;
-      cip_jacobian(prm, cx, cy, cz, xi, Ji, det); // (J^-1 and det J of the trilinear mapping at this lane's point)
+      double Ji[3][3];
+      const double det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx, cy, cz, xi, Ji); // (at this lane's point)
       const double JxW = det * wabc;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
@@ -282,8 +282,9 @@ __global__ __launch_bounds__(256) void stokes_inflow_kernel(const ConvectionPara
           double xi[3];
 #pragma unroll
           for (int k = 0; k < 3; ++k) xi[k] = k == d ? double(s) : tX[k == t1 ? q1 : q2];
-          double Ji[3][3], det;
-          cip_jacobian(prm, cx, cy, cz, xi, Ji, det);
+          double Ji[3][3];
+          const double det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx, cy, cz, xi, Ji);
+          // (not mapping_q1_face_normal: m stays un-normalised and b . m is divided by |m| once, other roundings than b . (m / |m|))
           double m[3], len = 0.0;
           for (int k = 0; k < 3; ++k) {
             m[k] = (s ? 1.0 : -1.0) * (d == 0 ? Ji[0][k] : (d == 1 ? Ji[1][k] : Ji[2][k]));

@@ -96,38 +96,9 @@ __global__ __launch_bounds__(256) void stokes_divergence_kernel(const Divergence
     }
 
     // ---- quadrature-point operation (operators.h:1432-1436): div u = sum_f sum_e (dxi_e / dx_f) g[f][e]
-    const double x = prm.xq[a], y = prm.xq[b], z = prm.xq[c];
-    const double fx[2] = {1 - x, x}, fy[2] = {1 - y, y}, fz[2] = {1 - z, z}, dd[2] = {-1.0, 1.0};
-    double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-    const long long nvx = prm.ncx + 1, nvy = prm.ncy + 1;
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const double *V = prm.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
-#pragma unroll
-          for (int d = 0; d < 3; ++d) {
-            const double Vd = V[d];
-            J[d][0] += Vd * dd[i] * fy[j] * fz[k];
-            J[d][1] += Vd * fx[i] * dd[j] * fz[k];
-            J[d][2] += Vd * fx[i] * fy[j] * dd[k];
-          }
-        }
-    const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-                       J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-    const double id = 1.0 / det;
+    const double xi[3] = {prm.xq[a], prm.xq[b], prm.xq[c]};
     double Ji[3][3];
-    Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
-    Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-    Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-    Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
-    Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-    Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-    Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
-    Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-    Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+    const double det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx, cy, cz, xi, Ji);
     double div = 0.0;
 #pragma unroll
     for (int f = 0; f < 3; ++f)

@@ -2,6 +2,7 @@
 // pressure,convection,cip,divergence,traction}.hip): the description of a launch, the context and the launchers.  Not part of the boundary.
 #pragma once
 #include "stfem_internal.h"
+#include "stfem_mapping_q1.h"
 #include "stfem_stokes_set.h"
 
 #include <hip/hip_runtime.h>
@@ -140,11 +141,6 @@ struct CipSlabParams : CipParams {
   const double *ghost_vertices[2];
   // per source the two velocity DoF planes beyond each interface, [comp][plane, ascending z][ndy][ndx] (stfem_stokes_cip_pack)
   const double *ghost_lo[MAXSRC], *ghost_hi[MAXSRC];
-};
-// (what cip_jacobian reads of its Params: the two-plane vertex arrays above)
-struct CipGhostGeometry {
-  const double *vertices;
-  int ncx, ncy;
 };
 
 struct stfem_stokes_ctx {
@@ -321,42 +317,6 @@ template <class Launch> inline void stokes_colour_launches(const stfem_stokes_ct
 
 // What the CIP kernel of the operator (stfem_stokes_cip.hip) and the CIP cell matrices of the per-cell Vanka blocks
 // (stfem_stokes_vanka_cell.hip) share.
-// J^-1 and det J of the trilinear mapping of cell (cx, cy, cz) at the reference point xi (Params: vertices, ncx, ncy)
-template <typename Params>
-__device__ __forceinline__ void cip_jacobian(const Params &prm, int cx, int cy, int cz, const double xi[3], double Ji[3][3], double &det)
-{
-  const double fx[2] = {1 - xi[0], xi[0]}, fy[2] = {1 - xi[1], xi[1]}, fz[2] = {1 - xi[2], xi[2]}, dd[2] = {-1.0, 1.0};
-  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  const long long nvx = prm.ncx + 1, nvy = prm.ncy + 1;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const double *V = prm.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-          const double Ve = V[e];
-          J[e][0] += Ve * dd[i] * fy[j] * fz[k];
-          J[e][1] += Ve * fx[i] * dd[j] * fz[k];
-          J[e][2] += Ve * fx[i] * fy[j] * dd[k];
-        }
-      }
-  det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-        J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-  const double id = 1.0 / det;
-  Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
-  Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-  Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-  Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
-  Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-  Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-  Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
-  Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-  Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-}
-
 // The face tables: (g0, g1, g2) = d phi_n / d xi_e of FE_Q(2) node n at point q = q1 + 3 q2 (lower tangential axis fastest) of face
 // f = 2 d + s, from the 1D tables tS / tD [q * 3 + a] at the Gauss points and tE / tED [s * 3 + a] at the end points 0 and 1
 __device__ __forceinline__ void cip_face_gradient(const double *tS, const double *tD, const double *tE, const double *tED, int f, int q, int n,

@@ -2,8 +2,9 @@
 //   StokesMatrixFreeOperator::compute_drag_lift (reference include/operators.h:1344-1389):
 //   f = scale sum_{faces of obstacle_id} sum_q ( p n - nu (grad u + grad u^T) n ) JxW_face   (tau of 1372-1377, integrate_value 1379)
 // at the operator's 3 x 3 face Gauss points, n the outward unit normal (J^-T e_d normalised, signed by the side), JxW_face and the
-// normal as the weak-face kernel has them (stfem_stokes_boundary.hip).  The full physical gradient at a face point: tangential
-// derivatives from Su / Du, the normal one from the end-point derivative table EDu, all with the cell's own Jacobian.
+// normal from stfem_mapping_q1.h, as the weak-face kernel takes them (stfem_stokes_boundary.hip).  The full physical gradient at a
+// face point: tangential derivatives from Su / Du, the normal one from the end-point derivative table EDu, all with the cell's own
+// Jacobian.
 // Work items are the pairs (selected face, boundary cell of that face) in the order of stfem_stokes_face_points; nothing is scattered,
 // so there are no colours: one launch over all items, every item writes its three sums, then one workgroup sums the items in a fixed
 // order - no atomics, bitwise reproducible.  Up to MAXSRC (u, p) pairs ride in one launch of each stage: the geometry of an item is
@@ -98,39 +99,9 @@ __global__ __launch_bounds__(256) void stokes_traction_kernel(const TractionPara
     if (point) {
       const double x1 = tX[q1], x2 = tX[q2], xd = s;
       const double xi0 = d == 0 ? xd : x1, xi1 = d == 1 ? xd : (d == 0 ? x1 : x2), xi2 = d == 2 ? xd : x2;
-      const double fx[2] = {1 - xi0, xi0}, fy[2] = {1 - xi1, xi1}, fz[2] = {1 - xi2, xi2}, dd[2] = {-1.0, 1.0};
-      double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-      const long long nvx = prm.ncx + 1, nvy = prm.ncy + 1;
-      for (int k = 0; k < 2; ++k)
-        for (int j = 0; j < 2; ++j)
-          for (int i = 0; i < 2; ++i) {
-            const double *V = prm.vertices + 3 * ((cx + i) + nvx * ((cy + j) + nvy * (long long)(cz + k)));
-            for (int e = 0; e < 3; ++e) {
-              const double Ve = V[e];
-              J[e][0] += Ve * dd[i] * fy[j] * fz[k];
-              J[e][1] += Ve * fx[i] * dd[j] * fz[k];
-              J[e][2] += Ve * fx[i] * fy[j] * dd[k];
-            }
-          }
-      const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-                         J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-      const double id = 1.0 / det;
-      Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
-      Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-      Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-      Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
-      Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-      Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-      Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
-      Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-      Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-      double m[3], len = 0.0;
-      for (int k = 0; k < 3; ++k) {
-        m[k] = (s ? 1.0 : -1.0) * (d == 0 ? Ji[0][k] : (d == 1 ? Ji[1][k] : Ji[2][k]));
-        len += m[k] * m[k];
-      }
-      len = sqrt(len);
-      for (int k = 0; k < 3; ++k) nrm[k] = m[k] / len;
+      const double xi[3] = {xi0, xi1, xi2};
+      const double det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx, cy, cz, xi, Ji);
+      const double len = mapping_q1_face_normal(Ji, d, s ? 1 : -1, nrm);
       JxW = fabs(det) * len * tW[q1] * tW[q2];
     }
 

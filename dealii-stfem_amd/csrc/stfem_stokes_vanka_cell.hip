@@ -127,10 +127,10 @@ __global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesC
     auto lv = [&](int q, int k, int dg) { return normal(k) ? (dg ? (fs ? sqrt(3.0) : -sqrt(3.0)) : 1.0) : tL[dg * N1 + q1d(q, k)]; }; // l_1(s) = sqrt 3 (2 s - 1)
     // ---- geometry of the points: MappingQ1 from the eight vertices
     if (tid < npts) {
-      double xi[3], Ji[3][3], det;
+      double xi[3], Ji[3][3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) xi[k] = normal(k) ? double(fs) : tX[q1d(tid, k)];
-      cip_jacobian(P, cx, cy, cz, xi, Ji, det);
+      const double det = mapping_q1_inverse(P.vertices, P.ncx, P.ncy, cx, cy, cz, xi, Ji);
 #pragma unroll
       for (int e = 0; e < 3; ++e)
 #pragma unroll
@@ -138,13 +138,9 @@ __global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesC
       if (!face) {
         W[tid] = det * tW[q1d(tid, 0)] * tW[q1d(tid, 1)] * tW[q1d(tid, 2)];
       } else {
-        double mm[3], len = 0.0;
-        for (int k = 0; k < 3; ++k) {
-          mm[k] = (fs ? 1.0 : -1.0) * JI[tid][3 * fd + k];
-          len += mm[k] * mm[k];
-        }
-        len = sqrt(len);
-        for (int k = 0; k < 3; ++k) NR[tid][k] = mm[k] / len;
+        double nrm[3];
+        const double len = mapping_q1_face_normal(Ji, fd, fs ? 1 : -1, nrm);
+        for (int k = 0; k < 3; ++k) NR[tid][k] = nrm[k];
         W[tid] = fabs(det) * len * tW[tid % 3] * tW[tid / 3];
       }
     }
@@ -324,20 +320,15 @@ __global__ __launch_bounds__(256) void stokes_cip_cell_matrices_kernel(const Sto
         double xi[3], Ji[3][3], det;
 #pragma unroll
         for (int k = 0; k < 3; ++k) xi[k] = k == d ? double(s) : P.xq[k == t1 ? q1 : q2];
-        cip_jacobian(P, cx, cy, cz, xi, Ji, det);
-        double len = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { nrm[k] = Ji[d][k]; len += nrm[k] * nrm[k]; } // J^-T e_d
-        len = sqrt(len);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) nrm[k] /= len;
+        det = mapping_q1_inverse(P.vertices, P.ncx, P.ncy, cx, cy, cz, xi, Ji);
+        const double len = mapping_q1_face_normal(Ji, d, 0, nrm); // J^-T e_d, unsigned
         JxW = fabs(det) * len * P.wq[q1] * P.wq[q2];
 #pragma unroll
         for (int e = 0; e < 3; ++e) go[e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
         // behind an outer face there is no cell in this mesh (cz -+ 1 would read vertex plane -1 or ncz + 1): the cell itself is
         // evaluated in its place, in bounds, and the result dropped (one call either way: a branch here cost 66 VGPRs)
         xi[d] = double(1 - s);
-        cip_jacobian(P, cx + (d == 0 ? (s ? 1 : -1) : 0), cy + (d == 1 ? (s ? 1 : -1) : 0), cz + (d == 2 && !outer ? (s ? 1 : -1) : 0), xi, Ji, det);
+        det = mapping_q1_inverse(P.vertices, P.ncx, P.ncy, cx + (d == 0 ? (s ? 1 : -1) : 0), cy + (d == 1 ? (s ? 1 : -1) : 0), cz + (d == 2 && !outer ? (s ? 1 : -1) : 0), xi, Ji);
 #pragma unroll
         for (int e = 0; e < 3; ++e) gnb[e] = outer ? 0.0 : Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
       }

@@ -24,6 +24,7 @@
 // (reference include/operators.h:1112-1133, distribute_local_to_global) and the dst = 0 /
 // dst.add(...) traffic of SystemMatrix::vmult (operators.h:536-559).
 #include "stfem_core.h"
+#include "stfem_mapping_q1.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -813,7 +814,7 @@ template <int P, int NBM> int launch_tile_t(const SweepParams &prm, const TilePl
 #if !STFEM_TILE_P
 namespace {
 
-// One thread per (cell, quadrature point): MappingQ1 Jacobian from the 8 cell vertices, then
+// One thread per (cell, quadrature point): MappingQ1 Jacobian from the 8 cell vertices (stfem_mapping_q1.h, in double), then
 // G = c_L w detJ J^-1 J^-T and Mq = c_M w detJ (what FEEvaluation::submit_gradient /
 // submit_value multiply with, reference include/operators.h:1149-1163).
 __global__ __launch_bounds__(256) void build_metric_kernel(int n, int ncx, int ncy, int64_t ncells,
@@ -831,34 +832,9 @@ __global__ __launch_bounds__(256) void build_metric_kernel(int n, int ncx, int n
   const int q = int(gid - cell * n3);
   const int qx = q % n, qy = (q / n) % n, qz = q / (n * n);
   const int cx = int(cell % ncx), cy = int((cell / ncx) % ncy), cz = int(cell / (int64_t(ncx) * ncy));
-  const int64_t nvx = ncx + 1, nvy = ncy + 1;
   const double xi[3] = {xq[qx], xq[qy], xq[qz]};
-  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  for (int c = 0; c < 2; ++c)
-    for (int b = 0; b < 2; ++b)
-      for (int a = 0; a < 2; ++a) {
-        const double *X = vert + 3 * ((cx + a) + nvx * ((cy + b) + nvy * int64_t(cz + c)));
-        const double fx = a ? xi[0] : 1.0 - xi[0], fy = b ? xi[1] : 1.0 - xi[1], fz = c ? xi[2] : 1.0 - xi[2];
-        const double dx = a ? 1.0 : -1.0, dy = b ? 1.0 : -1.0, dz = c ? 1.0 : -1.0;
-        for (int d = 0; d < 3; ++d) {
-          J[d][0] += X[d] * dx * fy * fz;
-          J[d][1] += X[d] * fx * dy * fz;
-          J[d][2] += X[d] * fx * fy * dz;
-        }
-      }
-  const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-                     J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-  const double id = 1.0 / det;
   double Ji[3][3]; // Ji[e][d] = d xi_e / d x_d
-  Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
-  Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-  Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-  Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id;
-  Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-  Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-  Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
-  Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-  Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+  const double det = mapping_q1_inverse(vert, ncx, ncy, cx, cy, cz, xi, Ji);
   const double JxW = det * wq[qx] * wq[qy] * wq[qz];
   const double fl = cl_layout == 0 ? 1.0 : (cl_layout == 1 ? cl[cell] : cl[gid]);
   const double fm = cm_layout == 0 ? 1.0 : (cm_layout == 1 ? cm[cell] : cm[gid]);

@@ -279,6 +279,16 @@ PRESSURE_SPACE_SIGNATURES = {
     "stfem_stokes_last_divergence_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
 }
 
+# every symbol the companion header include/stfem_stokes_boundary_space.h declares (tests/test_stokes_boundary_space_header_cpu.py)
+BOUNDARY_SPACE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "stfem_stokes_boundary_space.h")
+BOUNDARY_SPACE_SIGNATURES = {
+    "stfem_stokes_set_weak_boundaries_space": SIGNATURES["stfem_stokes_set_weak_boundaries"],
+    "stfem_stokes_n_face_points_space": SIGNATURES["stfem_stokes_n_face_points"],
+    "stfem_stokes_face_points_space": SIGNATURES["stfem_stokes_face_points"],
+    "stfem_stokes_nitsche_rhs_space": SIGNATURES["stfem_stokes_nitsche_rhs"],
+    "stfem_stokes_last_face_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+}
+
 
 def lib():
     """Loads the HIP library; raises (never falls back) if it has not been built."""
@@ -290,7 +300,7 @@ def lib():
         L = C.CDLL(os.environ.get("STFEM_LIB", LIB_PATH))  # STFEM_LIB: experiment builds only
         for name, (res, args) in (list(SIGNATURES.items()) + list(SPACE_SIGNATURES.items()) + list(VANKA_SPACE_SIGNATURES.items()) +
                                   list(CONVECTION_SPACE_SIGNATURES.items()) + list(VANKA_LINEARISED_SPACE_SIGNATURES.items()) +
-                                  list(PRESSURE_SPACE_SIGNATURES.items())):
+                                  list(PRESSURE_SPACE_SIGNATURES.items()) + list(BOUNDARY_SPACE_SIGNATURES.items())):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -895,8 +905,8 @@ class StokesMatrixFreeOperator:
     vmult / st_vmult / st_vmult_slice_add take the convection mode (CONVECTION_FORM / CONVECTION_JACOBIAN) and the linearisation
     velocity `lin` that the reference's set_data hands in; with the defaults they are the linear operator.  delta0 != 0 adds the
     CIP interior-face stabilisation (operators.h:1605-1633) to all of them, see set_cip.  with_degree(3, ...): FE_Q(3)^3 x FE_Q(2) /
-    FE_DGP(2), the linear cell operator with the convection modes (cell term; no weak faces), StokesPreconditionVanka.for_space
-    over it, the pressure space helpers and divergence_space."""
+    FE_DGP(2), the linear cell operator with the convection modes (cell term), weak (Nitsche) faces of the linear operator through
+    set_weak_boundaries_space (no mode then), StokesPreconditionVanka.for_space over it, the pressure space helpers and divergence_space."""
 
     def __init__(self, ncell, vertices=None, lower=(0, 0, 0), upper=(1, 1, 1), dirichlet_mask=63,
                  viscosity=1.0, velocity_degree=2, device=0, weak_boundary_ids=(), outflow_boundary_ids=(),
@@ -946,7 +956,8 @@ class StokesMatrixFreeOperator:
         operator of the constructor, bit for bit.  Degree 3: FE_Q(3)^3 x FE_Q(2), or FE_DGP(2) with dg_pressure (ten DoFs per cell),
         QGauss(4) - the pair of the reference's time degree 2 - with the cell operator alone: vmult, mass_vmult, st_vmult, st_Tvmult,
         st_vmult_slice_add, with the convection modes (lin=, mode=: the cell term); its smoother is StokesPreconditionVanka.for_space,
-        over the linear operator.  Weak / outflow ids, delta0 != 0 and everything else raise StfemError with status -2 and the reason.
+        over the linear operator.  Weak / outflow ids as keywords, delta0 != 0 and everything else raise StfemError with status -2 and the
+        reason; the weak faces of a degree-3 operator are set with set_weak_boundaries_space afterwards.
         An operator made here sends lin= / mode= through the _space entries of include/stfem_stokes_convection_space.h, and
         pressure_mean_vectors, pressure_quadrature_points, pressure_difference, pressure_ctx and (between two such operators)
         stokes_dgp_prolongate / stokes_dgp_restrict through those of include/stfem_stokes_pressure_space.h (at degree 2 the entries of
@@ -1035,6 +1046,46 @@ class StokesMatrixFreeOperator:
         out = np.zeros((n, 3))
         _check(lib().stfem_stokes_face_points(self._h, _p(out)), "stfem_stokes_face_points")
         return out
+
+    def set_weak_boundaries_space(self, weak_boundary_ids, outflow_boundary_ids=(), penalty1=20.0, penalty2=10.0):
+        """The weak (Nitsche) / outflow faces through stfem_stokes_set_weak_boundaries_space (include/stfem_stokes_boundary_space.h):
+        either velocity degree; at degree 2 the setter behind the constructor's keywords, bit for bit.  Every later vmult / st_vmult /
+        st_Tvmult / st_vmult_slice_add of the linear operator includes the face launches, and StokesPreconditionVanka.for_space over
+        this operator builds blocks with the Nitsche terms.  At degree 3 with weak faces a convection mode (lin= / mode=) and the
+        linearised blocks raise status -2: the inflow term of the faces is not built there."""
+        weak = sum(1 << int(f) for f in set(weak_boundary_ids))
+        outflow = sum(1 << int(f) for f in set(outflow_boundary_ids))
+        _check(lib().stfem_stokes_set_weak_boundaries_space(self._h, weak, outflow, float(penalty1), float(penalty2)),
+               "stfem_stokes_set_weak_boundaries_space")
+        self.weak_mask, self.outflow_mask = weak, outflow
+
+    def n_face_points_space(self):
+        """number of face quadrature points of the weak faces, (degree + 1)^2 per face cell (stfem_stokes_n_face_points_space)"""
+        n = lib().stfem_stokes_n_face_points_space(self._h)
+        if n < 0:
+            raise StfemError(int(n), "stfem_stokes_n_face_points_space")
+        return int(n)
+
+    def face_points_space(self):
+        """face_points through stfem_stokes_face_points_space: either velocity degree, QGauss(degree + 1) on the faces"""
+        out = np.zeros((self.n_face_points_space(), 3))
+        _check(lib().stfem_stokes_face_points_space(self._h, _p(out)), "stfem_stokes_face_points_space")
+        return out
+
+    def nitsche_rhs_space(self, g, dst_u, dst_p, stream=None):
+        """nitsche_rhs through stfem_stokes_nitsche_rhs_space: either velocity degree; g at face_points_space(), in its order"""
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        assert g.shape == (self.n_face_points_space(), 3)
+        _check(lib().stfem_stokes_nitsche_rhs_space(self._h, _p(g), getattr(dst_u, "ptr", dst_u), getattr(dst_p, "ptr", dst_p), stream),
+               "stfem_stokes_nitsche_rhs_space")
+
+    def last_face_plan(self):
+        """(workgroups, longest run of boundary cells per wave - per half-wave at degree 2) of the last boundary colour launch; the
+        environment variable STFEM_STOKES_FACE_WORKGROUPS, read at every launch, caps the workgroups of those launches.  A context that
+        has not launched the boundary kernel raises status -2."""
+        out = (C.c_int32 * 2)()
+        _check(lib().stfem_stokes_last_face_plan(self._h, out), "stfem_stokes_last_face_plan")
+        return tuple(out)
 
     def nitsche_rhs(self, g_at_face_points, dst_u, dst_p, stream=None):
         """StokesNitscheMatrixFreeOperator::vmult(dst) (operators.h:1833-1849): dst += boundary functional of the Dirichlet data"""

@@ -99,6 +99,9 @@ int stokes_require_q2(const stfem_stokes_ctx *c, const char *entry);
 // stfem_stokes.hip: stfem_stokes_internal_desc without that question (stfem_stokes_vanka_create_space serves degree 3 too)
 int stokes_desc_any_degree(const stfem_stokes_ctx *c, stfem_stokes_desc *out);
 int stokes_velocity_degree(const stfem_stokes_ctx *c);
+// stfem_stokes.hip: what takes a linearisation velocity asks this too.  On a context of velocity degree 3 with weak faces
+// (stfem_stokes_set_weak_boundaries_space): STFEM_ERR_UNSUPPORTED - the inflow term - min(b.n, 0) u of the faces is not built there.
+int stokes_refuse_inflow_q3(const stfem_stokes_ctx *c, const char *entry);
 // stfem_vanka.hip: vanka_invert_kernel<double> on `count` m x m matrices at B (row-major, destroyed), the inverses in the apply's
 // layout [kpad][mpad] from block cell0 of out; *singular (device) is set to 1 by a matrix without a pivot.  `stream`: a hipStream_t.
 int stfem_vanka_invert_launch(double *B, double *out, int m, int mpad, int kpad, long long cell0, unsigned count, int *singular, void *stream);

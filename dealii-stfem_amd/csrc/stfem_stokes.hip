@@ -11,8 +11,10 @@
 // context's description of its degree (stokes_params<DEG>, stfem_stokes_internal.h); the degree becomes a template parameter in
 // stokes_with_degree alone.
 // A context of velocity degree 3 (stfem_stokes_create_space) has one implementation of the linear cell operator, the same cell kernel
-// at DEG = 3 (stfem_stokes_cell.hip), and on top of it the convection launches of the Navier-Stokes modes alone
-// (the same kernel at DEG = 3, stfem_stokes_convection.hip), reached through the _space entries of stfem_stokes_convection_space.h:
+// at DEG = 3 (stfem_stokes_cell.hip), and on top of it either the boundary launches of the weak faces (the boundary kernel at DEG = 3,
+// set through stfem_stokes_set_weak_boundaries_space of stfem_stokes_boundary_space.h) or the convection launches of the
+// Navier-Stokes modes (the same kernel at DEG = 3, stfem_stokes_convection.hip), reached through the _space entries of
+// stfem_stokes_convection_space.h - not both: a mode on a context with weak faces is refused (stokes_refuse_inflow_q3).
 // stokes_require_q2 refuses the rest, so that stokes_launch finds nothing else to launch there
 // (beside the operator such a context has its per-cell Vanka smoother, stfem_stokes_vanka_create_space in stfem_stokes_vanka.hip).
 #include "stfem_stokes_internal.h"
@@ -276,6 +278,13 @@ int stfem_stokes_internal_desc(const stfem_stokes_ctx *c, stfem_stokes_desc *d)
   return stokes_desc_any_degree(c, d);
 }
 int stokes_velocity_degree(const stfem_stokes_ctx *c) { return c->degree; }
+int stokes_refuse_inflow_q3(const stfem_stokes_ctx *c, const char *entry)
+{
+  if (c && c->degree == 3 && c->weak_mask)
+    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "%s on a context of velocity degree 3 with weak faces (mask %d): the inflow term - min(b.n, 0) u of the "
+                           "faces is not built at degree 3", entry, c->weak_mask);
+  return STFEM_OK;
+}
 int stokes_desc_any_degree(const stfem_stokes_ctx *c, stfem_stokes_desc *d)
 {
   d->device = c->device; d->cart = c->cart; d->pspace = c->pspace; d->dmask = c->dmask;
@@ -454,8 +463,9 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesSet &set, hipStream_t st
 int stokes_launch(stfem_stokes_ctx *c, const StokesSet &set, int mode, const double *const *lin, hipStream_t st)
 {
   // axis-aligned uniform mesh at degree 2: the Kronecker path; otherwise the cell kernel.  (A context of degree 3 has no scalar
-  // context, no weak faces and no CIP term - their entry points are kept to degree 2: the cell operator, then the convection colours)
-  assert(c->degree == 2 || (!c->scalar && !c->weak_mask && c->cip_delta0 == 0.0));
+  // context and no CIP term - their entry points are kept to degree 2: the cell operator, its boundary launches when
+  // stfem_stokes_set_weak_boundaries_space has set weak faces, then the convection colours - never both, stokes_refuse_inflow_q3)
+  assert(c->degree == 2 || (!c->scalar && c->cip_delta0 == 0.0 && (!c->weak_mask || mode == STFEM_CONVECTION_NONE)));
   const int rc = c->scalar ? stokes_cart_launch(c, set, st) : stokes_cell_launch(c, set, st);
   if (rc != STFEM_OK) return rc;
   // LoopType::Full: the boundary-face loop of the same vmult (the mass operator has none)
@@ -494,6 +504,8 @@ int stokes_vmult_convection(stfem_stokes_ctx *c, int mode, double *dst_u, double
   if (mode != STFEM_CONVECTION_NONE && (lin_u == dst_u || lin_u == dst_p)) return STFEM_ERR_ALIAS;
   if (mode != STFEM_CONVECTION_NONE && require_q2)
     if (const int rq = stokes_require_q2(c, "stfem_stokes_vmult_convection with a convection mode")) return rq;
+  if (mode != STFEM_CONVECTION_NONE)
+    if (const int rq = stokes_refuse_inflow_q3(c, "stfem_stokes_vmult_convection_space with a convection mode")) return rq;
   if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
   STFEM_TRY(hipSetDevice(c->device));
   auto launch = stokes_set_builder(c, static_cast<hipStream_t>(stream), mode);
@@ -601,6 +613,8 @@ int stokes_st_vmult_convection(stfem_stokes_ctx *c, int mode, int n_timesteps_at
           if (dst_blocks[j] == lin_blocks[index(it, 0, d)]) return STFEM_ERR_ALIAS;
   if (navier && require_q2)
     if (const int rq = stokes_require_q2(c, "stfem_stokes_st_vmult_convection with a convection mode")) return rq;
+  if (navier)
+    if (const int rq = stokes_refuse_inflow_q3(c, "stfem_stokes_st_vmult_convection_space with a convection mode")) return rq;
   for (int it = 0; it < ns; ++it)
     for (int d = 0; d < nt; ++d)
       if (const int rg = stokes_cip_source_ready(c, src_blocks[index(it, 0, d)])) return rg;
@@ -696,6 +710,8 @@ int stokes_st_vmult_slice_add_convection(stfem_stokes_ctx *c, int mode, int n_ti
   }
   if (mode != STFEM_CONVECTION_NONE && require_q2)
     if (const int rq = stokes_require_q2(c, "stfem_stokes_st_vmult_slice_add_convection with a convection mode")) return rq;
+  if (mode != STFEM_CONVECTION_NONE)
+    if (const int rq = stokes_refuse_inflow_q3(c, "stfem_stokes_st_vmult_slice_add_convection_space with a convection mode")) return rq;
   if (const int rg = stokes_cip_source_ready(c, src_u)) return rg;
   STFEM_TRY(hipSetDevice(c->device));
   auto launch = stokes_set_builder(c, static_cast<hipStream_t>(stream), mode);

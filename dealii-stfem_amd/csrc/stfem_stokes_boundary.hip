@@ -1,15 +1,20 @@
-// Stokes two-field operator: the weak (Nitsche) boundary faces.
+// Stokes two-field operator: the weak (Nitsche) boundary faces, for velocity degree DEG = 2 and 3.
 // The boundary faces of the linear operator (LoopType::Full, reference include/operators.h:1640-1741)
 // Weak (Nitsche) faces: v <- -nu grad u n + p n + gamma1/h u + gamma2/h n (u.n), dv/dn <- -nu u, q <- -u.n with
 // gamma1 = nu penalty1, gamma2 = penalty2 (1220-1221) and h = sqrt(face area) (get_h_face, 184-209); outflow faces add
 // nothing to the linear operator (1680-1711: the back-flow term carries a factor 0.0, the rest is nonlinear-only).
 // The same kernel evaluates StokesNitscheMatrixFreeOperator::vmult (1898-1940): the functional of the Dirichlet data g.
-// One half-wave per boundary CELL (a cell on several weak faces is handled once, by its lowest face, for all of them);
-// eight colour launches after the cell loop's, plain read-add-write: no atomics, reproducible.
+// One half-wave (degree 2: 27 of 32 lanes) or wave (degree 3: 64 lanes) per boundary CELL - a cell on several weak faces is handled
+// once, by its lowest face, for all of them; eight colour launches after the cell loop's, plain read-add-write: no atomics,
+// reproducible.  Lane t = a + (DEG + 1) b + (DEG + 1)^2 c is velocity node (a, b, c); the first (DEG + 1)^2 lanes are the face's Gauss
+// points q1 + (DEG + 1) q2, lower tangential direction fastest; the FE_Q(DEG - 1) pressure rides on the lanes with a, b, c < DEG, the
+// FE_DGP(DEG - 1) functions on the first 4 or 10 lanes.  A face point is evaluated as a direct sum over the cell's nodes, c slowest, a
+// fastest, on its own lane (the work scales with the surface); the integration sums over the face points in ascending order.
 // Face geometry: stfem_mapping_q1.h.
 #include "stfem_stokes_internal.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 
 namespace {
@@ -17,26 +22,42 @@ namespace {
 
 // MULTI: several sources, their weighted sums in registers (operator mode only); otherwise one source, or the data g (rhs mode:
 // no source is read), with the weights applied at scatter time
-template <bool MULTI>
-__global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams prm, const BoundaryParams bp)
+template <int DEG, bool MULTI>
+__global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParamsT<DEG> prm, const BoundaryParams bp)
 {
-  __shared__ double tS[9], tD[9], tP[6], tE[6], tED[6], tEP[4], tX[3], tW[3];
-  __shared__ double sX[8][89], sF[8][9][7], sG[8][9][12], sJ[8][9];
-  if (threadIdx.x < 9) { tS[threadIdx.x] = prm.Su[threadIdx.x]; tD[threadIdx.x] = prm.Du[threadIdx.x]; }
-  if (threadIdx.x < 6) { tP[threadIdx.x] = prm.Sp[threadIdx.x]; tE[threadIdx.x] = bp.Eu[threadIdx.x]; tED[threadIdx.x] = bp.EDu[threadIdx.x]; }
-  if (threadIdx.x < 4) tEP[threadIdx.x] = bp.Ep[threadIdx.x];
-  if (threadIdx.x < 3) { tX[threadIdx.x] = prm.xq[threadIdx.x]; tW[threadIdx.x] = prm.wq[threadIdx.x]; }
+  constexpr int N1 = DEG + 1, N2 = N1 * N1, NN = N1 * N2; // nodes per direction, face points, nodes per cell
+  constexpr int LANES = NN <= 32 ? 32 : 64, SLOTS = 256 / LANES;
+  constexpr int NPQ = DEG * DEG * DEG, NDGP = DEG * (DEG + 1) * (DEG + 2) / 6; // pressure DoFs of a cell: FE_Q(DEG - 1), FE_DGP(DEG - 1)
+  constexpr int XP = 3 * NN;                                                   // the cell's pressure values: X[XP ..]
+  __shared__ double tS[N2], tD[N2], tP[N1 * DEG], tE[2 * N1], tED[2 * N1], tEP[2 * DEG], tX[N1], tW[N1], tL[DEG == 2 ? 1 : (DEG - 1) * N1];
+  __shared__ double sX[SLOTS][XP + (NPQ > NDGP ? NPQ : NDGP)], sF[SLOTS][N2][7], sG[SLOTS][N2][12], sJ[SLOTS][N2];
+  if (threadIdx.x < N2) { tS[threadIdx.x] = prm.Su[threadIdx.x]; tD[threadIdx.x] = prm.Du[threadIdx.x]; }
+  if (threadIdx.x < N1 * DEG) tP[threadIdx.x] = prm.Sp[threadIdx.x];
+  if (threadIdx.x < 2 * N1) { tE[threadIdx.x] = bp.Eu[threadIdx.x]; tED[threadIdx.x] = bp.EDu[threadIdx.x]; }
+  if (threadIdx.x < 2 * DEG) tEP[threadIdx.x] = bp.Ep[threadIdx.x];
+  if (threadIdx.x < N1) { tX[threadIdx.x] = prm.xq[threadIdx.x]; tW[threadIdx.x] = prm.wq[threadIdx.x]; }
+  if constexpr (DEG > 2) {
+    if (threadIdx.x < (DEG - 1) * N1) tL[threadIdx.x] = prm.lq[threadIdx.x / N1][threadIdx.x % N1]; // l_1, l_2 at the Gauss points
+  }
   __syncthreads();
-  const int slot = threadIdx.x >> 5, t32 = threadIdx.x & 31;
-  const bool lane27 = t32 < 27;
-  const int t = lane27 ? t32 : 0;
-  const int a = t % 3, b = (t / 3) % 3, c = t / 9;
-  const bool pnode = prm.pdg ? t32 < 4 : (lane27 && a < 2 && b < 2 && c < 2);
-  const int pslot = prm.pdg ? t32 : a + 2 * b + 4 * c;
+  const int slot = threadIdx.x / LANES, tl = threadIdx.x % LANES;
+  const bool lane_on = NN == LANES || tl < NN;
+  const int t = lane_on ? tl : 0;
+  const int a = t % N1, b = (t / N1) % N1, c = t / N2;
+  const bool pnode = prm.pdg ? tl < NDGP : (lane_on && a < DEG && b < DEG && c < DEG);
+  const int pslot = prm.pdg ? tl : a + DEG * b + DEG * DEG * c;
+  // FE_DGP: the degrees (i, j, k) of the function this lane integrates
+  int ei = 0, ej = 0, ek = 0;
+  {
+    constexpr DgpDegrees<DEG> dgp = dgp_degrees<DEG>();
+#pragma unroll
+    for (int f = 0; f < NDGP; ++f)
+      if (tl == f) { ei = dgp.d[f][0]; ej = dgp.d[f][1]; ek = dgp.d[f][2]; }
+  }
   const int nc[3] = {prm.ncx, prm.ncy, prm.ncz};
   double *X = sX[slot];
-  for (long long item = (long long)blockIdx.x * 8 + slot; item - slot < bp.foff[6]; item += (long long)gridDim.x * 8) {
-    // (all half-waves of the workgroup run the same number of rounds: nothing below is a workgroup barrier, but keep it uniform)
+  for (long long item = (long long)blockIdx.x * SLOTS + slot; item - slot < bp.foff[6]; item += (long long)gridDim.x * SLOTS) {
+    // (all slots of the workgroup run the same number of rounds: nothing below is a workgroup barrier, but keep it uniform)
     bool ok = item < bp.foff[6];
     int f0 = 0;
     for (int f = 0; f < 6; ++f)
@@ -58,12 +79,13 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
       if ((bp.weak_mask >> f & 1) && cc[d] == (s ? nc[d] - 1 : 0)) faces |= 1 << f;
     }
     ok = ok && (faces & ((1 << f0) - 1)) == 0;
-    if (!__builtin_amdgcn_readfirstlane(__ballot(ok) != 0)) continue; // (wave-uniform skip only: the two half-waves fence together)
-    const int ix = 2 * cx + a, iy = 2 * cy + b, iz = 2 * cz + c;
+    if (!__builtin_amdgcn_readfirstlane(__ballot(ok) != 0)) continue; // (wave-uniform skip only: the half-waves of a wave fence together)
+    const int ix = DEG * cx + a, iy = DEG * cy + b, iz = DEG * cz + c;
     const bool con = constrained_u(prm, ix, iy, iz);
     const long long gu = ix + (long long)prm.ndu[0] * (iy + (long long)prm.ndu[1] * iz);
-    const long long gp = prm.pdg ? (cx + (long long)prm.ncx * (cy + (long long)prm.ncy * cz)) * 4 + (t32 & 3)
-                                 : (cx + (a < 2 ? a : 1)) + (long long)prm.ndp[0] * ((cy + (b < 2 ? b : 1)) + (long long)prm.ndp[1] * (cz + (c < 2 ? c : 1)));
+    const long long gp = prm.pdg ? (cx + (long long)prm.ncx * (cy + (long long)prm.ncy * cz)) * NDGP + (tl < NDGP ? tl : 0)
+                                 : ((DEG - 1) * cx + (a < DEG ? a : DEG - 1)) +
+                                       (long long)prm.ndp[0] * (((DEG - 1) * cy + (b < DEG ? b : DEG - 1)) + (long long)prm.ndp[1] * ((DEG - 1) * cz + (c < DEG ? c : DEG - 1)));
     double accU[MULTI ? MAXSRC : 1][3], accP[MULTI ? MAXSRC : 1];
 #pragma unroll
     for (int o = 0; o < (MULTI ? MAXSRC : 1); ++o) accU[o][0] = accU[o][1] = accU[o][2] = accP[o] = 0.0;
@@ -71,48 +93,55 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
     for (int src = 0; src < nsrc; ++src) {
       if (!bp.g) { // gather (read_dof_values: constrained velocity entries read as 0)
         const double *us = prm.us[src], *ps = prm.ps[src];
-        if (lane27)
-          for (int comp = 0; comp < 3; ++comp) X[comp * 27 + t] = (ok && !con) ? us[comp * prm.Nu + gu] : 0.0;
-        if (pnode) X[81 + pslot] = (ok && ps) ? ps[gp] : 0.0;
+        if (lane_on)
+          for (int comp = 0; comp < 3; ++comp) X[comp * NN + t] = (ok && !con) ? us[comp * prm.Nu + gu] : 0.0;
+        if (pnode) X[XP + pslot] = (ok && ps) ? ps[gp] : 0.0;
       }
       double rU[3] = {0, 0, 0}, rP = 0.0;
       for (int f = 0; f < 6; ++f) {
         if (!__builtin_amdgcn_readfirstlane(__ballot(ok && (faces >> f & 1)) != 0)) continue;
-        const bool on = ok && (faces >> f & 1); // per half-wave
+        const bool on = ok && (faces >> f & 1); // per slot
         const int d = f >> 1, s = f & 1, t1 = d == 0 ? 1 : 0, t2 = d == 2 ? 1 : 2;
-        const int q1 = t32 % 3, q2 = (t32 / 3) % 3;
+        const int q1 = tl % N1, q2 = (tl / N1) % N1;
         // 1D tables of face point (q1, q2) / of any point q: value and derivative of node n along direction dir
-        auto tv = [&](int dir, int qa, int qb, int n) { return dir == d ? tE[s * 3 + n] : tS[(dir == t1 ? qa : qb) * 3 + n]; };
-        auto td = [&](int dir, int qa, int qb, int n) { return dir == d ? tED[s * 3 + n] : tD[(dir == t1 ? qa : qb) * 3 + n]; };
-        auto tp = [&](int dir, int qa, int qb, int n) { return dir == d ? tEP[s * 2 + n] : tP[(dir == t1 ? qa : qb) * 2 + n]; };
-        // FE_DGP(1) function j at face point (qa, qb): 1, l(xi), l(eta), l(zeta), l(x) = sqrt 3 (2 x - 1)
+        auto tv = [&](int dir, int qa, int qb, int n) { return dir == d ? tE[s * N1 + n] : tS[(dir == t1 ? qa : qb) * N1 + n]; };
+        auto td = [&](int dir, int qa, int qb, int n) { return dir == d ? tED[s * N1 + n] : tD[(dir == t1 ? qa : qb) * N1 + n]; };
+        auto tp = [&](int dir, int qa, int qb, int n) { return dir == d ? tEP[s * DEG + n] : tP[(dir == t1 ? qa : qb) * DEG + n]; };
+        // FE_DGP(DEG - 1) at face point (qa, qb).  Degree 2, function j: 1, l(xi), l(eta), l(zeta), l(x) = sqrt 3 (2 x - 1); degree 3,
+        // degrees (i, j, k): l_i(xi) l_j(eta) l_k(zeta) from the tables of the cell kernel, at the end points l_1 = -+ sqrt 3, l_2 = sqrt 5
         auto dg = [&](int j, int qa, int qb) {
           if (j == 0) return 1.0;
           const int dir = j - 1;
           const double x = dir == d ? double(s) : tX[dir == t1 ? qa : qb];
           return 1.7320508075688772 * (2.0 * x - 1.0);
         };
+        auto leg = [&](int n, int dir, int qa, int qb) {
+          if (n == 0) return 1.0;
+          if (dir == d) return n == 1 ? (s ? 1.7320508075688772 : -1.7320508075688772) : 2.23606797749979;
+          return tL[(n - 1) * N1 + (dir == t1 ? qa : qb)];
+        };
+        auto dg3 = [&](int i, int j, int k, int qa, int qb) { return leg(i, 0, qa, qb) * leg(j, 1, qa, qb) * leg(k, 2, qa, qb); };
         double Ji[3][3], nrm[3], JxW = 0.0;
-        if (on && t32 < 9) { // geometry of this lane's face point
+        if (on && tl < N2) { // geometry of this lane's face point
           double xi[3];
           xi[d] = s; xi[t1] = tX[q1]; xi[t2] = tX[q2];
           const double det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx, cy, cz, xi, Ji);
           const double len = mapping_q1_face_normal(Ji, d, s ? 1 : -1, nrm);
           JxW = fabs(det) * len * tW[q1] * tW[q2];
-          sJ[slot][t32] = JxW;
+          sJ[slot][tl] = JxW;
         }
         wave_fence();
-        if (on && t32 < 9) {
+        if (on && tl < N2) {
           double area = 0.0;
-          for (int q = 0; q < 9; ++q) area += sJ[slot][q];
+          for (int q = 0; q < N2; ++q) area += sJ[slot][q];
           const double h = sqrt(area); // get_h_face: area^(1 / (dim - 1))
           double val[3], nd[3], pq;
           if (bp.g) { // operators.h:1921-1932
             const int c1 = cc[t1], c2 = cc[t2];
             long long pt = 0;
             for (int ff = 0; ff < f; ++ff)
-              if (bp.weak_mask >> ff & 1) pt += 9ll * (bp.foff[ff + 1] - bp.foff[ff]);
-            pt += 9ll * (c1 + (long long)nc[t1] * c2) + t32;
+              if (bp.weak_mask >> ff & 1) pt += (long long)N2 * (bp.foff[ff + 1] - bp.foff[ff]);
+            pt += (long long)N2 * (c1 + (long long)nc[t1] * c2) + tl;
             const double g0 = bp.g[3 * pt], g1 = bp.g[3 * pt + 1], g2 = bp.g[3 * pt + 2];
             const double gq[3] = {g0, g1, g2};
             const double gn = g0 * nrm[0] + g1 * nrm[1] + g2 * nrm[2];
@@ -123,24 +152,30 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
             pq = -gn * JxW;
           } else { // operators.h:1720-1739
             double uval[3] = {0, 0, 0}, gref[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, pval = 0.0;
-            for (int kc = 0; kc < 3; ++kc)
-              for (int kb = 0; kb < 3; ++kb)
-                for (int ka = 0; ka < 3; ++ka) {
+            for (int kc = 0; kc < N1; ++kc)
+              for (int kb = 0; kb < N1; ++kb)
+                for (int ka = 0; ka < N1; ++ka) {
                   const double sx = tv(0, q1, q2, ka), sy = tv(1, q1, q2, kb), sz = tv(2, q1, q2, kc);
                   const double dx = td(0, q1, q2, ka) * sy * sz, dy = sx * td(1, q1, q2, kb) * sz, dz = sx * sy * td(2, q1, q2, kc);
                   for (int comp = 0; comp < 3; ++comp) {
-                    const double w = X[comp * 27 + ka + 3 * kb + 9 * kc];
+                    const double w = X[comp * NN + ka + N1 * kb + N2 * kc];
                     gref[comp][0] += w * dx; gref[comp][1] += w * dy; gref[comp][2] += w * dz;
                     uval[comp] += w * sx * sy * sz;
                   }
                 }
             if (prm.pdg) {
-              for (int j = 0; j < 4; ++j) pval += X[81 + j] * dg(j, q1, q2);
+              if constexpr (DEG == 2) {
+                for (int j = 0; j < 4; ++j) pval += X[XP + j] * dg(j, q1, q2);
+              } else {
+                constexpr DgpDegrees<DEG> dgp = dgp_degrees<DEG>();
+#pragma unroll
+                for (int j = 0; j < NDGP; ++j) pval += X[XP + j] * dg3(dgp.d[j][0], dgp.d[j][1], dgp.d[j][2], q1, q2);
+              }
             } else
-            for (int kc = 0; kc < 2; ++kc)
-              for (int kb = 0; kb < 2; ++kb)
-                for (int ka = 0; ka < 2; ++ka)
-                  pval += X[81 + ka + 2 * kb + 4 * kc] * tp(0, q1, q2, ka) * tp(1, q1, q2, kb) * tp(2, q1, q2, kc);
+            for (int kc = 0; kc < DEG; ++kc)
+              for (int kb = 0; kb < DEG; ++kb)
+                for (int ka = 0; ka < DEG; ++ka)
+                  pval += X[XP + ka + DEG * kb + DEG * DEG * kc] * tp(0, q1, q2, ka) * tp(1, q1, q2, kb) * tp(2, q1, q2, kc);
             double un = 0.0, gn[3];
             for (int comp = 0; comp < 3; ++comp) {
               gn[comp] = 0.0;
@@ -154,7 +189,7 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
             }
             pq = -un * JxW;
           }
-          double *F = sF[slot][t32], *G = sG[slot][t32];
+          double *F = sF[slot][tl], *G = sG[slot][tl];
           for (int comp = 0; comp < 3; ++comp) { F[comp] = val[comp]; F[3 + comp] = nd[comp]; }
           F[6] = pq;
           for (int e = 0; e < 3; ++e)
@@ -162,9 +197,9 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
           for (int k = 0; k < 3; ++k) G[9 + k] = nrm[k];
         }
         wave_fence();
-        if (on && lane27) { // integrate: test values and test normal derivatives of node (a, b, c)
-          for (int q = 0; q < 9; ++q) {
-            const int qa = q % 3, qb = q / 3;
+        if (on && lane_on) { // integrate: test values and test normal derivatives of node (a, b, c)
+          for (int q = 0; q < N2; ++q) {
+            const int qa = q % N1, qb = q / N1;
             const double *F = sF[slot][q], *G = sG[slot][q];
             const double sx = tv(0, qa, qb, a), sy = tv(1, qa, qb, b), sz = tv(2, qa, qb, c);
             const double gr[3] = {td(0, qa, qb, a) * sy * sz, sx * td(1, qa, qb, b) * sz, sx * sy * td(2, qa, qb, c)};
@@ -172,7 +207,10 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
             for (int k = 0; k < 3; ++k) dn += (gr[0] * G[k] + gr[1] * G[3 + k] + gr[2] * G[6 + k]) * G[9 + k];
             const double v = sx * sy * sz;
             for (int comp = 0; comp < 3; ++comp) rU[comp] += v * F[comp] + dn * F[3 + comp];
-            if (pnode) rP += (prm.pdg ? dg(t32 & 3, qa, qb) : tp(0, qa, qb, a) * tp(1, qa, qb, b) * tp(2, qa, qb, c)) * F[6];
+            if (pnode) {
+              if constexpr (DEG == 2) rP += (prm.pdg ? dg(tl & 3, qa, qb) : tp(0, qa, qb, a) * tp(1, qa, qb, b) * tp(2, qa, qb, c)) * F[6];
+              else rP += (prm.pdg ? dg3(ei, ej, ek, qa, qb) : tp(0, qa, qb, a) * tp(1, qa, qb, b) * tp(2, qa, qb, c)) * F[6];
+            }
           }
         }
         wave_fence(); // the next face reuses the point buffers
@@ -191,7 +229,7 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
       wave_fence(); // the next source overwrites X
     }
     // distribute_local_to_global (add): constrained velocity rows are not written
-    if (ok && lane27) {
+    if (ok && lane_on) {
       for (int o = 0; o < prm.nout; ++o) {
         const double kU = MULTI ? 1.0 : prm.wKu[0][o], kP = MULTI ? 1.0 : prm.wKp[0][o]; // (several sources: the weights are in the sums)
         const int oa = MULTI ? o : 0;
@@ -204,34 +242,30 @@ __global__ __launch_bounds__(256) void stokes_boundary_kernel(const StokesParams
     }
   }
 }
-} // namespace
 
-int stokes_boundary_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *d_g, hipStream_t st)
+template <int DEG> int boundary_launch(stfem_stokes_ctx *c, const StokesSet &set, const BoundaryParams &bp, hipStream_t st)
 {
-  if (set.nsrc < 1 || set.nsrc > MAXSRC || set.nout > (set.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiation's bounds)
-  BoundaryParams bp = c->bnd;
-  bp.g = d_g;
+  constexpr int SLOTS = DEG == 2 ? 8 : 4; // boundary cells of a workgroup at a time
   const long long items = bp.foff[6];
-  if (items == 0) return STFEM_OK;
-  StokesParams prm = stokes_params<2>(c, set); // (weak faces: degree 2, stfem_stokes_set_weak_boundaries)
-  const unsigned grid = (unsigned)std::min<long long>((items + 7) / 8, 4ll * c->n_cu);
+  StokesParamsT<DEG> prm = stokes_params<DEG>(c, set);
+  long long grid = std::min<long long>((items + SLOTS - 1) / SLOTS, 4ll * c->n_cu);
+  if (const char *e = getenv("STFEM_STOKES_FACE_WORKGROUPS")) grid = std::min(grid, std::max(1ll, atoll(e)));
   stfem_launch_begin();
   for (int colour = 0; colour < 8; ++colour) {
     prm.colour = colour;
-    if (prm.nsrc > 1) hipLaunchKernelGGL(stokes_boundary_kernel<true>, dim3(grid), dim3(256), 0, st, prm, bp);
-    else hipLaunchKernelGGL(stokes_boundary_kernel<false>, dim3(grid), dim3(256), 0, st, prm, bp);
+    if (prm.nsrc > 1) hipLaunchKernelGGL((stokes_boundary_kernel<DEG, true>), dim3((unsigned)grid), dim3(256), 0, st, prm, bp);
+    else hipLaunchKernelGGL((stokes_boundary_kernel<DEG, false>), dim3((unsigned)grid), dim3(256), 0, st, prm, bp);
   }
+  c->face_launched = true;
+  c->face_plan[0] = (int)grid;
+  c->face_plan[1] = (int)((items + grid * SLOTS - 1) / (grid * SLOTS));
   return stfem_launch_end("stokes_boundary_kernel");
 }
 
-extern "C" {
-
-// ---- weak boundary conditions (operators.h:1206-1211, 1220-1221; StokesNitscheMatrixFreeOperator 1768-1951) ----
-int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *c, int weak_mask, int outflow_mask, double penalty1, double penalty2)
+// What the setter and its _space form share: masks, penalties, work items and the end-point tables of the context's degree
+int set_weak_boundaries(stfem_stokes_ctx *c, int weak_mask, int outflow_mask, double penalty1, double penalty2)
 {
-  if (!c || weak_mask < 0 || weak_mask > 63 || outflow_mask < 0 || outflow_mask > 63) return STFEM_ERR_INVALID_ARGUMENT;
   // a face in both sets takes the outflow branch in the reference (1680: checked first), i.e. no term in the linear operator
-  if (const int rq = stokes_require_q2(c, "stfem_stokes_set_weak_boundaries")) return rq;
   c->outflow_mask = outflow_mask;
   c->weak_mask = weak_mask & ~outflow_mask;
   c->penalty1 = penalty1;
@@ -248,28 +282,24 @@ int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *c, int weak_mask, int out
     if (c->weak_mask >> f & 1) off += c->nc[t1] * c->nc[t2];
   }
   b.foff[6] = off;
-  const stfem::ShapeTables tu = stfem::make_shape_tables(2), tp = stfem::make_shape_tables(1);
+  const int nu1 = c->degree + 1, np1 = c->degree;
+  const stfem::ShapeTables tu = stfem::make_shape_tables(c->degree), tp = stfem::make_shape_tables(c->degree - 1);
   const std::vector<double> ends = {0.0, 1.0};
   stfem::Mat Eu, EDu, Ep, EDp;
   stfem::lagrange_tables(tu.nodes, ends, Eu, EDu);
   stfem::lagrange_tables(tp.nodes, ends, Ep, EDp);
-  for (int i = 0; i < 6; ++i) { b.Eu[i] = Eu[i]; b.EDu[i] = EDu[i]; }
-  for (int i = 0; i < 4; ++i) b.Ep[i] = Ep[i];
+  for (int i = 0; i < 2 * nu1; ++i) { b.Eu[i] = Eu[i]; b.EDu[i] = EDu[i]; }
+  for (int i = 0; i < 2 * np1; ++i) b.Ep[i] = Ep[i];
   return STFEM_OK;
 }
 
-int64_t stfem_stokes_n_face_points(const stfem_stokes_ctx *c)
-{
-  if (const int rq = stokes_require_q2(c, "stfem_stokes_n_face_points")) return rq;
-  return c ? 9ll * c->bnd.foff[6] : 0;
-}
+int64_t n_face_points(const stfem_stokes_ctx *c) { return (long long)(c->degree + 1) * (c->degree + 1) * c->bnd.foff[6]; }
 
-int stfem_stokes_face_points(const stfem_stokes_ctx *c, double *out)
+int face_points(const stfem_stokes_ctx *c, double *out)
 {
-  if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
-  if (const int rq = stokes_require_q2(c, "stfem_stokes_face_points")) return rq;
+  const int nq = c->degree + 1;
   std::vector<double> xq, wq;
-  stfem::gauss_rule(3, xq, wq);
+  stfem::gauss_rule(nq, xq, wq);
   size_t pt = 0;
   for (int f = 0; f < 6; ++f) {
     if (!(c->weak_mask >> f & 1)) continue;
@@ -278,8 +308,8 @@ int stfem_stokes_face_points(const stfem_stokes_ctx *c, double *out)
       for (int c1 = 0; c1 < c->nc[t1]; ++c1) {
         int cc[3];
         cc[d] = s ? c->nc[d] - 1 : 0; cc[t1] = c1; cc[t2] = c2;
-        for (int q2 = 0; q2 < 3; ++q2)
-          for (int q1 = 0; q1 < 3; ++q1, ++pt) {
+        for (int q2 = 0; q2 < nq; ++q2)
+          for (int q1 = 0; q1 < nq; ++q1, ++pt) {
             double xi[3];
             xi[d] = s; xi[t1] = xq[q1]; xi[t2] = xq[q2];
             mapping_q1_point(c->h_vertices.data(), c->nc[0], c->nc[1], cc[0], cc[1], cc[2], xi, out + 3 * pt);
@@ -289,11 +319,9 @@ int stfem_stokes_face_points(const stfem_stokes_ctx *c, double *out)
   return STFEM_OK;
 }
 
-int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *c, const double *g_at_face_points, double *dst_u, double *dst_p, void *stream)
+int nitsche_rhs(stfem_stokes_ctx *c, const double *g_at_face_points, double *dst_u, double *dst_p, void *stream)
 {
-  if (!c || !g_at_face_points || !dst_u || !dst_p) return STFEM_ERR_INVALID_ARGUMENT;
-  if (const int rq = stokes_require_q2(c, "stfem_stokes_nitsche_rhs")) return rq;
-  const size_t npts = size_t(stfem_stokes_n_face_points(c));
+  const size_t npts = size_t(n_face_points(c));
   if (npts == 0) return STFEM_OK; // no Dirichlet functions: vmult does nothing (operators.h:1836)
   STFEM_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -310,6 +338,78 @@ int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *c, const double *g_at_face_points
   set.out_p[0] = dst_p;
   set.wKp[0][0] = 1.0;
   return stokes_boundary_launch(c, set, c->d_g, st);
+}
+
+} // namespace
+
+int stokes_boundary_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *d_g, hipStream_t st)
+{
+  if (set.nsrc < 1 || set.nsrc > MAXSRC || set.nout > (set.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiation's bounds)
+  BoundaryParams bp = c->bnd;
+  bp.g = d_g;
+  if (bp.foff[6] == 0) return STFEM_OK;
+  return stokes_with_degree(c, [&](auto deg) { return boundary_launch<deg()>(c, set, bp, st); });
+}
+
+extern "C" {
+
+// ---- weak boundary conditions (operators.h:1206-1211, 1220-1221; StokesNitscheMatrixFreeOperator 1768-1951) ----
+// The entries of stfem.h: velocity degree 2.  Their _space forms (stfem_stokes_boundary_space.h): the context's degree.
+int stfem_stokes_set_weak_boundaries(stfem_stokes_ctx *c, int weak_mask, int outflow_mask, double penalty1, double penalty2)
+{
+  if (!c || weak_mask < 0 || weak_mask > 63 || outflow_mask < 0 || outflow_mask > 63) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_set_weak_boundaries")) return rq;
+  return set_weak_boundaries(c, weak_mask, outflow_mask, penalty1, penalty2);
+}
+
+int stfem_stokes_set_weak_boundaries_space(stfem_stokes_ctx *c, int weak_mask, int outflow_mask, double penalty1, double penalty2)
+{
+  if (!c || weak_mask < 0 || weak_mask > 63 || outflow_mask < 0 || outflow_mask > 63)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_set_weak_boundaries_space: a null context or a mask outside 0..63");
+  return set_weak_boundaries(c, weak_mask, outflow_mask, penalty1, penalty2);
+}
+
+int64_t stfem_stokes_n_face_points(const stfem_stokes_ctx *c)
+{
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_n_face_points")) return rq;
+  return c ? n_face_points(c) : 0;
+}
+
+int64_t stfem_stokes_n_face_points_space(const stfem_stokes_ctx *c) { return c ? n_face_points(c) : 0; }
+
+int stfem_stokes_face_points(const stfem_stokes_ctx *c, double *out)
+{
+  if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_face_points")) return rq;
+  return face_points(c, out);
+}
+
+int stfem_stokes_face_points_space(const stfem_stokes_ctx *c, double *out)
+{
+  if (!c || !out) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_face_points_space: a null argument");
+  return face_points(c, out);
+}
+
+int stfem_stokes_nitsche_rhs(stfem_stokes_ctx *c, const double *g_at_face_points, double *dst_u, double *dst_p, void *stream)
+{
+  if (!c || !g_at_face_points || !dst_u || !dst_p) return STFEM_ERR_INVALID_ARGUMENT;
+  if (const int rq = stokes_require_q2(c, "stfem_stokes_nitsche_rhs")) return rq;
+  return nitsche_rhs(c, g_at_face_points, dst_u, dst_p, stream);
+}
+
+int stfem_stokes_nitsche_rhs_space(stfem_stokes_ctx *c, const double *g_at_face_points, double *dst_u, double *dst_p, void *stream)
+{
+  if (!c || !g_at_face_points || !dst_u || !dst_p) return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_nitsche_rhs_space: a null argument");
+  return nitsche_rhs(c, g_at_face_points, dst_u, dst_p, stream);
+}
+
+int stfem_stokes_last_face_plan(const stfem_stokes_ctx *c, int32_t out[2])
+{
+  if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  if (!c->face_launched) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "stfem_stokes_last_face_plan: this context has not launched the boundary kernel");
+  out[0] = c->face_plan[0];
+  out[1] = c->face_plan[1];
+  return STFEM_OK;
 }
 
 } // extern "C"

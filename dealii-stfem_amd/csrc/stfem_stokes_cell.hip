@@ -25,21 +25,6 @@
 
 namespace {
 
-// FE_DGP(DEG - 1): function f is l_i(xi) l_j(eta) l_k(zeta) with i + j + k <= DEG - 1, i fastest (l_n: the orthonormal Legendre
-// functions on [0, 1]); d[f] = (i, j, k).  Degree 2: 1, l(xi), l(eta), l(zeta), deal.II's basis.
-template <int DEG> struct DgpDegrees {
-  int d[DEG * (DEG + 1) * (DEG + 2) / 6][3];
-};
-template <int DEG> constexpr DgpDegrees<DEG> dgp_degrees()
-{
-  DgpDegrees<DEG> r{};
-  int f = 0;
-  for (int k = 0; k < DEG; ++k)
-    for (int j = 0; j + k < DEG; ++j)
-      for (int i = 0; i + j + k < DEG; ++i, ++f) { r.d[f][0] = i; r.d[f][1] = j; r.d[f][2] = k; }
-  return r;
-}
-
 // 256 threads = 8 (degree 2) or 4 (degree 3) cells at a time; the workgroups walk over the cells.
 // Sum-factorised: evaluation and integration are three 1D stages each (x, y, z), handed from lane to lane through two wave-private
 // LDS regions per cell that alternate as source and destination, ordered with wave_fence() (a cell never leaves its wave: no

@@ -77,7 +77,9 @@ struct BoundaryParams {
   double gamma1, gamma2;
   int foff[7];             // first work item (cell of a face, t1 fastest) of every face, [6] = total
   const double *g;         // rhs mode: Dirichlet data at the face quadrature points [point][3]; nullptr: operator mode
-  double Eu[6], EDu[6], Ep[4]; // end-point tables [s * n + a]: FE_Q(2) values / derivatives, FE_Q(1) values at 0 and 1
+  // end-point tables [s * n + a] of the context's degree: FE_Q(DEG) values / derivatives (n = DEG + 1), FE_Q(DEG - 1) values (n = DEG)
+  // at 0 and 1; sized for degree 3
+  double Eu[8], EDu[8], Ep[6];
 };
 
 // The convection launches of the Navier-Stokes modes (stfem_stokes_convection.hip): a description of their own, so that StokesParams,
@@ -199,6 +201,8 @@ struct stfem_stokes_ctx {
   BoundaryParams bnd;
   double *d_g = nullptr; // Dirichlet data at the face quadrature points (stfem_stokes_nitsche_rhs)
   size_t g_points = 0;
+  bool face_launched = false;
+  int face_plan[2] = {0, 0}; // workgroups and longest run of items per wave / half-wave of the last boundary colour launch (stfem_stokes_last_face_plan)
   std::vector<double> h_vertices;
   // CIP interior-face stabilisation (stfem_stokes_set_cip): 0.0 = no launches; whose velocity weighs it (STFEM_CIP_WEIGHT_*)
   double cip_delta0 = 0.0;
@@ -249,6 +253,21 @@ __device__ __forceinline__ void wave_fence()
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// FE_DGP(DEG - 1): function f is l_i(xi) l_j(eta) l_k(zeta) with i + j + k <= DEG - 1, i fastest (l_n: the orthonormal Legendre
+// functions on [0, 1]); d[f] = (i, j, k).  Degree 2: 1, l(xi), l(eta), l(zeta), deal.II's basis.  (The cell kernel and the boundary kernel)
+template <int DEG> struct DgpDegrees {
+  int d[DEG * (DEG + 1) * (DEG + 2) / 6][3];
+};
+template <int DEG> constexpr DgpDegrees<DEG> dgp_degrees()
+{
+  DgpDegrees<DEG> r{};
+  int f = 0;
+  for (int k = 0; k < DEG; ++k)
+    for (int j = 0; j + k < DEG; ++j)
+      for (int i = 0; i + j + k < DEG; ++i, ++f) { r.d[f][0] = i; r.d[f][1] = j; r.d[f][2] = k; }
+  return r;
 }
 
 // What the sum-factorised cell kernels (stokes_cell_kernel in stfem_stokes_cell.hip, stokes_convection_kernel in
@@ -349,7 +368,8 @@ int stokes_cell_matrices_launch(const stfem_stokes_ctx *c, double *Ac, double *M
 // left to the caller's stfem_launch_end (stokes_cart_launch).
 void stokes_grad_launch(const CouplingParams &k, hipStream_t st);
 void stokes_div_launch(const CouplingParams &k, long long Np, hipStream_t st);
-// The eight colour launches of the boundary kernel (stfem_stokes_boundary.hip); d_g: the Dirichlet data of the rhs mode, or nullptr
+// The eight colour launches of the boundary kernel (stfem_stokes_boundary.hip), at the context's degree; d_g: the Dirichlet data of
+// the rhs mode, or nullptr.  STFEM_STOKES_FACE_WORKGROUPS=<n>, read at every launch: at most n workgroups per colour launch.
 int stokes_boundary_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *d_g, hipStream_t st);
 // The convection launches after those of the linear operator (stfem_stokes_convection.hip), at the context's degree: eight colour
 // launches of the cell kernel, then, with weak faces (degree 2), eight of the inflow-face kernel.  mode: STFEM_CONVECTION_FORM /

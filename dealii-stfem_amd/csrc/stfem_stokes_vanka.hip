@@ -462,6 +462,8 @@ int stfem_stokes_vanka_create_linearised_space(stfem_stokes_ctx *ctx, const stfe
   }
   if (stokes_velocity_degree(ctx) == 2)
     return stfem_stokes_vanka_create_linearised(ctx, desc->n_blocks, desc->block_variable, desc->Alpha, desc->Beta, desc->mode, desc->lin_blocks, out);
+  if (desc->mode != STFEM_CONVECTION_NONE) // (degree 3 with weak faces: the linear blocks hold the Nitsche terms, the inflow term of a mode is not built)
+    if (const int rq = stokes_refuse_inflow_q3(ctx, "stfem_stokes_vanka_create_linearised_space with a convection mode")) return rq;
   return create_per_cell(ctx, desc->n_blocks, desc->block_variable, desc->Alpha, desc->Beta, desc->mode, desc->lin_blocks, 0.0, out, nullptr, 0, 0, true);
 }
 

@@ -11,8 +11,8 @@
 //   stokes_cell_matrices_kernel   the cell's own (81 + npl)^2 matrix of A(b) and its 27 x 27 scalar mass, in plain matrix form, a launch per state
 //   stokes_vanka_assemble_kernel  restriction of the assembled matrices to the cell's DoFs, constraints, valence, Alpha / Beta
 //   vanka_invert_kernel<double>   (stfem_vanka.hip) Gauss-Jordan, straight into the apply's layout
-// Velocity degree 3 (stfem_stokes_vanka_create_space, _create_linearised_space; FE_Q(3)^3 x FE_Q(2) / FE_DGP(2) with QGauss(4), no weak
-// faces, no CIP term): the same kernels - the cell matrices (192 + npl)^2 and 64 x 64 from the degree's instantiation of the one
+// Velocity degree 3 (stfem_stokes_vanka_create_space, _create_linearised_space; FE_Q(3)^3 x FE_Q(2) / FE_DGP(2) with QGauss(4), weak
+// faces in the blocks of the linear operator alone, no CIP term): the same kernels - the cell matrices (192 + npl)^2 and 64 x 64 from the degree's instantiation of the one
 // degree-templated kernel, the assembling kernel instantiated for 64 nodes per component, the apply told the degree.
 // Apply: stokes_vanka_apply_percell_kernel streams every block from HBM once and leaves the rows in the scratch array; the collecting
 // launch of stfem_stokes_vanka.hip sums them per DoF: two launches, no colours, no atomics, fixed summation order.
@@ -44,14 +44,13 @@ template <int DEG> struct StokesCellMatParamsT {
   const double *b;        // linearisation velocity (3 Nu, component-major)
   long long Nu;
   int ndu[3], dmask;
-};
-// Degree 2 with the weak faces (a degree-3 context has none), as ConvectionParams holds them
-struct StokesCellMatParams : StokesCellMatParamsT<2> {
+  // the weak faces (all zero until the context has some), behind the rest: where the description of degree 2 has always had them
   int weak_mask;
   double gamma1, gamma2;
-  double Eu[6], EDu[6], Ep[4]; // the end-point tables of BoundaryParams
+  double Eu[2 * (DEG + 1)], EDu[2 * (DEG + 1)], Ep[2 * DEG]; // the end-point tables of BoundaryParams, [s * n + a]
 };
-template <int DEG> using StokesCellMat = std::conditional_t<DEG == 2, StokesCellMatParams, StokesCellMatParamsT<DEG>>;
+template <int DEG> using StokesCellMat = StokesCellMatParamsT<DEG>;
+static_assert(sizeof(StokesCellMat<2>) == 504, "the degree-2 description: the layout it had as a description of its own");
 
 // Ac[cell][NL][NL]: the cell's own matrix of A(b), rows / columns: 3 x NN velocity DoFs (component-major, node a + N1 b + N1^2 c on the
 // Gauss-Lobatto nodes), then the DEG^3 FE_Q(DEG - 1) nodes or the FE_DGP(DEG - 1) functions in the order include/stfem_stokes_space.h
@@ -60,24 +59,26 @@ template <int DEG> using StokesCellMat = std::conditional_t<DEG == 2, StokesCell
 // One workgroup per cell, plain matrix form: the physical gradients, values and pressure functions of all points are tabulated in LDS
 // from the 1D tables of the context - the ones its cell kernel applies, no closed form typed again -, then every thread takes entries
 // (row, column) and sums over the points in ascending order: a fixed summation order.  Degree 3: G 96 KiB + PH 32 KiB + PS 13.5 KiB +
-// geometry 5 KiB = 146.7 KiB of the 160 KiB a workgroup may declare on gfx950, one workgroup per CU; a mode adds b at the cell's nodes and
-// at the points, 1.5 KiB each.  Phase 0: the cell term at the operator's N1^3 Gauss points (MappingQ1 Jacobian from the eight vertices);
-// phases 1 - 6, degree 2 only: the Nitsche and inflow terms of the cell's weak faces at their 3 x 3 points, h = sqrt(face area)
-// (get_h_face, operators.h:184-209); there the 1D factor of the face's normal direction comes from the end-point tables.
+// geometry 5 KiB + face normals and end-point tables 0.6 KiB = 147.5 KiB (150 992 B with FE_Q(2), the larger) of the 163 840 B a workgroup may declare on gfx950, one workgroup
+// per CU; a mode adds b at the cell's nodes and at the points, 1.5 KiB each.  Phase 0: the cell term at the operator's N1^3 Gauss points
+// (MappingQ1 Jacobian from the eight vertices); phases 1 - 6: the Nitsche and (degree 2 only: a degree-3 context with weak faces
+// takes no mode) inflow terms of the cell's weak faces at their N1 x N1 points, lower tangential index fastest, h = sqrt(face area)
+// (get_h_face, operators.h:184-209); there the 1D factor of the face's normal direction comes from the end-point tables, l_1 = -+ sqrt 3
+// and l_2 = sqrt 5 for FE_DGP.
 // Set-up code, not tuned.
 template <int DEG, bool PDG, int MODE>
 __global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesCellMat<DEG> P)
 {
   constexpr int N1 = DEG + 1, NQ = N1 * N1 * N1, NN = NQ, NV = 3 * NN;
   constexpr int NPL = PDG ? (DEG == 2 ? 4 : 10) : DEG * DEG * DEG, NL = NV + NPL;
-  constexpr bool FACES = DEG == 2; // (a degree-3 context has no weak faces)
-  constexpr int NF = FACES ? 9 : 1;
+  constexpr bool FACES = true;
+  constexpr int NF = N1 * N1; // points of a face
   __shared__ double G[NQ][NN][3]; // physical gradient of velocity node n at point q
   __shared__ double PH[NQ][NN];   // its value
   __shared__ double PS[NQ][NPL];  // pressure functions
   __shared__ double JI[NQ][9], W[NQ];
   __shared__ double tS[N1 * N1], tD[N1 * N1], tP[N1 * DEG], tL[DEG * N1], tX[N1], tW[N1]; // the 1D tables; Legendre [degree * N1 + q], degree 0 = 1
-  __shared__ double tE[FACES ? 6 : 1], tED[FACES ? 6 : 1], tEp[FACES ? 4 : 1], NR[NF][3];   // end-point tables [s * n + a]; normals of a face
+  __shared__ double tE[2 * N1], tED[2 * N1], tEp[2 * DEG], NR[NF][3];   // end-point tables [s * n + a]; normals of a face
   __shared__ double bl[MODE ? NV : 1], BQ[MODE ? NQ : 1][3], INF[MODE ? NF : 1]; // b at the cell's nodes [component * NN + n] and at the points; inflow
   const int tid = threadIdx.x;
   const long long cell = P.cell0 + blockIdx.x;
@@ -91,8 +92,8 @@ __global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesC
     tX[tid] = P.xq[tid]; tW[tid] = P.wq[tid];
   }
   if constexpr (FACES) {
-    if (tid < 6) { tE[tid] = P.Eu[tid]; tED[tid] = P.EDu[tid]; }
-    if (tid < 4) tEp[tid] = P.Ep[tid];
+    if (tid < 2 * N1) { tE[tid] = P.Eu[tid]; tED[tid] = P.EDu[tid]; }
+    if (tid < 2 * DEG) tEp[tid] = P.Ep[tid];
   }
   if constexpr (MODE != 0) {
     if (tid < NV) { // read_dof_values: entries on strongly constrained DoFs read as 0
@@ -118,13 +119,14 @@ __global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesC
     // the 1D Gauss point of point q, q = qa + N1 qb + N1^2 qc in the cell and lower tangential index fastest on a face
     auto normal = [&](int k) { return face && k == fd; };
     auto q1d = [&](int q, int k) {
-      if (face) return k == t1 ? q % 3 : q / 3;
+      if (face) return k == t1 ? q % N1 : q / N1;
       return k == 0 ? q % N1 : (k == 1 ? (q / N1) % N1 : q / (N1 * N1));
     };
-    auto su = [&](int q, int k, int a) { return normal(k) ? tE[fs * 3 + a] : tS[q1d(q, k) * N1 + a]; };
-    auto du = [&](int q, int k, int a) { return normal(k) ? tED[fs * 3 + a] : tD[q1d(q, k) * N1 + a]; };
+    auto su = [&](int q, int k, int a) { return normal(k) ? tE[fs * N1 + a] : tS[q1d(q, k) * N1 + a]; };
+    auto du = [&](int q, int k, int a) { return normal(k) ? tED[fs * N1 + a] : tD[q1d(q, k) * N1 + a]; };
     auto sp = [&](int q, int k, int a) { return normal(k) ? tEp[fs * DEG + a] : tP[q1d(q, k) * DEG + a]; };
-    auto lv = [&](int q, int k, int dg) { return normal(k) ? (dg ? (fs ? sqrt(3.0) : -sqrt(3.0)) : 1.0) : tL[dg * N1 + q1d(q, k)]; }; // l_1(s) = sqrt 3 (2 s - 1)
+    // at the end points l_1(s) = sqrt 3 (2 s - 1), l_2(s) = sqrt 5
+    auto lv = [&](int q, int k, int dg) { return normal(k) ? (dg ? (dg == 1 ? (fs ? sqrt(3.0) : -sqrt(3.0)) : sqrt(5.0)) : 1.0) : tL[dg * N1 + q1d(q, k)]; };
     // ---- geometry of the points: MappingQ1 from the eight vertices
     if (tid < npts) {
       double xi[3], Ji[3][3];
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesC
         double nrm[3];
         const double len = mapping_q1_face_normal(Ji, fd, fs ? 1 : -1, nrm);
         for (int k = 0; k < 3; ++k) NR[tid][k] = nrm[k];
-        W[tid] = fabs(det) * len * tW[tid % 3] * tW[tid / 3];
+        W[tid] = fabs(det) * len * tW[tid % N1] * tW[tid / N1];
       }
     }
     __syncthreads();
@@ -180,12 +182,12 @@ __global__ __launch_bounds__(256) void stokes_cell_matrices_kernel(const StokesC
     if constexpr (FACES) {
       if (face) {
         double area = 0.0;
-        for (int q = 0; q < 9; ++q) area += W[q];
+        for (int q = 0; q < NF; ++q) area += W[q];
         const double h = sqrt(area);
         g1h = P.gamma1 / h;
         g2h = P.gamma2 / h;
         if constexpr (MODE != 0) {
-          if (tid < 9) INF[tid] = -fmin(BQ[tid][0] * NR[tid][0] + BQ[tid][1] * NR[tid][1] + BQ[tid][2] * NR[tid][2], 0.0) * W[tid];
+          if (tid < NF) INF[tid] = -fmin(BQ[tid][0] * NR[tid][0] + BQ[tid][1] * NR[tid][1] + BQ[tid][2] * NR[tid][2], 0.0) * W[tid];
           __syncthreads();
         }
       }
@@ -585,12 +587,10 @@ int cell_matrices_launch(const stfem_stokes_ctx *c, double *Ac, double *Mc, long
   p.b = mode ? b : nullptr;
   p.Nu = c->Nu; p.dmask = c->dmask;
   for (int i = 0; i < 3; ++i) p.ndu[i] = c->ndu[i];
-  if constexpr (DEG == 2) {
-    const BoundaryParams &w = c->bnd; // (all zero until stfem_stokes_set_weak_boundaries)
-    p.weak_mask = w.weak_mask; p.gamma1 = w.gamma1; p.gamma2 = w.gamma2;
-    for (int i = 0; i < 6; ++i) { p.Eu[i] = w.Eu[i]; p.EDu[i] = w.EDu[i]; }
-    for (int i = 0; i < 4; ++i) p.Ep[i] = w.Ep[i];
-  }
+  const BoundaryParams &w = c->bnd; // (all zero until stfem_stokes_set_weak_boundaries or its _space form)
+  p.weak_mask = w.weak_mask; p.gamma1 = w.gamma1; p.gamma2 = w.gamma2;
+  for (int i = 0; i < 2 * N1; ++i) { p.Eu[i] = w.Eu[i]; p.EDu[i] = w.EDu[i]; }
+  for (int i = 0; i < 2 * DEG; ++i) p.Ep[i] = w.Ep[i];
   return vk_launch(kernels[DEG - 2][c->pspace ? 1 : 0][mode], dim3(count), &p, nullptr, "stokes_cell_matrices_kernel");
 }
 

@@ -138,12 +138,18 @@ inline void rhs_minus(std::vector<StokesVector> &dst, const std::vector<StokesVe
 }
 
 // The operator by descriptor: what the second constructor of StokesMatrixFreeOperator takes.  velocity_degree 2 or 3; at degree 3 the
-// cell operator with the convection term of the nonlinear treatment (no weak faces, no CIP: a degree-3 context has neither).
+// cell operator with the convection term of the nonlinear treatment, or - linear operator only - with weak (Nitsche) faces; no CIP.
+// The trailing members are those of the first constructor's arguments of the same names, applied through
+// stfem_stokes_set_weak_boundaries_space (stfem_stokes_boundary_space.h), which serves either degree.
 template <typename Number> struct StokesSpace {
   unsigned velocity_degree = 2;
   bool dg_pressure = false;
   Number viscosity = 1;
   NonlinearTreatment nonlinear_treatment = NonlinearTreatment::None;
+  std::set<boundary_id> weak_boundary_ids = {};
+  std::set<boundary_id> outflow_boundary_ids = {};
+  Number penalty1 = 20;
+  Number penalty2 = 10;
 };
 
 // operators.h:1193-1766: cell loop + boundary-face loop for the weak (Nitsche) ids.  Same constructor arguments after the mesh as
@@ -188,11 +194,26 @@ public:
   }
   // By descriptor: a nonlinear treatment is accepted at velocity degree 3 too.  vmult, form and the SystemMatrixStokes calls over this
   // operator go through the _space entries of stfem_stokes_convection_space.h, which run a convection mode at either degree (degree 2:
-  // the entries of the first constructor's operator, bit for bit).
+  // the entries of the first constructor's operator, bit for bit).  Weak / outflow ids go through the _space setter of
+  // stfem_stokes_boundary_space.h: at degree 3 the linear operator and the per-cell Vanka blocks over it hold the Nitsche terms; a
+  // nonlinear treatment with weak ids is refused there (the inflow term of the faces is not built at degree 3).
   StokesMatrixFreeOperator(const Mesh &mesh, const StokesSpace<Number> &space)
     : nonlinear_treatment(space.nonlinear_treatment), nonlinear(space.nonlinear_treatment != NonlinearTreatment::None), space_entries_(true)
   {
+    int weak = 0, outflow = 0;
+    for (boundary_id f : space.weak_boundary_ids) weak |= 1 << f;
+    for (boundary_id f : space.outflow_boundary_ids) outflow |= 1 << f;
+    if (space.velocity_degree == 3 && nonlinear && (weak & ~outflow))
+      throw Error(STFEM_ERR_UNSUPPORTED, "StokesMatrixFreeOperator: a nonlinear treatment with weak boundary ids is built for velocity degree 2 only");
     create(mesh, space.velocity_degree, space.viscosity, space.dg_pressure);
+    if (weak || outflow) {
+      const int rc = stfem_stokes_set_weak_boundaries_space(h_, weak, outflow, space.penalty1, space.penalty2);
+      if (rc != STFEM_OK) { // (no destructor runs for a constructor that throws)
+        stfem_stokes_destroy(h_);
+        h_ = nullptr;
+        check(rc, "stfem_stokes_set_weak_boundaries_space");
+      }
+    }
   }
   // whether the convection entries of this operator are the _space forms (the constructor by descriptor)
   bool space_entries() const { return space_entries_; }
@@ -388,8 +409,14 @@ public:
 
   explicit StokesNitscheMatrixFreeOperator(const StokesMatrixFreeOperator<dim, Number> &op) : op_(op)
   {
-    points_.resize(3 * size_t(stfem_stokes_n_face_points(op.handle())));
-    if (!points_.empty()) check(stfem_stokes_face_points(op.handle(), points_.data()), "stfem_stokes_face_points");
+    // (an operator made by descriptor: the _space entries of stfem_stokes_boundary_space.h, which serve velocity degree 3 too)
+    if (op.space_entries()) {
+      points_.resize(3 * size_t(stfem_stokes_n_face_points_space(op.handle())));
+      if (!points_.empty()) check(stfem_stokes_face_points_space(op.handle(), points_.data()), "stfem_stokes_face_points_space");
+    } else {
+      points_.resize(3 * size_t(stfem_stokes_n_face_points(op.handle())));
+      if (!points_.empty()) check(stfem_stokes_face_points(op.handle(), points_.data()), "stfem_stokes_face_points");
+    }
   }
   // operators.h:1801-1807.  One function for all weak faces here (the reference maps boundary ids to functions; the
   // points of the faces come in ascending face order, so a caller with several functions can switch on the point)
@@ -404,7 +431,8 @@ public:
       const auto v = g_({{points_[3 * q], points_[3 * q + 1], points_[3 * q + 2]}});
       for (int e = 0; e < 3; ++e) gq[3 * q + e] = v[e];
     }
-    check(stfem_stokes_nitsche_rhs(op_.handle(), gq.data(), dst.at(0).data(), dst.at(1).data(), stream), "StokesNitscheMatrixFreeOperator::vmult");
+    check((op_.space_entries() ? stfem_stokes_nitsche_rhs_space : stfem_stokes_nitsche_rhs)(op_.handle(), gq.data(), dst.at(0).data(), dst.at(1).data(), stream),
+          "StokesNitscheMatrixFreeOperator::vmult");
   }
   unsigned long long m() const { return op_.m(); }
 

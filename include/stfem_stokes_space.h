@@ -27,8 +27,12 @@
  *     (stfem_stokes_convection_space.h), and the Vanka smoother of the linear and of the linearised operator through
  *     stfem_stokes_vanka_create_space and _create_linearised_space (stfem_stokes_vanka_space.h, stfem_stokes_vanka_linearised_space.h);
  *     the pressure helpers, the FE_DGP transfers and the divergence likewise through the _space forms of their entries, with the
- *     getter stfem_stokes_get_space (stfem_stokes_pressure_space.h).
- *     Not built at degree 3 either: GMGStokes and the drivers, slabs (untested, unclaimed), fp32.
+ *     getter stfem_stokes_get_space (stfem_stokes_pressure_space.h); the weak (Nitsche) / outflow faces of the linear operator, the
+ *     face points and the Nitsche functional through the _space forms of theirs (stfem_stokes_boundary_space.h) - once weak faces
+ *     are set there, the vmult entries above include the face launches and stfem_stokes_vanka_create_space builds blocks with the
+ *     Nitsche terms.
+ *     Not built at degree 3 either: with weak faces the inflow term of the convection modes and the linearised Vanka blocks (refused
+ *     with their reason), CIP, drag / lift, GMGStokes and the drivers, slabs (untested, unclaimed), fp32.
  *   Any other degree: STFEM_ERR_UNSUPPORTED; non-zero reserved or a pressure_space outside 0..1: STFEM_ERR_INVALID_ARGUMENT; both
  *   with their reason in stfem_last_error. */
 typedef struct {

@@ -289,6 +289,14 @@ BOUNDARY_SPACE_SIGNATURES = {
     "stfem_stokes_last_face_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
 }
 
+# every symbol the companion header include/stfem_stokes_cip_space.h declares (tests/test_stokes_cip_space_header_cpu.py)
+CIP_SPACE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "stfem_stokes_cip_space.h")
+CIP_SPACE_SIGNATURES = {
+    "stfem_stokes_set_cip_space": SIGNATURES["stfem_stokes_set_cip"],
+    "stfem_stokes_cip_add_space": SIGNATURES["stfem_stokes_cip_add"],
+    "stfem_stokes_last_cip_plan": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+}
+
 
 def lib():
     """Loads the HIP library; raises (never falls back) if it has not been built."""
@@ -300,7 +308,8 @@ def lib():
         L = C.CDLL(os.environ.get("STFEM_LIB", LIB_PATH))  # STFEM_LIB: experiment builds only
         for name, (res, args) in (list(SIGNATURES.items()) + list(SPACE_SIGNATURES.items()) + list(VANKA_SPACE_SIGNATURES.items()) +
                                   list(CONVECTION_SPACE_SIGNATURES.items()) + list(VANKA_LINEARISED_SPACE_SIGNATURES.items()) +
-                                  list(PRESSURE_SPACE_SIGNATURES.items()) + list(BOUNDARY_SPACE_SIGNATURES.items())):
+                                  list(PRESSURE_SPACE_SIGNATURES.items()) + list(BOUNDARY_SPACE_SIGNATURES.items()) +
+                                  list(CIP_SPACE_SIGNATURES.items())):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -906,7 +915,8 @@ class StokesMatrixFreeOperator:
     velocity `lin` that the reference's set_data hands in; with the defaults they are the linear operator.  delta0 != 0 adds the
     CIP interior-face stabilisation (operators.h:1605-1633) to all of them, see set_cip.  with_degree(3, ...): FE_Q(3)^3 x FE_Q(2) /
     FE_DGP(2), the linear cell operator with the convection modes (cell term), weak (Nitsche) faces of the linear operator through
-    set_weak_boundaries_space (no mode then), StokesPreconditionVanka.for_space over it, the pressure space helpers and divergence_space."""
+    set_weak_boundaries_space (no mode then), the CIP term through set_cip_space / cip_add_space, StokesPreconditionVanka.for_space
+    over it, the pressure space helpers and divergence_space."""
 
     def __init__(self, ncell, vertices=None, lower=(0, 0, 0), upper=(1, 1, 1), dirichlet_mask=63,
                  viscosity=1.0, velocity_degree=2, device=0, weak_boundary_ids=(), outflow_boundary_ids=(),
@@ -957,7 +967,7 @@ class StokesMatrixFreeOperator:
         QGauss(4) - the pair of the reference's time degree 2 - with the cell operator alone: vmult, mass_vmult, st_vmult, st_Tvmult,
         st_vmult_slice_add, with the convection modes (lin=, mode=: the cell term); its smoother is StokesPreconditionVanka.for_space,
         over the linear operator.  Weak / outflow ids as keywords, delta0 != 0 and everything else raise StfemError with status -2 and the
-        reason; the weak faces of a degree-3 operator are set with set_weak_boundaries_space afterwards.
+        reason; the weak faces of a degree-3 operator are set with set_weak_boundaries_space afterwards, its CIP term with set_cip_space.
         An operator made here sends lin= / mode= through the _space entries of include/stfem_stokes_convection_space.h, and
         pressure_mean_vectors, pressure_quadrature_points, pressure_difference, pressure_ctx and (between two such operators)
         stokes_dgp_prolongate / stokes_dgp_restrict through those of include/stfem_stokes_pressure_space.h (at degree 2 the entries of
@@ -993,6 +1003,27 @@ class StokesMatrixFreeOperator:
         """dst_u += C(weight_u; src_u): the CIP term by itself with the given delta0, independent of set_cip"""
         dst_u, src_u, weight_u = (getattr(v, "ptr", v) for v in (dst_u, src_u, weight_u))
         _check(lib().stfem_stokes_cip_add(self._h, dst_u, src_u, weight_u, float(delta0), stream), "stfem_stokes_cip_add")
+
+    def set_cip_space(self, delta0, weight=CIP_WEIGHT_SOURCE):
+        """set_cip through stfem_stokes_set_cip_space (include/stfem_stokes_cip_space.h): either velocity degree; at degree 2 the setter
+        behind set_cip, bit for bit.  At degree 3 the term is sum_F int_F delta0 h_F^2 / 3^3.5 (w.n)^2 [d_n u].[d_n v] at the 4 x 4 Gauss
+        points of the interior faces, added last by every later vmult / st_vmult / st_vmult_slice_add, with or without a convection mode
+        (not by mass_vmult; the Vanka blocks of a degree-3 operator do not take the term)."""
+        _check(lib().stfem_stokes_set_cip_space(self._h, float(delta0), int(weight)), "stfem_stokes_set_cip_space")
+        self.delta0, self.cip_weight = float(delta0), int(weight)
+
+    def cip_add_space(self, dst_u, src_u, weight_u, delta0, stream=None):
+        """cip_add through stfem_stokes_cip_add_space: dst_u += C(weight_u; src_u) at either velocity degree, independent of set_cip_space"""
+        dst_u, src_u, weight_u = (getattr(v, "ptr", v) for v in (dst_u, src_u, weight_u))
+        _check(lib().stfem_stokes_cip_add_space(self._h, dst_u, src_u, weight_u, float(delta0), stream), "stfem_stokes_cip_add_space")
+
+    def last_cip_plan(self):
+        """(workgroups, passes of the grid-stride loop: the longest run of cells per wave - per half-wave at degree 2) of the last CIP
+        colour launch; the environment variable STFEM_STOKES_CIP_WORKGROUPS, read at every launch, caps the workgroups of those
+        launches.  A context that has not launched the CIP kernel raises status -2."""
+        out = (C.c_int32 * 2)()
+        _check(lib().stfem_stokes_last_cip_plan(self._h, out), "stfem_stokes_last_cip_plan")
+        return tuple(out)
 
     def set_cip_neighbours(self, neighbour_mask, lower_vertices=None, upper_vertices=None):
         """This operator is a z-slab with a slab below (bit 4) and / or above (bit 5): the CIP term treats the interface faces as

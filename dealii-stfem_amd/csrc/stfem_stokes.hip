@@ -14,7 +14,8 @@
 // at DEG = 3 (stfem_stokes_cell.hip), and on top of it either the boundary launches of the weak faces (the boundary kernel at DEG = 3,
 // set through stfem_stokes_set_weak_boundaries_space of stfem_stokes_boundary_space.h) or the convection launches of the
 // Navier-Stokes modes (the same kernel at DEG = 3, stfem_stokes_convection.hip), reached through the _space entries of
-// stfem_stokes_convection_space.h - not both: a mode on a context with weak faces is refused (stokes_refuse_inflow_q3).
+// stfem_stokes_convection_space.h - not both: a mode on a context with weak faces is refused (stokes_refuse_inflow_q3) - and last,
+// with delta0 != 0, the CIP launches of the degree-3 kernel (stfem_stokes_set_cip_space of stfem_stokes_cip_space.h).
 // stokes_require_q2 refuses the rest, so that stokes_launch finds nothing else to launch there
 // (beside the operator such a context has its per-cell Vanka smoother, stfem_stokes_vanka_create_space in stfem_stokes_vanka.hip).
 #include "stfem_stokes_internal.h"
@@ -463,9 +464,10 @@ int stokes_cart_launch(stfem_stokes_ctx *c, const StokesSet &set, hipStream_t st
 int stokes_launch(stfem_stokes_ctx *c, const StokesSet &set, int mode, const double *const *lin, hipStream_t st)
 {
   // axis-aligned uniform mesh at degree 2: the Kronecker path; otherwise the cell kernel.  (A context of degree 3 has no scalar
-  // context and no CIP term - their entry points are kept to degree 2: the cell operator, its boundary launches when
-  // stfem_stokes_set_weak_boundaries_space has set weak faces, then the convection colours - never both, stokes_refuse_inflow_q3)
-  assert(c->degree == 2 || (!c->scalar && c->cip_delta0 == 0.0 && (!c->weak_mask || mode == STFEM_CONVECTION_NONE)));
+  // context - its entry point is kept to degree 2: the cell operator, its boundary launches when
+  // stfem_stokes_set_weak_boundaries_space has set weak faces, then the convection colours - never both, stokes_refuse_inflow_q3 -,
+  // then the CIP colours when stfem_stokes_set_cip_space has set delta0)
+  assert(c->degree == 2 || (!c->scalar && (!c->weak_mask || mode == STFEM_CONVECTION_NONE)));
   const int rc = c->scalar ? stokes_cart_launch(c, set, st) : stokes_cell_launch(c, set, st);
   if (rc != STFEM_OK) return rc;
   // LoopType::Full: the boundary-face loop of the same vmult (the mass operator has none)

@@ -18,10 +18,18 @@
 // On a z-slab of a partitioned mesh (stfem_stokes_set_cip_neighbours) the same design partitions: the cells next to an interface plane
 // treat that face as interior, read the neighbour slab's cell from two ghost DoF planes per source (stfem_stokes_cip_pack on the
 // sender) and one ghost vertex plane, and write inside the slab - partial sums in the interface planes, like every other launch.
+// Velocity degree 3 (the _space entries of stfem_stokes_cip_space.h): the same design - cell-centric, own side only, eight colour
+// launches, no atomics - in a kernel of its own, stokes_cip_q3_kernel below: 64 nodes, the 16 points of QGauss(4)^2 per face,
+// pa = 3^3.5, one wave per cell, the normal derivatives from the 1D tables instead of a tabulated sT.  No slabs at degree 3.
+// STFEM_STOKES_CIP_WORKGROUPS caps the workgroups of the colour launches at either degree; stfem_stokes_last_cip_plan reports the last
+// launch (stfem_stokes_cip_plan.h).
 #include "stfem_stokes_internal.h"
+#include "stfem_stokes_cip_plan.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
+#include <vector>
 #include <type_traits>
 
 namespace {
@@ -260,6 +268,234 @@ __global__ __launch_bounds__(256) void stokes_cip_kernel(const std::conditional_
   }
 }
 
+// Velocity degree 3: FE_Q(3), 64 nodes, the 4 x 4 Gauss points of a face, pa = 3^3.5.  A kernel beside the degree-2 one, not an
+// instantiation of it: that kernel is built on 27 nodes = 9 points x 3 components on one half-wave and on the
+// tabulated sT, neither of which exists here, so a shared body would be two bodies under if constexpr and would put the degree-2
+// arithmetic, which must not move, at the mercy of every later edit of the degree-3 one.
+// One wave per cell and one wave per workgroup (64 threads: nothing is shared between cells but 448 B of 1D tables, so a larger
+// workgroup would buy nothing, and a colour of few cells still spreads over the CUs), lane t = a + 4 b + 16 c is node (a, b, c).
+// No derivative table: sT[3][6][16][64]
+// is 147 KB and leaves no room for the per-wave buffers.  The normal derivative is built from the 1D tables instead (Su, Du at the
+// Gauss points, Eu, EDu at the end points: 448 B): d phi_n / d xi_e of node n = (kd, k1, k2) at face point (q1, q2) is a product of
+// three 1D entries, so a point sums over kd first (4 fma per derivative and side) and then over the 16 (k1, k2) with the tangential
+// 1D values: 16 x (16 + 12) fma per (point, component) in place of 6 x 64 table reads, and the LDS holds the three 192-value
+// buffers of a cell and the 16 point records (5.7 KB per workgroup; 13.6 KB on a general mesh with the face geometry sG).
+// Per source and interior face: the 64 lanes gather the neighbour's 3 x 64 values; lanes 0..47 as (face point q = t & 15, component
+// t >> 4) evaluate the geometry of q (the three component lanes redundantly), the normal derivatives of their component on both sides,
+// w.n from the 16 nodes of the face and the flux; the 64 node lanes integrate, again from the 1D tables.  CART / MULTI as at degree 2;
+// on a general mesh the geometry of the face points is evaluated once per cell, before the sources (sG, 7.7 KB more).
+// No array is indexed at run time: the face loop is unrolled, so directions, strides and end points are constants of each copy.
+template <bool CART, bool MULTI>
+__global__ __launch_bounds__(64) void stokes_cip_q3_kernel(const CipQ3Params prm)
+{
+  __shared__ double tS[16], tD[16], tE[8], tED[8], tX[4], tW[4];
+  __shared__ double sU[192], sW[192], sN[192]; // own source, own weight velocity, the neighbour's source
+  __shared__ double sF[16][6], sA[16];         // per face point: flux[3] and J^-1 n [3]; JxW
+  __shared__ double sG[CART ? 1 : 6 * 16 * 10]; // general meshes, per face and point: JxW, n [3], J^-1 n of this side [3] and of the neighbour's [3]
+  if (threadIdx.x < 16) { tS[threadIdx.x] = prm.Su[threadIdx.x]; tD[threadIdx.x] = prm.Du[threadIdx.x]; }
+  if (threadIdx.x < 8) { tE[threadIdx.x] = prm.Eu[threadIdx.x]; tED[threadIdx.x] = prm.EDu[threadIdx.x]; }
+  if (threadIdx.x < 4) { tX[threadIdx.x] = prm.xq[threadIdx.x]; tW[threadIdx.x] = prm.wq[threadIdx.x]; }
+  __syncthreads();
+  const int t = threadIdx.x;
+  const int a = t & 3, b = (t >> 2) & 3, c = t >> 4;
+  const bool point = t < 48;                                             // the point phase: 16 points x 3 components
+  const int q = t & 15, comp_q = point ? t >> 4 : 0, q1 = q & 3, q2 = q >> 2;
+  const int px = prm.colour & 1, py = (prm.colour >> 1) & 1, pz = prm.colour >> 2;
+  const int ncxc = (prm.ncx - px + 1) / 2, ncyc = (prm.ncy - py + 1) / 2, nczc = (prm.ncz - pz + 1) / 2;
+  const long long ncells = (long long)ncxc * ncyc * nczc;
+  double *U = sU, *Wv = sW, *N = sN;
+  for (long long item = blockIdx.x; item < ncells; item += gridDim.x) {
+    const int cx = 2 * int(item % ncxc) + px, cy = 2 * int((item / ncxc) % ncyc) + py, cz = 2 * int(item / ((long long)ncxc * ncyc)) + pz;
+    // the interior faces of the cell, bit 2 d + s: one cell per wave, so a scalar
+    const int faces = __builtin_amdgcn_readfirstlane((cx > 0 ? 1 : 0) | (cx < prm.ncx - 1 ? 2 : 0) | (cy > 0 ? 4 : 0) | (cy < prm.ncy - 1 ? 8 : 0) |
+                                                     (cz > 0 ? 16 : 0) | (cz < prm.ncz - 1 ? 32 : 0));
+    if (faces == 0) continue;
+    const int ix = 3 * cx + a, iy = 3 * cy + b, iz = 3 * cz + c;
+    const bool con = constrained_u(prm, ix, iy, iz);
+    const long long gu = ix + (long long)prm.ndu[0] * (iy + (long long)prm.ndu[1] * iz);
+    if constexpr (!CART) {
+      // The geometry of the 16 points of the interior faces, once per cell and point - not per source and component lane: 96 (face,
+      // point) items on the 64 lanes.  The face is a lane's own here, so direction and side are selects (stfem_mapping_q1.h) and the
+      // vertices of the two cells come by vector loads; inside the source loop they held the scalar registers of that loop.
+#pragma unroll 1
+      for (int item = t; item < 96; item += 64) {
+        const int f = item >> 4, d = f >> 1, s = f & 1, t1 = d == 0 ? 1 : 0, g1 = item & 3, g2 = (item >> 2) & 3;
+        if (!(faces >> f & 1)) continue;
+        double xi[3], Ji[3][3], nrm[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xi[k] = k == d ? double(s) : tX[k == t1 ? g1 : g2];
+        double det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx, cy, cz, xi, Ji);
+        const double len = mapping_q1_face_normal(Ji, d, 0, nrm); // J^-T e_d, unsigned
+        double *G = sG + item * 10;
+        G[0] = fabs(det) * len * tW[g1] * tW[g2];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) { G[1 + e] = nrm[e]; G[4 + e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2]; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xi[k] = k == d ? double(1 - s) : xi[k];
+        // (the neighbour behind an interior face exists)
+        det = mapping_q1_inverse(prm.vertices, prm.ncx, prm.ncy, cx + (d == 0 ? 2 * s - 1 : 0), cy + (d == 1 ? 2 * s - 1 : 0),
+                                 cz + (d == 2 ? 2 * s - 1 : 0), xi, Ji);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) G[7 + e] = Ji[e][0] * nrm[0] + Ji[e][1] * nrm[1] + Ji[e][2] * nrm[2];
+      }
+    }
+    double accU[MULTI ? MAXSRC : 1][3];
+#pragma unroll
+    for (int o = 0; o < (MULTI ? MAXSRC : 1); ++o) accU[o][0] = accU[o][1] = accU[o][2] = 0.0;
+    const int nsrc = MULTI ? prm.nsrc : 1;
+    for (int src = 0; src < nsrc; ++src) {
+      const double *us = prm.us[src], *ws = prm.ws[src];
+#pragma unroll
+      for (int comp = 0; comp < 3; ++comp) { // gather (read_dof_values: constrained entries read as 0)
+        U[comp * 64 + t] = con ? 0.0 : us[comp * prm.Nu + gu];
+        Wv[comp * 64 + t] = con ? 0.0 : ws[comp * prm.Nu + gu];
+      }
+      // the source values of the neighbour behind face f: its node (a, b, c).  Read only behind an interior face, where the cell
+      // (cx, cy, cz) -+ e_d exists: jx = 3 (cx -+ 1) + a in [0, ndu[0]), likewise jy, jz
+      auto neighbour = [&](int f, double v[3]) {
+        const int d = f >> 1, s = f & 1;
+        const int jx = 3 * (cx + (d == 0 ? (s ? 1 : -1) : 0)) + a, jy = 3 * (cy + (d == 1 ? (s ? 1 : -1) : 0)) + b,
+                  jz = 3 * (cz + (d == 2 ? (s ? 1 : -1) : 0)) + c;
+        const bool take = (faces >> f & 1) && !constrained_u(prm, jx, jy, jz);
+        const long long gn = jx + (long long)prm.ndu[0] * (jy + (long long)prm.ndu[1] * jz);
+#pragma unroll
+        for (int comp = 0; comp < 3; ++comp) v[comp] = take ? us[comp * prm.Nu + gn] : 0.0;
+      };
+      double nb[CART ? 6 : 1][3]; // CART: all six fetched first, one memory latency; the general kernel fetches face by face (as at degree 2)
+      if constexpr (CART) {
+#pragma unroll
+        for (int f = 0; f < 6; ++f) neighbour(f, nb[f]);
+      }
+      wave_fence();
+      double rU[3] = {0, 0, 0};
+#pragma unroll
+      for (int f = 0; f < 6; ++f) {
+        if (!(faces >> f & 1)) continue; // scalar
+        const int d = f >> 1, s = f & 1, t1 = d == 0 ? 1 : 0, t2 = d == 2 ? 1 : 2;
+        const int sd = d == 0 ? 1 : (d == 1 ? 4 : 16), s1 = t1 == 0 ? 1 : 4, s2 = t2 == 1 ? 4 : 16; // node strides of the three directions
+        if constexpr (!CART) neighbour(f, nb[0]);
+#pragma unroll
+        for (int comp = 0; comp < 3; ++comp) N[comp * 64 + t] = nb[CART ? f : 0][comp];
+        wave_fence();
+        double go[3] = {0, 0, 0}, wn = 0.0, JxW = 0.0, jump = 0.0;
+        if (point) { // this lane's face point and component: geometry, normal derivatives of both sides, w.n
+          double gnb[3] = {0, 0, 0}, nrm[3] = {0, 0, 0};
+          if constexpr (CART) {
+            nrm[d] = 1.0;
+            go[d] = gnb[d] = prm.hinv[d];
+            JxW = prm.detJ * prm.hinv[d] * tW[q1] * tW[q2];
+          } else {
+            const double *G = sG + (f * 16 + q) * 10; // the cell's geometry phase
+            JxW = G[0];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) { nrm[e] = G[1 + e]; go[e] = G[4 + e]; gnb[e] = G[7 + e]; }
+          }
+          // reference-space derivatives of this lane's component at the point, along (d, t1, t2): this side (end point s of direction
+          // d) and the neighbour's (end point 1 - s)
+          const double *Uc = U + comp_q * 64, *Nc = N + comp_q * 64;
+          double od = 0.0, o1 = 0.0, o2 = 0.0, nd = 0.0, n1 = 0.0, n2 = 0.0;
+#pragma unroll 1
+          for (int k2 = 0; k2 < 4; ++k2) {
+            const double S2 = tS[q2 * 4 + k2], D2 = tD[q2 * 4 + k2];
+#pragma unroll
+            for (int k1 = 0; k1 < 4; ++k1) {
+              const double S1 = tS[q1 * 4 + k1], D1 = tD[q1 * 4 + k1];
+              const double *uo = Uc + k1 * s1 + k2 * s2, *un = Nc + k1 * s1 + k2 * s2;
+              double ao = 0.0, bo = 0.0, an = 0.0, bn = 0.0; // the sums over kd: derivative and value along d
+#pragma unroll
+              for (int kd = 0; kd < 4; ++kd) {
+                ao = fma(tED[s * 4 + kd], uo[kd * sd], ao);
+                an = fma(tED[(1 - s) * 4 + kd], un[kd * sd], an);
+                if constexpr (!CART) {
+                  bo = fma(tE[s * 4 + kd], uo[kd * sd], bo);
+                  bn = fma(tE[(1 - s) * 4 + kd], un[kd * sd], bn);
+                }
+              }
+              od = fma(S1 * S2, ao, od); nd = fma(S1 * S2, an, nd);
+              if constexpr (!CART) {
+                o1 = fma(D1 * S2, bo, o1); n1 = fma(D1 * S2, bn, n1);
+                o2 = fma(S1 * D2, bo, o2); n2 = fma(S1 * D2, bn, n2);
+              }
+            }
+          }
+          jump = go[d] * od - gnb[d] * nd;
+          if constexpr (!CART) jump += go[t1] * o1 - gnb[t1] * n1 + go[t2] * o2 - gnb[t2] * n2;
+          // w at the point: the 16 nodes of the face
+          double wval[3] = {0, 0, 0};
+#pragma unroll
+          for (int j2 = 0; j2 < 4; ++j2)
+#pragma unroll
+            for (int j1 = 0; j1 < 4; ++j1) {
+              const double phi = tS[q1 * 4 + j1] * tS[q2 * 4 + j2];
+#pragma unroll
+              for (int c3 = 0; c3 < 3; ++c3) wval[c3] = fma(phi, Wv[c3 * 64 + 3 * s * sd + j1 * s1 + j2 * s2], wval[c3]);
+            }
+          wn = wval[0] * nrm[0] + wval[1] * nrm[1] + wval[2] * nrm[2];
+          if (comp_q == 0) sA[q] = JxW;
+        }
+        wave_fence();
+        if (point) { // h_F^2 = the face's area: the 16 JxW in point order
+          double area = 0.0;
+#pragma unroll
+          for (int p = 0; p < 16; ++p) area += sA[p];
+          const double delta = prm.scale * area * wn * wn;
+          sF[q][comp_q] = delta * jump * JxW;
+          if (comp_q == 0) {
+#pragma unroll
+            for (int e = 0; e < 3; ++e) sF[q][3 + e] = go[e];
+          }
+        }
+        wave_fence();
+        { // integrate: the normal derivative of the test function of node (a, b, c), this cell's side
+          const int kd = d == 0 ? a : (d == 1 ? b : c), k1 = t1 == 0 ? a : b, k2 = t2 == 1 ? b : c;
+          const double vd = tE[s * 4 + kd], dd = tED[s * 4 + kd];
+#pragma unroll 4
+          for (int p = 0; p < 16; ++p) {
+            const int p1 = p & 3, p2 = p >> 2;
+            const double *F = sF[p];
+            const double S1 = tS[p1 * 4 + k1], S2 = tS[p2 * 4 + k2];
+            double dv = F[3 + d] * (dd * S1 * S2);
+            if constexpr (!CART) dv += F[3 + t1] * (vd * tD[p1 * 4 + k1] * S2) + F[3 + t2] * (vd * S1 * tD[p2 * 4 + k2]);
+#pragma unroll
+            for (int comp = 0; comp < 3; ++comp) rU[comp] = fma(dv, F[comp], rU[comp]);
+          }
+        }
+        wave_fence(); // the next face reuses the neighbour and point buffers
+      }
+      if constexpr (MULTI) {
+#pragma unroll
+        for (int o = 0; o < MAXSRC; ++o)
+          if (o < prm.nout) {
+#pragma unroll
+            for (int comp = 0; comp < 3; ++comp) accU[o][comp] = fma(prm.wKu[src][o], rU[comp], accU[o][comp]);
+          }
+      } else {
+#pragma unroll
+        for (int comp = 0; comp < 3; ++comp) accU[0][comp] = rU[comp];
+      }
+      wave_fence(); // the next source overwrites U, Wv
+    }
+    // distribute_local_to_global (add): constrained velocity rows are not written
+    if (!con) {
+      if constexpr (MULTI) {
+#pragma unroll
+        for (int o = 0; o < MAXSRC; ++o)
+          if (o < prm.nout) {
+            double *dptr = prm.out_u[o] + gu;
+#pragma unroll
+            for (int comp = 0; comp < 3; ++comp) dptr[comp * prm.Nu] += accU[o][comp];
+          }
+      } else {
+        for (int o = 0; o < prm.nout; ++o) {
+          double *dptr = prm.out_u[o] + gu;
+#pragma unroll
+          for (int comp = 0; comp < 3; ++comp) dptr[comp * prm.Nu] += prm.wKu[0][o] * accU[0][comp];
+        }
+      }
+    }
+  }
+}
+
 } // namespace
 
 void stokes_cip_end_tables(double Eu[6], double EDu[6])
@@ -329,6 +565,61 @@ int stokes_cip_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *c
 
 namespace {
 
+// STFEM_STOKES_CIP_WORKGROUPS=<n>, read at every launch: at most n workgroups per CIP colour launch, at either degree
+long long cip_workgroup_cap() { return cip_parse_cap(getenv("STFEM_STOKES_CIP_WORKGROUPS")); }
+
+// The eight colour launches at velocity degree 3 (a context without slab neighbours: the slab entries are kept to degree 2)
+int cip_q3_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *weight, double delta0, hipStream_t st)
+{
+  const StokesParamsT<3> &g = c->desc<3>();
+  CipQ3Params k;
+  k.vertices = g.vertices;
+  k.ncx = g.ncx; k.ncy = g.ncy; k.ncz = g.ncz;
+  for (int d = 0; d < 3; ++d) { k.ndu[d] = g.ndu[d]; k.hinv[d] = g.hinv[d]; }
+  k.Nu = g.Nu;
+  k.dmask = g.dmask;
+  for (int i = 0; i < 16; ++i) { k.Su[i] = g.Su[i]; k.Du[i] = g.Du[i]; }
+  for (int i = 0; i < 4; ++i) { k.xq[i] = g.xq[i]; k.wq[i] = g.wq[i]; }
+  static const std::vector<double> ends_tables = [] { // FE_Q(3) values / derivatives at the end points 0 and 1, [s * 4 + a]
+    const stfem::ShapeTables tu = stfem::make_shape_tables(3);
+    const std::vector<double> ends = {0.0, 1.0};
+    stfem::Mat E, ED;
+    stfem::lagrange_tables(tu.nodes, ends, E, ED);
+    std::vector<double> r(16);
+    for (int i = 0; i < 8; ++i) { r[i] = E[i]; r[8 + i] = ED[i]; }
+    return r;
+  }();
+  for (int i = 0; i < 8; ++i) { k.Eu[i] = ends_tables[i]; k.EDu[i] = ends_tables[8 + i]; }
+  k.colour = 0; k.cart = g.cart;
+  k.detJ = g.detJ;
+  k.scale = delta0 / (27.0 * std::sqrt(3.0)); // pa = degree^3.5, degree 3 (operators.h:1614-1615)
+  k.nsrc = set.nsrc;
+  for (int s = 0; s < MAXSRC; ++s) {
+    k.us[s] = s < set.nsrc ? set.us[s] : nullptr;
+    k.ws[s] = s < set.nsrc ? weight[s] : nullptr;
+    if (s < set.nsrc && (!set.us[s] || !weight[s])) return STFEM_ERR_INVALID_ARGUMENT;
+  }
+  k.nout = stokes_k_destinations(set, k.out_u, k.wKu);
+  if (k.nout == 0) return STFEM_OK;
+  const bool multi = set.nsrc > 1;
+  const void *kerns[4] = {(const void *)stokes_cip_q3_kernel<false, false>, (const void *)stokes_cip_q3_kernel<true, false>,
+                          (const void *)stokes_cip_q3_kernel<false, true>, (const void *)stokes_cip_q3_kernel<true, true>};
+  const void *kern = kerns[(multi ? 2 : 0) + (k.cart ? 1 : 0)];
+  const long long cap = cip_workgroup_cap();
+  stfem_launch_begin();
+  for (int colour = 0; colour < 8; ++colour) {
+    const long long n = cip_colour_cells(c->nc, colour);
+    if (n == 0) continue;
+    k.colour = colour;
+    const CipPlan plan = cip_plan(n, 1, 32ll * c->n_cu, cap); // one wave per cell, one wave per workgroup
+    void *args[] = {(void *)&k};
+    (void)hipLaunchKernel(kern, dim3((unsigned)plan.grid), dim3(64), args, 0, st);
+    c->cip_launched = true;
+    c->cip_plan[0] = (int)plan.grid; c->cip_plan[1] = (int)plan.passes;
+  }
+  return stfem_launch_end("stokes_cip_q3_kernel");
+}
+
 int cip_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *weight, double delta0, const double *const *ghost_lo,
                const double *const *ghost_hi, hipStream_t st)
 {
@@ -336,7 +627,8 @@ int cip_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *w
   const int neighbours = ghost_lo && ghost_hi ? c->cip_neighbours : 0;
   if (c->nc[0] < 2 && c->nc[1] < 2 && c->nc[2] < 2 && !neighbours) return STFEM_OK; // no interior face
   if (set.nsrc < 1 || set.nsrc > MAXSRC || set.nout > (set.nsrc > 1 ? MAXSRC : MAXOUT)) return STFEM_ERR_UNSUPPORTED; // (the instantiations' bounds)
-  const StokesParams &g = c->desc<2>(); // (the entry points have kept the term to degree 2)
+  if (c->degree == 3) return cip_q3_launch(c, set, weight, delta0, st);
+  const StokesParams &g = c->desc<2>(); // (the slab entries have kept the rest to degree 2)
   CipSlabParams k; // (the instantiations without SLAB read its CipParams part alone)
   k.neighbours = neighbours;
   for (int side = 0; side < 2; ++side) k.ghost_vertices[side] = c->d_cip_vertices[side];
@@ -377,15 +669,17 @@ int cip_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *w
   const void *slab_kerns[4] = {(const void *)stokes_cip_kernel<false, false, true>, (const void *)stokes_cip_kernel<true, false, true>,
                                (const void *)stokes_cip_kernel<false, true, true>, (const void *)stokes_cip_kernel<true, true, true>};
   const void *kern = neighbours ? slab_kerns[which] : kerns[which];
+  const long long cap = cip_workgroup_cap();
   stfem_launch_begin();
   for (int colour = 0; colour < 8; ++colour) { // ascending, like every colour sequence of the operator
-    const long long n = (long long)((c->nc[0] - (colour & 1) + 1) / 2) * ((c->nc[1] - ((colour >> 1) & 1) + 1) / 2) *
-                        ((c->nc[2] - (colour >> 2) + 1) / 2);
+    const long long n = cip_colour_cells(c->nc, colour);
     if (n == 0) continue; // a colour without cells
     k.colour = colour;
-    const unsigned grid = (unsigned)std::min<long long>((n + 7) / 8, 8ll * c->n_cu);
+    const CipPlan plan = cip_plan(n, 8, 8ll * c->n_cu, cap); // (without a cap min(ceil(n / 8), 8 n_cu) workgroups, as ever)
     void *args[] = {neighbours ? (void *)&k : (void *)static_cast<CipParams *>(&k)};
-    (void)hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, st);
+    (void)hipLaunchKernel(kern, dim3((unsigned)plan.grid), dim3(256), args, 0, st);
+    c->cip_launched = true;
+    c->cip_plan[0] = (int)plan.grid; c->cip_plan[1] = (int)plan.passes;
   }
   return stfem_launch_end("stokes_cip_kernel");
 }
@@ -394,11 +688,21 @@ int cip_launch(stfem_stokes_ctx *c, const StokesSet &set, const double *const *w
 
 extern "C" {
 
+// The entries of stfem.h: velocity degree 2.  Their _space forms (stfem_stokes_cip_space.h): the context's degree.
 int stfem_stokes_set_cip(stfem_stokes_ctx *c, double delta0, int weight)
 {
   if (!c || !std::isfinite(delta0) || weight < STFEM_CIP_WEIGHT_SOURCE || weight > STFEM_CIP_WEIGHT_LINEARISATION)
     return STFEM_ERR_INVALID_ARGUMENT;
   if (const int rq = stokes_require_q2(c, "stfem_stokes_set_cip")) return rq;
+  c->cip_delta0 = delta0;
+  c->cip_weight = weight;
+  return STFEM_OK;
+}
+
+int stfem_stokes_set_cip_space(stfem_stokes_ctx *c, double delta0, int weight)
+{
+  if (!c || !std::isfinite(delta0) || weight < STFEM_CIP_WEIGHT_SOURCE || weight > STFEM_CIP_WEIGHT_LINEARISATION)
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_set_cip_space: a null context, a non-finite delta0 or a weight outside 0..1");
   c->cip_delta0 = delta0;
   c->cip_weight = weight;
   return STFEM_OK;
@@ -412,6 +716,25 @@ int stfem_stokes_cip_add(stfem_stokes_ctx *c, double *dst_u, const double *src_u
   STFEM_TRY(hipSetDevice(c->device));
   const StokesSet set = stokes_single_set(src_u, dst_u); // the term by itself
   return cip_launch(c, set, &weight_u, delta0, nullptr, nullptr, static_cast<hipStream_t>(stream)); // (the faces inside the slab alone)
+}
+
+int stfem_stokes_cip_add_space(stfem_stokes_ctx *c, double *dst_u, const double *src_u, const double *weight_u, double delta0, void *stream)
+{
+  if (!c || !dst_u || !src_u || !weight_u || !std::isfinite(delta0))
+    return stfem_set_error(STFEM_ERR_INVALID_ARGUMENT, "stfem_stokes_cip_add_space: a null argument or a non-finite delta0");
+  if (dst_u == src_u || dst_u == weight_u) return stfem_set_error(STFEM_ERR_ALIAS, "stfem_stokes_cip_add_space: dst_u is src_u or weight_u");
+  STFEM_TRY(hipSetDevice(c->device));
+  const StokesSet set = stokes_single_set(src_u, dst_u);
+  return cip_launch(c, set, &weight_u, delta0, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int stfem_stokes_last_cip_plan(const stfem_stokes_ctx *c, int32_t out[2])
+{
+  if (!c || !out) return STFEM_ERR_INVALID_ARGUMENT;
+  if (!c->cip_launched) return stfem_set_error(STFEM_ERR_UNSUPPORTED, "stfem_stokes_last_cip_plan: this context has not launched the CIP kernel");
+  out[0] = c->cip_plan[0];
+  out[1] = c->cip_plan[1];
+  return STFEM_OK;
 }
 
 int stfem_stokes_set_cip_neighbours(stfem_stokes_ctx *c, int neighbour_mask, const double *lower_vertices, const double *upper_vertices)

@@ -134,6 +134,25 @@ struct CipParams {
   double hinv[3], detJ;
   double scale; // delta0 / pa
 };
+// The same at velocity degree 3 (stokes_cip_q3_kernel): FE_Q(3) tables, QGauss(4).  A description of its own: CipParams is the
+// by-value argument of the degree-2 kernel, and its layout stays.
+struct CipQ3Params {
+  const double *vertices;
+  int ncx, ncy, ncz;
+  int ndu[3];
+  long long Nu;
+  int dmask;
+  int nsrc;
+  const double *us[MAXSRC], *ws[MAXSRC];
+  int nout;
+  double *out_u[MAXOUT];
+  double wKu[MAXSRC][MAXOUT];
+  double Su[16], Du[16], Eu[8], EDu[8]; // [q*4+a] at the Gauss points, [s*4+a] at the end points 0 and 1
+  double xq[4], wq[4];
+  int colour, cart;
+  double hinv[3], detJ;
+  double scale; // delta0 / pa, pa = 3^3.5
+};
 // The same on a z-slab with neighbours (stfem_stokes_set_cip_neighbours): the kernel's SLAB instantiations take this description, the
 // others CipParams as before.
 struct CipSlabParams : CipParams {
@@ -207,6 +226,8 @@ struct stfem_stokes_ctx {
   // CIP interior-face stabilisation (stfem_stokes_set_cip): 0.0 = no launches; whose velocity weighs it (STFEM_CIP_WEIGHT_*)
   double cip_delta0 = 0.0;
   int cip_weight = 0;
+  bool cip_launched = false;
+  int cip_plan[2] = {0, 0}; // workgroups and passes of the grid-stride loop of the last CIP colour launch (stfem_stokes_last_cip_plan)
   // the slab's z neighbours for that term (stfem_stokes_set_cip_neighbours): mask, the two-plane vertex arrays of
   // CipSlabParams::ghost_vertices (general meshes), and the ghost planes bound to velocity sources (stfem_stokes_cip_bind_ghosts)
   int cip_neighbours = 0;

@@ -365,7 +365,7 @@ static int create_per_cell(stfem_stokes_ctx *ctx, int n_blocks, const int32_t *b
     if (const int rq = stokes_require_q2(ctx, "stfem_stokes_vanka_create_linearised")) return rq;
   const int degree = stokes_velocity_degree(ctx);
   if (degree != 2 && delta0 != 0.0)
-    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "per-cell Stokes blocks with delta0 = %g at velocity degree %d: a context of that degree has no CIP term", delta0, degree);
+    return stfem_set_error(STFEM_ERR_UNSUPPORTED, "per-cell Stokes blocks with delta0 = %g at velocity degree %d: the CIP term is not built into the blocks of that degree", delta0, degree);
   stfem_stokes_desc d;
   int rc = stokes_desc_any_degree(ctx, &d);
   if (rc != STFEM_OK) return rc;

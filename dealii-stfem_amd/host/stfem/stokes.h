@@ -138,9 +138,11 @@ inline void rhs_minus(std::vector<StokesVector> &dst, const std::vector<StokesVe
 }
 
 // The operator by descriptor: what the second constructor of StokesMatrixFreeOperator takes.  velocity_degree 2 or 3; at degree 3 the
-// cell operator with the convection term of the nonlinear treatment, or - linear operator only - with weak (Nitsche) faces; no CIP.
+// cell operator with the convection term of the nonlinear treatment, or - linear operator only - with weak (Nitsche) faces; with
+// delta0 != 0 the CIP interior-face term on top of either.
 // The trailing members are those of the first constructor's arguments of the same names, applied through
-// stfem_stokes_set_weak_boundaries_space (stfem_stokes_boundary_space.h), which serves either degree.
+// stfem_stokes_set_weak_boundaries_space (stfem_stokes_boundary_space.h) and stfem_stokes_set_cip_space (stfem_stokes_cip_space.h),
+// which serve either degree; cip_weight is what set_cip_weight would set afterwards.
 template <typename Number> struct StokesSpace {
   unsigned velocity_degree = 2;
   bool dg_pressure = false;
@@ -150,6 +152,8 @@ template <typename Number> struct StokesSpace {
   std::set<boundary_id> outflow_boundary_ids = {};
   Number penalty1 = 20;
   Number penalty2 = 10;
+  Number delta0 = 0;
+  int cip_weight = STFEM_CIP_WEIGHT_SOURCE;
 };
 
 // operators.h:1193-1766: cell loop + boundary-face loop for the weak (Nitsche) ids.  Same constructor arguments after the mesh as
@@ -196,10 +200,12 @@ public:
   // operator go through the _space entries of stfem_stokes_convection_space.h, which run a convection mode at either degree (degree 2:
   // the entries of the first constructor's operator, bit for bit).  Weak / outflow ids go through the _space setter of
   // stfem_stokes_boundary_space.h: at degree 3 the linear operator and the per-cell Vanka blocks over it hold the Nitsche terms; a
-  // nonlinear treatment with weak ids is refused there (the inflow term of the faces is not built at degree 3).
+  // nonlinear treatment with weak ids is refused there (the inflow term of the faces is not built at degree 3).  delta0 / cip_weight go
+  // through stfem_stokes_set_cip_space of stfem_stokes_cip_space.h: the CIP term at either degree, added last by every vmult.
   StokesMatrixFreeOperator(const Mesh &mesh, const StokesSpace<Number> &space)
     : nonlinear_treatment(space.nonlinear_treatment), nonlinear(space.nonlinear_treatment != NonlinearTreatment::None), space_entries_(true)
   {
+    if (!std::isfinite(space.delta0)) throw Error(STFEM_ERR_INVALID_ARGUMENT, "StokesMatrixFreeOperator: delta0 is not finite");
     int weak = 0, outflow = 0;
     for (boundary_id f : space.weak_boundary_ids) weak |= 1 << f;
     for (boundary_id f : space.outflow_boundary_ids) outflow |= 1 << f;
@@ -214,6 +220,16 @@ public:
         check(rc, "stfem_stokes_set_weak_boundaries_space");
       }
     }
+    delta0_ = space.delta0;
+    cip_weight_ = space.cip_weight;
+    if (space.delta0 != 0.0 || space.cip_weight != STFEM_CIP_WEIGHT_SOURCE) {
+      const int rc = stfem_stokes_set_cip_space(h_, space.delta0, space.cip_weight);
+      if (rc != STFEM_OK) {
+        stfem_stokes_destroy(h_);
+        h_ = nullptr;
+        check(rc, "stfem_stokes_set_cip_space");
+      }
+    }
   }
   // whether the convection entries of this operator are the _space forms (the constructor by descriptor)
   bool space_entries() const { return space_entries_; }
@@ -222,8 +238,16 @@ public:
   // Krylov method needs).  form(x) about x itself is the same with both.  The state of the device context, like set_data.
   void set_cip_weight(int weight) const
   {
-    check(stfem_stokes_set_cip(h_, delta0_, weight), "stfem_stokes_set_cip");
+    if (space_entries_) check(stfem_stokes_set_cip_space(h_, delta0_, weight), "stfem_stokes_set_cip_space"); // (either degree)
+    else check(stfem_stokes_set_cip(h_, delta0_, weight), "stfem_stokes_set_cip");
     cip_weight_ = weight;
+  }
+  // dst_u += C(weight_u; src_u) with the given delta0: the CIP term by itself, independent of the operator's own delta0
+  // (stfem_stokes_cip_add; over an operator made by descriptor its _space form, which serves either degree)
+  void cip_add(double *dst_u, const double *src_u, const double *weight_u, Number delta0, void *stream = nullptr) const
+  {
+    if (space_entries_) check(stfem_stokes_cip_add_space(h_, dst_u, src_u, weight_u, delta0, stream), "stfem_stokes_cip_add_space");
+    else check(stfem_stokes_cip_add(h_, dst_u, src_u, weight_u, delta0, stream), "stfem_stokes_cip_add");
   }
   Number delta0() const { return delta0_; }
   unsigned velocity_degree() const { return velocity_degree_; }
@@ -658,7 +682,7 @@ public:
     const std::vector<const double *> l = linearization(solution_linearization);
     stfem_stokes_vanka *v = nullptr;
     if (K.velocity_degree() != 2) { // FE_Q(3)^3 x FE_Q(2) / FE_DGP(2): the constructor by descriptor of the linearised blocks
-      if (delta0 != 0) throw Error(STFEM_ERR_UNSUPPORTED, "PreconditionVankaStokes: delta0 != 0 at velocity degree 3 (an operator of that degree has no CIP term)");
+      if (delta0 != 0) throw Error(STFEM_ERR_UNSUPPORTED, "PreconditionVankaStokes: delta0 != 0 at velocity degree 3 (the CIP term is not built into the blocks of that degree)");
       stfem_stokes_vanka_linearised_space_desc d{}; // (reserved: 0)
       d.n_blocks = int32_t(nb_);
       d.block_variable = var.data();

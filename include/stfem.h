@@ -706,6 +706,9 @@ int stfem_stokes_vanka_create_linearised_cip(stfem_stokes_ctx *ctx, int n_blocks
  * _face_points and _nitsche_rhs above refuse; the _space entries run) and the diagnostic of the boundary kernel: the companion header,
  * part of this boundary and included here. */
 #include "stfem_stokes_boundary_space.h"
+/* The CIP interior-face stabilisation for a context of either degree (at degree 3 stfem_stokes_set_cip and _cip_add above refuse; the
+ * _space entries run) and the diagnostic of the CIP kernel: the companion header, part of this boundary and included here. */
+#include "stfem_stokes_cip_space.h"
 int stfem_stokes_vanka_update(stfem_stokes_vanka *v, const double *const *lin_blocks);
 void stfem_stokes_vanka_destroy(stfem_stokes_vanka *v);
 int stfem_stokes_vanka_n_classes(const stfem_stokes_vanka *v);

@@ -24,7 +24,8 @@
  * Refused at degree 3 with weak faces, STFEM_ERR_UNSUPPORTED with the reason in stfem_last_error, before the device is touched and with
  * the operands untouched: a convection mode (form / jacobian) of the _convection_space entries and of
  * stfem_stokes_vanka_create_linearised_space - the inflow term - min(b.n, 0) u of the faces is not built.  Not built at degree 3 at
- * all: CIP, drag / lift, GMGStokes and the drivers, slabs, fp32. */
+ * all: CIP in the Vanka blocks and on slabs (the operator's term: stfem_stokes_cip_space.h), drag / lift, GMGStokes and the drivers,
+ * slabs, fp32. */
 int stfem_stokes_set_weak_boundaries_space(stfem_stokes_ctx *ctx, int weak_mask, int outflow_mask, double penalty1, double penalty2);
 int64_t stfem_stokes_n_face_points_space(const stfem_stokes_ctx *ctx);
 int stfem_stokes_face_points_space(const stfem_stokes_ctx *ctx, double *out_xyz);

@@ -972,7 +972,11 @@ class StokesMatrixFreeOperator:
         pressure_mean_vectors, pressure_quadrature_points, pressure_difference, pressure_ctx and (between two such operators)
         stokes_dgp_prolongate / stokes_dgp_restrict through those of include/stfem_stokes_pressure_space.h (at degree 2 the entries of
         the constructor's operator, bit for bit).  divergence_space is the divergence at either degree; divergence stays the entry of
-        stfem.h, which refuses degree 3."""
+        stfem.h, which refuses degree 3.  On z-slabs (each slab an operator of its own, its interface faces 4 / 5 left out of the
+        strong mask, the weak set and the outflow set; the interface planes hold partial sums) a degree-3 operator is held against
+        the whole mesh for vmult, the modes without weak faces, st_vmult, st_vmult_slice_add, st_Tvmult, mass_vmult, nitsche_rhs_space,
+        divergence_space and the CIP term without the interface faces (tests/test_gpu_stokes_q3_slabs.py); set_cip_neighbours, the
+        partitioned Vanka blocks, StokesSpaces::set_partition of the C++ mirror and GMGStokes are still missing there."""
         assert "velocity_degree" not in keywords and "_space" not in keywords
         return cls(ncell, _space=(velocity_degree, tuple(int(v) for v in reserved)), **keywords)
 

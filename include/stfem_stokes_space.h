@@ -32,7 +32,12 @@
  *     are set there, the vmult entries above include the face launches and stfem_stokes_vanka_create_space builds blocks with the
  *     Nitsche terms.
  *     Not built at degree 3 either: with weak faces the inflow term of the convection modes and the linearised Vanka blocks (refused
- *     with their reason), CIP, drag / lift, GMGStokes and the drivers, slabs (untested, unclaimed), fp32.
+ *     with their reason), CIP in the Vanka blocks, drag / lift, GMGStokes and the drivers, fp32.
+ *     On z-slabs (a z-slab is a mesh of its own, the caller leaves its interface faces out of the masks; the interface planes of the
+ *     velocity and of the FE_Q(2) pressure hold partial sums) the degree-3 context is held against the whole mesh for vmult, the
+ *     modes without weak faces, st_vmult, st_vmult_slice_add, Tvmult, mass_vmult, the Nitsche functional, the divergence and the
+ *     CIP term WITHOUT the interface faces (tests/test_gpu_stokes_q3_slabs.py).  Still missing there: stfem_stokes_set_cip_neighbours
+ *     (the interface faces of the CIP term), the partitioned Vanka blocks, StokesSpaces::set_partition, GMGStokes.
  *   Any other degree: STFEM_ERR_UNSUPPORTED; non-zero reserved or a pressure_space outside 0..1: STFEM_ERR_INVALID_ARGUMENT; both
  *   with their reason in stfem_last_error. */
 typedef struct {
